@@ -22,11 +22,13 @@ Prints ONE JSON line (rank 0) with the driver's contract fields plus
 import argparse
 import json
 import os
+import re
 import socket
 import subprocess
 import sys
 import tempfile
 import time
+import zlib
 from pathlib import Path
 
 # dmabuf IPC: RCCL across processes needs it on this driver, and the HSA runtime reads it when it starts (first GPU call of the process)
@@ -387,6 +389,60 @@ def emulate_rank_share(cfg_id: int, world: int, backbone: str, k_hyp: int, steps
         shutil.rmtree(tmp2, ignore_errors=True)
 
 
+DUMP_BUDGET_BYTES = 63 << 20   # --dump-outputs: 64 MB in all, with room for the .npy headers
+
+
+def collect_outputs(final, extra) -> dict:
+    """Host copies of what a caller of `run_inference_pipeline` receives from one call: every tensor and numeric `infos` column of the
+    returned collection and of the extra-data dict, by path (`final.poses`, `extra.coarse.data.logits`, ...), as float32 (float64 for
+    float64 and integer data).  Timings, strings and other scalars are left out; an object reachable twice is stored once."""
+    out, seen = {}, {}   # (`seen` keeps what it has visited alive, so that no id is reused)
+
+    def add(name, v):
+        if isinstance(v, (str, bytes, int, float, bool)) or v is None:
+            return
+        if id(v) in seen:
+            return
+        seen[id(v)] = v
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        if isinstance(v, np.ndarray):
+            if v.dtype.kind in "biuf":
+                out[name] = v.astype(np.float64 if v.dtype.kind in "biu" or v.dtype == np.float64 else np.float32)
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                add(f"{name}.{k}", x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                add(f"{name}.{i}", x)
+        elif hasattr(v, "columns") and hasattr(v, "select_dtypes"):   # pandas DataFrame
+            for c in v.select_dtypes(include=["number", "bool"]).columns:
+                add(f"{name}.{c}", v[c].to_numpy())
+        else:
+            if hasattr(v, "infos"):   # PandasTensorCollection
+                add(f"{name}.infos", v.infos)
+            if hasattr(v, "tensors"):
+                add(name, dict(v.tensors))
+
+    add("final", final)
+    add("extra", extra)
+    return {re.sub(r"[^A-Za-z0-9_.-]", "_", k): a for k, a in out.items()}
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """DIR/<name>.npy for every array; over the budget, every array is cut to the same fraction by a sample of its elements whose indices
+    are seeded by the array's name (the same from run to run and build to build)"""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            k = max(1, int(a.size * frac))
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -493,7 +549,11 @@ def main():
                     help="one GPU only, never `value`: run ONE rank's share of the N-GPU workload of --config (rows rank::N, gathers stubbed) and "
                          "the whole workload, print projected_speedup = T(one GPU, whole) / T(rank share) with the per-stage split, and exit")
     ap.add_argument("--emulate-rank", type=int, default=0, help="which rank --emulate-rank-of emulates (default 0)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (final table + extra data) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.emulate_rank_of:
         if a.gpus != 1 or "WORLD_SIZE" in os.environ:
@@ -567,6 +627,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     prof = eng.profile_end()
+    if a.dump_outputs and rank == 0:   # before any other call can reuse the engine's buffers
+        dump_outputs(Path(a.dump_outputs), collect_outputs(final, extra))
     stem_bg, stem_wgs = eng.conv_stem_bg_stats(reset=True)   # stem workgroups that took the background-tile walk / all, of the refiner-stem launches
     conv_mhz = eng.conv_clock(reset=True)   # shader clock INSIDE the (direct fp32) conv kernels of the timed steps
     wb_mhz, wb_cps = eng.conv_wino_bf16_clock(reset=True)   # ... and inside the K loops of the bf16x9 Winograd launches (+ cycles per step)

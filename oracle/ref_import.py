@@ -2,7 +2,7 @@
 pure-torch hot-path math can generate golden vectors.  TEST INFRASTRUCTURE ONLY and
 CONTAINER-ONLY: /root/reference does not exist on the GPU box, so nothing that runs
 there (tests -m gpu, smoke(), bench.py) may import this module.  Only
-``oracle/make_golden.py`` and the (skipped-when-absent) pinning tests use it.
+``oracle/make_golden.py`` and ``oracle/make_reference_fixtures.py`` use it.
 
 Recipe:
   * env CONDA_PREFIX / MEGAPOSE_DATA_DIR / CUDA_VISIBLE_DEVICES so megapose.config imports

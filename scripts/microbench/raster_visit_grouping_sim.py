@@ -1,11 +1,12 @@
 """Offline count (numpy, no GPU): how many block visits would the rasteriser save if one visit served several records, one per lane group
 (pixel rows / halves / 2x2 quads of a 4x4 block)?  Bench mesh, pipeline-like camera, bbox-based touching.  Result:
 rows 0.75, halves 0.83, quads 0.71 of the present visit count -- the densest group of a block dominates."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo')
+import sys, tempfile, numpy as np
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
 from tests.support import synthetic as syn
 from megapose6d_amd import mesh_io
-ds = syn.make_object_dataset('/tmp/mp_vs', 1, 0)
+ds = syn.make_object_dataset(tempfile.mkdtemp(prefix='mp_vs_'), 1, 0)
 m = mesh_io.load_rigid_object(ds[0])
 V = np.asarray(m['vertices'], np.float64); F = np.asarray(m['faces'])
 print(V.shape, F.shape, np.abs(V).max())

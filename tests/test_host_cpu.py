@@ -487,7 +487,7 @@ def test_load_cfg_reads_python_tagged_legacy_configs_without_instantiating_them(
 
 def test_detector_wrapper_builds_the_detections_collection():
     """Detector.get_detections (reference inference/detector.py:63-136) on a stand-in model with torchvision's Mask R-CNN output
-    format; the same cases are compared with the imported reference class in tests/_ref_api_check.py (build container)."""
+    format; the same cases are compared with the reference class in tests/_ref_api_check.py (tables recorded in tests/golden/reference_api.json)."""
     from types import SimpleNamespace
 
     from megapose6d_amd.detector import Detector

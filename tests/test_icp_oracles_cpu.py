@@ -6,7 +6,6 @@ import tempfile
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 
 def _rot_err_deg(A, B):
@@ -88,12 +87,11 @@ def test_user_masks_replace_the_threshold_mask():
     assert r1 == 0 and np.linalg.norm(T1[:3, 3] - gt[:3, 3]) < 5e-3
 
 
-@pytest.mark.skipif(not Path("/root/reference/src/megapose/__init__.py").is_file(), reason="reference sources only exist in the build container")
 def test_restatement_is_pinned_to_the_references_own_refiner_code_around_opencv():
     """getXYZ, get_normal, compute_masks and the orchestration of icp_refinement (mask / range selection, 1000-point rule, centroid
-    pre-shift, float32 pose update, accept rule) are the REFERENCE's functions, imported and run; only cv2.inpaint and
-    cv2.ppf_match_3d_ICP are stand-ins (the oracle's own): everything of row a20 except those two third-party calls is pinned
-    bit for bit (tests/_ref_icp_check.py)."""
+    pre-shift, float32 pose update, accept rule) are the REFERENCE's functions, run by oracle/make_reference_fixtures.py and recorded in
+    tests/golden/reference_icp.npz; only cv2.inpaint and cv2.ppf_match_3d_ICP are stand-ins (the oracle's own): everything of row a20
+    except those two third-party calls is pinned bit for bit (tests/_ref_icp_check.py)."""
     import json
     import subprocess
     import sys
