@@ -72,7 +72,7 @@ __device__ unsigned long long g_wb_phase[10];
 // DIAG (timing experiments only, wrong results; MP_WINO_DIAG): 1 = no split work, 2 = no patch requests / transform, 4 = no weight requests
 // RES: the launch has a residual input; its 16 loads per thread ride under the MFMAs of the LAST K step (round 6).
 // ACT: the launch writes the second, pre-activated output relu(y * scale + shift) (WideResNet blocks).  Both compile-time, and ReLU is a
-// maximum with 0 or -inf: the store loop of the epilogue is straight-line code (it was 48 branches + their mask bookkeeping per workgroup).
+// maximum with 0 or NaN (= no-op, NaN kept): the store loop of the epilogue is straight-line code (it was 48 branches + their mask bookkeeping per workgroup).
 // PERSIST (round 6, the default launch form; MP_WINO_PERSIST=0 = one workgroup per unit): one workgroup per CU walks the units blockIdx,
 // blockIdx + gridDim, ...; the next unit's indices and tile table are computed before the exchange of the current unit's epilogue, its 16
 // patch requests go out four at a time behind the four accumulator blocks of the exchange (the memory pipe is idle there, the patch registers
@@ -444,6 +444,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #define MP_WINO_WS 64
 #endif
   constexpr int WS = MP_WINO_WS;   // (a pitch of 72 floats -- lanes 32..63 of a fragment 32 banks away from lanes 0..31 -- measured 130 cycles SLOWER per workgroup: r6 call 10)
+  // the exchange spans 4 * 2 * WT * WS floats; tile_tab sits at 4 * 2 * WT * WCOUT and already holds the NEXT unit's table here
+  static_assert(WS == WCOUT || !PERSIST, "conv3x3_wino_bf16x9: a wider exchange pitch overwrites the next unit's tile table (persistent form)");
   float* S = smem;
   {
     float* sw = S + (size_t)wave * (2 * WT * WS) + ((lane >> 5) * 4) * WS + (lane & 31);
@@ -479,7 +481,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   //  queue in front of the stores): a net loss on every layer, removed.  profiles/r06_wino_kloop_experiments.txt)
   const __amdgpu_buffer_rsrc_t r_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.y, 0, p.y ? out_bytes : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_act = __builtin_amdgcn_make_buffer_rsrc((void*)p.y_act, 0, (ACT && p.y_act) ? out_bytes : 0, 0x00020000);
-  const float relu_floor = p.relu != 0 ? 0.f : -__builtin_inff();
+  // ReLU without a branch: fmaxf(v, 0) or fmaxf(v, NaN).  fmaxf returns the other operand when one is NaN, so the NaN floor leaves every
+  // value as it is, a NaN included (a floor of -inf turned NaN into -inf: non-ReLU launches must propagate NaN as the direct and the fp32
+  // Winograd kernel do).  ReLU launches keep the project-wide fmaxf(NaN, 0) = 0.
+  const float relu_floor = p.relu != 0 ? 0.f : __builtin_nanf("");
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int tl = it * 16 + (tid >> 4);

@@ -351,6 +351,16 @@ def conv3x3_wino_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_borde
     check(_lib.load().mp_conv3x3_wino_nhwc(C.byref(d), u_packed.data_ptr(), _stream()))
 
 
+def conv_wino_eligible(N: int, H: int, W: int, Cp: int, in_border: int, Cout: int, out_border: int, n_cu: int) -> bool:
+    """True if the backbone would run this 3x3 / stride-1 / pad-1 layer on a Winograd kernel (mp_conv_wino_eligible): channel counts
+    that tile, tensors small enough for 32-bit byte offsets, and a grid of at least a quarter of `n_cu` workgroups"""
+    d = ConvDesc()
+    d.N, d.H, d.W, d.C, d.in_border = N, H, W, Cp, in_border
+    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, 3, 3, 1, 1
+    d.out_border = out_border
+    return bool(_lib.load().mp_conv_wino_eligible(C.byref(d), n_cu))
+
+
 def conv_wino_bf16_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     """U = G g G^T of a 3x3 layer split into three exact bf16 pieces, MFMA fragment order (mp_conv_wino_bf16_pack_weights); uint8 blob"""
     lib = _lib.load()

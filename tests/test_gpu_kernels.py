@@ -10,6 +10,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.support.wino import CONV_TOL, wino_input
+from tests.support.wino import conv_ref_f64 as _conv_ref_f64
+from tests.support.wino import from_padded as _from_padded
+from tests.support.wino import to_padded as _to_padded
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,18 +26,6 @@ def eng():
     n_cu, lds, arch = engine.device_info()
     assert arch.startswith("gfx950")
     return engine
-
-
-def _to_padded(eng, x_nchw, cp, border):
-    n, c, h, w = x_nchw.shape
-    buf = eng.padded_nhwc(n, h, w, cp, border, "cuda")
-    v = eng.padded_view(buf, n, h, w, cp, border)
-    v[..., :c] = x_nchw.permute(0, 2, 3, 1).cuda()
-    return buf
-
-
-def _from_padded(eng, buf, n, h, w, c, border):
-    return eng.padded_view(buf, n, h, w, c, border).permute(0, 3, 1, 2).contiguous().cpu()
 
 
 CONV_CASES = [
@@ -47,21 +40,6 @@ CONV_CASES = [
     (5, 256, 4, 5, 512, 3, 1, 1, 1),    # M = 100: partial tile
     (1, 512, 8, 10, 512, 3, 1, 1, 2),   # border larger than pad
 ]
-
-
-# What the hardware achieves (profiles/r04_wino_bf16_native_check.txt, r04_stem_native_check_v1.txt: <= 7e-6 of the output scale for every
-# convolution kernel against the direct fp32 sum) with a margin of 3: a kernel that loses a piece product or a bit of an operand (2^-16
-# relative and up) fails this; the round-4 bound of 2e-4 would have let a 20x regression pass.  The reference sum is formed in float64
-# from the fp32 operands (the folded weight w * scale rounded to fp32 first, as the packers do), so the bound measures OUR error only.
-CONV_TOL = 2e-5
-
-
-def _conv_ref_f64(x, w, scale, bias, stride, pad):
-    wf = (w.double() * scale.double().view(-1, 1, 1, 1)).float() if scale is not None else w
-    y = F.conv2d(x.double(), wf.double(), None, stride=stride, padding=pad)
-    if bias is not None:
-        y = y + bias.double().view(1, -1, 1, 1)
-    return y.float()
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -137,10 +115,8 @@ def test_winograd_conv_matches_torch_fp32(eng, case, epi, kernel):
     scale = torch.rand(Cout, generator=g) + 0.5
     bias = torch.randn(Cout, generator=g) * 0.1
     res = torch.randn(N, Cout, H, W, generator=g)
-    xb0 = _to_padded(eng, x, Cin, ib)
-    n_x = N * (H + 2 * ib) * (W + 2 * ib) * Cin
-    xb = torch.full((n_x + (W + 2 * ib + 1) * Cin + 64,), float("nan"), device="cuda")
-    xb[:n_x] = xb0.flatten()[:n_x]
+    xb = wino_input(eng, N, H, W, Cin, ib)
+    eng.padded_view(xb, N, H, W, Cin, ib)[:] = x.permute(0, 2, 3, 1).cuda()
     use_scale = epi != "plain"
     pack = eng.conv_wino_bf16_pack_weights if kernel == "bf16x9" else eng.conv_wino_pack_weights
     up = torch.from_numpy(pack(w.numpy(), Cin, scale.numpy() if use_scale else None)).cuda()

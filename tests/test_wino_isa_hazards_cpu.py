@@ -101,3 +101,12 @@ def test_the_lint_rules_on_small_sequences():
 	v_mfma_f32_32x32x16_bf16 a[0:15], v[20:23], v[24:27], a[0:15]
 	s_cbranch_scc1 .LBB0_1
 """)["findings"] == []
+
+
+def test_generated_schedule_header_is_current_and_passes_its_checks():
+    """conv_wino_bf16_sched.h is generated: gen_wino_schedule.py --check re-runs the budget and dependence checks the kernel's correctness
+    rests on and fails if the header on disk differs from what the script generates (a hand edit)"""
+    import subprocess
+
+    r = subprocess.run([sys.executable, str(ROOT / "scripts" / "gen_wino_schedule.py"), "--check"], capture_output=True, text=True, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
