@@ -239,6 +239,16 @@ int mp_conv2d_plan(const mp_conv_desc* desc, int n_cu, int32_t* out5);
 /* the name of the kernel instantiation mp_conv2d_nhwc would launch (for profiling)        */
 const char* mp_conv2d_kernel_name(const mp_conv_desc* desc);
 
+/* The direct convolution of mp_conv2d_nhwc with its multiplications on the bf16 MFMA through EXACT operand pieces (csrc/conv_bf16x9.hip):
+ * the weights (scale folded as in mp_conv_pack_weights) and every fp32 activation fragment are split by truncation into three bf16 pieces
+ * and ALL nine piece products are accumulated in fp32 -- the result differs from mp_conv2d_nhwc only in the order of the fp32 additions.
+ * Same descriptor and fused epilogue; d_w_pieces = the blob of mp_conv_bf16x9_pack_weights uploaded to the device; `desc->d_w` and the
+ * split-K fields are ignored (always one single-pass launch), x_f16 is refused.  Needs C % 16 == 0 and KW * C % 32 == 0. */
+size_t mp_conv_bf16x9_packed_bytes(int Cin_p, int Cout, int KH, int KW);
+int mp_conv_bf16x9_pack_weights(const float* h_w_oihw, int Cout, int Cin, int KH, int KW, int Cin_p, const float* h_scale /*[Cout] or NULL*/,
+                                void* h_packed);
+int mp_conv2d_bf16x9_nhwc(const mp_conv_desc* desc, const void* d_w_pieces, mp_stream stream);
+
 /* Fused Winograd F(2x2, 3x3) form of the 3x3 / stride-1 / pad-1 convolutions of the residual stages (same call sites as
  * mp_conv2d_nhwc: models/torchvision_resnet.py:74-120 BasicBlock conv1 / conv2, models/wide_resnet.py:29-56) -- 16 instead of 36
  * multiplications per (2x2 output tile, cin, cout); fp32 MFMA, fp32 transforms; same fused epilogue (bias, residual, ReLU, second

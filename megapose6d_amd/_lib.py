@@ -114,6 +114,9 @@ SIGNATURES = {
     "mp_conv_pack_weights": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mp_conv2d_nhwc": (_i, [C.POINTER(ConvDesc), _vp]),
     "mp_conv2d_plan": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
+    "mp_conv_bf16x9_packed_bytes": (_sz, [_i, _i, _i, _i]),
+    "mp_conv_bf16x9_pack_weights": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mp_conv2d_bf16x9_nhwc": (_i, [C.POINTER(ConvDesc), _vp, _vp]),
     "mp_conv2d_kernel_name": (C.c_char_p, [C.POINTER(ConvDesc)]),
     "mp_conv_wino_packed_floats": (_sz, [_i, _i]),
     "mp_conv_wino_pack_weights": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -22,6 +22,7 @@ struct ConvLayer {
   float* d_w = nullptr;   // packed fp32 weights
   float* d_u = nullptr;   // Winograd-transformed weights of an eligible 3x3 / stride-1 layer: fp32 (conv_wino.hip, MP_CONV_WINO=1) ...
   void* d_ub = nullptr;   // ... or split into three exact bf16 pieces (conv_wino_bf16.hip, the default)
+  void* d_wb = nullptr;   // the direct weights split into three exact bf16 pieces (conv_bf16x9.hip) of an eligible non-Winograd layer
   float* d_b = nullptr;  // folded BN shift (may be null)
 };
 
@@ -45,6 +46,7 @@ struct mp_backbone {
   int width = 1;      // WideResNet width multiplier (`resnet34_width=N`, training/pose_models_cfg.py:114-116): stage widths 64N .. 512N
   int stageC[4] = {64, 128, 256, 512};
   bool wide;
+  bool direct_bf16 = true;   // MP_CONV_DIRECT_BF16 when the backbone was created: 0 = the non-Winograd layers stay on the fp32-MFMA kernel
   ConvLayer stem;
   std::vector<Block> blocks;
   std::vector<int> stage_of_block;  // 0..3
@@ -138,6 +140,15 @@ int make_conv(mp_backbone* bb, const StateMap& sm, const std::string& wkey, cons
       L->d_ub = d;
     }
   }
+  // the other 3x3 / 1x1 layers of the residual stages (stride 2: layer{2,3,4}.0.conv1 / .downsample) also get the exact-piece direct form
+  if (!rc && bb->direct_bf16 && L != &bb->stem && !L->d_u && !L->d_ub && (K == 1 || K == 3) && Cin_p % 16 == 0 && (K * Cin_p) % 32 == 0 &&
+      Cout % 64 == 0) {
+    std::vector<float> wb((mp_conv_bf16x9_packed_bytes(Cin_p, Cout, K, K) + 3) / 4);
+    rc = mp_conv_bf16x9_pack_weights(w, Cout, Cin, K, K, Cin_p, bnkey.empty() ? nullptr : scale.data(), wb.data());
+    float* d = nullptr;
+    if (!rc) rc = upload(bb, wb, &d);
+    L->d_wb = d;
+  }
   if (rc) return rc;
   if (!bnkey.empty()) {
     rc = upload(bb, shift, &L->d_b);
@@ -169,7 +180,7 @@ int run_conv(const mp_backbone* bb, const ConvLayer& L, const float* x, int N, i
   if (y_act) { d.d_act_scale = act->d_scale; d.d_act_shift = act->d_shift; }
   d.d_splitk_ws = splitk_ws;
   d.splitk_ws_floats = splitk_ws ? (int64_t)SPLITK_WS_FLOATS : 0;
-  if ((L.d_u || L.d_ub) && !x_f16) {
+  if ((L.d_u || L.d_ub || L.d_wb) && !x_f16) {
     static int n_cu = 0, n_cu_dev = -1, lds_ok = 0;
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -179,8 +190,16 @@ int run_conv(const mp_backbone* bb, const ConvLayer& L, const float* x, int N, i
       lds_ok = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds >= 132 * 1024;
       n_cu_dev = dev;
     }
-    if (lds_ok && mp_conv_wino_eligible(&d, n_cu))   // (the workspace buffers carry the read slack the Winograd kernels need)
+    if ((L.d_u || L.d_ub) && lds_ok && mp_conv_wino_eligible(&d, n_cu))   // (the workspace buffers carry the read slack the Winograd kernels need)
       return L.d_ub ? mp_conv3x3_wino_bf16_nhwc(&d, L.d_ub, s) : mp_conv3x3_wino_nhwc(&d, L.d_u, s);
+    // exact-piece direct kernel unless the fp32 kernel's plan splits every tile along K (small grids: mode 1).  A "whole rounds + split-K
+    // tail" plan (mode 2) runs as ONE single-pass launch here: on the bf16 pipe its extra, partly filled round costs less than the split tail.
+    if (L.d_wb) {
+      int32_t plan[5] = {0, 1, 0, 0, 0};
+      const int rc = mp_conv2d_plan(&d, n_cu, plan);
+      if (rc) return rc;
+      if (plan[0] != 1) return mp_conv2d_bf16x9_nhwc(&d, L.d_wb, s);
+    }
   }
   return mp_conv2d_nhwc(&d, s);
 }
@@ -227,6 +246,7 @@ extern "C" int mp_backbone_create_wide(int kind, int width, int c_in, int head_k
   mp_backbone* bb = new mp_backbone();
   bb->kind = kind;
   bb->wide = kind != MP_BACKBONE_VANILLA_RESNET34;
+  bb->direct_bf16 = !(getenv("MP_CONV_DIRECT_BF16") && atoi(getenv("MP_CONV_DIRECT_BF16")) == 0);   // read per backbone: one process can build both forms
   bb->c_in = c_in;
   bb->c_in_p = (c_in + 3) / 4 * 4;
   bb->head_kind = head_kind;

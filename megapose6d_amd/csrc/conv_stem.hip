@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "bf16x9_split.h"
 #include "common.h"
 
 namespace mp {
@@ -383,21 +384,6 @@ extern "C" size_t mp_conv_stem_packed_bytes(int KS, int n_f32, int n_u8, int Cou
   return (size_t)(Cout / stem::NCO) * 4 * stem::n_steps(KS, Q) * 3072;
 }
 
-// exact truncation split of a float into three bf16 pieces (hi, mid, lo): v == hi + mid + lo
-static void split3(float v, unsigned short out[3]) {
-  unsigned vb, rb, qb;
-  memcpy(&vb, &v, 4);
-  const unsigned h = vb & 0xFFFF0000u;
-  float hf; memcpy(&hf, &h, 4);
-  const float r = v - hf;
-  memcpy(&rb, &r, 4);
-  const unsigned m = rb & 0xFFFF0000u;
-  float mf; memcpy(&mf, &m, 4);
-  const float q = r - mf;
-  memcpy(&qb, &q, 4);
-  out[0] = (unsigned short)(h >> 16); out[1] = (unsigned short)(m >> 16); out[2] = (unsigned short)(qb >> 16);
-}
-
 // packed[cb][wave][step][piece][lane][e]: lane = (cout = cb*64 + wave*16 + (lane & 15), slice group lane >> 4), slice s = 4 step + group
 // = (kh, kw, chunk q of the pixel record), element e of the chunk = record slot 8q + e -> input channel; piece = w1 | w2 | w3 of
 // w * scale (* 1/255 for the integer channels, one rounding of the exact product)
@@ -468,7 +454,7 @@ static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t
         else continue;
         const float v = (float)((double)w[(((size_t)co * Cin + ch) * KS + kh) * KS + kw] * f);
         unsigned short pc[3];
-        split3(v, pc);
+        bf16x9_split3(v, pc);
         for (int piece = 0; piece < 3; ++piece)
           out[((((size_t)(cb * 4 + wave) * T + t) * 3 + piece) * 64 + (g * 16 + i)) * 8 + e] = pc[piece];
       }

@@ -31,6 +31,7 @@
 #include <mutex>
 #include <vector>
 
+#include "bf16x9_split.h"
 #include "wino_common.h"
 
 namespace mp {
@@ -604,18 +605,8 @@ extern "C" int mp_conv_wino_bf16_pack_weights(const float* w, int Cout, int Cin,
       const int st = c / WCK, kh = (c % WCK) / 8, e = c % 8;
       const int lane = kh * 32 + nl;
       for (int f = 0; f < 16; ++f) {
-        const float v = (float)U[f / 4][f % 4];
-        unsigned vb, rb, qb;
-        memcpy(&vb, &v, 4);
-        const unsigned h = vb & 0xFFFF0000u;
-        float hf; memcpy(&hf, &h, 4);
-        const float r = v - hf;
-        memcpy(&rb, &r, 4);
-        const unsigned m = rb & 0xFFFF0000u;
-        float mf; memcpy(&mf, &m, 4);
-        const float q = r - mf;
-        memcpy(&qb, &q, 4);
-        const unsigned short pc[3] = {(unsigned short)(h >> 16), (unsigned short)(m >> 16), (unsigned short)(qb >> 16)};
+        unsigned short pc[3];
+        bf16x9_split3((float)U[f / 4][f % 4], pc);
         for (int piece = 0; piece < 3; ++piece)
           out[(((((size_t)(cb * n_steps + st) * 16 + f) * 2 + j) * 3 + piece) * 64 + lane) * 8 + e] = pc[piece];
       }

@@ -321,6 +321,33 @@ def conv2d_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int
     check(lib.mp_conv2d_nhwc(C.byref(d), _stream()))
 
 
+def conv_bf16x9_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
+    """direct-convolution weights (scale folded as in conv_pack_weights) split into three exact bf16 pieces, MFMA fragment order
+    (mp_conv_bf16x9_pack_weights); uint8 blob for conv2d_bf16x9_nhwc"""
+    lib = _lib.load()
+    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    Cout, Cin, KH, KW = w.shape
+    out = np.empty(lib.mp_conv_bf16x9_packed_bytes(cin_p, Cout, KH, KW), dtype=np.uint8)
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+    check(lib.mp_conv_bf16x9_pack_weights(w.ctypes.data, Cout, Cin, KH, KW, cin_p, None if sc is None else sc.ctypes.data, out.ctypes.data))
+    return out
+
+
+def conv2d_bf16x9_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int, w_pieces: torch.Tensor,
+                       bias: Optional[torch.Tensor], Cout: int, K: int, stride: int, pad: int, y: Optional[torch.Tensor], out_border: int,
+                       residual: Optional[torch.Tensor] = None, relu: bool = False, y_act: Optional[torch.Tensor] = None,
+                       act_scale: Optional[torch.Tensor] = None, act_shift: Optional[torch.Tensor] = None) -> None:
+    """conv2d_nhwc on the bf16 MFMA through exact operand pieces (mp_conv2d_bf16x9_nhwc): always one single-pass launch;
+    `w_pieces` = conv_bf16x9_pack_weights(...) on the device.  Needs Cp % 16 == 0 and K * Cp % 32 == 0."""
+    d = ConvDesc()
+    d.d_x, d.N, d.H, d.W, d.C, d.in_border = x.data_ptr(), N, H, W, Cp, in_border
+    d.d_w, d.d_bias = w_pieces.data_ptr(), _ptr(bias)
+    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, K, K, stride, pad
+    d.d_y, d.out_border, d.d_residual, d.relu = _ptr(y), out_border, _ptr(residual), int(relu)
+    d.d_y_act, d.d_act_scale, d.d_act_shift = _ptr(y_act), _ptr(act_scale), _ptr(act_shift)
+    check(_lib.load().mp_conv2d_bf16x9_nhwc(C.byref(d), w_pieces.data_ptr(), _stream()))
+
+
 def conv_wino_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     """Winograd-transformed weights U = G g G^T of a 3x3 layer in MFMA fragment order (mp_conv_wino_pack_weights)"""
     lib = _lib.load()
