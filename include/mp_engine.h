@@ -516,7 +516,8 @@ int mp_detector_forward(mp_detector* det, const float* d_images, int n_images, i
                         int32_t* d_labels, int32_t* d_counts, float* d_masks, void* d_workspace, size_t workspace_bytes,
                         mp_stream stream);
 /* Parity taps (tests): after a forward, the device address + logical shape of an intermediate inside `d_workspace`:
- * "P2".."P6" padded-NHWC pyramid levels {n, h, w, 256} with border 1; "proposals" {n, post_nms_top_n, 4} + "proposal_counts" {n} (int32);
+ * "P2".."P6" padded-NHWC pyramid levels {n, h, w, 256} with border 1; "x0" the preprocessed batch {n, Hp, Wp, 4} with border 3;
+ * "keys" the RPN objectness logits {n, anchors} in (level, y, x, anchor) order; "proposals" {n, post_nms_top_n, 4} + "proposal_counts" {n} (int32);
  * "class_logits" {n*post, padded 5*n_classes row: n_classes logits then 4*n_classes deltas}; "mask_logits" {n*D*14*14*4, padded n_classes}.
  * Returns MP_ERR_INVALID for an unknown name or before the first forward. */
 int mp_detector_debug_tensor(const mp_detector* det, const char* what, const void** d_ptr, int64_t* shape4, int32_t* border,

@@ -358,10 +358,11 @@ __global__ __launch_bounds__(256) void det_box_post_kernel(const float* __restri
   }
 }
 
-// sorted copies of a segment's candidates: out[seg][r] = in[seg][idx[seg][r]] for r < min(cnt, K); keep = 1 there, 0 beyond
+// sorted copies of a segment's candidates: out[seg][r] = in[seg][idx[seg][r]] for r < min(cnt, K); keep = 1 there, 0 beyond;
+// inv[seg][idx[seg][r]] = r (the sorted position of every live candidate)
 __global__ __launch_bounds__(256) void det_sorted_gather_kernel(const float4* __restrict__ box, const float* __restrict__ key, const int* __restrict__ idx,
                                                                 const int* __restrict__ cnt, int K, long n_total, float4* __restrict__ sbox,
-                                                                float* __restrict__ skey, int* __restrict__ keep) {
+                                                                float* __restrict__ skey, int* __restrict__ keep, int* __restrict__ inv) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_total) return;
   const int seg = (int)(t / K), r = (int)(t % K);
@@ -370,11 +371,27 @@ __global__ __launch_bounds__(256) void det_sorted_gather_kernel(const float4* __
   sbox[t] = live ? box[(size_t)seg * K + j] : make_float4(0.f, 0.f, 0.f, 0.f);
   skey[t] = live ? key[(size_t)seg * K + j] : -INFINITY;
   keep[t] = live ? 1 : 0;
+  if (live) inv[(size_t)seg * K + j] = r;
 }
 
-// final outputs of one image: the D best surviving candidates over all classes; boxes mapped back to the original frame
-__global__ __launch_bounds__(256) void det_final_kernel(const float4* __restrict__ sbox, const float* __restrict__ skey, const int* __restrict__ idx,
-                                                        const int* __restrict__ cnt, int D, int per_image, int R, int n_images, float ratio_h,
+// keys of the final selection in torchvision's candidate order (roi_heads.py flattens [proposal, class]): fkey[n][r * (C - 1) + c - 1] =
+// the class-c candidate of proposal r if it survived its class's NMS, else -inf.  The stable rank sort then breaks score ties by
+// (proposal, class) as torchvision's stable score sort of batched_nms does, not by class first.
+__global__ __launch_bounds__(256) void det_final_keys_kernel(const float* __restrict__ key, const int* __restrict__ keep, const int* __restrict__ inv,
+                                                             int C1, int R, long n_total, float* __restrict__ fkey) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_total) return;
+  const long nr = t / C1;
+  const int c1 = (int)(t - nr * C1), n = (int)(nr / R), r = (int)(nr % R);
+  const size_t o = ((size_t)n * C1 + c1) * R + r;   // class-major candidate slot
+  const float k = key[o];
+  fkey[t] = (k > -INFINITY && keep[((size_t)n * C1 + c1) * R + inv[o]]) ? k : -INFINITY;
+}
+
+// final outputs of one image: the D best surviving candidates over all classes (idx in det_final_keys_kernel's proposal-major order,
+// box / key read from the class-major candidate lists); boxes mapped back to the original frame
+__global__ __launch_bounds__(256) void det_final_kernel(const float4* __restrict__ box, const float* __restrict__ key, const int* __restrict__ idx,
+                                                        const int* __restrict__ cnt, int D, int C1, int R, int n_images, float ratio_h,
                                                         float ratio_w, float4* __restrict__ out_box, float* __restrict__ out_score,
                                                         int* __restrict__ out_label, int* __restrict__ out_cnt, float4* __restrict__ resized_box) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -385,10 +402,11 @@ __global__ __launch_bounds__(256) void det_final_kernel(const float4* __restrict
   float s = 0.f;
   int lab = 0;
   if (d < c) {
-    const int j = idx[t];
-    br = sbox[(size_t)n * per_image + j];
-    s = skey[(size_t)n * per_image + j];
-    lab = j / R + 1;
+    const int j = idx[t], r = j / C1, c1 = j - r * C1;
+    const size_t o = ((size_t)n * C1 + c1) * R + r;
+    br = box[o];
+    s = key[o];
+    lab = c1 + 1;
     b = make_float4(br.x * ratio_w, br.y * ratio_h, br.z * ratio_w, br.w * ratio_h);   // transform.py resize_boxes
   }
   out_box[t] = b;
@@ -721,6 +739,7 @@ int det_make_plan(const mp_detector* d, int n, int H, int W, DetPlan* p) {
   p->take("c2_sbox", n_c2 * 4);
   p->take("c2_skey", n_c2);
   p->take("c2_keep", n_c2);
+  p->take("c2_inv", n_c2);
   p->take("c2_fkey", n_c2);
   p->take("f_idx", (size_t)n * D);
   p->take("f_cnt", (size_t)n + 64);
@@ -1055,16 +1074,17 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
   {
     const long total = (long)n_seg2 * R;
     hipLaunchKernelGGL(det_sorted_gather_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_box")), F("c2_key"),
-                       I("c2_idx"), I("c2_cnt"), R, total, reinterpret_cast<float4*>(F("c2_sbox")), F("c2_skey"), I("c2_keep"));
+                       I("c2_idx"), I("c2_cnt"), R, total, reinterpret_cast<float4*>(F("c2_sbox")), F("c2_skey"), I("c2_keep"), I("c2_inv"));
     hipLaunchKernelGGL(det_nms_kernel, dim3(n_seg2), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_sbox")), I("c2_keep"), I("c2_cnt"), R,
                        cfg.box_nms_thresh);
-    hipLaunchKernelGGL(det_masked_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("c2_skey"), I("c2_keep"), total, F("c2_fkey"));
+    hipLaunchKernelGGL(det_final_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("c2_key"), I("c2_keep"), I("c2_inv"), C - 1, R, total,
+                       F("c2_fkey"));
   }
   hipLaunchKernelGGL(det_seg_offsets_kernel, dim3(ceil_div((long)n + 1, 256)), dim3(256), 0, s, n, (C - 1) * R, I("seg_off3"));
   hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div((long)(C - 1) * R, 256), n), dim3(256), 0, s, F("c2_fkey"), I("seg_off3"), D, I("f_idx"),
                      I("f_cnt"));
-  hipLaunchKernelGGL(det_final_kernel, dim3(ceil_div((long)n * D, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_sbox")), F("c2_skey"),
-                     I("f_idx"), I("f_cnt"), D, (C - 1) * R, R, n, p.ratio_h, p.ratio_w, reinterpret_cast<float4*>(d_boxes), d_scores, d_labels,
+  hipLaunchKernelGGL(det_final_kernel, dim3(ceil_div((long)n * D, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_box")), F("c2_key"),
+                     I("f_idx"), I("f_cnt"), D, C - 1, R, n, p.ratio_h, p.ratio_w, reinterpret_cast<float4*>(d_boxes), d_scores, d_labels,
                      d_counts, reinterpret_cast<float4*>(F("det_resized")));
 
   // ---- mask head --------------------------------------------------------------------------------------------------------------------
@@ -1116,6 +1136,8 @@ extern "C" int mp_detector_debug_tensor(const mp_detector* d, const char* what, 
     shape4[0] = p.n; shape4[1] = R; shape4[2] = 4; shape4[3] = 1; *row_stride = 4;
   } else if (w == "proposal_scores") {
     shape4[0] = p.n; shape4[1] = R; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
+  } else if (w == "keys") {   // RPN objectness logits of every anchor, (level, y, x, a) order
+    shape4[0] = p.n; shape4[1] = p.a_total; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
   } else if (w == "proposal_counts" || w == "f_cnt") {
     shape4[0] = p.n; shape4[1] = 1; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
   } else if (w == "class_logits") {

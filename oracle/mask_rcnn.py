@@ -290,7 +290,9 @@ def batched_nms(boxes, scores, idxs, thr) -> torch.Tensor:
     return ki[torch.sort(scores[ki], descending=True, stable=True).indices]
 
 
-def rpn_proposals(sd, feats: List[torch.Tensor], image_sizes, padded_hw) -> Tuple[List[torch.Tensor], Dict[str, object]]:
+def rpn_proposals(sd, feats: List[torch.Tensor], image_sizes, padded_hw, objectness_override=None) -> Tuple[List[torch.Tensor], Dict[str, object]]:
+    """objectness_override: optional [N, anchors] logits that replace the head's own ones in the selection and the scores (tests feed the
+    values an implementation under test ranked, so that its decisions are judged on its own keys); the deltas still come from `feats`"""
     obj, dlt = [], []
     for f in feats:
         t = F.relu(F.conv2d(f, sd["rpn.head.conv.weight"], sd["rpn.head.conv.bias"], padding=1))
@@ -303,6 +305,9 @@ def rpn_proposals(sd, feats: List[torch.Tensor], image_sizes, padded_hw) -> Tupl
     n_per = [a.shape[0] for a in anchors]
     all_anchors = torch.cat(anchors)
     objectness, deltas = torch.cat(obj, 1), torch.cat(dlt, 1)
+    if objectness_override is not None:
+        assert objectness_override.shape == objectness.shape, (objectness_override.shape, objectness.shape)
+        objectness = objectness_override.to(objectness.dtype)
     N = objectness.shape[0]
     proposals = decode_boxes(deltas.reshape(-1, 4), all_anchors.repeat(N, 1), (1.0, 1.0, 1.0, 1.0)).view(N, -1, 4)
     levels = torch.cat([torch.full((n,), i, dtype=torch.long) for i, n in enumerate(n_per)])
@@ -351,7 +356,8 @@ def multiscale_roi_align(feats4: List[torch.Tensor], boxes: List[torch.Tensor], 
 
 
 def box_branch(sd, feats4, proposals, image_sizes):
-    x = multiscale_roi_align(feats4, proposals, image_sizes, 7).flatten(1)
+    # (RoIAlign samples in float32, as ops/roi_align does; the layers after it run in the dtype of the weights -- float64 for tests)
+    x = multiscale_roi_align(feats4, proposals, image_sizes, 7).flatten(1).to(sd["roi_heads.box_head.fc6.weight"].dtype)
     x = F.relu(F.linear(x, sd["roi_heads.box_head.fc6.weight"], sd["roi_heads.box_head.fc6.bias"]))
     x = F.relu(F.linear(x, sd["roi_heads.box_head.fc7.weight"], sd["roi_heads.box_head.fc7.bias"]))
     logits = F.linear(x, sd["roi_heads.box_predictor.cls_score.weight"], sd["roi_heads.box_predictor.cls_score.bias"])
