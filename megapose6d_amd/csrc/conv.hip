@@ -42,98 +42,31 @@ __device__ unsigned long long g_conv_seg[8];
 #define CPROF(slot)
 #endif
 
-// LDS-transposed epilogue with 16-byte stores (Cout % 4 == 0).  The MFMA C layout gives a lane ONE column of 16 scattered rows, so the
-// direct epilogue above needs TM*TN*16 dword stores (and as many dword residual loads) per wave -- store-ISSUE-bound: 9 % of an
-// 18-chunk layer-1 tile.  Here each wave parks its WM x WN accumulator tile in its own slice of the (now idle) A/B staging LDS
-// (row stride = WN floats: conflict-free for both the ds_write_b32 column writes and the ds_read_b128 row reads) and walks it back in
-// rows: a lane owns 4 consecutive channels of one output pixel -> one buffer_load_b128 of the residual, one buffer_store_b128 of the
-// result (4x fewer VMEM instructions, whole 128/256-byte row segments per 8/16 lanes).  Same arithmetic per element, same masking
-// through the buffer range check.  The wave only touches its own slice: no workgroup barrier.
-template <int TM, int TN, bool RES, bool RELU, bool ACT>
-__device__ __forceinline__ void conv_epilogue_vec(const ConvParams& p, const f32x16 (&acc)[TM][TN], const int* row_off, float* stage,
-                                                  int wave_row0, int n_wave0) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  constexpr int LDW = TN * 32;              // floats per staged row
-  constexpr int LPR = TN * 8;               // lanes per row (one float4 each)
-  constexpr int RPI = 64 / LPR;             // rows per iteration
-  constexpr int NIT = TM * 32 / RPI;        // iterations
-  const int lane = threadIdx.x & 63;
-  {
-    float* st = stage + ((lane >> 5) * 4) * LDW + (lane & 31);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[(i * 32 + (r & 3) + 8 * (r >> 2)) * LDW + j * 32] = acc[i][j][r];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int base = __builtin_amdgcn_readfirstlane(row_off[0]);
-  const int lr = lane / LPR, lc = (lane % LPR) * 4;
-  const int n = n_wave0 + lc;
-  const bool n_ok = n < p.Cout;
-  unsigned voff[NIT];
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int o = row_off[wave_row0 + it * RPI + lr];
-    voff[it] = (o >= 0 && n_ok) ? (unsigned)(o - base + n) * 4u : EPI_WINDOW;
-  }
-  u32x4 res[NIT];
-  if (RES) {
-    const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual + base), 0, (int)EPI_WINDOW, 0x00020000);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) res[it] = __builtin_amdgcn_raw_buffer_load_b128(r_res, voff[it], 0, 0);
-  }
-  float4 bias = make_float4(0.f, 0.f, 0.f, 0.f), sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (p.bias && n_ok) bias = *reinterpret_cast<const float4*>(p.bias + n);
-  if (ACT && n_ok) {
-    sc = *reinterpret_cast<const float4*>(p.act_scale + n);
-    sh = *reinterpret_cast<const float4*>(p.act_shift + n);
-  }
-  const __amdgpu_buffer_rsrc_t r_y = __builtin_amdgcn_make_buffer_rsrc((void*)(p.y ? p.y + base : nullptr), 0, p.y ? (int)EPI_WINDOW : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t r_act =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(ACT ? p.y_act + base : nullptr), 0, ACT ? (int)EPI_WINDOW : 0, 0x00020000);
-  const float* rd = stage + lr * LDW + lc;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    float4 v = *reinterpret_cast<const float4*>(rd + it * RPI * LDW);
-    v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
-    if (RES) {
-      v.x += __uint_as_float(res[it].x); v.y += __uint_as_float(res[it].y);
-      v.z += __uint_as_float(res[it].z); v.w += __uint_as_float(res[it].w);
-    }
-    if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-    u32x4 o;
-    o.x = __float_as_uint(v.x); o.y = __float_as_uint(v.y); o.z = __float_as_uint(v.z); o.w = __float_as_uint(v.w);
-    __builtin_amdgcn_raw_buffer_store_b128(o, r_y, voff[it], 0, 0);
-    if (ACT) {
-      u32x4 a;
-      a.x = __float_as_uint(fmaxf(fmaf(v.x, sc.x, sh.x), 0.f)); a.y = __float_as_uint(fmaxf(fmaf(v.y, sc.y, sh.y), 0.f));
-      a.z = __float_as_uint(fmaxf(fmaf(v.z, sc.z, sh.z), 0.f)); a.w = __float_as_uint(fmaxf(fmaf(v.w, sc.w, sh.w), 0.f));
-      __builtin_amdgcn_raw_buffer_store_b128(a, r_act, voff[it], 0, 0);
-    }
-  }
-}
+constexpr int CONV_BM = 128;   // output pixels per tile; the tile width BN (64 or 128 output channels) is the one the weights are packed for
 
+// Tile: CONV_BM x BN, four waves of 64 x BN/2 (2 x BN/64 accumulators of 32 x 32).  A and B come through buffer_load_dwordx4: one scalar
+// resource per operand (A: based at the tile's first pixel -- addresses ascend with the row index, the tile spans a few image rows; B: at
+// this n-block's packed weights; neither range check can trigger, num_records = 2^32 - 1), a loop-invariant 32-bit lane offset and the
+// chunk position in the scalar offset.  K loop: one 32-float chunk and one barrier per iteration; chunk c+1 is requested at the top and
+// written to the other LDS buffer under an MFMA group.
 // waves_per_eu(2,2): LDS already limits residency to 2 workgroups per CU (= 2 waves per SIMD); telling the compiler so lets it
 // keep the prefetch registers live across the MFMA block instead of spilling them to scratch to chase a higher occupancy.
-// VARIANT: 1 = the LDS store of the next chunk sits under the LAST MFMA group, | 256 = under the 3rd of 4; | 4096 = the two-chunks-ahead
-// pipeline (barrier before the last group); | 8192 = buffer loads (scalar resource + 32-bit offsets) instead of global loads;
-// | 16384 = persistent workgroups: the launch has one workgroup per resident slot (2 per CU) and each walks the tiles
-// blockIdx.x, blockIdx.x + gridDim.x, ... (p.k_split carries the tile count of the launch) -- no workgroup dispatch between tiles.
+// RAGGED: K runs that are not a multiple of 32 (the 7x7 / 5x5 stems): per-lane run position.  SPLITK: blockIdx.y owns a range of chunks
+// and writes raw partial sums (conv_splitk_reduce applies the epilogue).
 // AHALF: the INPUT tensor holds IEEE binary16 values (the "fp16 renders" CNN input the rasteriser writes with MP_RASTER_F16): the A
 // tile is fetched as 8-byte pieces (4 halves), stays packed in registers across the MFMA block and is widened to fp32 on its way
 // into LDS -- everything after the LDS store (fragments, MFMA, epilogue) is the fp32 path unchanged.
-template <int BM, int BN, int WM, int WN, int VARIANT = 0, bool RAGGED = false, bool SPLITK = false, bool AHALF = false>
+// (Measured against this schedule, bit-identical and within +-1 %, and dropped: persistent workgroups, a 16-byte LDS-transposed epilogue,
+//  global_load addressing, a two-chunks-ahead pipeline -- profiles/r03_conv_ab_epilogue_persistent.txt, docs/history.md section 3.1.)
+template <int BN, bool RAGGED, bool SPLITK, bool AHALF>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_nhwc_f32_mfma(ConvParams p) {
+  constexpr int BM = CONV_BM, WM = 64, WN = BN / 2;
   constexpr int NBUF = 2;
   constexpr int LDT = LDS_LD;
-  static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
   constexpr int TM = WM / 32, TN = WN / 32;
   constexpr int A_LD4 = BM / 32;  // float4 loads per thread for the A tile
   constexpr int B_LD4 = BN / 32;
+  static_assert(BN == 64 || BN == 128, "staging code is written for BM = 128, BN in {64, 128}");
 
   const bool clk_sample = threadIdx.x == 0 && (blockIdx.x & 63) == 0;
   unsigned long long clk_c0 = 0, clk_r0 = 0;
@@ -149,15 +82,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int wm = wave / (BN / WN);
   const int wn = wave % (BN / WN);
 
-  constexpr bool PERSIST = (VARIANT & 16384) != 0;
-  constexpr bool VEC_EPI = (VARIANT & 65536) != 0;   // LDS-transposed epilogue with 16-byte stores (conv_epilogue_vec)
-  static_assert(4 * WM * WN <= NBUF * (BM + BN) * LDT, "the epilogue stages the accumulators in the A/B buffers");
-  static_assert(!PERSIST || !SPLITK, "persistent workgroups are a single-pass launch mode");
-  for (int tile = blockIdx.x; PERSIST ? tile < p.k_split : true; tile += gridDim.x) {   // (not PERSIST: exactly one trip, the loop folds away)
-  if constexpr (PERSIST) {
-    if (clk_sample) { clk_c0 = __builtin_readcyclecounter(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
-  }
-  const int lb = (PERSIST ? xcd_remap(tile, p.k_split) : xcd_remap(blockIdx.x, gridDim.x)) + p.tile_begin;
+  const int lb = xcd_remap(blockIdx.x, gridDim.x) + p.tile_begin;
   const int nblk = lb % p.n_nblocks;
   const int mblk = lb / p.n_nblocks;
   const int m0 = mblk * BM;
@@ -193,20 +118,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 
   const int a_col = a_c4 * 4;  // this thread's float offset in a chunk row
+  // b_ptr / bp: this thread's B position as a pointer.  No load reads it (they use b_rsrc + b_su), but the compiler's instruction order
+  // in the prologue, and so every instance's machine code, depends on it being there (scripts/isa_digest.py).
   const float* b_ptr = p.w + (size_t)nblk * p.n_chunks * (BN * BK) + (tid >> 3) * BK + a_col;
-  // VARIANT bit 8192: buffer_load_dwordx4 (scalar resource + 32-bit lane offset + scalar chunk offset) instead of global_load_dwordx4
-  // with 64-bit lane addresses.  The A resource starts at the tile's first pixel (addresses ascend with the row index, the tile spans
-  // a few image rows), the B resource at this n-block's packed weights; neither range check can trigger (num_records = 2^32 - 1).
-  constexpr bool BUFLD = (VARIANT & 8192) != 0;
-  static_assert(!AHALF || BUFLD, "the half-precision input path is written for the buffer-load variants");
   constexpr int A_ES = AHALF ? 2 : 4;   // bytes per input element
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  int a_voff[A_LD4] = {0, 0, 0, 0};
-  int b_voff = 0;
+  int a_voff[A_LD4];
+  int b_voff;
   __amdgpu_buffer_rsrc_t a_rsrc, b_rsrc;
-  if constexpr (BUFLD) {
+  {
     const int mb = m0 < p.M ? m0 : p.M - 1;
     const int wo = mb % p.Wo;
     const int t = mb / p.Wo;
@@ -235,17 +157,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
   // Straight-line software pipeline (no lambdas / no conditional loads: hipcc otherwise parks the prefetch registers in
   // scratch and waits for the loads right away).  The loads of chunk c+1 are issued before the MFMAs of chunk c and written
-  // to the other LDS buffer after them; the last iteration harmlessly re-loads the last chunk.
+  // to the other LDS buffer under them; the last iteration harmlessly re-loads the last chunk.
 // (explicit scalars, not arrays: the arrays only become registers after loop unrolling, and the sched_barrier intrinsic
 //  that pins the prefetch is a memory barrier to the optimiser, which would leave them in scratch)
-#define MP_LD4(P) (*reinterpret_cast<const float4*>(P))
 #define MP_BUF4(R, V, S) ([&] { const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(R, V, S, 0);              \
     return make_float4(__uint_as_float(v_.x), __uint_as_float(v_.y), __uint_as_float(v_.z), __uint_as_float(v_.w)); }())
-#define MP_CONV_LOAD(AOFF, BP)                                                                                     \
-  if constexpr (BUFLD) {                                                                                           \
+#define MP_CONV_LOAD()                                                                                             \
+  {                                                                                                                \
     /* RAGGED: the run position is per lane (vector offset); otherwise only a_col is, the rest rides in the scalar offset */ \
-    const int av_ = RAGGED ? (AOFF) * A_ES : a_col * A_ES;                                                         \
-    const int as_ = RAGGED ? 0 : a_su * A_ES;   /* a_su / b_su: the wave-uniform parts of AOFF / BP, tracked separately */ \
+    const int av_ = RAGGED ? aoff * A_ES : a_col * A_ES;                                                           \
+    const int as_ = RAGGED ? 0 : a_su * A_ES;   /* a_su / b_su: the wave-uniform chunk positions (A: non-RAGGED only) */ \
     const int bs_ = b_su * 4;                                                                                      \
     if constexpr (AHALF) {   /* 4 halves per lane and tile row: widened when they are written to LDS */            \
       ah0 = __builtin_amdgcn_raw_buffer_load_b64(a_rsrc, a_voff[0] + av_, as_, 0);                                 \
@@ -263,17 +184,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if constexpr (B_LD4 > 2) {                                                                                     \
       b2 = MP_BUF4(b_rsrc, b_voff, bs_ + 8192);                                                                    \
       b3 = MP_BUF4(b_rsrc, b_voff, bs_ + 12288);                                                                   \
-    }                                                                                                              \
-  } else {                                                                                                         \
-    a0 = MP_LD4(a_ptr0 + (AOFF));                                                                                  \
-    a1 = MP_LD4(a_ptr1 + (AOFF));                                                                                  \
-    a2 = MP_LD4(a_ptr2 + (AOFF));                                                                                  \
-    a3 = MP_LD4(a_ptr3 + (AOFF));                                                                                  \
-    b0 = MP_LD4((BP));                                                                                             \
-    b1 = MP_LD4((BP) + 1024);                                                                                      \
-    if constexpr (B_LD4 > 2) {                                                                                     \
-      b2 = MP_LD4((BP) + 2048);                                                                                    \
-      b3 = MP_LD4((BP) + 3072);                                                                                    \
     }                                                                                                              \
   }
 #define MP_ST4(P, V) (*reinterpret_cast<float4*>(P) = (V))
@@ -300,11 +210,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       MP_ST4(bs_w + 96 * LDT, b3);                                             \
     }                                                                             \
   }
-  static_assert(A_LD4 == 4 && (B_LD4 == 2 || B_LD4 == 4), "staging code is written for BM = 128, BN in {64, 128}");
-  const float* a_ptr0 = a_ptr[0];
-  const float* a_ptr1 = a_ptr[1];
-  const float* a_ptr2 = a_ptr[2];
-  const float* a_ptr3 = a_ptr[3];
   float4 a0, a1, a2, a3, b0, b1, b2, b3;
   u32x2 ah0, ah1, ah2, ah3;   // AHALF: the packed halves of the prefetched A pieces
 
@@ -314,13 +219,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // the bump is wave-uniform (scalar registers), which is what the 3x3 / 1x1 layers use.
   int j = a_col, aoff = a_col;
   int ju = 0;  // uniform run position (non-RAGGED)
-  int a_su = 0, b_su = 0;  // buffer-load variant: uniform float offsets of the current chunk (A: non-RAGGED only)
-  const float* bp = b_ptr;
+  int a_su = 0, b_su = 0;  // uniform float offsets of the current chunk (A: non-RAGGED only)
+  [[maybe_unused]] const float* bp = b_ptr;
   int c_begin = 0, c_end = p.n_chunks;
   if constexpr (SPLITK) {
     c_begin = blockIdx.y * p.chunks_per_split;
     c_end = min(p.n_chunks, c_begin + p.chunks_per_split);
-    bp += (size_t)c_begin * (BN * BK);
     b_su = c_begin * (BN * BK);
     if constexpr (RAGGED) {
       const int jj = a_col + c_begin * BK;
@@ -330,13 +234,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     } else {
       const int kh = (c_begin * BK) / p.run;
       ju = c_begin * BK - kh * p.run;
-      aoff = a_col + kh * row_stride + ju;
       a_su = kh * row_stride + ju;
     }
   } else if constexpr (RAGGED) {
     while (j >= p.run) { j -= p.run; aoff += row_stride - p.run; }
   }
-  MP_CONV_LOAD(aoff, bp)
+  MP_CONV_LOAD()
   MP_CONV_STORE(0)
   __syncthreads();
 
@@ -347,106 +250,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   unsigned long long cprof_acc[5] = {0, 0, 0, 0, 0};
   unsigned long long cprof_t = __builtin_readcyclecounter();
 #endif
-// advance the load position to the next chunk (guarded by COND; the loads themselves are unconditional, the last one is repeated)
-#define MP_CONV_ADVANCE(COND)                                                                                      \
-  if (COND) {                                                                                                      \
-    bp += BN * BK;                                                                                                 \
-    b_su += BN * BK;                                                                                               \
-    aoff += BK;                                                                                                    \
-    a_su += BK;                                                                                                    \
-    if constexpr (RAGGED) {                                                                                        \
-      j += BK;                                                                                                     \
-      while (j >= p.run) { /* crossed into the next kernel row(s) (runs shorter than BK wrap more than once) */    \
-        j -= p.run;                                                                                                \
-        aoff += row_wrap;                                                                                          \
-      }                                                                                                            \
-    } else {                                                                                                       \
-      ju += BK;                                                                                                    \
-      if (ju == p.run) {                                                                                           \
-        ju = 0;                                                                                                    \
-        aoff += row_wrap;                                                                                          \
-        a_su += row_wrap;                                                                                          \
-      }                                                                                                            \
-    }                                                                                                              \
-  }
-  if constexpr ((VARIANT & 4096) != 0) {
-    // Two-chunks-ahead pipeline, ONE barrier per chunk placed before the LAST MFMA group:
-    //   registers G hold chunk c+1 (requested a whole chunk ago), fragments of k-group g+1 are read from LDS under the 16 MFMAs of
-    //   group g -- across the chunk boundary too: the barrier sits where (i) every wave has written chunk c+1 to the other buffer
-    //   (under group 0) and (ii) every wave has READ its last fragments of chunk c (requested under group 2), so after it the other
-    //   buffer may be read (group 0 of chunk c+1, under group 3 of chunk c) and this buffer may be overwritten (top of chunk c+1).
-    static_assert(BK == 32, "four k-groups per chunk");
-    MP_CONV_ADVANCE(c_begin + 1 < c_end)
-    MP_CONV_LOAD(aoff, bp)
-    float4 afr[2][TM], bfr[2][TN];
-    {
-      const float* as0 = As + (wm * WM + frag_row) * LDT + frag_k;
-      const float* bs0 = Bs + (wn * WN + frag_row) * LDT + frag_k;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) afr[0][i] = *reinterpret_cast<const float4*>(as0 + i * 32 * LDT);
-#pragma unroll
-      for (int jn = 0; jn < TN; ++jn) bfr[0][jn] = *reinterpret_cast<const float4*>(bs0 + jn * 32 * LDT);
-    }
-#define MP_FRAG_READ(SLOT, AS, BS, KOFF)                                                                          \
-  _Pragma("unroll") for (int i = 0; i < TM; ++i) afr[SLOT][i] = *reinterpret_cast<const float4*>((AS) + i * 32 * LDT + (KOFF));  \
-  _Pragma("unroll") for (int jn = 0; jn < TN; ++jn) bfr[SLOT][jn] = *reinterpret_cast<const float4*>((BS) + jn * 32 * LDT + (KOFF));
-#define MP_MFMA_ROW(SLOT, I)                                                                                       \
-  _Pragma("unroll") for (int jn = 0; jn < TN; ++jn) {                                                              \
-    acc[I][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[SLOT][I].x, bfr[SLOT][jn].x, acc[I][jn], 0, 0, 0);       \
-    acc[I][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[SLOT][I].y, bfr[SLOT][jn].y, acc[I][jn], 0, 0, 0);       \
-    acc[I][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[SLOT][I].z, bfr[SLOT][jn].z, acc[I][jn], 0, 0, 0);       \
-    acc[I][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(afr[SLOT][I].w, bfr[SLOT][jn].w, acc[I][jn], 0, 0, 0);       \
-  }
-    for (int chunk = c_begin; chunk < c_end; ++chunk) {
-      const int buf = (chunk - c_begin) & 1;
-      const float* as = As + buf * BM * LDT + (wm * WM + frag_row) * LDT + frag_k;
-      const float* bs = Bs + buf * BN * LDT + (wn * WN + frag_row) * LDT + frag_k;
-      const float* as_n = As + (buf ^ 1) * BM * LDT + (wm * WM + frag_row) * LDT + frag_k;
-      const float* bs_n = Bs + (buf ^ 1) * BN * LDT + (wn * WN + frag_row) * LDT + frag_k;
-      // group 0 (+ chunk c+1: registers -> other buffer; chunk c+2: global -> registers)
-      MP_FRAG_READ(1, as, bs, 8)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_MFMA_ROW(0, 0)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_CONV_STORE(buf ^ 1)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_MFMA_ROW(0, 1)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_CONV_ADVANCE(chunk + 2 < c_end)
-      MP_CONV_LOAD(aoff, bp)
-      __builtin_amdgcn_sched_barrier(0);
-      // group 1
-      MP_FRAG_READ(0, as, bs, 16)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_MFMA_ROW(1, 0)
-      MP_MFMA_ROW(1, 1)
-      __builtin_amdgcn_sched_barrier(0);
-      // group 2
-      MP_FRAG_READ(1, as, bs, 24)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_MFMA_ROW(0, 0)
-      MP_MFMA_ROW(0, 1)
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();
-      // group 3, with the first fragments of the next chunk
-      MP_FRAG_READ(0, as_n, bs_n, 0)
-      __builtin_amdgcn_sched_barrier(0);
-      MP_MFMA_ROW(1, 0)
-      MP_MFMA_ROW(1, 1)
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#undef MP_FRAG_READ
-#undef MP_MFMA_ROW
-  } else
+  // The LDS store of the next chunk sits under the 3rd of the 4 MFMA groups in the single pass, under the last one in a split-K pass.
+  constexpr int STORE_KK = SPLITK ? BK / 8 - 1 : 2;
   for (int chunk = c_begin; chunk < c_end; ++chunk) {
     const int buf = (chunk - c_begin) & 1;
-    MP_CONV_ADVANCE(chunk + 1 < c_end)
-    MP_CONV_LOAD(aoff, bp)
+    if (chunk + 1 < c_end) {   // advance the load position to the next chunk (the last one is loaded again)
+      bp += BN * BK;
+      b_su += BN * BK;
+      if constexpr (RAGGED) {
+        aoff += BK;
+        j += BK;
+        while (j >= p.run) {   // crossed into the next kernel row(s) (runs shorter than BK wrap more than once)
+          j -= p.run;
+          aoff += row_wrap;
+        }
+      } else {
+        a_su += BK;
+        ju += BK;
+        if (ju == p.run) {
+          ju = 0;
+          a_su += row_wrap;
+        }
+      }
+    }
+    MP_CONV_LOAD()
     __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the MFMA block (the scheduler otherwise sinks it to the end)
     CPROF(0)
     const float* as = As + buf * BM * LDT + (wm * WM + frag_row) * LDT + frag_k;
     const float* bs = Bs + buf * BN * LDT + (wn * WN + frag_row) * LDT + frag_k;
-    constexpr int STORE_KK = (VARIANT & 256) ? 2 : BK / 8 - 1;
 #pragma unroll
     for (int kk = 0; kk < BK / 8; ++kk) {
       float4 af[TM], bf[TN];
@@ -461,9 +292,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         __builtin_amdgcn_sched_barrier(0);
         CPROF(2)
       }
-      // (experiment, MP_CONV_EXPERIMENTS builds only: | 32768 = raise the wave's issue priority for the duration of an MFMA group, so
-      //  that the co-resident workgroup's loads / LDS traffic never delay the next MFMA of the wave that owns the matrix pipe)
-      if constexpr ((VARIANT & 32768) != 0) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -473,7 +301,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].z, bf[j].z, acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
         }
-      if constexpr ((VARIANT & 32768) != 0) __builtin_amdgcn_s_setprio(0);
     }
     CPROF(3)
     __syncthreads();
@@ -487,8 +314,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #undef MP_BUF4
 #undef MP_CONV_STORE
 #undef MP_H4
-#undef MP_CONV_ADVANCE
-#undef MP_LD4
 #undef MP_ST4
 
   if (clk_sample) {   // prologue + K loop of this workgroup
@@ -515,20 +340,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     return;
   }
   const int emode = (p.residual ? 1 : 0) | (p.relu ? 2 : 0) | (p.y_act ? 4 : 0);
-  if (VEC_EPI && (p.Cout & 3) == 0) {   // 16-byte path (every backbone layer); Cout % 4 != 0 (detector predictor heads) takes the dword path
-    float* stage = smem + wave * (WM * WN);   // the wave's slice of the idle A/B staging buffers (the K loop ended with a barrier)
-    const int vr0 = wm * WM, vn0 = n0 + wn * WN;
-    switch (emode) {
-      case 0: conv_epilogue_vec<TM, TN, false, false, false>(p, acc, row_off, stage, vr0, vn0); break;
-      case 1: conv_epilogue_vec<TM, TN, true, false, false>(p, acc, row_off, stage, vr0, vn0); break;
-      case 2: conv_epilogue_vec<TM, TN, false, true, false>(p, acc, row_off, stage, vr0, vn0); break;
-      case 3: conv_epilogue_vec<TM, TN, true, true, false>(p, acc, row_off, stage, vr0, vn0); break;
-      case 4: conv_epilogue_vec<TM, TN, false, false, true>(p, acc, row_off, stage, vr0, vn0); break;
-      case 5: conv_epilogue_vec<TM, TN, true, false, true>(p, acc, row_off, stage, vr0, vn0); break;
-      case 6: conv_epilogue_vec<TM, TN, false, true, true>(p, acc, row_off, stage, vr0, vn0); break;
-      default: conv_epilogue_vec<TM, TN, true, true, true>(p, acc, row_off, stage, vr0, vn0); break;
-    }
-  } else
   switch (emode) {
     case 0: conv_epilogue<TM, TN, false, false, false>(p, acc, row_off, erow0, en0); break;
     case 1: conv_epilogue<TM, TN, true, false, false>(p, acc, row_off, erow0, en0); break;
@@ -538,9 +349,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     case 5: conv_epilogue<TM, TN, true, false, true>(p, acc, row_off, erow0, en0); break;
     case 6: conv_epilogue<TM, TN, false, true, true>(p, acc, row_off, erow0, en0); break;
     default: conv_epilogue<TM, TN, true, true, true>(p, acc, row_off, erow0, en0); break;
-  }
-  if constexpr (!PERSIST) break;
-  __syncthreads();   // the next tile rewrites row_off (and the LDS stages) that slower waves may still be reading in their epilogue
   }
 }
 
@@ -581,18 +389,17 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce(ConvParams p) {
   }
 }
 
-// resident workgroup slots of the device (2 per CU: LDS-limited); set by mp_conv2d_nhwc before the first launch
-static int g_resident_workgroups = 0;
+static size_t conv_lds_bytes(int BN) { return (size_t)(2 * CONV_BM * LDS_LD + 2 * BN * LDS_LD) * sizeof(float) + CONV_BM * sizeof(int); }
 
-template <int BM, int BN, int WM, int WN, int VARIANT, bool RAGGED = false>
+template <int BN, bool RAGGED = false>
 static int launch_splitk(const ConvParams& p, hipStream_t s, double alg_k) {
   ConvParams q = p;
-  q.n_mblocks = ceil_div(p.M, BM);
+  q.n_mblocks = ceil_div(p.M, CONV_BM);
   q.n_nblocks = ceil_div(p.Cout, BN);
-  const size_t lds = (size_t)(2 * BM * LDS_LD + 2 * BN * LDS_LD) * sizeof(float) + BM * sizeof(int);
+  const size_t lds = conv_lds_bytes(BN);
   static bool attr_set = false;
   if (!attr_set) {
-    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_nhwc_f32_mfma<BM, BN, WM, WN, VARIANT, RAGGED, true>,
+    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_nhwc_f32_mfma<BN, RAGGED, true, false>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
@@ -601,7 +408,7 @@ static int launch_splitk(const ConvParams& p, hipStream_t s, double alg_k) {
     ProfScope prof(BN == 64 ? "conv_nhwc_f32_mfma<128,64,64,32>/splitk" : "conv_nhwc_f32_mfma<128,128,64,64>/splitk",
                    2.0 * m_part * p.Cout * alg_k,
                    4.0 * (m_part * p.stride * p.stride * p.C + (double)p.n_chunks * BK * p.Cout + m_part * p.Cout), s);
-    hipLaunchKernelGGL((conv_nhwc_f32_mfma<BM, BN, WM, WN, VARIANT, RAGGED, true>),
+    hipLaunchKernelGGL((conv_nhwc_f32_mfma<BN, RAGGED, true, false>),
                        dim3(q.n_mblocks * q.n_nblocks - q.tile_begin, q.k_split), dim3(256), lds, s, q);
   }
   ProfScope prof("conv_splitk_reduce", 0.0, 4.0 * m_part * p.Cout * (q.k_split + 1), s);
@@ -610,31 +417,21 @@ static int launch_splitk(const ConvParams& p, hipStream_t s, double alg_k) {
   return MP_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int VARIANT, bool RAGGED = false, bool AHALF = false>
+template <int BN, bool RAGGED = false, bool AHALF = false>
 static int launch(const ConvParams& p, hipStream_t s, double alg_k, int n_tiles_main = 0) {
   ConvParams q = p;
-  q.n_mblocks = ceil_div(p.M, BM);
+  q.n_mblocks = ceil_div(p.M, CONV_BM);
   q.n_nblocks = ceil_div(p.Cout, BN);
-  constexpr int NBUF = 2;
-  constexpr int LDT = LDS_LD;
-  // MP_CONV_LDS_PAD_KB (tuning experiment): extra, unused LDS per workgroup -- e.g. 30 forces ONE workgroup per CU, which separates the
-  // main loop's own efficiency from the interplay of two co-resident workgroups (scripts/conv_slope.py)
-  static const size_t lds_pad = getenv("MP_CONV_LDS_PAD_KB") ? (size_t)atoi(getenv("MP_CONV_LDS_PAD_KB")) * 1024 : 0;
-  const size_t lds = (size_t)(NBUF * BM * LDT + NBUF * BN * LDT) * sizeof(float) + BM * sizeof(int) + lds_pad;
+  const size_t lds = conv_lds_bytes(BN);
   static bool attr_set = false;
   if (!attr_set) {
-    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_nhwc_f32_mfma<BM, BN, WM, WN, VARIANT, RAGGED, false, AHALF>,
+    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_nhwc_f32_mfma<BN, RAGGED, false, AHALF>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
   // n_tiles_main > 0: only the first n_tiles_main tiles (whole rounds of resident workgroups); a split-K launch covers the rest
   const int n_tiles = n_tiles_main > 0 ? n_tiles_main : q.n_mblocks * q.n_nblocks;
-  const double m_here = n_tiles_main > 0 ? (double)(n_tiles_main / q.n_nblocks) * BM : (double)p.M;
-  dim3 grid(n_tiles);
-  if constexpr ((VARIANT & 16384) != 0) {   // persistent: one workgroup per resident slot, each walks its share of the tiles
-    q.k_split = n_tiles;
-    grid = dim3(std::min(n_tiles, g_resident_workgroups > 0 ? g_resident_workgroups : 512));
-  }
+  const double m_here = n_tiles_main > 0 ? (double)(n_tiles_main / q.n_nblocks) * CONV_BM : (double)p.M;
   // algorithmic work of this launch: 2*MACs over the REAL (unpadded) reduction length; bytes = input + weights + output once
   static const bool detail = getenv("MP_PROF_DETAIL") != nullptr;  // tuning aid: one profiler row per layer shape
   const char* pname = BN == 64 ? "conv_nhwc_f32_mfma<128,64,64,32>" : "conv_nhwc_f32_mfma<128,128,64,64>";
@@ -649,7 +446,7 @@ static int launch(const ConvParams& p, hipStream_t s, double alg_k, int n_tiles_
   }
   ProfScope prof(pname, 2.0 * m_here * p.Cout * alg_k,
                  (AHALF ? 2.0 : 4.0) * m_here * p.stride * p.stride * p.C + 4.0 * ((double)p.n_chunks * BK * p.Cout + m_here * p.Cout), s);
-  hipLaunchKernelGGL((conv_nhwc_f32_mfma<BM, BN, WM, WN, VARIANT, RAGGED, false, AHALF>), grid, dim3(256), lds, s, q);
+  hipLaunchKernelGGL((conv_nhwc_f32_mfma<BN, RAGGED, false, AHALF>), dim3(n_tiles), dim3(256), lds, s, q);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
@@ -821,11 +618,10 @@ extern "C" int mp_conv2d_nhwc(const mp_conv_desc* d, mp_stream stream) {
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   const double alg_k = (double)d->KH * d->KW * (d->c_real > 0 ? d->c_real : d->C);
-  static const int variant = getenv("MP_CONV_VARIANT") ? atoi(getenv("MP_CONV_VARIANT")) : 8449;  // default: buffer loads, LDS store under the 3rd of 4 MFMA groups; others = A/B timing
   const bool small = conv_bn_tile(d->Cout) == 64;
   if (d->x_f16) {   // half-precision input (the stems of the "fp16 renders" mode): single-pass launches of the 128x64 tile only
     MP_REQUIRE(small, "mp_conv2d_nhwc: x_f16 is implemented for Cout <= 64 (the stem convolutions), got Cout = %d", d->Cout);
-    return p.run % BK != 0 ? launch<128, 64, 64, 32, 8449, true, true>(p, s, alg_k) : launch<128, 64, 64, 32, 8449, false, true>(p, s, alg_k);
+    return p.run % BK != 0 ? launch<64, true, true>(p, s, alg_k) : launch<64, false, true>(p, s, alg_k);
   }
   static const int splitk_on = getenv("MP_CONV_SPLITK") ? atoi(getenv("MP_CONV_SPLITK")) : 1;
   static const int tail_on = getenv("MP_CONV_TAIL") ? atoi(getenv("MP_CONV_TAIL")) : 1;
@@ -835,55 +631,30 @@ extern "C" int mp_conv2d_nhwc(const mp_conv_desc* d, mp_stream stream) {
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     resident = 2 * n_cu;
-    g_resident_workgroups = resident;
   }
   const ConvPlan plan = plan_conv(p, small, d->d_splitk_ws ? d->splitk_ws_floats : 0, resident, splitk_on != 0, tail_on != 0);
   if (plan.mode == 1) {  // small grid: every tile split along K
     p.chunks_per_split = plan.chunks_per_split;
     p.k_split = plan.k_split;
     p.partial = d->d_splitk_ws;
-    if (p.run % BK != 0) return small ? launch_splitk<128, 64, 64, 32, 8193, true>(p, s, alg_k) : launch_splitk<128, 128, 64, 64, 8193, true>(p, s, alg_k);
-    return small ? launch_splitk<128, 64, 64, 32, 8193>(p, s, alg_k) : launch_splitk<128, 128, 64, 64, 8193>(p, s, alg_k);
+    if (p.run % BK != 0) return small ? launch_splitk<64, true>(p, s, alg_k) : launch_splitk<128, true>(p, s, alg_k);
+    return small ? launch_splitk<64>(p, s, alg_k) : launch_splitk<128>(p, s, alg_k);
   }
-  // The product library holds ONE schedule (8449).  The alternatives measured against it on the MI355X -- persistent workgroups (24833),
-  // the LDS-transposed 16-byte epilogue (73985), both (90369), 64-bit global_load addressing (257): all bit-identical, all within +-1 %
-  // (profiles/r03_conv_ab_epilogue_persistent.txt) -- are compiled only into MP_CONV_EXPERIMENTS builds (scripts/microbench).
-#ifdef MP_CONV_EXPERIMENTS
-  const bool vec = (variant & 65536) != 0;   // LDS-transposed 16-byte epilogue (A/B against the dword epilogue)
-#else
-  (void)variant;
-#endif
+  // One schedule per pass (conv_nhwc_f32_mfma); its measured alternatives are recorded in profiles/r03_conv_ab_epilogue_persistent.txt
+  // and docs/history.md section 3.1.
   if (plan.mode == 2) {  // whole rounds single-pass, the tiles of the half-empty last round split along K
-    int rc2;
-#ifdef MP_CONV_EXPERIMENTS
-    if (vec) rc2 = small ? launch<128, 64, 64, 32, 73985>(p, s, alg_k, plan.n_main) : launch<128, 128, 64, 64, 73985>(p, s, alg_k, plan.n_main);
-    else
-#endif
-    rc2 = small ? launch<128, 64, 64, 32, 8449>(p, s, alg_k, plan.n_main) : launch<128, 128, 64, 64, 8449>(p, s, alg_k, plan.n_main);
+    const int rc2 = small ? launch<64>(p, s, alg_k, plan.n_main) : launch<128>(p, s, alg_k, plan.n_main);
     if (rc2) return rc2;
     p.chunks_per_split = plan.chunks_per_split;
     p.k_split = plan.k_split;
     p.partial = d->d_splitk_ws;
     p.tile_begin = plan.n_main;
     p.m_part_begin = plan.m_begin;
-    return small ? launch_splitk<128, 64, 64, 32, 8193>(p, s, alg_k) : launch_splitk<128, 128, 64, 64, 8193>(p, s, alg_k);
+    return small ? launch_splitk<64>(p, s, alg_k) : launch_splitk<128>(p, s, alg_k);
   }
-  if (p.run % BK != 0) {  // ragged K (stems): per-lane K bookkeeping
-#ifdef MP_CONV_EXPERIMENTS
-    if (vec) return small ? launch<128, 64, 64, 32, 73985, true>(p, s, alg_k) : launch<128, 128, 64, 64, 73985, true>(p, s, alg_k);
-#endif
-    return small ? launch<128, 64, 64, 32, 8449, true>(p, s, alg_k) : launch<128, 128, 64, 64, 8449, true>(p, s, alg_k);
-  }
-#ifdef MP_CONV_EXPERIMENTS
-  switch (variant) {  // every variant computes the same result; the others are kept for A/B timing
-    case 257: return small ? launch<128, 64, 64, 32, 257>(p, s, alg_k) : launch<128, 128, 64, 64, 257>(p, s, alg_k);  // the default schedule with global_load (64-bit lane addresses)
-    case 24833: return small ? launch<128, 64, 64, 32, 24833>(p, s, alg_k) : launch<128, 128, 64, 64, 24833>(p, s, alg_k);  // 8449 with persistent workgroups
-    case 73985: return small ? launch<128, 64, 64, 32, 73985>(p, s, alg_k) : launch<128, 128, 64, 64, 73985>(p, s, alg_k);  // 8449 + 16-byte epilogue
-    case 90369: return small ? launch<128, 64, 64, 32, 90369>(p, s, alg_k) : launch<128, 128, 64, 64, 90369>(p, s, alg_k);  // persistent + 16-byte epilogue
-    default: break;
-  }
-#endif
-  return small ? launch<128, 64, 64, 32, 8449>(p, s, alg_k) : launch<128, 128, 64, 64, 8449>(p, s, alg_k);
+  if (p.run % BK != 0)  // ragged K (stems): per-lane K bookkeeping
+    return small ? launch<64, true>(p, s, alg_k) : launch<128, true>(p, s, alg_k);
+  return small ? launch<64>(p, s, alg_k) : launch<128>(p, s, alg_k);
 }
 
 extern "C" int mp_conv2d_plan(const mp_conv_desc* d, int n_cu, int32_t* out5) {

@@ -17,9 +17,9 @@ def short_name(k: str) -> str:
         return k
     name, targs = m.group(1), (m.group(3) or "")
     args = [a.strip() for a in targs.split(",")] if targs else []
-    if name == "conv_nhwc_f32_mfma" and len(args) >= 4:
-        s = f"{name}<{','.join(args[:4])}>"
-        if len(args) >= 7 and args[6] in ("true", "1"):
+    if name == "conv_nhwc_f32_mfma" and len(args) >= 4:   # <BN, RAGGED, SPLITK, AHALF>
+        s = f"{name}<128,{args[0]},64,{int(args[0]) // 2}>"
+        if args[2] in ("true", "1"):
             s += "/splitk"
         return s
     if name == "conv3x3_wino_f32":
