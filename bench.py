@@ -10,14 +10,18 @@ Default workload = BASELINE.json configs[1]: megapose-1.0-RGB structure (coarse 
 N > 1: `python bench.py --gpus N` re-launches itself through `python -m torch.distributed.run` (one rank per GPU, backend
 "nccl" = RCCL) unless it already runs under torchrun (WORLD_SIZE set).  Weak scaling: config 2 puts one object x 576
 hypotheses per GPU; rows are sharded rank::world and the packed logits/poses are all-gathered once per stage.  Beside it the line then
-carries `strong_scaling_config4` (BASELINE configs[3]: 64 detections, K = 5, the same total work at every N), `rccl` (world size, 3
-gathers per step, final poses bit-identical across ranks: asserted) and `per_rank` diagnostics.
+carries `rccl` (world size, 3 gathers per step) and, with `--full`, `strong_scaling_config4` (BASELINE configs[3]: 64 detections, K = 5,
+the same total work at every N), `rccl.final_poses_identical_across_ranks` (asserted) and `per_rank` diagnostics.
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus
   "roofline":     the dominant kernel (conv3x3_wino_bf16x9: the fused Winograd 3x3 convolution on the bf16 MFMA through exact operand
                   pieces, csrc/conv_wino_bf16.hip) measured live with HIP events on its launch stream: executed bf16 rate / 2.5 PFLOP/s
+and, with `--full` only (a plain run sets up, warms up, times the steps, dumps and prints; everything below runs after the timed steps):
+  "stage_s":      the per-stage split from one extra fenced call, and the `roofline.clock` probe of the shader clock
+  "extras":       secondary lines (released K = 1 / 5, other modes and precisions, config 4, the other backbone, emulated ranks of 8)
   "cpu_baseline": the oracle ("port" of the reference's CPU path) timed on this box's host cores on a bounded sample
-  "parity":       the rows the cpu_baseline leg computed, compared with the same rows of the timed GPU call (N = 1).
+  "parity":       the rows the cpu_baseline leg computed, compared with the same rows of the timed GPU call (N = 1)
+  N > 1:          `strong_scaling_config4`, `per_rank` and the check that the final poses are bit-identical across ranks.
 """
 import argparse
 import json
@@ -541,10 +545,14 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5), help="BASELINE.json configuration (1-based, as SURVEY.md 8d numbers them); 2 = headline")
     ap.add_argument("--k-hyp", type=int, default=0, help="n_pose_hypotheses (default: 576 for configs 2/3, 5 for configs 4/5)")
     ap.add_argument("--backbone", default="vanilla_resnet34")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the stage split and clock probe, the secondary "
+                         "measurements, the CPU baseline with its parity check and, N > 1, the cross-rank checks and the strong-scaling companion")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--cpu-thread-sweep", default="", help="comma list of thread counts: time the cpu_baseline sample at each, write "
                                                           "gpurun_out/cpu_thread_sweep.json and exit")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (faithful K=1/K=5 configs, other backbone / modes)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary measurements (faithful K=1/K=5 configs, other backbone / modes)")
     ap.add_argument("--emulate-rank-of", type=int, default=0, metavar="N",
                     help="one GPU only, never `value`: run ONE rank's share of the N-GPU workload of --config (rows rank::N, gathers stubbed) and "
                          "the whole workload, print projected_speedup = T(one GPU, whole) / T(rank share) with the per-stage split, and exit")
@@ -642,8 +650,9 @@ def main():
         dt = t.item()
     assert len(final) == n_obj and torch.isfinite(final.poses).all()
     poses_identical = None
-    if world > 1:   # every rank must hold the SAME final table: identical gathered inputs -> identical top-K / arg-max -> identical poses, bit for bit
+    if world > 1:
         assert torch.distributed.get_world_size() == a.gpus, (torch.distributed.get_world_size(), a.gpus)
+    if world > 1 and a.full:   # every rank must hold the SAME final table: identical gathered inputs -> identical top-K / arg-max -> identical poses, bit for bit
         mine_p = final.poses.detach().to(torch.float32).contiguous()
         if torch.distributed.get_backend() == "gloo":
             mine_p = mine_p.cpu()
@@ -652,7 +661,7 @@ def main():
         poses_identical = bool(all(torch.equal(all_p[0], q) for q in all_p[1:]))
         assert poses_identical, "final poses differ between ranks"
     per_rank = None
-    if world > 1:   # one diagnostic row per rank, so that the first multi-GPU run says where each rank's time went
+    if world > 1 and a.full:   # one diagnostic row per rank, so that the first multi-GPU run says where each rank's time went
         mine = {"rank": rank, "timed_region_ms_per_step": dt_local / a.steps * 1e3, "all_gather_ms_per_step": gather_ms / a.steps,
                 "host_topk_ms_per_step": host_topk_ms,
                 "kernel_ms_per_step": {k: round(v["ms"] / a.steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])[:6]}}
@@ -661,13 +670,15 @@ def main():
             torch.distributed.all_gather_object(per_rank, mine)
         except Exception as e:  # noqa: BLE001  (diagnostics must never take the measurement down)
             per_rank = [{"error": f"{type(e).__name__}: {e}"[:200]}]
-    # stage times from HIP events: one extra, untimed call with cuda_timer=True (each stage fenced, DEVICE render/model times)
-    _, extra_t = step(cuda_timer=True)
-    # sustained shader clock of THIS box under fp32-MFMA load (boxes of one pool differ by ~10 %): context for `roofline.frac`, not part of it
-    clk = eng.clock_probe(30.0)
+    extra_t, clk = None, None
+    if a.full:
+        # stage times from HIP events: one extra, untimed call with cuda_timer=True (each stage fenced, DEVICE render/model times)
+        _, extra_t = step(cuda_timer=True)
+        # sustained shader clock of THIS box under fp32-MFMA load (boxes of one pool differ by ~10 %): context for `roofline.frac`, not part of it
+        clk = eng.clock_probe(30.0)
 
     strong = None
-    if world > 1 and a.config == 2 and not a.no_extras:
+    if a.full and world > 1 and a.config == 2 and not a.no_extras:
         strong = strong_scaling_companion(world, rank, a.backbone, min(a.steps, 3))
 
     rc = 0
@@ -711,7 +722,7 @@ def main():
         dom_mhz = wb_mhz if dom_name.startswith("conv3x3_wino_bf16") and wb_mhz > 0 else conv_mhz
         rows_per_obj = N_HYP + k_hyp * N_ITERS + k_hyp
         views_per_obj = N_HYP + 4 * k_hyp * N_ITERS + k_hyp
-        sd = {s: extra_t[s]["data"] for s in ("coarse", "refiner", "scoring")}
+        sd = {s: extra_t[s]["data"] for s in ("coarse", "refiner", "scoring")} if extra_t is not None else None
         out = {
             "metric": METRIC, "value": n_obj * N_HYP * a.steps / dt, "unit": "pose-hypotheses/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -740,20 +751,22 @@ def main():
                          "shader_clock_mhz": dom_mhz,
                          "frac_at_measured_clock": achieved / (dom["peak_tflops"] * dom_mhz / 2400.0) if dom_mhz > 0 else None,
                          "k_loop_cycles_per_16_channel_step": wb_cps if dom_name.startswith("conv3x3_wino_bf16") else None,
-                         "clock": {"bf16_winograd_k_loops_mhz": wb_mhz, "fp32_direct_kernels_mhz": conv_mhz, "probe_fp32_mfma_mhz": clk["shader_mhz"],
-                                   "probe_fp32_mfma_tflops": clk["mfma_tflops"],
+                         "clock": {"bf16_winograd_k_loops_mhz": wb_mhz, "fp32_direct_kernels_mhz": conv_mhz,
+                                   "probe_fp32_mfma_mhz": clk["shader_mhz"] if clk else None,
+                                   "probe_fp32_mfma_tflops": clk["mfma_tflops"] if clk else None,
                                    "note": "s_memtime / s_memrealtime accumulated INSIDE the kernels of the timed steps (every 64th workgroup): the chip "
                                            "clocks to its power budget, and bf16 MFMA work on real operands runs well below the 2400 MHz `peak` is "
-                                           "priced at; probe_* = a register-only fp32 MFMA loop right after the timed region (mp_clock_probe)"}},
+                                           "priced at; probe_* (--full) = a register-only fp32 MFMA loop right after the timed region (mp_clock_probe)"}},
             "raster": None if rb is None else {"bound": "hbm", "kernel": rb_name, "achieved": rb["bytes"] / (rb["ms"] * 1e-3) / 1e9,
                                                "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": rb["bytes"] / (rb["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBPS,
                                                "traffic": r_traffic, "alg_bytes_per_launch": rb["bytes"] / rb["launches"],
                                                "avg_launch_ms": rb["ms"] / rb["launches"], "ms_per_step": rb["ms"] / a.steps,
                                                "parts_ms_per_step": rb["parts_ms_per_step"]},
             "kernel_ms_per_step": kernel_ms,
-            "stage_s": {"source": "HIP events, one extra call with cuda_timer=True (stages fenced)",
-                        **{s: {"time": sd[s]["time"], "render_time": sd[s]["render_time"], "model_time": sd[s]["model_time"]} for s in sd},
-                        "total": extra_t["time"]},
+            **({} if sd is None else {"stage_s": {"source": "HIP events, one extra call with cuda_timer=True (stages fenced)",
+                                                  **{s: {"time": sd[s]["time"], "render_time": sd[s]["render_time"], "model_time": sd[s]["model_time"]}
+                                                     for s in sd},
+                                                  "total": extra_t["time"]}}),
         }
         if stem_wgs > 0:
             # K steps of the stem's slice walk (csrc/conv_stem.hip stem::n_steps): short walk over the dense walk, for this workload's
@@ -772,19 +785,21 @@ def main():
                        "projected_share_at_8_gpus_same_total_work": host_topk_ms / (dt / a.steps * 1e3 / 8.0 + host_topk_ms * 7.0 / 8.0),
                        "note": "every rank repeats the pandas top-K / arg-max on the gathered table (DESIGN.md 5); if the projected share at 8 "
                                "GPUs exceeds 0.05 move it to rank 0 + broadcast (measured 0.044 in round 5: left replicated)"}
-        if world > 1:
+        if per_rank is not None:
             out["per_rank"] = per_rank
+        if world > 1:
             out["rccl"] = {"backend": torch.distributed.get_backend(), "world_size": torch.distributed.get_world_size(),
                            "all_gathers_per_step": gather_calls / a.steps, "all_gather_bytes_per_step": gather_bytes / a.steps,
                            "all_gather_ms_per_step": gather_ms / a.steps}
             # one all-gather per stage (coarse | refiner, all iterations packed | scoring); config 5 adds none (ICP shards by object)
             assert abs(out["rccl"]["all_gathers_per_step"] - 3.0) < 1e-9, out["rccl"]
-            out["rccl"]["final_poses_identical_across_ranks"] = poses_identical
+            if poses_identical is not None:
+                out["rccl"]["final_poses_identical_across_ranks"] = poses_identical
         if strong is not None:
             out["strong_scaling_config4"] = strong
-        if world == 1 and a.config == 2 and not a.no_extras:
+        if a.full and world == 1 and a.config == 2 and not a.no_extras:
             out["extras"] = extras(est, obs, det, min(a.steps, 3))   # (secondary lines: at most 3 timed calls each)
-        if world == 1 and a.config == 5 and not a.no_extras:   # the "fp16 renders" variant BASELINE.json names for this configuration
+        if a.full and world == 1 and a.config == 5 and not a.no_extras:   # the "fp16 renders" variant BASELINE.json names for this configuration
             try:
                 est.render_dtype = torch.float16
                 step()
@@ -800,7 +815,7 @@ def main():
                 out["extras"] = {"fp16_renders": {"error": f"{type(e).__name__}: {e}"[:300]}}
             finally:
                 est.render_dtype = torch.float32
-        if not a.no_cpu_baseline and world == 1 and a.config == 2 and k_hyp == N_HYP:
+        if a.full and not a.no_cpu_baseline and world == 1 and a.config == 2 and k_hyp == N_HYP:
             cb = cpu_baseline(ds, obs.images, obs.K, det.bboxes)
             out["parity"] = parity_block(cb.pop("_values"), extra)
             # The port is the SLOWER stand-in: the reference's own orchestration (imported from /root/reference, same CNN / rasteriser) ran the

@@ -5,7 +5,7 @@ O=gpurun_out/r4c2
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_stem_records.py tests/test_gpu_refiner_graph.py tests/test_gpu_pipeline.py tests/test_gpu_parity_full_size.py -x -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log
 tail -n 25 $O/pytest.log
-timeout 300 python bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
+timeout 300 python bench.py --steps 5 --warmup 2 --full --no-extras --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r4c2/bench.json"))

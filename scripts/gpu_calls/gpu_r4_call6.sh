@@ -5,7 +5,7 @@ O=gpurun_out/r4c6
 mkdir -p $O
 timeout 600 python -m pytest "tests/test_gpu_pipeline.py::test_bench_multi_rank_code_path_with_two_ranks_on_one_gpu" -x -q -p no:cacheprovider > $O/pytest.log 2>&1; echo "rc=$?" >> $O/pytest.log
 tail -n 15 $O/pytest.log
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "rc=$?" >> $O/bench.err
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r4c6/bench.json"))

@@ -277,7 +277,8 @@ def test_bench_multi_rank_code_path_with_two_ranks_on_one_gpu():
     """The world > 1 path of bench.py (row sharding, the three all-gathers per step, max-over-ranks timing, the per-rank diagnostic rows,
     the host-share estimate) exactly as the driver launches it -- `python -m torch.distributed.run --nproc-per-node 2 ... bench.py
     --gpus 2` -- on the one GPU a test box has: MP_BENCH_SHARED_GPU=1 puts both ranks on GPU 0 and swaps RCCL for gloo (a test rig, not a
-    measurement).  The RCCL variant of the same call is test_bench_self_launches_two_ranks_over_rccl (needs two GPUs)."""
+    measurement).  `--full` adds the cross-rank pose check, the per-rank rows and the strong-scaling companion asserted below.  The RCCL
+    variant of the same call is test_bench_self_launches_two_ranks_over_rccl (needs two GPUs)."""
     import json
     import subprocess
     import sys
@@ -286,7 +287,7 @@ def test_bench_multi_rank_code_path_with_two_ranks_on_one_gpu():
     env = dict(os.environ, MP_BENCH_SHARED_GPU="1")
     port = 29800 + os.getpid() % 1000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(root / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
+           str(root / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=2400, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -302,6 +303,28 @@ def test_bench_multi_rank_code_path_with_two_ranks_on_one_gpu():
     assert sc["pose_hypotheses_per_s"] > 0
     assert [r["rank"] for r in j["per_rank"]] == [0, 1] and all(r["timed_region_ms_per_step"] > 0 for r in j["per_rank"])
     assert 0.0 < j["host"]["replicated_topk_ms_per_step"] < 200.0
+
+
+def test_bench_plain_run_prints_the_headline_line_only(tmp_path):
+    """a plain `python bench.py --gpus 1 --steps N --warmup W` times the steps, writes --dump-outputs and prints the headline line; what
+    runs after the timed steps beyond that (stage split, clock probe, extras, CPU baseline + parity) waits for --full"""
+    import json
+    import subprocess
+    import sys
+
+    root = Path(__file__).resolve().parent.parent
+    p = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["unit"] == "pose-hypotheses/s" and j["higher_is_better"] is True and j["metric"] and j["dtype"].startswith("f32")
+    assert j["steps"] == 1 and j["warmup"] == 1 and j["value"] > 0
+    assert abs(j["value"] - j["config"]["objects"] * 576 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert j["roofline"]["frac"] > 0 and j["roofline"]["clock"]["probe_fp32_mfma_mhz"] is None
+    assert not {"stage_s", "extras", "cpu_baseline", "parity", "vs_cpu_baseline", "cpu_baseline_1thread"} & set(j)
+    assert (tmp_path / "final.poses.npy").is_file()
 
 
 def test_bench_refuses_more_gpus_than_visible():
