@@ -177,6 +177,34 @@ const unsigned char* mp_raster_job_flags(const mp_mesh_db* db, const void* d_wor
 int mp_pack_observation_nhwc4(const float* d_images, int n_im, int C, int H, int W, float* d_out, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Scene rasteriser: replaces Panda3dSceneRenderer.render_scene                           */
+/* (panda3d_renderer/panda3d_scene_renderer.py:298-358, setup_scene :218-236,             */
+/*  render_images :255-272, binary mask :329-335; CameraRenderingData types.py:43-55).    */
+/* Several objects per camera image, depth-tested against each other.                     */
+/* ------------------------------------------------------------------------------------ */
+/* scratch of one mp_raster_render_scene launch with n_objects objects in all (summed over the cameras) at h x w */
+size_t mp_raster_scene_workspace_bytes(const mp_mesh_db* db, int n_objects, int h, int w);
+
+/* Render n_cams cameras; camera c owns the objects [obj_off[c], obj_off[c+1]) (h_obj_off: the same n_cams + 1 offsets on the HOST, for
+ * validation and sizing; obj_off[0] = 0).  Per object o: mesh d_mesh_ids[o], camera-from-object pose d_TCO[o] (float32 [4,4]) and light
+ * rig d_lights[o] (DEVICE array of mp_lights, given in the object's frame: point light l sits at point_dir[l] * 10 * scene radius +
+ * point_offset[l]).  Per camera: d_K[c] ([3,3]) and the scene radius d_radius[c], which replaces the mesh radius in that formula.
+ * Output addressing and values as mp_raster_render with views_per_item = 1: element (camera c, y, x, channel k) at
+ * d_out[c*stride_v + y*stride_y + x*stride_x + k], fp32 only (flags: MP_RASTER_NORMALS / _DEPTH / _NORMALS_GL / _MSAA4).
+ * d_instance (optional, int32 [n_cams][h][w]): the slot, relative to the camera's first object, of the object that owns sample 0 of the
+ * pixel (the sample whose depth the depth channel reports); -1 = background.
+ * Contract: per sample, the coverage and depth rules of mp_raster_render applied to the pieces of ALL objects of the camera, the nearest
+ * piece wins; on exactly equal depth the object listed first wins (draw order under a less-than depth test), within one object the lower
+ * piece id.  Shading once per (pixel, winning piece) with that object's mesh, texture, pose and light rig; 4-sample 8-bit resolve; depth
+ * = metric z of sample 0, 0 for background.  An object with a non-finite pose contributes nothing; a camera with a non-finite K or with
+ * no object renders background.  At most 256 objects per camera, h, w <= 1024. */
+int mp_raster_render_scene(const mp_mesh_db* db, int n_cams, const int32_t* h_obj_off, const int32_t* d_obj_off,
+                           const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K, const float* d_radius,
+                           const mp_lights* d_lights, int h, int w, uint32_t flags, float* d_out, int64_t stride_v, int64_t stride_y,
+                           int64_t stride_x, int c_rgb, int c_normals, int c_depth, int32_t* d_instance, void* d_workspace,
+                           size_t workspace_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Crop: replaces lib3d/cropping.py:113-144 crop_images (torchvision.ops.roi_align,       */
 /* sampling_ratio=4, aligned=False) incl. the RGBD validity rule (:131-142), reading the  */
 /* observation by batch_im_id (no per-row gather, pose_estimator.py:389).                 */

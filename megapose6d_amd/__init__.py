@@ -5,7 +5,7 @@ of the reference's renderer / PosePredictor / PoseEstimator interfaces.  Importi
 first engine call loads `libmp_engine.so` and raises if it is missing (there is no CPU fallback).
 """
 from . import (detector, distributed, engine, icp_refiner, load_model, mask_rcnn, mesh_db, mesh_io, object_dataset, pose_estimator,  # noqa: F401
-               pose_rigid, prediction_runner, renderer, tcoll, types)
+               pose_rigid, prediction_runner, renderer, scene_renderer, tcoll, types)
 from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner  # noqa: F401
 from .mask_rcnn import DetectorMaskRCNN  # noqa: F401
@@ -15,6 +15,8 @@ from .pose_estimator import CoarseRefinePoseEstimator, PoseEstimator  # noqa: F4
 from .pose_rigid import PosePredictor  # noqa: F401
 from .prediction_runner import PredictionRunner  # noqa: F401
 from .renderer import Panda3dBatchRenderer  # noqa: F401
-from .types import BatchRenderOutput, ObservationTensor, Panda3dLightData, PosePredictorOutput  # noqa: F401
+from .scene_renderer import Panda3dSceneRenderer  # noqa: F401
+from .types import (BatchRenderOutput, CameraRenderingData, ObservationTensor, Panda3dCameraData, Panda3dLightData,  # noqa: F401
+                    Panda3dObjectData, PosePredictorOutput)
 
 __version__ = "0.1.0"

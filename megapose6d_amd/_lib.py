@@ -107,6 +107,9 @@ SIGNATURES = {
                                    _vp, _sz, _vp, _i, _i, _i, _i, _i, _vp, _vp, _u32, _vp, _i, _vp]),
     "mp_raster_job_flags": (_vp, [_vp, _vp, _i, _i, _i]),
     "mp_pack_observation_nhwc4": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "mp_raster_scene_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "mp_raster_render_scene": (_i, [_vp, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _u32, _vp, _i64, _i64, _i64, _i, _i,
+                                    _i, _vp, _vp, _sz, _vp]),
     "mp_crop_roi_align": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i64, _i64, _i64, _i, _vp]),
     "mp_normalize_depth": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _vp, _i, _vp]),
     "mp_normalize_depth_f16": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _vp, _i, _vp]),

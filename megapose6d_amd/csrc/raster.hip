@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "crop_device.h"
+#include "raster_bin.h"
 #include "raster_core.h"
 
 namespace mp {
@@ -61,16 +62,8 @@ struct CropArgs {
   int C, H, W, c0, nhwc4;
 };
 
-// per-view workspace, in ints (every section starts 16-byte aligned):
-//   [hdr HDR_INTS][tile_off n_tiles + 1][tile_off_l n_tiles + 1][list_l: cap_large piece indices][list: cap_list TileRec records of 8 ints]
-// tile_off / list: the binned (small) pieces of every tile as 32-byte records; tile_off_l / list_l: the indices of the LARGE pieces
-// (too big for the 32-bit edge functions or touching > LARGE_TILES tiles) per tile they can own a sample in -- recomputed from the mesh
-// by the tile kernel, but only by the tiles they touch.
-struct BinLayout {
-  long long view_ints;
-  int n_tiles, tiles_x, tiles_y, cap_list, cap_large, max_faces;
-  int off_tl, off_large, off_list;   // int offsets of tile_off_l / list_l / list inside a view's block
-};
+static_assert(HDR_INTS == RASTER_BIN_HDR_INTS, "raster_bin.h states the view header size");
+// per-view workspace layout: BinLayout (raster_bin.h)
 
 __device__ __forceinline__ void tile_range(const Piece& p, int ns, int w, int h, int& tx0, int& ty0, int& tx1, int& ty1) {
   int x0, y0, x1, y1;
@@ -1348,3 +1341,27 @@ extern "C" int mp_raster_render_xrec(const mp_mesh_db* db, const int32_t* d_mesh
                             stride_v, views_per_item, stride_view, stride_y, stride_x, c_rgb, c_normals, c_depth, d_ws, ws_bytes, stream, crop,
                             f32_mask, d_tCR, depth_mode);
 }
+
+// ---- private interface for the other rasteriser translation units (raster_bin.h) -------------------------------------------------------
+namespace mp {
+
+BinLayout raster_bin_layout(const mp_mesh_db* db, int h, int w) { return bin_layout(db, h, w); }
+const rc::MeshRef* raster_db_meshes(const mp_mesh_db* db) { return db->d_meshes; }
+const rc::TexRef* raster_db_textures(const mp_mesh_db* db) { return db->d_texs; }
+
+int raster_bin_launch(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K, int n_views, int h, int w,
+                      int ns, int* d_ws, const BinLayout& lay, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    MP_CHECK_HIP(hipFuncSetAttribute((const void*)raster_bin, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    attr_set = true;
+  }
+  const size_t lds = (size_t)2 * lay.n_tiles * sizeof(int);
+  ProfScope prof("raster_bin", 0.0, (double)n_views * (12.0 * db->max_faces + 12.0 * db->max_verts + 4.0 * lay.n_tiles), stream);
+  hipLaunchKernelGGL(raster_bin, dim3(n_views), dim3(BIN_THREADS), lds, stream, db->d_meshes, d_mesh_ids, d_TCO, d_K, h, w, ns, d_ws, lay,
+                     (int*)nullptr, (unsigned char*)nullptr);
+  MP_CHECK_HIP(hipGetLastError());
+  return MP_OK;
+}
+
+}  // namespace mp

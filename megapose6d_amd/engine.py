@@ -243,6 +243,35 @@ def raster_render(db: MeshDB, mesh_ids: torch.Tensor, TCO: torch.Tensor, K: torc
                                c_normals, c_depth, ws.data_ptr(), ws.numel(), _stream()))
 
 
+def lights_array(rigs: Sequence[Lights], device) -> torch.Tensor:
+    """Per-object light rigs as the device array of mp_lights that raster_render_scene reads (raw bytes)."""
+    arr = (Lights * max(len(rigs), 1))(*rigs)
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
+def raster_render_scene(db: MeshDB, obj_off: Sequence[int], mesh_ids: torch.Tensor, TCO: torch.Tensor, K: torch.Tensor, radius: torch.Tensor,
+                        lights: torch.Tensor, h: int, w: int, flags: int, out: Optional[torch.Tensor], stride_v: int, stride_y: int,
+                        stride_x: int, c_rgb: int, c_normals: int, c_depth: int, instance: Optional[torch.Tensor] = None) -> None:
+    """Render n_cams = len(obj_off) - 1 scenes (mp_raster_render_scene): camera c draws the objects obj_off[c] .. obj_off[c+1] - 1 of
+    mesh_ids [n_obj] / TCO [n_obj,4,4] / lights (lights_array of n_obj object-frame rigs), with K [n_cams,3,3] and scene radius
+    radius [n_cams], into the float32 `out` at the given element strides; `instance` (int32 [n_cams,h,w]) receives the object slot of
+    sample 0 (-1 = background)."""
+    lib = _lib.load()
+    n_cams = len(obj_off) - 1
+    off = (C.c_int32 * len(obj_off))(*[int(v) for v in obj_off])
+    dev = K.device
+    d_off = torch.tensor([int(v) for v in obj_off], dtype=torch.int32, device=dev)
+    mesh_ids, TCO, K, radius = _dev_i32(mesh_ids), _dev_f32(TCO), _dev_f32(K), _dev_f32(radius)
+    assert out is None or (out.dtype == torch.float32 and out.is_cuda)
+    assert instance is None or (instance.dtype == torch.int32 and instance.is_cuda and instance.is_contiguous() and instance.numel() >= n_cams * h * w)
+    n_obj = int(obj_off[-1])
+    need = lib.mp_raster_scene_workspace_bytes(db.handle, n_obj, h, w)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    check(lib.mp_raster_render_scene(db.handle, n_cams, off, d_off.data_ptr(), mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(),
+                                     radius.data_ptr(), lights.data_ptr(), h, w, flags, _ptr(out), stride_v, stride_y, stride_x, c_rgb,
+                                     c_normals, c_depth, _ptr(instance), ws.data_ptr(), ws.numel(), _stream()))
+
+
 def raster_job_flags(db: MeshDB, n_views: int, h: int, w: int, device, slot: int = 0) -> int:
     """Device address of the job flags the LAST compacted raster launch on this database's workspace (`slot`) wrote: one byte per
     (item, 8x8-pixel tile), 0 = no view of the item reaches the tile (mp_raster_job_flags).  Valid on the same stream until the next

@@ -3,6 +3,7 @@
 ObservationTensor / InferenceConfig / assert_detections_valid: src/megapose/inference/types.py:77-235
 BatchRenderOutput: src/megapose/panda3d_renderer/panda3d_batch_renderer.py:61-71
 Panda3dLightData: src/megapose/panda3d_renderer/types.py:104-114; make_scene_lights: panda3d_scene_renderer.py:104-136
+CameraRenderingData / Panda3dCameraData / Panda3dObjectData: src/megapose/panda3d_renderer/types.py:43-125
 PosePredictorOutput: src/megapose/models/pose_rigid.py:50-66
 """
 from __future__ import annotations
@@ -196,6 +197,56 @@ def resolve_light_position(positioning_function: Callable) -> Tuple[Tuple[float,
         if abs(a[k] * 4.0 + b[k] - pts[2][k]) > 1e-9 * (1.0 + abs(pts[2][k])):
             raise NotImplementedError("positioning_function is not affine in the bounding radius")
     return a, b
+
+
+# identity pose, the default TWC / TWO of the scene data classes (reference: Transform((0, 0, 0, 1), (0, 0, 0)))
+IDENTITY_POSE = ((1.0, 0.0, 0.0, 0.0), (0.0, 1.0, 0.0, 0.0), (0.0, 0.0, 1.0, 0.0), (0.0, 0.0, 0.0, 1.0))
+
+
+def pose_matrix(T: Any) -> np.ndarray:
+    """4x4 float64 matrix of a pose given as a 4x4 array-like or as an object with toHomogeneousMatrix() (the reference's Transform)."""
+    if hasattr(T, "toHomogeneousMatrix"):
+        T = T.toHomogeneousMatrix()
+    if isinstance(T, torch.Tensor):
+        T = T.detach().cpu().numpy()
+    M = np.asarray(T, dtype=np.float64)
+    if M.shape != (4, 4):
+        raise ValueError(f"a pose must be a 4x4 matrix, got shape {M.shape}")
+    return M
+
+
+@dataclass
+class CameraRenderingData:
+    """reference panda3d_renderer/types.py:43-55.  rgb: (h, w, 3) uint8; normals: (h, w, 3) uint8; depth: (h, w, 1) float32;
+    binary_mask: (h, w) bool."""
+    rgb: np.ndarray
+    normals: Optional[np.ndarray] = None
+    depth: Optional[np.ndarray] = None
+    binary_mask: Optional[np.ndarray] = None
+
+
+@dataclass
+class Panda3dCameraData:
+    """reference panda3d_renderer/types.py:58-101.  TWC: world-from-camera pose (OpenCV camera axes), 4x4 array-like or Transform."""
+    K: np.ndarray
+    resolution: Tuple[int, int]
+    TWC: Any = IDENTITY_POSE
+    z_near: float = 0.1
+    z_far: float = 10
+    node_name: str = "camera"
+    positioning_function: Optional[Callable] = None
+
+
+@dataclass
+class Panda3dObjectData:
+    """reference panda3d_renderer/types.py:117-125.  TWO: world-from-object pose, 4x4 array-like or Transform."""
+    label: str
+    TWO: Any = IDENTITY_POSE
+    color: Optional[RgbaColor] = None
+    material: Optional[Any] = None
+    remove_mesh_material: bool = False
+    scale: float = 1
+    positioning_function: Optional[Callable] = None
 
 
 @dataclass
