@@ -473,6 +473,43 @@ int mp_pose_update(const float* d_TCO /*[b,4,4]*/, const float* d_K_crop /*[b,3,
                    float* d_TCO_out, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Pose errors (evaluation): the arithmetic between two pose tables and a mesh, fused so    */
+/* that no point pair is stored (csrc/pose_error.hip; contract in csrc/pose_error_core.h).  */
+/* Points are addressed as in mp_pose_prepare: row i reads mesh d_mesh_ids[i] of d_points   */
+/* [n_mesh, n_pts_stride, 3] and averages its first min(d_n_points[mesh], n_pts) points     */
+/* (d_n_points NULL: all n_pts), so BatchedMeshes.points with mesh ids and a per-row        */
+/* [b,N,3] tensor (ids 0..b-1) both fit.  Outputs sized by n_pts have a zero / -1 tail.     */
+/* A pose with a non-finite entry gives NaN errors and index -1.  split = 0 picks the work  */
+/* split per row; > 0 forces it (any value gives the same bits).                            */
+/* ------------------------------------------------------------------------------------ */
+#define MP_POSE_ERROR_MEAN 0
+#define MP_POSE_ERROR_MAX 1
+/* bytes of device scratch any of the launches below needs for b rows (pass S_max = 1 for the nearest-neighbour launch alone). */
+size_t mp_pose_error_workspace_bytes(int b, int n_pts, int S_max);
+/* evaluation/utils.py:175-238 mssd_torch, lib3d/distances.py:26-41 dists_add (S_max = 1) and dists_add_symmetries: errs[i,s] =
+   reduce_p |T_gt_s p - T_pred p| with reduce = mean (the reference) or max (BOP's MSSD), idx = argmin_s (lowest index on a tie).
+   Composed form: d_symmetries [n_mesh,S_max,4,4] identity-padded, d_n_sym [n_mesh] (NULL: S_max), d_T_gt [b,4,4], T_gt_s = T_gt
+   Sym_s.  Explicit form (d_symmetries NULL): d_T_gt holds the candidates [b,S_max,4,4].  Optional (NULL to skip): d_err_alt [b] the
+   minimum of the OTHER reduction, d_T_gt_sym [b,4,4], d_errs [b,S_max] (+inf beyond n_sym), d_diffs [b,n_pts,3] = T_gt_idx p -
+   T_pred p.  S_max <= 512. */
+int mp_pose_error_sym(const float* d_T_pred /*[b,4,4]*/, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
+                      const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids /*[b]*/, const int32_t* d_n_points, int n_pts,
+                      int b, int reduce, int split, float* d_err /*[b]*/, float* d_err_alt, int32_t* d_idx /*[b]*/, float* d_T_gt_sym,
+                      float* d_errs, float* d_diffs, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* lib3d/distances.py:44-53 dists_add_symmetric (ADD-S): for every ground-truth point j, assign[i,j] = argmin_k |T_gt p_j - T_pred
+   p_k|^2 over the row's valid points (lowest k on a tie), d_diffs [b,n_pts,3] = T_gt p_j - T_pred p_assign, d_assign [b,n_pts]
+   (both optional), d_mean / d_max [b] of the norms.  b * n_pts^2 pairs, none stored. */
+int mp_pose_error_nn(const float* d_T_pred /*[b,4,4]*/, const float* d_T_gt /*[b,4,4]*/, const float* d_points, int n_pts_stride,
+                     const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts, int b, int split, float* d_diffs, int32_t* d_assign,
+                     float* d_mean /*[b]*/, float* d_max /*[b]*/, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* evaluation/utils.py:50-66 compute_pose_error (trans_err = |t_a - t_b|, rot_err_deg = angle of R_b R_a^T, by atan2 and not acos)
+   and, when d_proj_err is given, evaluation/meters/modelnet_meters.py:75-79: the mean over the valid points of the 2D distance
+   between project_points (lib3d/camera_geometry.py:26-37) of the two poses with d_K [b,3,3].  Without it K / points may be NULL. */
+int mp_pose_error_rigid(const float* d_T_a /*[b,4,4]*/, const float* d_T_b /*[b,4,4]*/, int b, const float* d_K, const float* d_points,
+                        int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts, float* d_trans_err /*[b]*/,
+                        float* d_rot_err_deg /*[b]*/, float* d_proj_err, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

@@ -4,8 +4,8 @@ Only what the hot path needs: the HIP/C-ABI engine (`csrc/
 of the reference's renderer / PosePredictor / PoseEstimator interfaces.  Importing the package never touches the GPU; the
 first engine call loads `libmp_engine.so` and raises if it is missing (there is no CPU fallback).
 """
-from . import (detector, distributed, engine, icp_refiner, load_model, mask_rcnn, mesh_db, mesh_io, object_dataset, pose_estimator,  # noqa: F401
-               pose_rigid, prediction_runner, renderer, scene_renderer, tcoll, types)
+from . import (detector, distances, distributed, engine, evaluation, icp_refiner, load_model, mask_rcnn, mesh_db, mesh_io, object_dataset, pose_estimator,  # noqa: F401
+               pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, types)
 from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner  # noqa: F401
 from .mask_rcnn import DetectorMaskRCNN  # noqa: F401
@@ -16,6 +16,7 @@ from .pose_rigid import PosePredictor  # noqa: F401
 from .prediction_runner import PredictionRunner  # noqa: F401
 from .renderer import Panda3dBatchRenderer  # noqa: F401
 from .scene_renderer import Panda3dSceneRenderer  # noqa: F401
+from .symmetries import ContinuousSymmetry, DiscreteSymmetry, make_symmetries_poses  # noqa: F401
 from .types import (BatchRenderOutput, CameraRenderingData, ObservationTensor, Panda3dCameraData, Panda3dLightData,  # noqa: F401
                     Panda3dObjectData, PosePredictorOutput)
 

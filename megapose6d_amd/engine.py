@@ -713,6 +713,107 @@ def pose_update(TCO, K_crop, out9, tCR, k_stride_floats: int = 9) -> torch.Tenso
     return out
 
 
+# --------------------------------------------------------------------------- #
+# pose errors (evaluation): csrc/pose_error.hip
+POSE_ERROR_MEAN, POSE_ERROR_MAX = 0, 1
+
+
+def _pose_error_points(points: torch.Tensor, mesh_ids, n_points, b: int):
+    points = _dev_f32(points)
+    if points.dim() != 3 or points.shape[-1] != 3 or points.shape[1] < 1:
+        raise EngineError(f"points must be [n_mesh, n_pts >= 1, 3], got {tuple(points.shape)}")
+    if mesh_ids is None:
+        if points.shape[0] != b:
+            raise EngineError("without mesh ids the points are per row: [b, n_pts, 3]")
+        mesh_ids = torch.arange(b, dtype=torch.int32, device=points.device)
+    return points, _dev_i32(mesh_ids), (None if n_points is None else _dev_i32(n_points))
+
+
+def pose_error_workspace(b: int, n_pts: int, S_max: int, device) -> torch.Tensor:
+    n = int(_lib.load().mp_pose_error_workspace_bytes(b, n_pts, S_max))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+
+
+def pose_error_sym(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Optional[torch.Tensor], n_sym: Optional[torch.Tensor],
+                   points: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None,
+                   reduce: int = POSE_ERROR_MEAN, split: int = 0, with_errs: bool = True, with_diffs: bool = False,
+                   with_alt: bool = False) -> Dict[str, torch.Tensor]:
+    """Symmetry-set error (mp_pose_error_sym).  `symmetries` [n_mesh,S,4,4] + `n_sym` [n_mesh]: T_gt [b,4,4] is composed with them;
+    `symmetries` None: T_gt holds the candidates [b,S,4,4].  -> err, idx, T_gt_sym (+ errs [b,S], diffs [b,N,3], err_alt)."""
+    T_pred, T_gt = _dev_f32(T_pred), _dev_f32(T_gt)
+    b = T_pred.shape[0]
+    points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
+    if symmetries is not None:
+        symmetries = _dev_f32(symmetries)
+        S = symmetries.shape[1]
+        if T_gt.shape != (b, 4, 4):
+            raise EngineError(f"T_gt must be [b,4,4], got {tuple(T_gt.shape)}")
+    else:
+        if T_gt.dim() != 4 or T_gt.shape[0] != b:
+            raise EngineError(f"candidate poses must be [b,S,4,4], got {tuple(T_gt.shape)}")
+        S = T_gt.shape[1]
+    n_sym = None if symmetries is None or n_sym is None else _dev_i32(n_sym)
+    n_pts = points.shape[1]
+    dev = T_pred.device
+    f = dict(dtype=torch.float32, device=dev)
+    out = dict(err=torch.empty(b, **f), idx=torch.empty(b, dtype=torch.int32, device=dev), T_gt_sym=torch.empty(b, 4, 4, **f))
+    if with_errs:
+        out["errs"] = torch.empty(b, S, **f)
+    if with_diffs:
+        out["diffs"] = torch.empty(b, n_pts, 3, **f)
+    if with_alt:
+        out["err_alt"] = torch.empty(b, **f)
+    ws = pose_error_workspace(b, n_pts, S, dev)
+    check(_lib.load().mp_pose_error_sym(T_pred.data_ptr(), T_gt.data_ptr(), _ptr(symmetries), _ptr(n_sym),
+                                        S, points.data_ptr(), n_pts, mesh_ids.data_ptr(), _ptr(n_points), n_pts, b, int(reduce), int(split),
+                                        out["err"].data_ptr(), _ptr(out.get("err_alt")), out["idx"].data_ptr(), out["T_gt_sym"].data_ptr(),
+                                        _ptr(out.get("errs")), _ptr(out.get("diffs")), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+def pose_error_nn(T_pred: torch.Tensor, T_gt: torch.Tensor, points: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None,
+                  n_points: Optional[torch.Tensor] = None, split: int = 0, with_diffs: bool = True,
+                  with_assign: bool = True) -> Dict[str, torch.Tensor]:
+    """Nearest-neighbour error (mp_pose_error_nn) -> mean, max [b] (+ diffs [b,N,3], assign [b,N] int32)."""
+    T_pred, T_gt = _dev_f32(T_pred), _dev_f32(T_gt)
+    b = T_pred.shape[0]
+    points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
+    n_pts = points.shape[1]
+    dev = T_pred.device
+    f = dict(dtype=torch.float32, device=dev)
+    out = dict(mean=torch.empty(b, **f), max=torch.empty(b, **f))
+    if with_diffs:
+        out["diffs"] = torch.empty(b, n_pts, 3, **f)
+    if with_assign:
+        out["assign"] = torch.empty(b, n_pts, dtype=torch.int32, device=dev)
+    ws = pose_error_workspace(b, n_pts, 1, dev)
+    check(_lib.load().mp_pose_error_nn(T_pred.data_ptr(), T_gt.data_ptr(), points.data_ptr(), n_pts, mesh_ids.data_ptr(), _ptr(n_points),
+                                       n_pts, b, int(split), _ptr(out.get("diffs")), _ptr(out.get("assign")), out["mean"].data_ptr(),
+                                       out["max"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+def pose_error_rigid(T_a: torch.Tensor, T_b: torch.Tensor, K: Optional[torch.Tensor] = None, points: Optional[torch.Tensor] = None,
+                     mesh_ids: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """trans_err = |t_a - t_b|, rot_err_deg = angle of R_b R_a^T (+ proj_error with K and points): mp_pose_error_rigid."""
+    T_a, T_b = _dev_f32(T_a), _dev_f32(T_b)
+    b = T_a.shape[0]
+    f = dict(dtype=torch.float32, device=T_a.device)
+    out = dict(trans_err=torch.empty(b, **f), rot_err_deg=torch.empty(b, **f))
+    n_pts = 0
+    if K is not None:
+        K = _dev_f32(K)
+        points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
+        n_pts = points.shape[1]
+        out["proj_error"] = torch.empty(b, **f)
+    check(_lib.load().mp_pose_error_rigid(T_a.data_ptr(), T_b.data_ptr(), b, _ptr(K), _ptr(points) if K is not None else None,
+                                          n_pts, _ptr(mesh_ids) if K is not None else None, _ptr(n_points) if K is not None else None, n_pts,
+                                          out["trans_err"].data_ptr(), out["rot_err_deg"].data_ptr(), _ptr(out.get("proj_error")), _stream()))
+    return out
+
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

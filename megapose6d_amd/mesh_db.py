@@ -62,6 +62,10 @@ class BatchedMeshes(TensorCollection):
         self.label_to_id = {label: n for n, label in enumerate(labels)}
         self._sampled: Dict[int, torch.Tensor] = {}
 
+    @property
+    def n_sym_mapping(self) -> Dict[str, int]:
+        return {label: obj["n_sym"] for label, obj in self.infos.items()}
+
     def ids(self, labels: Sequence[str]) -> List[int]:
         return [self.label_to_id[l] for l in labels]  # KeyError for unknown labels, like the reference
 
@@ -106,6 +110,11 @@ class MeshDataBase:
         if aabb or resample_n_points:
             raise NotImplementedError("only the hot-path configuration (all vertices) is supported")
         pts = [torch.from_numpy(self.engine_meshes[l]["points"]) for l in self.labels]
-        infos = {l: {"n_points": int(p.shape[0]), "n_sym": 1} for l, p in zip(self.labels, pts)}
-        sym = torch.eye(4).repeat(len(pts), 1, 1, 1)
+        # symmetry sets, identity-padded to the longest one (rigid_mesh_database.py:117-129)
+        syms = [torch.as_tensor(np.asarray(self.obj_dict[l].make_symmetry_poses(n_symmetries_continuous=n_sym))).float() for l in self.labels]
+        infos = {l: {"n_points": int(p.shape[0]), "n_sym": int(s.shape[0])} for l, p, s in zip(self.labels, pts, syms)}
+        s_max = max(s.shape[0] for s in syms)
+        sym = torch.eye(4).repeat(len(pts), s_max, 1, 1)
+        for n, s in enumerate(syms):
+            sym[n, : s.shape[0]] = s
         return BatchedMeshes(infos, self.labels, _pad_points(pts).float(), sym)

@@ -41,13 +41,12 @@ class RigidObject:
         return self.scaling_factor_mesh_units_to_meters * self.scaling_factor
 
     def make_symmetry_poses(self, n_symmetries_continuous: int = 64):
-        """object_dataset.py:124-137.  Symmetry sets feed the evaluation metrics (out of scope); an object without
-        symmetries has the identity alone, which is what the hot path's callers get."""
-        import numpy as np
+        """object_dataset.py:124-137: the object's symmetry set [n_sym, 4, 4] (float64, metres, identity first): what the pose-error
+        metrics minimise over (megapose6d_amd.symmetries.make_symmetries_poses with scale=self.scale)."""
+        from .symmetries import make_symmetries_poses
 
-        if self.is_symmetric:
-            raise NotImplementedError("symmetry pose sets (lib3d/symmetries.py) are part of the evaluation side, not of the pose engine")
-        return np.eye(4, dtype=np.float32)[None]
+        return make_symmetries_poses(self.symmetries_discrete, self.symmetries_continuous, n_symmetries_continuous=n_symmetries_continuous,
+                                     scale=self.scale)
 
 
 class RigidObjectDataset:
