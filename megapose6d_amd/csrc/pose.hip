@@ -357,6 +357,9 @@ extern "C" int mp_pose_prepare_ex(const float* d_TCO_in, const float* d_K, const
   MP_REQUIRE(!(multiview & MP_MV_INPLANE) || (multiview & MP_MV_REMOVE_TCO), "mp_pose_prepare: views_inplane_rotations needs remove_TCO_rendering "
              "(lib3d/multiview.py:237)");
   MP_REQUIRE(n_pts_main <= n_pts_stride && n_pts_views <= n_pts_stride && n_pts_main > 0, "mp_pose_prepare: bad point counts");
+  // every unit but the main one reduces over n_pts_views points: over none, its crop intrinsics would be inf / NaN
+  MP_REQUIRE(n_pts_views > 0 || (V == 1 && !(multiview & MP_MV_REMOVE_TCO)), "mp_pose_prepare: n_pts_views must be positive when a view "
+             "other than the main one is cropped (V > 1 or remove_TCO_rendering)");
   if (b == 0) return MP_OK;
   const bool extra = (multiview & MP_MV_REMOVE_TCO) != 0;   // no view carries crop_inputs' 2000-point crop: one more unit computes it
   ProfScope prof("pose_prepare", 0.0, (double)b * (12.0 * n_pts_main + (V - 1) * 12.0 * n_pts_views), (hipStream_t)stream);
