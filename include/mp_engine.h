@@ -509,6 +509,44 @@ int mp_pose_error_rigid(const float* d_T_a /*[b,4,4]*/, const float* d_T_b /*[b,
                         int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts, float* d_trans_err /*[b]*/,
                         float* d_rot_err_deg /*[b]*/, float* d_proj_err, mp_stream stream);
 
+/* BOP's MSPD (maximum symmetry-aware projection distance): mp_pose_error_sym with the norm taken between pixel positions, errs[i,s] =
+   reduce_p |proj(K_i, T_pred p) - proj(K_i, T_gt_s p)|_2 with proj the projection of mp_pose_error_rigid's d_proj_err (P = K T[:3],
+   perspective division), reduce = max for MSPD (mean is there too), idx = argmin_s with the lowest index on a tie.  Every other
+   argument (composed / explicit symmetry forms, point addressing, S_max <= 512, optional outputs, NaN and -1 for a non-finite pose,
+   workspace of mp_pose_error_workspace_bytes(b, n_pts, S_max)) means what it means for mp_pose_error_sym; d_K [b,3,3] is required.
+   Pixels, not metres.  The maximum does not depend on the order of reduction: the same bits for every split. */
+int mp_pose_error_mspd(const float* d_T_pred /*[b,4,4]*/, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
+                       const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids /*[b]*/, const int32_t* d_n_points, int n_pts,
+                       int b, int reduce, int split, const float* d_K /*[b,3,3]*/, float* d_err /*[b]*/, float* d_err_alt,
+                       int32_t* d_idx /*[b]*/, float* d_T_gt_sym, float* d_errs, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
+/* BOP's VSD (visible surface discrepancy, BOP 2019: visibility "bop19", step cost) between */
+/* rendered depth maps and an observed frame (csrc/vsd.hip; contract in csrc/vsd_core.h).   */
+/* All maps are [n,h,w] fp32 metres along the optical axis (0 = nothing), pixel centres as   */
+/* in mp_render's geometric depth; an observed depth that is not finite or < 0 counts as 0.  */
+/* Row i compares map d_est_ids[i] of d_depth_est with map d_gt_ids[i] of d_depth_gt under   */
+/* frame d_im_ids[i] of d_depth_test (an id array NULL: map i), so K hypotheses share one     */
+/* ground-truth render and many rows one frame; the ids are the caller's responsibility.     */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_vsd needs for b rows (0 for arguments mp_vsd rejects). */
+size_t mp_vsd_workspace_bytes(int b, int n_tau);
+/* With r the length of pixel (x, y)'s ray at unit depth under K_i and dist = depth * r: vis_gt = dist_gt > 0 and (dist_test == 0 or
+   dist_gt - dist_test <= delta); vis_est the same with dist_est, or-ed with vis_gt inside the bracket; n_union / n_inter count the
+   union / intersection of the two masks, n_far_t the intersection pixels with |dist_gt - dist_est| >= thr_t, thr_t = h_taus[t] *
+   d_diameter[i] (h_taus[t] alone when normalized == 0); d_errs[i,t] = (n_far_t + n_union - n_inter) / n_union, 1 on an empty union.
+   h_taus is a HOST array of n_tau in 1..16 values, read before the call returns.  A row whose K has a non-finite entry or whose
+   diameter is not positive and finite gives NaN errors and counts of -1.  d_counts [b,2+n_tau] = n_union, n_inter, n_far_t is optional
+   (NULL to skip).  h, w in 1..1024.  split = 0 picks the number of strips of image rows a row is cut into; > 0 forces it (counts are
+   integers: any value gives the same bits).  The counters live in d_workspace and are zeroed on `stream` inside the call.  b == 0
+   is a successful no-op; any other bad argument returns non-zero before anything is launched. */
+int mp_vsd(const float* d_depth_est /*[n_est,h,w]*/, const int32_t* d_est_ids /*[b] or NULL: 0..b-1*/,
+           const float* d_depth_gt /*[n_gt,h,w]*/, const int32_t* d_gt_ids, const float* d_depth_test /*[n_im,h,w]*/,
+           const int32_t* d_im_ids, int n_est, int n_gt, int n_im, const float* d_K /*[b,3,3]*/, const float* d_diameter /*[b]*/,
+           int b, int h, int w, float delta, const float* h_taus, int n_tau /*1..16*/, int normalized, int split,
+           float* d_errs /*[b,n_tau]*/, int32_t* d_counts /*[b,2+n_tau]: n_union, n_inter, n_far_t; optional*/,
+           void* d_workspace, size_t workspace_bytes, mp_stream stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */

@@ -10,6 +10,7 @@
 //
 //   sym_partial_kernel   (a) one wave per 256-point chunk of a row, all symmetries: per (row, symmetry, chunk) sum and max of the norms
 //   sym_finalize_kernel  (a) one workgroup per row: chunk partials -> errs[s], arg-min, T_gt_sym, optional difference vectors
+//   mspd_partial_kernel  (a') sym_partial_kernel with the norm taken between projections (MSPD); finalized by sym_finalize_kernel
 //   nn_pairs_kernel      (b) one workgroup per (row, 1024 ground-truth points, range of predicted points): running (d2, k), merged by
 //                            a 64-bit atomic minimum on (bits(d2) << 32 | k)
 //   nn_finalize_kernel   (b) one workgroup per row: assignment -> difference vectors, mean and max of their norms
@@ -176,6 +177,67 @@ __global__ __launch_bounds__(256) void sym_finalize_kernel(const float* __restri
       dx = gx - qx; dy = gy - qy; dz = gz - qz;
     }
     D[3 * j] = dx; D[3 * j + 1] = dy; D[3 * j + 2] = dz;   // the padded tail is zero
+  }
+}
+
+// the projected sibling of sym_partial_kernel (MSPD): the same chunks, the same partial layout, the norm taken between the two pixel
+// positions pe::proj_dist gives under P = K T (the projection of the rigid launch).  LDS keeps P_s = K (T_gt Sym_s) per symmetry.
+__global__ __launch_bounds__(256) void mspd_partial_kernel(const float* __restrict__ T_pred, const float* __restrict__ T_gt,
+                                                           const float* __restrict__ syms, const int32_t* __restrict__ n_sym, int S_max,
+                                                           const float* __restrict__ K, const float* __restrict__ points, int n_pts_stride,
+                                                           const int32_t* __restrict__ mesh_ids, const int32_t* __restrict__ n_points,
+                                                           int n_pts, int n_chunks, float* __restrict__ partial) {
+  __shared__ float Pgs[kMaxSym * 12];
+  const int row = blockIdx.x, mesh = mesh_ids[row];
+  const int ns = syms ? (n_sym ? min(n_sym[mesh], S_max) : S_max) : S_max;
+  const int nv = n_points ? min(n_points[mesh], n_pts) : n_pts;
+  float Kr[9];
+  for (int k = 0; k < 9; ++k) Kr[k] = K[(size_t)row * 9 + k];
+  for (int s = threadIdx.x; s < ns; s += 256) {
+    float O[16], Pg[12];
+    if (syms) {
+      pe::compose(T_gt + (size_t)row * 16, syms + ((size_t)mesh * S_max + s) * 16, O);
+    } else {
+      for (int k = 0; k < 12; ++k) O[k] = T_gt[((size_t)row * S_max + s) * 16 + k];
+    }
+    pe::proj_matrix(Kr, O, Pg);
+    for (int k = 0; k < 12; ++k) Pgs[s * 12 + k] = Pg[k];
+  }
+  __syncthreads();
+  float Pp[12];
+  pe::proj_matrix(Kr, T_pred + (size_t)row * 16, Pp);
+  const float* P = points + (size_t)mesh * n_pts_stride * 3;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = blockIdx.y * 4 + wave; c < n_chunks; c += gridDim.y * 4) {
+    float px[kPerLane], py[kPerLane], pz[kPerLane], qu[kPerLane], qv[kPerLane];
+    bool ok[kPerLane];
+#pragma unroll
+    for (int p = 0; p < kPerLane; ++p) {
+      const int j = c * kChunk + p * 64 + lane;
+      ok[p] = j < nv;
+      const int jj = ok[p] ? j : 0;
+      px[p] = P[3 * jj]; py[p] = P[3 * jj + 1]; pz[p] = P[3 * jj + 2];
+      pe::project(Pp, px[p], py[p], pz[p], qu[p], qv[p]);
+    }
+    for (int s = 0; s < ns; ++s) {
+      const float* G = Pgs + s * 12;
+      float sum = 0.f, mx = 0.f;
+#pragma unroll
+      for (int p = 0; p < kPerLane; ++p) {
+        float gu, gv;
+        pe::project(G, px[p], py[p], pz[p], gu, gv);
+        const float n = pe::pixel_dist(qu[p], qv[p], gu, gv);
+        sum = sum + (ok[p] ? n : 0.f);
+        mx = fmaxf(mx, ok[p] ? n : 0.f);
+      }
+      sum = wave_sum_all(sum);
+      mx = wave_max_all(mx);
+      if (lane == 0) {
+        float* o = partial + (((size_t)row * S_max + s) * n_chunks + c) * 2;
+        o[0] = sum;
+        o[1] = mx;
+      }
+    }
   }
 }
 
@@ -377,6 +439,35 @@ extern "C" int mp_pose_error_sym(const float* d_T_pred, const float* d_T_gt, con
   hipLaunchKernelGGL(sym_finalize_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points,
                      n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, reduce == MP_POSE_ERROR_MAX ? 1 : 0, part, d_err, d_err_alt, d_idx,
                      d_T_gt_sym, d_errs, d_diffs);
+  MP_CHECK_HIP(hipGetLastError());
+  return MP_OK;
+}
+
+extern "C" int mp_pose_error_mspd(const float* d_T_pred, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
+                                  const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts,
+                                  int b, int reduce, int split, const float* d_K, float* d_err, float* d_err_alt, int32_t* d_idx,
+                                  float* d_T_gt_sym, float* d_errs, void* d_workspace, size_t workspace_bytes, mp_stream stream) {
+  MP_REQUIRE(d_T_pred && d_T_gt && d_points && d_mesh_ids && d_K && d_err && d_idx && d_workspace, "mp_pose_error_mspd: null pointer");
+  MP_REQUIRE(n_pts >= 1 && n_pts <= n_pts_stride && b >= 0, "mp_pose_error_mspd: bad sizes (n_pts %d, stride %d, b %d)", n_pts, n_pts_stride, b);
+  MP_REQUIRE(S_max >= 1 && S_max <= kMaxSym, "mp_pose_error_mspd: S_max %d outside [1, %d]", S_max, kMaxSym);
+  MP_REQUIRE(reduce == MP_POSE_ERROR_MEAN || reduce == MP_POSE_ERROR_MAX, "mp_pose_error_mspd: unknown reduce %d", reduce);
+  MP_REQUIRE(split >= 0, "mp_pose_error_mspd: split < 0");
+  MP_REQUIRE(workspace_bytes >= mp_pose_error_workspace_bytes(b, n_pts, S_max), "mp_pose_error_mspd: workspace too small");
+  if (b == 0) return MP_OK;
+  const int nch = n_chunks_of(n_pts);
+  const int max_wgs = ceil_div(nch, 4);
+  int wgs = split > 0 ? split : ceil_div(1024, b);
+  wgs = wgs < 1 ? 1 : (wgs > max_wgs ? max_wgs : wgs);
+  MP_REQUIRE(wgs <= 65535, "mp_pose_error_mspd: split too large");
+  float* part = (float*)d_workspace;
+  ProfScope prof("pose_error_mspd", 0.0, (double)b * n_pts * 12.0, (hipStream_t)stream);
+  hipLaunchKernelGGL(mspd_partial_kernel, dim3(b, wgs), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_K,
+                     d_points, n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, part);
+  MP_CHECK_HIP(hipGetLastError());
+  // the chunk partials have the layout of the 3D launch: the same finalize picks the symmetry (no difference vectors)
+  hipLaunchKernelGGL(sym_finalize_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points,
+                     n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, reduce == MP_POSE_ERROR_MAX ? 1 : 0, part, d_err, d_err_alt, d_idx,
+                     d_T_gt_sym, d_errs, (float*)nullptr);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }

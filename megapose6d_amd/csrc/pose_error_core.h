@@ -14,6 +14,8 @@
 //     (<= ~20 roundings for any point count); the emulation accumulates in double and rounds once.  They are compared with a tolerance.
 //   * rotation error = angle of dR = R_b R_a^T as atan2f(|(dR - dR^T)^v| / 2, (tr dR - 1) / 2) * (180 / pi)             [rigid]
 //   * projection: P = K T[:3] (fmaf chain over k = 0..2), suv = P (x y z 1) as `apply`, (u, v) = (su / sw, sv / sw)    [proj_matrix, project]
+//     and the distance of two projections sqrtf(fmaf(dv, dv, du * du)): its mean over the points is proj_error, its maximum over the
+//     points, minimised over the symmetry set as in `arg-min` above, is MSPD                                     [pixel_dist, proj_dist]
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -98,13 +100,18 @@ PE_HD void project(const float* P, float x, float y, float z, float& u, float& v
   v = sv / sw;
 }
 
-// 2D distance between the projections of one point under two projection matrices
+// distance between two pixel positions
+PE_HD float pixel_dist(float ua, float va, float ub, float vb) {
+  const float du = ua - ub, dv = va - vb;
+  return sqrtf(fmaf(dv, dv, du * du));
+}
+
+// 2D distance between the projections of one point under two projection matrices (the mean of it is proj_error, the maximum MSPD)
 PE_HD float proj_dist(const float* Pa, const float* Pb, float x, float y, float z) {
   float ua, va, ub, vb;
   project(Pa, x, y, z, ua, va);
   project(Pb, x, y, z, ub, vb);
-  const float du = ua - ub, dv = va - vb;
-  return sqrtf(fmaf(dv, dv, du * du));
+  return pixel_dist(ua, va, ub, vb);
 }
 
 }  // namespace pe

@@ -812,6 +812,88 @@ def pose_error_rigid(T_a: torch.Tensor, T_b: torch.Tensor, K: Optional[torch.Ten
     return out
 
 
+def pose_error_mspd(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Optional[torch.Tensor], n_sym: Optional[torch.Tensor],
+                    points: torch.Tensor, K: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None,
+                    reduce: int = POSE_ERROR_MAX, split: int = 0, with_errs: bool = True, with_alt: bool = False) -> Dict[str, torch.Tensor]:
+    """Projected symmetry-set error (mp_pose_error_mspd; reduce = max is BOP's MSPD, in pixels).  Arguments as `pose_error_sym` plus
+    K [b,3,3] -> err, idx, T_gt_sym (+ errs [b,S], err_alt)."""
+    T_pred, T_gt, K = _dev_f32(T_pred), _dev_f32(T_gt), _dev_f32(K)
+    b = T_pred.shape[0]
+    if K.shape != (b, 3, 3):
+        raise EngineError(f"K must be [b,3,3], got {tuple(K.shape)}")
+    points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
+    if symmetries is not None:
+        symmetries = _dev_f32(symmetries)
+        S = symmetries.shape[1]
+        if T_gt.shape != (b, 4, 4):
+            raise EngineError(f"T_gt must be [b,4,4], got {tuple(T_gt.shape)}")
+    else:
+        if T_gt.dim() != 4 or T_gt.shape[0] != b:
+            raise EngineError(f"candidate poses must be [b,S,4,4], got {tuple(T_gt.shape)}")
+        S = T_gt.shape[1]
+    n_sym = None if symmetries is None or n_sym is None else _dev_i32(n_sym)
+    n_pts = points.shape[1]
+    dev = T_pred.device
+    f = dict(dtype=torch.float32, device=dev)
+    out = dict(err=torch.empty(b, **f), idx=torch.empty(b, dtype=torch.int32, device=dev), T_gt_sym=torch.empty(b, 4, 4, **f))
+    if with_errs:
+        out["errs"] = torch.empty(b, S, **f)
+    if with_alt:
+        out["err_alt"] = torch.empty(b, **f)
+    ws = pose_error_workspace(b, n_pts, S, dev)
+    check(_lib.load().mp_pose_error_mspd(T_pred.data_ptr(), T_gt.data_ptr(), _ptr(symmetries), _ptr(n_sym), S, points.data_ptr(), n_pts,
+                                         mesh_ids.data_ptr(), _ptr(n_points), n_pts, b, int(reduce), int(split), K.data_ptr(),
+                                         out["err"].data_ptr(), _ptr(out.get("err_alt")), out["idx"].data_ptr(), out["T_gt_sym"].data_ptr(),
+                                         _ptr(out.get("errs")), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# visible surface discrepancy (evaluation): csrc/vsd.hip
+VSD_TAUS = tuple(0.05 * k for k in range(1, 11))
+
+
+def vsd(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: torch.Tensor, K: torch.Tensor, diameter: torch.Tensor,
+        delta: float = 0.015, taus=None, normalized_by_diameter: bool = True, est_ids: Optional[torch.Tensor] = None,
+        gt_ids: Optional[torch.Tensor] = None, im_ids: Optional[torch.Tensor] = None, split: int = 0,
+        with_counts: bool = True) -> Dict[str, torch.Tensor]:
+    """BOP 2019 VSD (mp_vsd).  depth_* [n,h,w] metres; row i compares depth_est[est_ids[i]] with depth_gt[gt_ids[i]] under
+    depth_test[im_ids[i]] (ids None: map i); K [b,3,3], diameter [b] -> errs [b,n_tau] (+ counts [b,2+n_tau] int32: n_union, n_inter,
+    n_far_t).  The ids are not range-checked."""
+    depth_est, depth_gt, depth_test = _dev_f32(depth_est), _dev_f32(depth_gt), _dev_f32(depth_test)
+    K, diameter = _dev_f32(K), _dev_f32(diameter)
+    if depth_est.dim() != 3 or depth_gt.dim() != 3 or depth_test.dim() != 3 or depth_gt.shape[1:] != depth_est.shape[1:] \
+            or depth_test.shape[1:] != depth_est.shape[1:]:
+        raise EngineError(f"depth maps must be [n,h,w] of one size, got {tuple(depth_est.shape)}, {tuple(depth_gt.shape)}, {tuple(depth_test.shape)}")
+    b = K.shape[0]
+    if K.shape != (b, 3, 3) or diameter.shape != (b,):
+        raise EngineError(f"K must be [b,3,3] and diameter [b], got {tuple(K.shape)}, {tuple(diameter.shape)}")
+    h, w = depth_est.shape[1:]
+    ids = []
+    for name, i, maps in (("est_ids", est_ids, depth_est), ("gt_ids", gt_ids, depth_gt), ("im_ids", im_ids, depth_test)):
+        if i is None:
+            if maps.shape[0] < b:
+                raise EngineError(f"without {name} the maps are per row: need {b}, got {maps.shape[0]}")
+        else:
+            i = _dev_i32(i)
+            if i.shape != (b,):
+                raise EngineError(f"{name} must be [b], got {tuple(i.shape)}")
+        ids.append(i)
+    taus = [float(t) for t in (VSD_TAUS if taus is None else taus)]
+    n_tau = len(taus)
+    h_taus = (C.c_float * max(n_tau, 1))(*taus)
+    dev = K.device
+    out = dict(errs=torch.empty(b, n_tau, dtype=torch.float32, device=dev))
+    if with_counts:
+        out["counts"] = torch.empty(b, 2 + n_tau, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.mp_vsd_workspace_bytes(b, n_tau)), 256), dtype=torch.uint8, device=dev)
+    check(lib.mp_vsd(depth_est.data_ptr(), _ptr(ids[0]), depth_gt.data_ptr(), _ptr(ids[1]), depth_test.data_ptr(), _ptr(ids[2]),
+                     depth_est.shape[0], depth_gt.shape[0], depth_test.shape[0], K.data_ptr(), diameter.data_ptr(), b, h, w, float(delta),
+                     C.cast(h_taus, C.c_void_p), n_tau, int(bool(normalized_by_diameter)), int(split), out["errs"].data_ptr(),
+                     _ptr(out.get("counts")), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
 
 # --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
