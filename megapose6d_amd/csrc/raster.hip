@@ -21,16 +21,20 @@
 //                     distinct winning piece) from a dense per-wave task list; the observation crop (roi_align) of the item is
 //                     another role of the same wave.  All channels of the tile's pixels are staged in LDS and leave as whole,
 //                     contiguous pixel records (one launch fills the CNN input with full-line writes).
+//   (3) raster_classify + raster_tiles_light (compacted launch form): the (item, tile) pairs no view reaches leave (2) at once and are
+//                     written, background + crop, by a lighter kernel through the same TileWriter (raster_tile_io.h).
+// The mesh database and the workspace layout live in raster_db.hip (private interface: raster_bin.h).
 // Roofline: HBM-bound on the output writes ((3+3[+1])*4*h*w bytes per view + the mesh once per view).
 #include <cmath>
 #include <map>
 #include <mutex>
-#include <vector>
+#include <type_traits>
 
 #include "common.h"
 #include "crop_device.h"
 #include "raster_bin.h"
 #include "raster_core.h"
+#include "raster_tile_io.h"
 
 namespace mp {
 
@@ -52,7 +56,7 @@ constexpr int BIN_THREADS = 512;
 constexpr int LARGE_TILES = 16;    // a piece whose bbox touches more tiles is not replicated into tile lists
 constexpr int TILE_WAVES = 4;      // tiles (waves) per workgroup of raster_tiles: a 32 x 8 pixel strip
 constexpr int MAX_RUN = 32;        // channels per pixel one launch may stage
-constexpr int HDR_INTS = 4;        // per-view header: n_large, n_entries, overflow, unused
+constexpr int HDR_INTS = RASTER_BIN_HDR_INTS;   // per-view header (raster_bin.h, with the per-view workspace layout BinLayout)
 
 // optional fused crop role: roi_align of the observation into channels c0.. of the same pixels
 struct CropArgs {
@@ -62,8 +66,6 @@ struct CropArgs {
   int C, H, W, c0, nhwc4;
 };
 
-static_assert(HDR_INTS == RASTER_BIN_HDR_INTS, "raster_bin.h states the view header size");
-// per-view workspace layout: BinLayout (raster_bin.h)
 
 __device__ __forceinline__ void tile_range(const Piece& p, int ns, int w, int h, int& tx0, int& ty0, int& tx1, int& ty1) {
   int x0, y0, x1, y1;
@@ -211,30 +213,8 @@ __global__ __launch_bounds__(BIN_THREADS) void raster_bin(const MeshDev* __restr
   }
 }
 
-// a TileRec as two 16-byte loads (a struct copy is split into six ushort + four dword loads by the compiler)
-__device__ __forceinline__ rc::TileRec load_tile_rec(const rc::TileRec* __restrict__ p) {
-  const int4 a = reinterpret_cast<const int4*>(p)[0], b = reinterpret_cast<const int4*>(p)[1];
-  rc::TileRec r;
-  r.rx0 = (short)(a.x & 0xFFFF); r.ry0 = (short)(a.x >> 16);
-  r.rx1 = (short)(a.y & 0xFFFF); r.ry1 = (short)(a.y >> 16);
-  r.rx2 = (short)(a.z & 0xFFFF); r.ry2 = (short)(a.z >> 16);
-  r.pad0 = (short)(a.w & 0xFFFF);   // flags (orientation swap / clipped)
-  r.pad1 = 0;
-  r.iz0 = __int_as_float(b.x); r.iz1 = __int_as_float(b.y); r.iz2 = __int_as_float(b.z);
-  r.id = b.w;
-  return r;
-}
-
 __device__ __forceinline__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 __device__ __forceinline__ float rlf(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
-// Intra-wave LDS hand-off: the LDS unit executes one wave's DS operations in issue order, so all that is needed for lane A's write
-// to be seen by lane B's later read is that the compiler keeps the program order (the asm is a compiler barrier) and that pending DS
-// results have landed.  Unlike a workgroup-scope fence this does NOT wait for vmcnt: global loads issued as prefetches for the next
-// view stay in flight across it.
-__device__ __forceinline__ void wave_lds_fence() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
 
 #ifdef MP_RASTER_PROF   // scripts/microbench build only (never in libmp_engine.so): per-phase shader-cycle totals of raster_tiles,
 // accumulated in registers and flushed once per wave by every 32nd workgroup (so the probe does not perturb what it measures)
@@ -433,17 +413,26 @@ struct ViewHdr {   // what a wave needs to know about one view's lists for its t
   int begin, n_list, begin_l, n_large, overflow;
   int front_swap;   // screen orientation (Piece.flags & 1) of the view's nearest piece: a hint for the order of the two visit phases
 };
+// the header of `view` for `tile` (scalar loads where view is wave-uniform, one view per lane in the prefetch of raster_tiles)
+__device__ __forceinline__ ViewHdr read_view_hdr(const int* __restrict__ ws, BinLayout lay, const MeshDev* __restrict__ meshes,
+                                                 const int32_t* __restrict__ mesh_ids, int view, int tile) {
+  const int* hdr = ws + (size_t)view * lay.view_ints;
+  ViewHdr v;
+  v.overflow = hdr[2];
+  v.front_swap = hdr[3];
+  v.begin = 0; v.begin_l = 0; v.n_large = 0;
+  if (v.overflow) {   // rare: the view's lists did not fit -> its tiles walk all 2F piece indices through the recompute path
+    v.n_list = 2 * meshes[mesh_ids[view]].n_faces;
+  } else {
+    v.begin = hdr[HDR_INTS + tile];
+    v.n_list = hdr[HDR_INTS + tile + 1] - v.begin;
+    v.begin_l = hdr[lay.off_tl + tile];
+    v.n_large = hdr[lay.off_tl + tile + 1] - v.begin_l;
+  }
+  return v;
+}
 
-// OUT = OUT_F16 (MP_RASTER_F16, the "fp16 renders" mode of BASELINE.json configs[4]): `out` holds IEEE binary16 elements -- same element
-// strides, every written channel (renders and the fused crop) is rounded to nearest-even on its way out; nothing else changes.
-// OUT = OUT_XREC (MP_RASTER_XREC): `out` holds the bf16 pixel RECORDS the exact-piece stem convolution consumes (conv_stem.hip):
-// [x1,x2,x3 of every crop channel | the 8-bit integer k of every render channel | zero padding], stride_x = record length; the
-// record is staged in LDS in that form and leaves as 16-byte chunks.  Channel numbers (c_rgb, c_normals, stride_view, crop.c0) stay
-// logical channel numbers; stride_v / stride_y / stride_x count bf16 elements.
-constexpr int OUT_F32 = 0, OUT_F16 = 1, OUT_XREC = 2;
-// DEPTHREC (OUT_XREC only): the record's fp32-kind channels are a general mask and depth channels are normalised here (RGBD models); false =
-// the fp32-kind channels are the crop's leading ones, no depth channel (the RGB models: the round-4 form, free of the extra arithmetic --
-// this kernel sits exactly at its register budget)
+// OUT, DEPTHREC: the output form (raster_tile_io.h)
 template <int NS, int OUT = OUT_F32, bool FULL = true, bool DEPTHREC = false>
 __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(MP_RASTER_WAVES, MP_RASTER_WAVES))) void raster_tiles(
     const MeshDev* __restrict__ meshes, const TexDev* __restrict__ texs, const int32_t* __restrict__ mesh_ids, const float* __restrict__ TCO,
@@ -462,35 +451,8 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
   uint2* res = (uint2*)mine;                                    // aliases zb once the samples are in registers
   uint4* blk = (uint4*)mine;                                    // aliases zb + tasks while the binned records are being covered
   unsigned* tasks = (unsigned*)(mine + (size_t)64 * NS * sizeof(unsigned long long));
-  float* stage = (float*)(mine + ZT_BYTES);
-  float* my_stage = stage + (size_t)lane * run;
-  // OUT_XREC: the staging area holds the pixel records themselves, [64][stride_x] bf16 (never larger than [64][run] floats: the
-  // launcher checks); `put` files a channel value into the lane's pixel in whichever form the launch stages
-  // (OUT_XREC) logical channel c is fp32-kind (three record slots) iff bit c of xrec_mask is set -- the crop's channels and, for RGBD
-  // models, every depth channel --; the fp32-kind channels come first in the record, in channel order, then the integer channels
-  const int xrec_nf = DEPTHREC ? __builtin_popcount(xrec_mask) : crop.C;
-  unsigned short* my_rec = reinterpret_cast<unsigned short*>(stage) + (size_t)lane * (int)stride_x;
-  auto put = [&](int ch, float v) {   // ch = logical channel number
-    if constexpr (OUT == OUT_XREC) {
-      const int f_below = DEPTHREC ? __builtin_popcount(xrec_mask & ((1u << ch) - 1u)) : min(ch, xrec_nf);   // fp32-kind channels in front of ch (ch < 32)
-      if (DEPTHREC ? (bool)((xrec_mask >> ch) & 1u) : ch < xrec_nf) {   // exact truncation split x = x1 + x2 + x3 (three bf16 pieces)
-        const unsigned b1 = __float_as_uint(v) & 0xFFFF0000u;
-        const float r1 = v - __uint_as_float(b1);
-        const unsigned b2 = __float_as_uint(r1) & 0xFFFF0000u;
-        const float r2 = r1 - __uint_as_float(b2);
-        my_rec[3 * f_below] = (unsigned short)(b1 >> 16); my_rec[3 * f_below + 1] = (unsigned short)(b2 >> 16);
-        my_rec[3 * f_below + 2] = (unsigned short)(__float_as_uint(r2) >> 16);
-      } else {              // an integer 0..255: one bf16, exactly
-        my_rec[3 * xrec_nf + (ch - f_below)] = (unsigned short)(__float_as_uint(v) >> 16);
-      }
-    } else {
-      my_stage[ch - c_lo] = v;
-    }
-  };
-  if constexpr (OUT == OUT_XREC) {   // zero the whole record once (the padding slots are never written again)
-    uint4* z = reinterpret_cast<uint4*>(my_rec);
-    for (int q = 0; q < (int)stride_x / 8; ++q) z[q] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  TileWriter<OUT, DEPTHREC> tw((float*)(mine + ZT_BYTES), lane, c_lo, run, stride_x, xrec_mask, crop.C, depth_mode);
+  tw.clear_record();   // (a stem record is zeroed once: every view's channels are written again below, the padding slots never)
   const int groups_x = (lay.tiles_x + TILE_WAVES - 1) / TILE_WAVES;
   int b = blockIdx.x;
   const int gx = b % groups_x; b /= groups_x;
@@ -510,20 +472,7 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
   const bool do_depth = (flags & MP_RASTER_DEPTH) && c_depth >= 0;
   const bool gl_eye = flags & MP_RASTER_NORMALS_GL;
   const bool need_shade = c_rgb >= 0 || do_norm;   // a depth-only render (the depth refiner's) has nothing to shade
-  // (OUT_XREC) depth channels enter the record NORMALISED, with the operations of normalize_depth_kernel (crop.hip; reference
-  // models/pose_rigid.py:466-496) in the same order, so that the three pieces add up to the fp32 tensor path's value bit for bit
-  float depth_zr = 1.f;
-  if constexpr (OUT == OUT_XREC && DEPTHREC) {
-    if (depth_mode != 0 && depth_tcr) depth_zr = depth_tcr[3 * (size_t)item + 2];
-  }
-  auto nd = [&](float d) {
-    if constexpr (OUT == OUT_XREC && DEPTHREC) {
-      if (depth_mode == 1) d = d / depth_zr;
-      else if (depth_mode == 2) d = fminf(fmaxf(d / depth_zr, 0.f), 2.f) - 1.f;
-      else if (depth_mode == 3) d = fminf(fmaxf(d - depth_zr, -2.f), 2.f);
-    }
-    return d;
-  };
+  tw.set_item(depth_tcr, item);
   // block-visit coverage: the lane's sample position in each block (relative to the tile) and whether its pixel is inside the image
   uint32_t rel[NB];
   unsigned ok_mask = 0;
@@ -544,44 +493,15 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
   // they are reached.  The first 64 records of view r + 1 are requested before view r is processed.
   constexpr int FAST_VIEWS = 4;
   const int view0 = item * views_per_item;
-  auto fetch_hdr = [&](int view) {   // scalar loads (uniform address)
-    const int* hdr = ws + (size_t)view * lay.view_ints;
-    ViewHdr v;
-    v.overflow = hdr[2];
-    v.front_swap = hdr[3];
-    v.begin = 0; v.begin_l = 0; v.n_large = 0;
-    if (v.overflow) {   // rare: the view's lists did not fit -> its tiles walk all 2F piece indices through the recompute path
-      v.n_list = 2 * meshes[mesh_ids[view]].n_faces;
-    } else {
-      v.begin = hdr[HDR_INTS + tile];
-      v.n_list = hdr[HDR_INTS + tile + 1] - v.begin;
-      v.begin_l = hdr[lay.off_tl + tile];
-      v.n_large = hdr[lay.off_tl + tile + 1] - v.begin_l;
-    }
-    return v;
-  };
   int* hdr_lds = (int*)(mine + per_wave - HDR_LDS_BYTES);   // [FAST_VIEWS][6] ints of this wave (behind its staging area)
-  {
-    if (lane < min(views_per_item, FAST_VIEWS)) {
-      int h_begin = 0, h_nlist = 0, h_begin_l = 0, h_nlarge = 0, h_over = 0;
-      const int* hdr = ws + (size_t)(view0 + lane) * lay.view_ints;
-      h_over = hdr[2];
-      const int h_front = hdr[3];
-      if (h_over) {
-        h_nlist = 2 * meshes[mesh_ids[view0 + lane]].n_faces;
-      } else {
-        h_begin = hdr[HDR_INTS + tile];
-        h_nlist = hdr[HDR_INTS + tile + 1] - h_begin;
-        h_begin_l = hdr[lay.off_tl + tile];
-        h_nlarge = hdr[lay.off_tl + tile + 1] - h_begin_l;
-      }
-      int* d = hdr_lds + lane * 6;
-      d[0] = h_begin; d[1] = h_nlist; d[2] = h_begin_l; d[3] = h_nlarge; d[4] = h_over; d[5] = h_front;
-    }
-    wave_lds_fence();
+  if (lane < min(views_per_item, FAST_VIEWS)) {
+    const ViewHdr v = read_view_hdr(ws, lay, meshes, mesh_ids, view0 + lane, tile);
+    int* d = hdr_lds + lane * 6;
+    d[0] = v.begin; d[1] = v.n_list; d[2] = v.begin_l; d[3] = v.n_large; d[4] = v.overflow; d[5] = v.front_swap;
   }
+  wave_lds_fence();
   auto hdr_of = [&](int r) {   // r is wave-uniform: broadcast LDS reads, straight into scalar registers
-    if (r >= FAST_VIEWS) return fetch_hdr(view0 + r);
+    if (r >= FAST_VIEWS) return read_view_hdr(ws, lay, meshes, mesh_ids, view0 + r, tile);
     const int* d = hdr_lds + r * 6;
     ViewHdr v;
     v.begin = __builtin_amdgcn_readfirstlane(d[0]); v.n_list = __builtin_amdgcn_readfirstlane(d[1]);
@@ -614,13 +534,7 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
     const int n_total = vh.n_list + vh.n_large;
     const long long cv = (long long)r * stride_view;
     if (n_total == 0) {   // nothing of this view reaches the tile (most tiles of a crop): background
-      if constexpr (OUT != OUT_XREC) {   // (a stem record was cleared as a whole when the wave started)
-        if (c_rgb >= 0) { put(c_rgb + (int)cv, 0.f); put(c_rgb + (int)cv + 1, 0.f); put(c_rgb + (int)cv + 2, 0.f); }
-        if (do_norm) { put(c_normals + (int)cv, 0.f); put(c_normals + (int)cv + 1, 0.f); put(c_normals + (int)cv + 2, 0.f); }
-        if (do_depth) put(c_depth + (int)cv, 0.f);
-      } else {
-        if (do_depth) put(c_depth + (int)cv, nd(0.f));   // background depth 0 is normalised like any other value (e.g. to -1)
-      }
+      tw.background((int)cv, c_rgb, c_normals, c_depth, do_norm, do_depth);
       PROF(0)
       continue;
     }
@@ -768,54 +682,21 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
     }
     if (c_rgb >= 0) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) put(c_rgb + (int)cv + c, OUT == OUT_XREC ? rc::resolve_k(acc[c], NS) : rc::resolve_channel(acc[c], NS, false));
+      for (int c = 0; c < 3; ++c) tw.put(c_rgb + (int)cv + c, OUT == OUT_XREC ? rc::resolve_k(acc[c], NS) : rc::resolve_channel(acc[c], NS, false));
     }
     if (do_norm) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) put(c_normals + (int)cv + c, OUT == OUT_XREC ? rc::resolve_k(acc[3 + c], NS) : rc::resolve_channel(acc[3 + c], NS, false));
+      for (int c = 0; c < 3; ++c) tw.put(c_normals + (int)cv + c, OUT == OUT_XREC ? rc::resolve_k(acc[3 + c], NS) : rc::resolve_channel(acc[3 + c], NS, false));
     }
-    if (do_depth) put(c_depth + (int)cv, nd(st[0].id >= 0 ? 1.0f / st[0].wsum : 0.f));
+    if (do_depth) tw.put(c_depth + (int)cv, tw.nd(st[0].id >= 0 ? 1.0f / st[0].wsum : 0.f));
     wave_lds_fence();  // the z-buffer / task arrays are reused by the next view
     PROF(6)
   }
-  if (crop.images && px < w && py < h) {  // crop role: roi_align of the item's observation for this lane's pixel
-    const float4 cv4 = crop_lane(crop, item, h, w, px, py);
-    put(crop.c0, cv4.x); put(crop.c0 + 1, cv4.y); put(crop.c0 + 2, cv4.z);
-    if (crop.C == 4) put(crop.c0 + 3, nd(cv4.w));   // (the observation's depth channel: normalised like the rendered ones)
-  }
+  if (crop.images && px < w && py < h)   // crop role: roi_align of the item's observation for this lane's pixel
+    tw.put_crop(crop.c0, crop.C, crop_lane(crop, item, h, w, px, py));
   wave_lds_fence();
   PROF(7)
-  // ---- store: each of the tile's 8 rows leaves as one contiguous run of 8 pixels x `run` channels (only written channels) -------
-  const int cols = min(TILE, w - tile_x0), rows = min(TILE, h - tile_y0);
-  const int per_row = cols * run;   // <= 256 floats
-  if constexpr (OUT == OUT_XREC) {
-    // the tile's records sit in LDS as [8 rows][8 pixels][stride_x bf16]; a tile row = cols * stride_x / 8 contiguous 16-byte chunks
-    const int rowlen = cols * ((int)stride_x / 8);   // <= 40 chunks
-    unsigned short* out_item = reinterpret_cast<unsigned short*>(out) + (size_t)item * stride_v;
-    const uint4* recs = reinterpret_cast<const uint4*>(stage);
-    if (lane < rowlen)
-      for (int row = 0; row < rows; ++row)
-        *reinterpret_cast<uint4*>(out_item + (size_t)(tile_y0 + row) * stride_y + (size_t)tile_x0 * stride_x + (size_t)lane * 8) =
-            recs[row * 8 * ((int)stride_x / 8) + lane];
-  } else if constexpr (OUT == OUT_F16) {
-    _Float16* out_item = reinterpret_cast<_Float16*>(out) + (size_t)item * stride_v + c_lo;
-    for (int i = lane; i < per_row; i += 64) {
-      const int x = i / run, c = i - x * run;
-      if (!((run_mask >> c) & 1u)) continue;
-      _Float16* o = out_item + (size_t)tile_y0 * stride_y + (size_t)(tile_x0 + x) * stride_x + c;
-      const float* sp = stage + (size_t)x * run + c;
-      for (int row = 0; row < rows; ++row) o[(size_t)row * stride_y] = (_Float16)sp[(size_t)row * 8 * run];   // v_cvt_f16_f32: round to nearest even
-    }
-  } else {
-  float* out_item = out + (size_t)item * stride_v + c_lo;
-  for (int i = lane; i < per_row; i += 64) {
-    const int x = i / run, c = i - x * run;   // once per lane and 64-float slice, reused for all 8 rows
-    if (!((run_mask >> c) & 1u)) continue;
-    float* o = out_item + (size_t)tile_y0 * stride_y + (size_t)(tile_x0 + x) * stride_x + c;
-    const float* sp = stage + (size_t)x * run + c;
-    for (int row = 0; row < rows; ++row) o[(size_t)row * stride_y] = sp[(size_t)row * 8 * run];
-  }
-  }
+  tw.store(out, item, stride_v, stride_y, tile_x0, tile_y0, w, h, lane, run_mask);
   PROF(8)
   PROF_FLUSH
 }
@@ -842,8 +723,8 @@ __global__ __launch_bounds__(256) void raster_classify(const unsigned char* __re
   if (valid && !heavy) light_list[base + __popcll(ml & ((1ull << lane) - 1ull))] = (int)idx;
 }
 
-// A light job: the tile of an item that no view reaches = background in every view channel + the observation crop, stored exactly as
-// raster_tiles stores a tile (same staging layout, same `put` forms).  One wave per job, strided over the list; no list headers, no mesh,
+// A light job: the tile of an item that no view reaches = background in every view channel + the observation crop, staged and stored by
+// the TileWriter raster_tiles uses.  One wave per job, strided over the list; no list headers, no mesh,
 // four waves per SIMD (the unrolled roi_align taps want 127 registers; the 80 of six waves spill): one more than raster_tiles, and no list headers to wait for.
 template <int OUT, bool DEPTHREC>
 __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void raster_tiles_light(const int* __restrict__ counters, const int* __restrict__ light_list, BinLayout lay,
@@ -854,29 +735,9 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t per_wave = ((size_t)64 * run * sizeof(float) + 15) & ~(size_t)15;
-  float* stage = (float*)(lds_raw + (size_t)wave * per_wave);
-  float* my_stage = stage + (size_t)lane * run;
-  unsigned short* my_rec = reinterpret_cast<unsigned short*>(stage) + (size_t)lane * (int)stride_x;
-  const int xrec_nf = DEPTHREC ? __builtin_popcount(xrec_mask) : crop.C;
+  TileWriter<OUT, DEPTHREC> tw((float*)(lds_raw + (size_t)wave * per_wave), lane, c_lo, run, stride_x, xrec_mask, crop.C, depth_mode);
   const bool do_norm = (flags & MP_RASTER_NORMALS) && c_normals >= 0;
   const bool do_depth = (flags & MP_RASTER_DEPTH) && c_depth >= 0;
-  auto put = [&](int ch, float v) {   // (raster_tiles' `put`, verbatim)
-    if constexpr (OUT == OUT_XREC) {
-      const int f_below = DEPTHREC ? __builtin_popcount(xrec_mask & ((1u << ch) - 1u)) : min(ch, xrec_nf);
-      if (DEPTHREC ? (bool)((xrec_mask >> ch) & 1u) : ch < xrec_nf) {
-        const unsigned b1 = __float_as_uint(v) & 0xFFFF0000u;
-        const float r1 = v - __uint_as_float(b1);
-        const unsigned b2 = __float_as_uint(r1) & 0xFFFF0000u;
-        const float r2 = r1 - __uint_as_float(b2);
-        my_rec[3 * f_below] = (unsigned short)(b1 >> 16); my_rec[3 * f_below + 1] = (unsigned short)(b2 >> 16);
-        my_rec[3 * f_below + 2] = (unsigned short)(__float_as_uint(r2) >> 16);
-      } else {
-        my_rec[3 * xrec_nf + (ch - f_below)] = (unsigned short)(__float_as_uint(v) >> 16);
-      }
-    } else {
-      my_stage[ch - c_lo] = v;
-    }
-  };
   const int n_jobs = counters[0];
   const int stride = gridDim.x * TILE_WAVES;
   for (int j = blockIdx.x * TILE_WAVES + wave; j < n_jobs; j += stride) {
@@ -885,67 +746,13 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
     const int tx = tile % lay.tiles_x, ty = tile / lay.tiles_x;
     const int tile_x0 = tx * TILE, tile_y0 = ty * TILE;
     const int px = tile_x0 + (lane & 7), py = tile_y0 + (lane >> 3);
-    float depth_zr = 1.f;
-    if constexpr (OUT == OUT_XREC && DEPTHREC) {
-      if (depth_mode != 0 && depth_tcr) depth_zr = depth_tcr[3 * (size_t)item + 2];
-    }
-    auto nd = [&](float d) {   // (raster_tiles' `nd`, verbatim)
-      if constexpr (OUT == OUT_XREC && DEPTHREC) {
-        if (depth_mode == 1) d = d / depth_zr;
-        else if (depth_mode == 2) d = fminf(fmaxf(d / depth_zr, 0.f), 2.f) - 1.f;
-        else if (depth_mode == 3) d = fminf(fmaxf(d - depth_zr, -2.f), 2.f);
-      }
-      return d;
-    };
-    if constexpr (OUT == OUT_XREC) {
-      uint4* z = reinterpret_cast<uint4*>(my_rec);
-      for (int q = 0; q < (int)stride_x / 8; ++q) z[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    for (int r = 0; r < views_per_item; ++r) {
-      const int cv = (int)((long long)r * stride_view);
-      if constexpr (OUT != OUT_XREC) {
-        if (c_rgb >= 0) { put(c_rgb + cv, 0.f); put(c_rgb + cv + 1, 0.f); put(c_rgb + cv + 2, 0.f); }
-        if (do_norm) { put(c_normals + cv, 0.f); put(c_normals + cv + 1, 0.f); put(c_normals + cv + 2, 0.f); }
-        if (do_depth) put(c_depth + cv, 0.f);
-      } else {
-        if (do_depth) put(c_depth + cv, nd(0.f));
-      }
-    }
-    if (crop.images && px < w && py < h) {
-      const float4 cv4 = crop_lane_body<true>(crop, item, h, w, px, py);   // (inlined: the shared out-of-line copy would impose raster_tiles' register count)
-      put(crop.c0, cv4.x); put(crop.c0 + 1, cv4.y); put(crop.c0 + 2, cv4.z);
-      if (crop.C == 4) put(crop.c0 + 3, nd(cv4.w));
-    }
+    tw.set_item(depth_tcr, item);
+    tw.clear_record();
+    for (int r = 0; r < views_per_item; ++r) tw.background((int)((long long)r * stride_view), c_rgb, c_normals, c_depth, do_norm, do_depth);
+    if (crop.images && px < w && py < h)   // (inlined: the shared out-of-line copy would impose raster_tiles' register count)
+      tw.put_crop(crop.c0, crop.C, crop_lane_body<true>(crop, item, h, w, px, py));
     wave_lds_fence();
-    const int cols = min(TILE, w - tile_x0), rows = min(TILE, h - tile_y0);
-    const int per_row = cols * run;
-    if constexpr (OUT == OUT_XREC) {
-      const int rowlen = cols * ((int)stride_x / 8);
-      unsigned short* out_item = reinterpret_cast<unsigned short*>(out) + (size_t)item * stride_v;
-      const uint4* recs = reinterpret_cast<const uint4*>(stage);
-      if (lane < rowlen)
-        for (int row = 0; row < rows; ++row)
-          *reinterpret_cast<uint4*>(out_item + (size_t)(tile_y0 + row) * stride_y + (size_t)tile_x0 * stride_x + (size_t)lane * 8) =
-              recs[row * 8 * ((int)stride_x / 8) + lane];
-    } else if constexpr (OUT == OUT_F16) {
-      _Float16* out_item = reinterpret_cast<_Float16*>(out) + (size_t)item * stride_v + c_lo;
-      for (int i = lane; i < per_row; i += 64) {
-        const int x = i / run, c = i - x * run;
-        if (!((run_mask >> c) & 1u)) continue;
-        _Float16* o = out_item + (size_t)tile_y0 * stride_y + (size_t)(tile_x0 + x) * stride_x + c;
-        const float* sp = stage + (size_t)x * run + c;
-        for (int row = 0; row < rows; ++row) o[(size_t)row * stride_y] = (_Float16)sp[(size_t)row * 8 * run];
-      }
-    } else {
-      float* out_item = out + (size_t)item * stride_v + c_lo;
-      for (int i = lane; i < per_row; i += 64) {
-        const int x = i / run, c = i - x * run;
-        if (!((run_mask >> c) & 1u)) continue;
-        float* o = out_item + (size_t)tile_y0 * stride_y + (size_t)(tile_x0 + x) * stride_x + c;
-        const float* sp = stage + (size_t)x * run + c;
-        for (int row = 0; row < rows; ++row) o[(size_t)row * stride_y] = sp[(size_t)row * 8 * run];
-      }
-    }
+    tw.store(out, item, stride_v, stride_y, tile_x0, tile_y0, w, h, lane, run_mask);
     wave_lds_fence();   // the next job restages
   }
 }
@@ -954,122 +761,36 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
 
 using namespace mp;
 
-struct mp_mesh_db {
-  int n;
-  int max_verts, max_faces;
-  bool any_texture;   // some mesh has uvs + a texture: raster_tiles needs its FULL instance
-  MeshDev* d_meshes;
-  TexDev* d_texs;
-  std::vector<MeshDev> h_meshes;
-  std::vector<TexDev> h_texs;
-  std::vector<void*> allocs;
-};
-
-extern "C" int mp_mesh_db_create(const mp_mesh_desc* hm, int n, mp_mesh_db** out) {
-  MP_REQUIRE(hm && out && n > 0, "mp_mesh_db_create: bad arguments");
-  mp_mesh_db* db = new mp_mesh_db();
-  db->n = n;
-  db->max_verts = db->max_faces = 0;
-  db->any_texture = false;
-  db->d_meshes = nullptr;
-  db->d_texs = nullptr;
-  for (int i = 0; i < n; ++i) {
-    const mp_mesh_desc& d = hm[i];
-    MP_REQUIRE(d.h_vertices && d.h_normals && d.h_colors && d.h_faces && d.n_vertices > 0 && d.n_faces > 0,
-               "mp_mesh_db_create: mesh %d incomplete", i);
-    MP_REQUIRE(d.n_faces < (1 << 22), "mp_mesh_db_create: mesh %d has %d faces (limit 4 194 303: piece ids are packed in 24 bits)", i, d.n_faces);
-    for (int f = 0; f < 3 * d.n_faces; ++f)
-      MP_REQUIRE(d.h_faces[f] >= 0 && d.h_faces[f] < d.n_vertices, "mp_mesh_db_create: mesh %d face index out of range", i);
-    MeshDev m;
-    float *dv, *dn, *dc;
-    int32_t* df;
-    const size_t vb = (size_t)d.n_vertices * 3 * sizeof(float);
-    MP_CHECK_HIP(hipMalloc(&dv, vb));
-    MP_CHECK_HIP(hipMalloc(&dn, vb));
-    MP_CHECK_HIP(hipMalloc(&dc, vb));
-    MP_CHECK_HIP(hipMalloc(&df, (size_t)d.n_faces * 3 * sizeof(int32_t)));
-    MP_CHECK_HIP(hipMemcpy(dv, d.h_vertices, vb, hipMemcpyHostToDevice));
-    MP_CHECK_HIP(hipMemcpy(dn, d.h_normals, vb, hipMemcpyHostToDevice));
-    MP_CHECK_HIP(hipMemcpy(dc, d.h_colors, vb, hipMemcpyHostToDevice));
-    MP_CHECK_HIP(hipMemcpy(df, d.h_faces, (size_t)d.n_faces * 3 * sizeof(int32_t), hipMemcpyHostToDevice));
-    db->allocs.push_back(dv); db->allocs.push_back(dn); db->allocs.push_back(dc); db->allocs.push_back(df);
-    m.verts = dv; m.normals = dn; m.colors = dc; m.faces = df;
-    m.n_verts = d.n_vertices; m.n_faces = d.n_faces;
-    m.uvs = nullptr;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int v = 0; v < d.n_vertices; ++v)
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = fminf(lo[k], d.h_vertices[3 * v + k]);
-        hi[k] = fmaxf(hi[k], d.h_vertices[3 * v + k]);
-      }
-    float center[3];
-    for (int k = 0; k < 3; ++k) center[k] = 0.5f * (lo[k] + hi[k]);
-    float r2 = 0.f;
-    for (int v = 0; v < d.n_vertices; ++v) {
-      float s = 0.f;
-      for (int k = 0; k < 3; ++k) {
-        const float dd = d.h_vertices[3 * v + k] - center[k];
-        s += dd * dd;
-      }
-      r2 = fmaxf(r2, s);
-    }
-    m.radius = sqrtf(r2);
-    db->h_meshes.push_back(m);
-    db->max_verts = std::max(db->max_verts, d.n_vertices);
-    db->max_faces = std::max(db->max_faces, d.n_faces);
+namespace mp {
+// the one place raster_bin is launched from (the batch renderer below and, through raster_bin.h, the scene renderer)
+int raster_bin_launch(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K, int n_views, int h, int w,
+                      int ns, int* d_ws, const BinLayout& lay, int* counters, unsigned char* view_flags, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    MP_CHECK_HIP(hipFuncSetAttribute((const void*)raster_bin, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    attr_set = true;
   }
-  MP_CHECK_HIP(hipMalloc(&db->d_meshes, n * sizeof(MeshDev)));
-  MP_CHECK_HIP(hipMemcpy(db->d_meshes, db->h_meshes.data(), n * sizeof(MeshDev), hipMemcpyHostToDevice));
-  db->h_texs.assign(n, TexDev{});
-  MP_CHECK_HIP(hipMalloc(&db->d_texs, n * sizeof(TexDev)));
-  MP_CHECK_HIP(hipMemcpy(db->d_texs, db->h_texs.data(), n * sizeof(TexDev), hipMemcpyHostToDevice));
-  *out = db;
+  const size_t lds = (size_t)2 * lay.n_tiles * sizeof(int);
+  ProfScope prof("raster_bin", 0.0, (double)n_views * (12.0 * db->max_faces + 12.0 * db->max_verts + 4.0 * lay.n_tiles), stream);
+  hipLaunchKernelGGL(raster_bin, dim3(n_views), dim3(BIN_THREADS), lds, stream, db->d_meshes, d_mesh_ids, d_TCO, d_K, h, w, ns, d_ws, lay,
+                     counters, view_flags);
+  MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
+}  // namespace mp
 
-extern "C" int mp_mesh_db_set_texture(mp_mesh_db* db, int mesh_id, const float* h_uvs, const uint32_t* h_texels, int tex_w, int tex_h,
-                                      int n_levels) {
-  MP_REQUIRE(db && mesh_id >= 0 && mesh_id < db->n && h_uvs && h_texels, "mp_mesh_db_set_texture: bad arguments");
-  MP_REQUIRE(tex_w > 0 && tex_h > 0 && tex_w <= 16384 && tex_h <= 16384 && n_levels >= 1 && n_levels <= MP_TEX_MAX_LEVELS,
-             "mp_mesh_db_set_texture: bad texture size %dx%d / %d levels", tex_w, tex_h, n_levels);
-  MeshDev& m = db->h_meshes[mesh_id];
-  TexDev& tx = db->h_texs[mesh_id];
-  size_t total = 0;
-  for (int l = 0; l < n_levels; ++l) {
-    tx.tex_off[l] = (int)total;
-    total += (size_t)std::max(1, tex_w >> l) * std::max(1, tex_h >> l);
-  }
-  float* duv;
-  uint32_t* dtex;
-  MP_CHECK_HIP(hipMalloc(&duv, (size_t)m.n_faces * 6 * sizeof(float)));
-  MP_CHECK_HIP(hipMalloc(&dtex, total * sizeof(uint32_t)));
-  MP_CHECK_HIP(hipMemcpy(duv, h_uvs, (size_t)m.n_faces * 6 * sizeof(float), hipMemcpyHostToDevice));
-  MP_CHECK_HIP(hipMemcpy(dtex, h_texels, total * sizeof(uint32_t), hipMemcpyHostToDevice));
-  db->allocs.push_back(duv); db->allocs.push_back(dtex);
-  m.uvs = duv;
-  db->any_texture = true;
-  tx.texels = dtex; tx.tex_w = tex_w; tx.tex_h = tex_h; tx.tex_levels = n_levels;
-  MP_CHECK_HIP(hipMemcpy(db->d_texs + mesh_id, &tx, sizeof(TexDev), hipMemcpyHostToDevice));
-  MP_CHECK_HIP(hipMemcpy(db->d_meshes + mesh_id, &m, sizeof(MeshDev), hipMemcpyHostToDevice));
-  return MP_OK;
+// The template arguments of the tile kernels from the launch's runtime switches; f is a generic lambda taking std::integral_constants.
+// The four output forms (fp32, binary16, stem records, stem records with depth) are the (OUT, DEPTHREC) pairs the library instantiates.
+template <class F>
+static void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F>
+static void with_out_form(bool f16, bool xrec, bool depthrec, F&& f) {
+  if (depthrec) f(std::integral_constant<int, OUT_XREC>{}, std::true_type{});
+  else if (xrec) f(std::integral_constant<int, OUT_XREC>{}, std::false_type{});
+  else if (f16) f(std::integral_constant<int, OUT_F16>{}, std::false_type{});
+  else f(std::integral_constant<int, OUT_F32>{}, std::false_type{});
 }
 
-extern "C" int mp_mesh_db_destroy(mp_mesh_db* db) {
-  if (!db) return MP_OK;
-  for (void* p : db->allocs) (void)hipFree(p);
-  if (db->d_meshes) (void)hipFree(db->d_meshes);
-  if (db->d_texs) (void)hipFree(db->d_texs);
-  delete db;
-  return MP_OK;
-}
-
-extern "C" int mp_mesh_db_max_vertices(const mp_mesh_db* db) { return db ? db->max_verts : 0; }
-extern "C" float mp_mesh_db_radius(const mp_mesh_db* db, int i) {
-  return (db && i >= 0 && i < db->n) ? db->h_meshes[i].radius : 0.f;
-}
-
-static BinLayout bin_layout(const mp_mesh_db* db, int h, int w);
-static size_t job_tail_offset_ints(const BinLayout& lay, int n_views);
 // what the last launch on a workspace left behind its view blocks (host-side record): the job flags are only handed out for the
 // launch that wrote them -- compacted form, same number of views, same image size
 struct LastLaunch { bool compact; int n_views, h, w; };
@@ -1088,35 +809,9 @@ extern "C" const unsigned char* mp_raster_job_flags(const mp_mesh_db* db, const 
     auto it = g_last_launch.find(d_ws);
     if (it == g_last_launch.end() || !it->second.compact || it->second.n_views != n_views || it->second.h != h || it->second.w != w) return nullptr;
   }
-  const BinLayout lay = bin_layout(db, h, w);
-  const int* counters = (const int*)d_ws + job_tail_offset_ints(lay, n_views);
+  const BinLayout lay = raster_bin_layout(db, h, w);
+  const int* counters = (const int*)d_ws + raster_job_tail_offset_ints(lay, n_views);
   return (const unsigned char*)(counters + 4 + (size_t)n_views * lay.n_tiles);
-}
-
-static BinLayout bin_layout(const mp_mesh_db* db, int h, int w) {
-  BinLayout lay;
-  lay.tiles_x = ceil_div(w, TILE);
-  lay.tiles_y = ceil_div(h, TILE);
-  lay.n_tiles = lay.tiles_x * lay.tiles_y;
-  lay.max_faces = db->max_faces;
-  lay.cap_list = 3 * db->max_faces + 2048;
-  lay.cap_large = 4 * db->max_faces + 4096;
-  lay.off_tl = (HDR_INTS + lay.n_tiles + 1 + 3) & ~3;
-  lay.off_large = (lay.off_tl + lay.n_tiles + 1 + 3) & ~3;
-  lay.off_list = (lay.off_large + lay.cap_large + 3) & ~3;
-  lay.view_ints = (long long)lay.off_list + (long long)lay.cap_list * (long long)(sizeof(rc::TileRec) / sizeof(int));
-  return lay;
-}
-
-// behind the per-view blocks: [4 counters][light job list: one int per (view, tile)][job flags: one byte per (item, tile), sized for items =
-// views][per-view tile flags: one byte per (view, tile)]
-static size_t job_tail_offset_ints(const BinLayout& lay, int n_views) { return ((size_t)n_views * (size_t)lay.view_ints + 3) & ~(size_t)3; }
-
-extern "C" size_t mp_raster_workspace_bytes(const mp_mesh_db* db, int n_views, int h, int w) {
-  if (!db || n_views <= 0 || h <= 0 || w <= 0) return 0;
-  const BinLayout lay = bin_layout(db, h, w);
-  const size_t pairs = (size_t)n_views * lay.n_tiles;
-  return (job_tail_offset_ints(lay, n_views) + 4 + pairs) * sizeof(int) + 2 * ((pairs + 15) & ~(size_t)15);   // + job flags + per-view tile flags
 }
 
 static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K,
@@ -1140,11 +835,11 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   memcpy(L.dir, lights->point_dir, sizeof(L.dir));
   memcpy(L.color, lights->point_color, sizeof(L.color));
   memcpy(L.offset, lights->point_offset, sizeof(L.offset));
-  const BinLayout lay = bin_layout(db, h, w);
+  const BinLayout lay = raster_bin_layout(db, h, w);
   const int ns = (flags & MP_RASTER_MSAA4) ? 4 : 1;
   const int n_items = n_views / views_per_item;
   // compacted launch form (light-job list + per-pair flags behind the view blocks) unless MP_RASTER_COMPACT=0 (read per launch: the A/B test flips it)
-  int* const counters = (int*)d_ws + job_tail_offset_ints(lay, n_views);
+  int* const counters = (int*)d_ws + raster_job_tail_offset_ints(lay, n_views);
   int* const light_list = counters + 4;
   unsigned char* const job_flags = (unsigned char*)(light_list + (size_t)n_views * lay.n_tiles);
   unsigned char* const view_flags = job_flags + (((size_t)n_views * lay.n_tiles + 15) & ~(size_t)15);
@@ -1153,36 +848,31 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   note_launch(d_ws, compact, n_views, h, w);
   const bool do_norm = (flags & MP_RASTER_NORMALS) && c_normals >= 0, do_depth = (flags & MP_RASTER_DEPTH) && c_depth >= 0;
   // channel run [c_lo, c_hi) one pixel record of this launch spans, and which of its channels are written
-  int c_lo = 1 << 30, c_hi = -1;
-  auto span = [&](int c0, int n) { c_lo = std::min(c_lo, c0); c_hi = std::max(c_hi, c0 + n); };
+  // (one pass over the channel groups; `written` is re-based whenever the run grows downwards, bit i = channel c_lo + i.  Bits beyond 64 are
+  // dropped: such a run is refused below)
+  int c_lo = 0, c_hi = 0;
+  unsigned long long written = 0ull;
+  auto add = [&](int c0, int n) {
+    if (c_hi == c_lo) c_lo = c_hi = c0;   // the first group
+    if (c0 < c_lo) { written = c_lo - c0 < 64 ? written << (c_lo - c0) : 0ull; c_lo = c0; }
+    c_hi = std::max(c_hi, c0 + n);
+    for (int c = c0; c < c0 + n && c - c_lo < 64; ++c) written |= 1ull << (c - c_lo);
+  };
   for (int r = 0; r < views_per_item; ++r) {
-    if (c_rgb >= 0) span(c_rgb + r * (int)stride_view, 3);
-    if (do_norm) span(c_normals + r * (int)stride_view, 3);
-    if (do_depth) span(c_depth + r * (int)stride_view, 1);
+    if (c_rgb >= 0) add(c_rgb + r * (int)stride_view, 3);
+    if (do_norm) add(c_normals + r * (int)stride_view, 3);
+    if (do_depth) add(c_depth + r * (int)stride_view, 1);
   }
-  if (crop.images) span(crop.c0, crop.C);
+  if (crop.images) add(crop.c0, crop.C);
   MP_REQUIRE(c_hi > c_lo, "mp_raster_render: nothing to write");
   const int run = c_hi - c_lo;
   MP_REQUIRE(run <= MAX_RUN, "mp_raster_render: one launch writes at most %d channels per pixel (asked for %d)", MAX_RUN, run);
   MP_REQUIRE(stride_x >= run, "mp_raster_render: stride_x (%lld) smaller than the channel run (%d)", (long long)stride_x, run);
-  uint32_t mask = 0;
-  auto mark = [&](int c0, int n) { for (int c = c0; c < c0 + n; ++c) mask |= 1u << (c - c_lo); };
-  for (int r = 0; r < views_per_item; ++r) {
-    if (c_rgb >= 0) mark(c_rgb + r * (int)stride_view, 3);
-    if (do_norm) mark(c_normals + r * (int)stride_view, 3);
-    if (do_depth) mark(c_depth + r * (int)stride_view, 1);
-  }
-  if (crop.images) mark(crop.c0, crop.C);
+  const uint32_t mask = (uint32_t)written;
   {
-    const size_t lds = (size_t)2 * lay.n_tiles * sizeof(int);
-    static bool attr_set = false;
-    if (!attr_set) {
-      MP_CHECK_HIP(hipFuncSetAttribute((const void*)raster_bin, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-      attr_set = true;
-    }
-    ProfScope prof("raster_bin", 0.0, (double)n_views * (12.0 * db->max_faces + 12.0 * db->max_verts + 4.0 * lay.n_tiles), s);
-    hipLaunchKernelGGL(raster_bin, dim3(n_views), dim3(BIN_THREADS), lds, s, db->d_meshes, d_mesh_ids, d_TCO, d_K, h, w, ns, (int*)d_ws, lay, counters,
-                       compact ? view_flags : (unsigned char*)nullptr);
+    const int rc_bin = raster_bin_launch(db, d_mesh_ids, d_TCO, d_K, n_views, h, w, ns, (int*)d_ws, lay, counters,
+                                         compact ? view_flags : (unsigned char*)nullptr, s);
+    if (rc_bin != MP_OK) return rc_bin;
   }
   const int groups_x = ceil_div(lay.tiles_x, TILE_WAVES);
   const long long n_wg = (long long)n_items * lay.tiles_y * groups_x;
@@ -1218,11 +908,6 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
                                (crop.images ? (double)n_items * crop.C * (out_es + 4.0) * h * w : 0.0);   // crop: C channels written + <= the same-sized fp32 source window read
   // FULL = texture + point-light code compiled in; the pose networks' renders (vertex colours, ambient light) take the lean instance
   const bool full = db->any_texture || L.n_point > 0;
-#define MP_LAUNCH_TILES(NSV, OUTV, FULLV)                                                                                              \
-  hipLaunchKernelGGL((raster_tiles<NSV, OUTV, FULLV>), dim3((unsigned)n_wg), dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs,    \
-                     d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L, d_out, (long long)stride_v, views_per_item, n_items,  \
-                     (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,       \
-                     f32_mask, d_tcr, depth_mode, compact ? job_flags : (const unsigned char*)nullptr)
   const bool depthrec = xrec && (do_depth || f32_mask != (1u << crop.C) - 1u);
   if (compact) {
     ProfScope prof_c("raster_classify", 0.0, (double)n_views * lay.n_tiles * 16.0, s);
@@ -1230,41 +915,20 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
     hipLaunchKernelGGL(raster_classify, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const unsigned char*)view_flags, lay, views_per_item,
                        n_items, job_flags, counters, light_list);
   }
-  const int sel = depthrec ? (ns == 4 ? 16 : 17) + (full ? 2 : 0) : (ns == 4 ? 8 : 0) | (xrec ? 4 : f16 ? 2 : 0) | (full ? 1 : 0);
   {
-  ProfScope prof(f16 ? "raster_tiles/f16" : xrec ? "raster_tiles/xrec" : "raster_tiles", 0.0, alg_bytes, s);
-  switch (sel) {
-    case 16: hipLaunchKernelGGL((raster_tiles<4, OUT_XREC, false, true>), dim3((unsigned)n_wg), dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs,
-                     d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L, d_out, (long long)stride_v, views_per_item, n_items,
-                     (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,
-                     f32_mask, d_tcr, depth_mode, compact ? job_flags : (const unsigned char*)nullptr); break;
-    case 17: hipLaunchKernelGGL((raster_tiles<1, OUT_XREC, false, true>), dim3((unsigned)n_wg), dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs,
-                     d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L, d_out, (long long)stride_v, views_per_item, n_items,
-                     (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,
-                     f32_mask, d_tcr, depth_mode, compact ? job_flags : (const unsigned char*)nullptr); break;
-    case 18: hipLaunchKernelGGL((raster_tiles<4, OUT_XREC, true, true>), dim3((unsigned)n_wg), dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs,
-                     d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L, d_out, (long long)stride_v, views_per_item, n_items,
-                     (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,
-                     f32_mask, d_tcr, depth_mode, compact ? job_flags : (const unsigned char*)nullptr); break;
-    case 19: hipLaunchKernelGGL((raster_tiles<1, OUT_XREC, true, true>), dim3((unsigned)n_wg), dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs,
-                     d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L, d_out, (long long)stride_v, views_per_item, n_items,
-                     (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,
-                     f32_mask, d_tcr, depth_mode, compact ? job_flags : (const unsigned char*)nullptr); break;
-    case 0: MP_LAUNCH_TILES(1, OUT_F32, false); break;
-    case 1: MP_LAUNCH_TILES(1, OUT_F32, true); break;
-    case 2: MP_LAUNCH_TILES(1, OUT_F16, false); break;
-    case 3: MP_LAUNCH_TILES(1, OUT_F16, true); break;
-    case 4: MP_LAUNCH_TILES(1, OUT_XREC, false); break;
-    case 5: MP_LAUNCH_TILES(1, OUT_XREC, true); break;
-    case 8: MP_LAUNCH_TILES(4, OUT_F32, false); break;
-    case 9: MP_LAUNCH_TILES(4, OUT_F32, true); break;
-    case 10: MP_LAUNCH_TILES(4, OUT_F16, false); break;
-    case 11: MP_LAUNCH_TILES(4, OUT_F16, true); break;
-    case 12: MP_LAUNCH_TILES(4, OUT_XREC, false); break;
-    default: MP_LAUNCH_TILES(4, OUT_XREC, true); break;
+    ProfScope prof(f16 ? "raster_tiles/f16" : xrec ? "raster_tiles/xrec" : "raster_tiles", 0.0, alg_bytes, s);
+    with_bool(ns == 4, [&](auto ns4) {
+      with_bool(full, [&](auto full_c) {
+        with_out_form(f16, xrec, depthrec, [&](auto out_c, auto depthrec_c) {
+          hipLaunchKernelGGL((raster_tiles<ns4.value ? 4 : 1, out_c.value, full_c.value, depthrec_c.value>), dim3((unsigned)n_wg),
+                             dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs, d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L,
+                             d_out, (long long)stride_v, views_per_item, n_items, (long long)stride_view, (long long)stride_y, (long long)stride_x,
+                             c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop, f32_mask, d_tcr, depth_mode,
+                             compact ? job_flags : (const unsigned char*)nullptr);
+        });
+      });
+    });
   }
-  }
-#undef MP_LAUNCH_TILES
   if (compact) {   // the pairs no view reaches: background + crop, strided over the light list, four waves per SIMD
     static int n_cu = 0;
     if (n_cu == 0) {
@@ -1275,15 +939,12 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
     const size_t lds_l = (size_t)TILE_WAVES * (((size_t)64 * run_lds * sizeof(float) + 15) & ~(size_t)15);
     const long long n_res = std::min<long long>((long long)n_cu * 8, std::max<long long>(1, ((long long)n_items * lay.n_tiles + TILE_WAVES - 1) / TILE_WAVES));
     ProfScope prof_l(f16 ? "raster_tiles_light/f16" : xrec ? "raster_tiles_light/xrec" : "raster_tiles_light", 0.0, 0.0, s);
-#define MP_LAUNCH_LIGHT(OUTV, DR)                                                                                                              \
-    hipLaunchKernelGGL((raster_tiles_light<OUTV, DR>), dim3((unsigned)n_res), dim3(64 * TILE_WAVES), lds_l, s, (const int*)counters,           \
-                       (const int*)light_list, lay, h, w, flags, d_out, (long long)stride_v, views_per_item, (long long)stride_view,           \
-                       (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop, f32_mask, d_tcr, depth_mode)
-    if (depthrec) MP_LAUNCH_LIGHT(OUT_XREC, true);
-    else if (xrec) MP_LAUNCH_LIGHT(OUT_XREC, false);
-    else if (f16) MP_LAUNCH_LIGHT(OUT_F16, false);
-    else MP_LAUNCH_LIGHT(OUT_F32, false);
-#undef MP_LAUNCH_LIGHT
+    with_out_form(f16, xrec, depthrec, [&](auto out_c, auto depthrec_c) {
+      hipLaunchKernelGGL((raster_tiles_light<out_c.value, depthrec_c.value>), dim3((unsigned)n_res), dim3(64 * TILE_WAVES), lds_l, s,
+                         (const int*)counters, (const int*)light_list, lay, h, w, flags, d_out, (long long)stride_v, views_per_item,
+                         (long long)stride_view, (long long)stride_y, (long long)stride_x, c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop,
+                         f32_mask, d_tcr, depth_mode);
+    });
   }
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
@@ -1341,27 +1002,3 @@ extern "C" int mp_raster_render_xrec(const mp_mesh_db* db, const int32_t* d_mesh
                             stride_v, views_per_item, stride_view, stride_y, stride_x, c_rgb, c_normals, c_depth, d_ws, ws_bytes, stream, crop,
                             f32_mask, d_tCR, depth_mode);
 }
-
-// ---- private interface for the other rasteriser translation units (raster_bin.h) -------------------------------------------------------
-namespace mp {
-
-BinLayout raster_bin_layout(const mp_mesh_db* db, int h, int w) { return bin_layout(db, h, w); }
-const rc::MeshRef* raster_db_meshes(const mp_mesh_db* db) { return db->d_meshes; }
-const rc::TexRef* raster_db_textures(const mp_mesh_db* db) { return db->d_texs; }
-
-int raster_bin_launch(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K, int n_views, int h, int w,
-                      int ns, int* d_ws, const BinLayout& lay, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    MP_CHECK_HIP(hipFuncSetAttribute((const void*)raster_bin, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_set = true;
-  }
-  const size_t lds = (size_t)2 * lay.n_tiles * sizeof(int);
-  ProfScope prof("raster_bin", 0.0, (double)n_views * (12.0 * db->max_faces + 12.0 * db->max_verts + 4.0 * lay.n_tiles), stream);
-  hipLaunchKernelGGL(raster_bin, dim3(n_views), dim3(BIN_THREADS), lds, stream, db->d_meshes, d_mesh_ids, d_TCO, d_K, h, w, ns, d_ws, lay,
-                     (int*)nullptr, (unsigned char*)nullptr);
-  MP_CHECK_HIP(hipGetLastError());
-  return MP_OK;
-}
-
-}  // namespace mp

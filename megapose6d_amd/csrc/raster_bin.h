@@ -1,12 +1,26 @@
-// raster_bin.h -- PRIVATE interface between raster.hip (which owns the mesh database and the binning kernel raster_bin) and the other
-// rasteriser translation units (raster_scene.hip).  Not part of the C-ABI: nothing here is exported from the library.
+// raster_bin.h -- PRIVATE interface between the rasteriser's translation units: raster_db.hip (the mesh database and the workspace
+// layout), raster.hip (the binning kernel raster_bin and the batch renderer) and raster_scene.hip (the scene renderer).  Not part of the
+// C-ABI: nothing here is exported from the library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "mp_engine.h"
 #include "raster_core.h"
+
+struct mp_mesh_db {   // (the C-ABI's opaque handle; written by raster_db.hip only)
+  int n;
+  int max_verts, max_faces;
+  bool any_texture;   // some mesh has uvs + a texture: raster_tiles needs its FULL instance
+  mp::rc::MeshRef* d_meshes;   // device tables: MeshRef / TexRef per mesh id
+  mp::rc::TexRef* d_texs;
+  std::vector<mp::rc::MeshRef> h_meshes;
+  std::vector<mp::rc::TexRef> h_texs;
+  std::vector<void*> allocs;
+};
 
 namespace mp {
 
@@ -26,14 +40,15 @@ struct BinLayout {
 // the layout raster_bin uses for this database at h x w (what mp_raster_workspace_bytes sizes per view)
 BinLayout raster_bin_layout(const mp_mesh_db* db, int h, int w);
 
-// device tables of the database: MeshRef / TexRef per mesh id, and whether some mesh carries a texture
-const rc::MeshRef* raster_db_meshes(const mp_mesh_db* db);
-const rc::TexRef* raster_db_textures(const mp_mesh_db* db);
+// behind the per-view blocks (batch renderer only): [4 counters][light job list: one int per (view, tile)][job flags: one byte per
+// (item, tile), sized for items = views][per-view tile flags: one byte per (view, tile)]
+inline size_t raster_job_tail_offset_ints(const BinLayout& lay, int n_views) { return ((size_t)n_views * (size_t)lay.view_ints + 3) & ~(size_t)3; }
 
 // Enqueue raster_bin for n_views views (one workgroup each): view v = mesh d_mesh_ids[v] under pose d_TCO[v] and intrinsics d_K[v]
 // (a non-finite pose or K gives empty lists), binned for `ns` samples per pixel into the view blocks of d_ws (n_views * lay.view_ints ints).
-// No light-job counters, no per-view tile flags.
+// counters (4 ints, or NULL): the light-job counters of the compacted launch form, zeroed here; view_flags (one byte per (view, tile), or
+// NULL): whether the view reaches the tile, what raster_classify reads.
 int raster_bin_launch(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K, int n_views, int h, int w,
-                      int ns, int* d_ws, const BinLayout& lay, hipStream_t stream);
+                      int ns, int* d_ws, const BinLayout& lay, int* counters, unsigned char* view_flags, hipStream_t stream);
 
 }  // namespace mp

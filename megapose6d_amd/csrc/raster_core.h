@@ -316,13 +316,6 @@ struct Sample {
 
 MP_HD bool depth_in_range(float wsum) { return wsum >= 1.0f / Z_FAR && wsum <= 1.0f / Z_NEAR; }
 
-MP_HD void sample_update(Sample& s, float wsum, int id) {
-  if (s.id < 0 || wsum > s.wsum || (wsum == s.wsum && id < s.id)) {
-    s.wsum = wsum;
-    s.id = id;
-  }
-}
-
 // ---- 32-bit fast path of the edge functions (the GPU's inner loop) -----------------------------------------------------------
 // For a piece whose extent D = max(Xmax - Xmin, Ymax - Ymin) and whose distance R to the farthest sample of the 8x8 tile are both
 // <= 23170 sub-pixel units (90 px), every |E| = |dx * ry - dy * rx| <= 2 * 23170^2 < 2^31 and every factor fits 24 bits, so the
@@ -360,16 +353,6 @@ MP_HD void piece_edges32(const Piece& p, Edges32& e) {
 
 // E_i at sample (sx, sy), int32 (valid under piece_is_small)
 MP_HD int edge32(const Edges32& e, int i, int sx, int sy) { return MP_MUL24(e.dx[i], sy - e.ay[i]) - MP_MUL24(e.dy[i], sx - e.ax[i]); }
-
-// conservative per-lane test of the 32-bit path: can ANY sample of pixel (px, py) be inside the (small) piece?
-// (no sample is farther than 96/256 px from the pixel centre in x or y)
-MP_HD bool maybe_covered32(const Edges32& e, int px, int py) {
-  const int cx = px * SUBPIX + 128, cy = py * SUBPIX + 128;
-  bool maybe = true;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) maybe = maybe && (edge32(e, i, cx, cy) + (abs(e.dx[i]) + abs(e.dy[i])) * 96 >= e.thr[i]);
-  return maybe;
-}
 
 // One SMALL piece (piece_is_small for the pixel's tile) against the NS samples of pixel (px, py): emit(s, wsum) is called for every
 // sample that is covered (top-left rule) and inside the depth range.  This is the arithmetic of both coverage forms of the kernel:
@@ -434,19 +417,6 @@ MP_HD float key_wsum(unsigned long long key) {
 MP_HD int key_id(unsigned long long key) { return key ? (int)(0x7FFFFFu - (uint32_t)((key >> 9) & 0x7FFFFFu)) : -1; }
 MP_HD int key_slot(unsigned long long key) { return (int)(key & 511u); }
 
-template <int NS>
-MP_HD void cover_lane(const Piece& p, int tile_x0, int tile_y0, int px, int py, Sample (&st)[NS]) {
-  if (piece_is_small(p, tile_x0, tile_y0)) {
-    Edges32 e;
-    piece_edges32(p, e);
-    cover_pixel32<NS>(p, e, px, py, [&](int s, float wsum) { sample_update(st[s], wsum, p.id); });
-  } else {
-    Edges e;
-    piece_edges(p, e);
-    cover_pixel64<NS>(p, e, px, py, [&](int s, float wsum) { sample_update(st[s], wsum, p.id); });
-  }
-}
-
 // ---- block-visit coverage form (every binned record) ---------------------------------------------------------------------------
 // The wave owns one 8x8 tile; its lanes are the SAMPLES of one block of the tile at a time (NS = 4: four 4x4-pixel blocks, lane =
 // pixel * 4 + sample; NS = 1: one 8x8 block, lane = pixel), the depth state of a lane's sample lives in registers, and the pieces
@@ -495,7 +465,6 @@ MP_HD BlkRec make_blk_rec(const Piece& p, const Edges32& e, int tile_x0, int til
 
 // block geometry: NS = 4 -> four 4x4-pixel blocks (k & 1 = column, k >> 1 = row), NS = 1 -> the whole tile
 MP_HD int blk_count(int ns) { return ns == 1 ? 1 : 4; }
-MP_HD int blk_size(int ns) { return ns == 1 ? 8 : 4; }
 // pixel (inside the tile, 0..63) and sample of lane `lane` in block k
 MP_HD int blk_lane_pixel(int ns, int k, int lane) {
   if (ns == 1) return lane;
@@ -544,9 +513,6 @@ MP_HD unsigned long long depth_key_lo(float wsum, uint32_t key_lo) {
   memcpy(&wb, &wsum, 4);
   return ((unsigned long long)wb << 32) | (unsigned long long)key_lo;
 }
-
-// piece index (in the [0, 2F) space) from a depth-tie id: they coincide (first piece: tri, second: F + tri)
-MP_HD int index_of_id(int id) { return id; }
 
 MP_HD float lut_val(int i) { return (float)((i * 255) >> 5); }  // floor(i*255/32), utils.py:65
 

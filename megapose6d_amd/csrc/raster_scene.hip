@@ -7,18 +7,19 @@
 // Structure:
 //   (0) raster_scene_prep   one thread per object: the camera's K copied next to the object (what raster_bin reads per view) and the
 //                           object's light rig copied with its point-light count clamped to 8.
-//   (1) raster_bin          (raster.hip, unchanged) one "view" per (camera, object): the object's pieces binned into 8x8-pixel tiles.
+//   (1) raster_bin          (raster.hip, launched through raster_bin.h) one "view" per (camera, object): the object's pieces binned into 8x8-pixel tiles.
 //   (2) raster_scene_tiles  one wave per (camera, 8x8 tile), four tiles per workgroup.  The lane owns one pixel and keeps the scene keys
 //                           of its NS samples in registers across ALL objects of the camera.  Per object the wave walks the tile's
 //                           binned records, then the object's large list (or, if its lists overflowed, every piece), 64 pieces at a
 //                           time: each lane turns one into a Piece in the wave's LDS slice, and the wave visits those whose snapped
 //                           bounding box reaches the tile (broadcast LDS reads).  Then each lane shades its pixel's distinct winners and
-//                           writes the resolved pixel once.
+//                           writes the resolved pixel once.  (Record decode and the intra-wave LDS fence: raster_tile_io.h.)
 // Roofline: bound by the output writes, (3 + 3 + 1) fp32 channels + one int32 instance id per pixel, ONCE per camera.
 #include "common.h"
 #include "raster_bin.h"
 #include "raster_core.h"
 #include "raster_scene_core.h"
+#include "raster_tile_io.h"
 
 namespace mp {
 namespace {
@@ -54,11 +55,6 @@ __global__ __launch_bounds__(256) void raster_scene_prep(const float* __restrict
   rc::Lights L = lights_in[o];
   L.n_point = min(max(L.n_point, 0), 8);
   lights_out[o] = L;
-}
-
-__device__ __forceinline__ void wave_lds_fence() {   // (raster.hip: intra-wave LDS hand-off)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
 }
 
 template <int NS>
@@ -105,15 +101,7 @@ __global__ __launch_bounds__(64 * SCENE_WAVES) void raster_scene_tiles(rc::Scene
       Piece p;
       p.id = -1;
       if (e < n_list) {
-        const int4 a = reinterpret_cast<const int4*>(list + begin + e)[0], c = reinterpret_cast<const int4*>(list + begin + e)[1];
-        rc::TileRec r;
-        r.rx0 = (short)(a.x & 0xFFFF); r.ry0 = (short)(a.x >> 16);
-        r.rx1 = (short)(a.y & 0xFFFF); r.ry1 = (short)(a.y >> 16);
-        r.rx2 = (short)(a.z & 0xFFFF); r.ry2 = (short)(a.z >> 16);
-        r.pad0 = (short)(a.w & 0xFFFF); r.pad1 = 0;
-        r.iz0 = __int_as_float(c.x); r.iz1 = __int_as_float(c.y); r.iz2 = __int_as_float(c.z);
-        r.id = c.w;
-        rc::unpack_tile_rec(r, tile_x0, tile_y0, p);
+        rc::unpack_tile_rec(load_tile_rec(list + begin + e), tile_x0, tile_y0, p);
       } else if (e < n_total) {
         rc::piece_from_index<false>(m, T, Kv, overflow ? e - n_list : large[begin_l + e - n_list], p);
       }
@@ -209,15 +197,15 @@ extern "C" int mp_raster_render_scene(const mp_mesh_db* db, int n_cams, const in
       hipLaunchKernelGGL(raster_scene_prep, dim3((unsigned)ceil_div(n_obj, 256)), dim3(256), 0, s, d_K, d_obj_off, n_cams, n_obj,
                          (const rc::Lights*)d_lights, K_obj, lights);
     }
-    const int rc_bin = raster_bin_launch(db, d_mesh_ids, d_TCO, K_obj, n_obj, h, w, ns, ws, lay, s);
+    const int rc_bin = raster_bin_launch(db, d_mesh_ids, d_TCO, K_obj, n_obj, h, w, ns, ws, lay, nullptr, nullptr, s);
     if (rc_bin != MP_OK) return rc_bin;
   }
   const int groups_x = ceil_div(lay.tiles_x, SCENE_WAVES);
   const long long n_wg = (long long)n_cams * lay.tiles_y * groups_x;
   MP_REQUIRE(n_wg < (1LL << 31), "mp_raster_render_scene: grid too large");
   rc::SceneObjects so;
-  so.meshes = raster_db_meshes(db);
-  so.texs = raster_db_textures(db);
+  so.meshes = db->d_meshes;
+  so.texs = db->d_texs;
   so.mesh_ids = d_mesh_ids;
   so.TCO = d_TCO;
   so.K = K_obj;

@@ -784,3 +784,102 @@ def test_raster_compacted_launch_equals_the_direct_form(eng, engine_meshes, monk
     if not mode.startswith("records"):
         img = outs["1"][..., 3:3 + 6 * V]
         assert (img[1] == 0).all() and (img[0] > 0).float().mean() < 0.1 and (img[3] > 0).float().mean() > 0.15   # empty item, small object, object filling its crop
+
+
+def _ragged_raster_inputs():
+    """2 items x 4 views at h = 52, w = 76 (both 4 mod 8: the last column and the last row of 8x8 tiles are cut to 4 pixels), MSAA 4;
+    item 0's object is far away (most of its tiles are light), item 1's fills its crop (heavy tiles on the ragged edges)"""
+    from tests.support import synthetic as syn
+
+    rng = np.random.RandomState(23)
+    n_items, V, h, w = 2, 4, 52, 76
+    T = np.stack([syn.random_pose(rng, z_range=(0.9, 1.6) if i // V == 0 else (0.2, 0.25)) for i in range(n_items * V)])
+    K = np.repeat(syn.K_EXAMPLE[None].astype(np.float32), n_items * V, 0)
+    K[:, 0] *= np.float32(w / 640.0)
+    K[:, 1] *= np.float32(h / 480.0)
+    return n_items, V, h, w, T, K
+
+
+def test_raster_ragged_tiles_every_output_form(eng, engine_meshes, oracle_meshes, monkeypatch):
+    """The store of a tile is ONE piece of code for raster_tiles and raster_tiles_light and the three output forms; its partial-tile
+    branch (cols < 8, rows < 8) only runs when h or w is no multiple of 8.  h = 52, w = 76, output embedded in a sentinel-poisoned
+    tensor with a margin of 4 pixels to the right and below and padding channels:
+      (a) fp32 without crop, direct form == oracle.raster.render, view by view, bit for bit;
+      (b) compacted form == direct form, bit for bit, in the five modes of test_raster_compacted_launch_equals_the_direct_form;
+      (c) binary16 with crop == (fp32 with crop).half();
+      (d) the RGB stem records, decoded, == fp32 with crop, bit for bit: a crop channel is the fp32 sum x1 + x2 + x3 of its three bf16
+          pieces in that order; a render channel is the bf16 integer k taken through what the fp32 form stores for k, the fp32 quotient
+          k / 255 (rc::resolve_channel: floorf(..) / 255.0f, where rc::resolve_k is the floorf(..));
+      and the sentinel survives in every element outside the written channels and pixels."""
+    from oracle import raster as orr
+
+    db = _mesh_db(eng, engine_meshes)
+    n_items, V, h, w, Tn, Kn = _ragged_raster_inputs()
+    T, K = torch.from_numpy(Tn).cuda(), torch.from_numpy(Kn).cuda()
+    mesh_of_item = [0, 1]
+    ids = torch.tensor(mesh_of_item, dtype=torch.int32).repeat_interleave(V).cuda()
+    g = torch.Generator().manual_seed(5)
+    images4 = torch.rand(2, 4, 480, 640, generator=g).cuda()
+    images4[:, 3] = torch.where(images4[:, 3] < 0.1, torch.zeros_like(images4[:, 3]), 0.3 + images4[:, 3])
+    im_ids = torch.tensor([1, 0], dtype=torch.int32).cuda()
+    boxes = torch.tensor([[100.0, 80, 400, 305], [-40.0, -30, 300, 225]]).cuda()
+    tCR = torch.tensor([[0.0, 0.0, 1.2], [0.1, 0.0, 0.22]]).cuda()
+    HP, WP, SENT = h + 4, w + 4, -3.0   # the padded tensor the h x w output sits in; -3 is exact in binary16 and bfloat16 and never a value
+
+    def render(mode, compact):
+        """-> (the whole padded tensor as float32 [n_items, HP, WP, channels], number of leading channels the launch writes)"""
+        monkeypatch.setenv("MP_RASTER_COMPACT", compact)
+        rgbd = mode == "records_rgbd"
+        C = 4 if rgbd else 3
+        nper = 7 if rgbd else 6
+        obs = eng.PackedObservation(images4[:, :C].contiguous())
+        if mode.startswith("records"):
+            mask = (1 << C) - 1
+            if rgbd:
+                for v in range(V):
+                    mask |= 1 << (C + 6 + nper * v)
+            n_f32 = bin(mask).count("1")
+            R = eng.xrec_elements(n_f32, C + nper * V - n_f32)
+            x = torch.full((n_items, HP, WP, R), SENT, device="cuda", dtype=torch.bfloat16)
+            eng.raster_render(db, ids, T, K, h, w, 1 | 16 | (2 if rgbd else 0), eng.make_lights(), x, HP * WP * R, WP * R, R, C, C + 3,
+                              C + 6 if rgbd else -1, views_per_item=V, stride_view=nper, crop=(obs, im_ids, boxes, 0),
+                              xrec=(mask, tCR, 2) if rgbd else None)
+            return x.float(), R   # (a record is written whole: its padding slots are zeros)
+        Cp = 32
+        x = torch.full((n_items, HP, WP, Cp), SENT, device="cuda", dtype=torch.float16 if mode == "f16_crop" else torch.float32)
+        eng.raster_render(db, ids, T, K, h, w, 1 | 16, eng.make_lights(), x, HP * WP * Cp, WP * Cp, Cp, 3, 6, -1, views_per_item=V,
+                          stride_view=6, crop=(obs, im_ids, boxes, 0) if mode != "fp32_plain" else None)
+        return x.float(), 3 + 6 * V
+
+    out = {}
+    for mode in ("fp32_crop", "fp32_plain", "f16_crop", "records_rgb", "records_rgbd"):
+        direct, n_written = render(mode, "0")
+        compacted, _ = render(mode, "1")
+        torch.cuda.synchronize()
+        assert torch.equal(direct, compacted), f"{mode}: the compacted form differs from the direct form"                      # (b)
+        c_first = 3 if mode == "fp32_plain" else 0
+        assert (direct[:, :h, :w, c_first:n_written] != SENT).all(), f"{mode}: a pixel of a written channel was not written"
+        assert (direct[:, h:] == SENT).all() and (direct[:, :, w:] == SENT).all(), f"{mode}: written below / right of the image"
+        assert (direct[:, :h, :w, n_written:] == SENT).all() and (direct[:, :h, :w, :c_first] == SENT).all(), f"{mode}: a padding channel was written"
+        out[mode] = direct[:, :h, :w]
+    # the inputs are what the docstring says: item 0 is mostly light tiles, item 1 has heavy tiles on both ragged edges
+    views = out["fp32_plain"][..., 3:3 + 6 * V]
+    assert (views[0] > 0).any(dim=-1).float().mean() < 0.1
+    assert (views[1, 48:] > 0).any() and (views[1, :, 72:] > 0).any() and not (views[0, 48:] > 0).any()
+    # (a) the oracle, view by view
+    for v in range(n_items * V):
+        rgb, nrm = orr.render(oracle_meshes[mesh_of_item[v // V]], Tn[v:v + 1], Kn[v:v + 1], h, w, 1 | 16)[:2]
+        got = out["fp32_plain"][v // V, :, :, 3 + 6 * (v % V): 9 + 6 * (v % V)].cpu().numpy()
+        assert np.array_equal(got[..., :3], rgb[0]), f"view {v}: rgb differs from the oracle"
+        assert np.array_equal(got[..., 3:], nrm[0]), f"view {v}: normals differ from the oracle"
+    ref = out["fp32_crop"][..., :3 + 6 * V]
+    assert torch.equal(ref[..., 3:], out["fp32_plain"][..., 3:3 + 6 * V])   # the crop role leaves the views alone
+    # (c) binary16 = the fp32 values rounded to nearest even
+    assert torch.equal(out["f16_crop"][..., :3 + 6 * V], ref.half().float())
+    # (d) the RGB records, decoded
+    rec, ref = out["records_rgb"].cpu(), ref.cpu()   # (decoded on the host: IEEE fp32 addition and division)
+    crop_dec = torch.stack([(rec[..., 3 * c] + rec[..., 3 * c + 1]) + rec[..., 3 * c + 2] for c in range(3)], dim=-1)
+    k = rec[..., 9:9 + 6 * V]
+    assert torch.equal(k, k.round()) and (k >= 0).all() and (k <= 255).all()
+    assert torch.equal(torch.cat([crop_dec, k / 255.0], dim=-1), ref)
+    assert (rec[..., 9 + 6 * V:] == 0).all()   # the record's zero padding
