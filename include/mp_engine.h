@@ -548,6 +548,36 @@ int mp_vsd(const float* d_depth_est /*[n_est,h,w]*/, const int32_t* d_est_ids /*
            void* d_workspace, size_t workspace_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* BOP's ground-truth info (what the reference reads from a BOP dataset's scene_gt_info:   */
+/* evaluation/meters/utils.py:86-104 visib_fract, datasets/bop_scene_dataset.py:238-262     */
+/* bbox_visib / bbox_obj, inference/utils.py:214-225 ground-truth detections) computed from  */
+/* depth renders of the object and an observed frame (csrc/gt_info.hip; contract in          */
+/* csrc/gt_info_core.h).  Maps are fp32 metres as for mp_vsd.  The object is rendered on a    */
+/* canvas of canvas x canvas tiles of the image's size (canvas 1 or 3, tiles row-major,       */
+/* c = (canvas - 1) / 2): tile (ty, tx) is the render under K with cx - (tx - c) w and         */
+/* cy - (ty - c) h, so its pixel (x, y) is image pixel (x + (tx - c) w, y + (ty - c) h); the    */
+/* centre tile is the render under K itself and the only one compared with the frame.         */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_gt_info needs for b rows (0 for b < 0). */
+size_t mp_gt_info_workspace_bytes(int b);
+/* Row i takes canvas map d_gt_ids[i] of d_depth_gt and frame d_im_ids[i] of d_depth_test (an id array NULL: map i; the ids are the
+   caller's responsibility).  With obj = depth_gt > 0: d_counts[i] = px_count_all (obj pixels over all tiles), px_count_image (obj pixels
+   of the centre tile), px_count_valid (centre tile: obj and an observed distance > 0), px_count_visib (centre tile: mp_vsd's vis_gt under
+   K_i and delta); d_visib_fract[i] = px_count_visib / px_count_all as one fp32 division, 0 when px_count_all == 0; d_boxes[i] = inclusive
+   extents xmin ymin xmax ymax in image coordinates (-w .. 2w - 1) of the obj pixels over all tiles, then of the vis_gt pixels; a box over
+   no pixel is -1 -1 -1 -1.  d_mask / d_mask_visib [b,h,w] uint8 (0 / 255: obj / vis_gt on the centre tile) are optional (NULL to skip).
+   A row whose K has a non-finite entry gives counts and boxes of -1, NaN and zero masks.  h, w in 1..1024.  split = 0 picks the number
+   of strips of image rows a tile is cut into; > 0 forces it (counts and extents are integers: any value gives the same bits).  The
+   accumulators live in d_workspace and are initialised on `stream` inside the call.  b == 0 is a successful no-op; any other bad
+   argument returns non-zero before anything is launched. */
+int mp_gt_info(const float* d_depth_gt /*[n_gt,canvas*canvas,h,w]*/, const int32_t* d_gt_ids /*[b] or NULL: 0..b-1*/,
+               const float* d_depth_test /*[n_im,h,w]*/, const int32_t* d_im_ids, int n_gt, int n_im, const float* d_K /*[b,3,3]*/,
+               int b, int h, int w, int canvas /*1 or 3*/, float delta, int split,
+               int32_t* d_counts /*[b,4]: all, image, valid, visib*/, int32_t* d_boxes /*[b,8]: obj, visib*/,
+               float* d_visib_fract /*[b]*/, uint8_t* d_mask /*[b,h,w] or NULL*/, uint8_t* d_mask_visib /*[b,h,w] or NULL*/,
+               void* d_workspace, size_t workspace_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

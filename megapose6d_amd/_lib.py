@@ -177,6 +177,8 @@ SIGNATURES = {
     "mp_pose_error_mspd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_vsd_workspace_bytes": (_sz, [_i, _i]),
     "mp_vsd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _f, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mp_gt_info_workspace_bytes": (_sz, [_i]),
+    "mp_gt_info": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_icp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mp_icp_refine": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_icp_nn_max_points": (_i, []),

@@ -896,6 +896,50 @@ def vsd(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: torch.Tenso
 
 
 # --------------------------------------------------------------------------- #
+# BOP's ground-truth info (evaluation): csrc/gt_info.hip
+def gt_info(depth_gt: torch.Tensor, depth_test: torch.Tensor, K: torch.Tensor, canvas: int = 3, delta: float = 0.015,
+            gt_ids: Optional[torch.Tensor] = None, im_ids: Optional[torch.Tensor] = None, with_masks: bool = False,
+            split: int = 0) -> Dict[str, torch.Tensor]:
+    """BOP's gt info (mp_gt_info).  depth_gt [n_gt,canvas*canvas,h,w] metres: the object's renders on the canvas' tiles, row-major
+    ([n_gt,h,w] is taken as canvas 1); depth_test [n_im,h,w]; row i takes depth_gt[gt_ids[i]] under depth_test[im_ids[i]] (ids None:
+    map i) and K [b,3,3] -> counts [b,4] int32 (px_count_all, _image, _valid, _visib), boxes [b,8] int32 (bbox_obj then bbox_visib as
+    inclusive xmin ymin xmax ymax, -1 over no pixel), visib_fract [b] (+ mask, mask_visib [b,h,w] uint8 0 / 255).  The ids are not
+    range-checked."""
+    depth_gt, depth_test, K = _dev_f32(depth_gt), _dev_f32(depth_test), _dev_f32(K)
+    if depth_gt.dim() == 3 and canvas == 1:
+        depth_gt = depth_gt.unsqueeze(1)
+    if depth_gt.dim() != 4 or depth_test.dim() != 3 or depth_gt.shape[1] != canvas * canvas or depth_gt.shape[2:] != depth_test.shape[1:]:
+        raise EngineError(f"depth_gt must be [n_gt,{canvas * canvas},h,w] and depth_test [n_im,h,w], got {tuple(depth_gt.shape)}, {tuple(depth_test.shape)}")
+    b = K.shape[0]
+    if K.shape != (b, 3, 3):
+        raise EngineError(f"K must be [b,3,3], got {tuple(K.shape)}")
+    h, w = depth_test.shape[1:]
+    ids = []
+    for name, i, maps in (("gt_ids", gt_ids, depth_gt), ("im_ids", im_ids, depth_test)):
+        if i is None:
+            if maps.shape[0] < b:
+                raise EngineError(f"without {name} the maps are per row: need {b}, got {maps.shape[0]}")
+        else:
+            i = _dev_i32(i)
+            if i.shape != (b,):
+                raise EngineError(f"{name} must be [b], got {tuple(i.shape)}")
+        ids.append(i)
+    dev = K.device
+    out = dict(counts=torch.empty(b, 4, dtype=torch.int32, device=dev), boxes=torch.empty(b, 8, dtype=torch.int32, device=dev),
+               visib_fract=torch.empty(b, dtype=torch.float32, device=dev))
+    if with_masks:
+        out["mask"] = torch.empty(b, h, w, dtype=torch.uint8, device=dev)
+        out["mask_visib"] = torch.empty(b, h, w, dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.mp_gt_info_workspace_bytes(b)), 256), dtype=torch.uint8, device=dev)
+    check(lib.mp_gt_info(depth_gt.data_ptr(), _ptr(ids[0]), depth_test.data_ptr(), _ptr(ids[1]), depth_gt.shape[0], depth_test.shape[0],
+                         K.data_ptr(), b, h, w, int(canvas), float(delta), int(split), out["counts"].data_ptr(), out["boxes"].data_ptr(),
+                         out["visib_fract"].data_ptr(), _ptr(out.get("mask")), _ptr(out.get("mask_visib")), ws.data_ptr(), ws.numel(),
+                         _stream()))
+    return out
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

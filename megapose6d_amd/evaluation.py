@@ -4,7 +4,8 @@ The arithmetic of the reference's evaluation side -- src/megapose/evaluation/uti
 (compute_errors), :175-238 (mssd_torch) and evaluation/meters/modelnet_meters.py:46-103 (ADD, 2D projection error, 5 deg / 5 cm) --
 as launches of csrc/pose_error.hip -- and the three pose errors of the BOP challenge 2019, whose recalls average to the "BOP score"
 the reference's tables report: VSD (csrc/vsd.hip, on depth renders of `Panda3dBatchRenderer.render_depth`), MSSD and MSPD
-(`bop_errors`, `bop_recall`).  Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
+(`bop_errors`, `bop_recall`) -- and the annotation BOP calls gt info (csrc/gt_info.hip: visibility fraction, masks, modal and
+amodal boxes; `gt_info`, `detections_from_gt_info`), which the reference reads from a BOP dataset's files.  Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
 
 Where this departs from the reference, on purpose:
   * symmetric objects are evaluated on ALL their model points, not on the seven stand-in points of `create_default_object_pts`
@@ -14,7 +15,9 @@ Where this departs from the reference, on purpose:
   * the rotation error is the angle of R2 R1^T by atan2, not the norm of a rotation vector recovered through acos;
   * VSD compares this engine's depth renders (one sample at each pixel centre, the rasteriser's fill rule), not `bop_toolkit`'s
     renderer (absent): pixels on a silhouette edge are unpinned against the toolkit.  Only BOP 2019's form is built (visibility
-    "bop19", step cost).
+    "bop19", step cost);
+  * `gt_info` blanks each box only when its own mask is empty; `bop_toolkit` (absent, so unpinned) blanks both boxes when nothing is
+    visible.  Its silhouette pixels are this engine's fill rule, as for VSD.
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ import pandas as pd
 import torch
 
 from . import engine as eng
+from .tcoll import PandasTensorCollection
 
 _REDUCE = {"mean": eng.POSE_ERROR_MEAN, "max": eng.POSE_ERROR_MAX}
 
@@ -239,10 +243,17 @@ def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
     return df
 
 
-def bop_recall(df: pd.DataFrame, image_width: int = 640) -> Dict[str, float]:
+def bop_recall(df: pd.DataFrame, image_width: int = 640, valid=None) -> Dict[str, float]:
     """BOP 2019 average recalls of the table of `bop_errors` (host arithmetic): ar_vsd = the share of (row, tau, theta) with vsd_tau <
     theta, ar_mssd = the share of (row, theta) with mssd < theta * diameter, both over theta = 0.05 ... 0.50; ar_mspd = the share of
-    (row, theta) with mspd < theta * image_width / 640 over theta = 5 ... 50 px; ar = their mean.  NaN rows are misses."""
+    (row, theta) with mspd < theta * image_width / 640 over theta = 5 ... 50 px; ar = their mean.  NaN rows are misses.
+      valid  optional boolean mask (array, or Series indexed like `df`) of the rows that are targets, e.g. `gt_info(...)["visib_fract"]
+             >= 0.1` taken at each row's ground truth (evaluation/meters/utils.py:86-104); the recalls are those of `df[valid]`."""
+    if valid is not None:
+        valid = valid.reindex(df.index).to_numpy() if isinstance(valid, pd.Series) else np.asarray(valid)
+        if valid.dtype != np.bool_ or valid.shape != (len(df),):
+            raise ValueError("valid must be one boolean per row of the table")
+        df = df[valid]
     thetas = np.asarray(BOP_THRESHOLDS, np.float64)
     cols = [c for c in df.columns if re.fullmatch(r"vsd_\d+\.\d+", c)]
     if not cols or len(df) == 0:
@@ -253,3 +264,129 @@ def bop_recall(df: pd.DataFrame, image_width: int = 640) -> Dict[str, float]:
     thetas_px = np.arange(5, 51, 5).astype(np.float64) * (float(image_width) / 640.0)
     ar_mspd = float((df["mspd"].to_numpy(np.float64)[:, None] < thetas_px[None, :]).mean())
     return {"ar_vsd": ar_vsd, "ar_mssd": ar_mssd, "ar_mspd": ar_mspd, "ar": (ar_vsd + ar_mssd + ar_mspd) / 3.0}
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# BOP's ground-truth info: visibility, masks, boxes
+# --------------------------------------------------------------------------------------------------------------------------------
+GT_INFO_COUNTS = ("px_count_all", "px_count_image", "px_count_valid", "px_count_visib")
+
+
+def tile_intrinsics(K: torch.Tensor, canvas: int, resolution) -> torch.Tensor:
+    """K [n,3,3] -> [n,canvas*canvas,3,3]: the intrinsics of the canvas' tiles, row-major, cx' = cx - (tx - c) * w and cy' = cy - (ty - c)
+    * h with c = (canvas - 1) / 2, one fp32 subtraction each (the shifts are integers: exact)."""
+    if canvas not in (1, 3):
+        raise ValueError(f"canvas {canvas} is not 1 or 3")
+    h, w = resolution
+    c = (canvas - 1) // 2
+    t = torch.arange(canvas * canvas, device=K.device)
+    Kt = K.to(torch.float32)[:, None].repeat(1, canvas * canvas, 1, 1)
+    Kt[:, :, 0, 2] = Kt[:, :, 0, 2] - ((t % canvas - c) * w).to(torch.float32)[None]
+    Kt[:, :, 1, 2] = Kt[:, :, 1, 2] - ((torch.div(t, canvas, rounding_mode="floor") - c) * h).to(torch.float32)[None]
+    return Kt
+
+
+def _bop_box(ext, count) -> list:
+    """inclusive [xmin, ymin, xmax, ymax] -> BOP's [x, y, w, h] with w = xmax - xmin; [-1] * 4 over no pixel"""
+    if count <= 0:
+        return [-1, -1, -1, -1]
+    return [int(ext[0]), int(ext[1]), int(ext[2] - ext[0]), int(ext[3] - ext[1])]
+
+
+def gt_info_table(counts: np.ndarray, boxes: np.ndarray, visib_fract: np.ndarray, index=None) -> pd.DataFrame:
+    """counts [n,4], boxes [n,8] (inclusive extents: obj, visib), visib_fract [n] of `engine.gt_info`, on the host -> the table of
+    `gt_info`.  Whether a box is blank is read from its count (a one-pixel box at image pixel (-1, -1) has the blank's numbers)."""
+    counts, boxes = np.asarray(counts).astype(np.int64), np.asarray(boxes).astype(np.int64)
+    df = pd.DataFrame({name: counts[:, k] for k, name in enumerate(GT_INFO_COUNTS)}, index=index)
+    df["visib_fract"] = np.asarray(visib_fract, np.float64)
+    n_obj, n_vis = counts[:, 0], counts[:, 3]
+    amodal = [[int(v) for v in boxes[i, :4]] if n_obj[i] > 0 else [-1] * 4 for i in range(len(counts))]
+    modal = [[int(v) for v in boxes[i, 4:]] if n_vis[i] > 0 else [-1] * 4 for i in range(len(counts))]
+    df["bbox_obj"] = [_bop_box(boxes[i, :4], n_obj[i]) for i in range(len(counts))]
+    df["bbox_visib"] = [_bop_box(boxes[i, 4:], n_vis[i]) for i in range(len(counts))]
+    df["bbox_amodal"] = amodal
+    df["bbox_modal"] = modal
+    return df
+
+
+def gt_info(gt, renderer, depth: torch.Tensor, K: torch.Tensor, delta: float = 0.015, canvas: int = 3, return_masks: bool = False):
+    """BOP's gt info of the objects of `gt` (`infos` with `label` and `batch_im_id`, `poses`) -> a DataFrame aligned with `gt.infos`:
+      px_count_all    pixels of the object's silhouette on a canvas of canvas x canvas images around the image (BOP renders on 3 x 3, so
+                      that the part outside the frame counts and visib_fract accounts for truncation)
+      px_count_image  of those, the pixels inside the image; px_count_valid  of those, the pixels with an observed depth
+      px_count_visib  pixels where the object is visible under the observed depth (the "bop19" rule of VSD, tolerance delta)
+      visib_fract     px_count_visib / px_count_all (0 for an object off the canvas)
+      bbox_obj, bbox_visib      BOP's [x, y, w, h] with w = xmax - xmin of the whole silhouette (x, y can be negative) / of the visible part
+      bbox_amodal, bbox_modal   the same boxes as the reference's ObjectData holds them, [xmin, ymin, xmax, ymax]
+                                (datasets/bop_scene_dataset.py:238-262)
+    A box over no pixel is [-1, -1, -1, -1].  With return_masks also (mask, mask_visib), two [n,H,W] uint8 tensors (0 / 255, BOP's PNG
+    format) that stay on the device.
+      renderer  a Panda3dBatchRenderer of the same objects (its `render_depth`: one sample at each pixel centre)
+      depth     [n_im,H,W] observed frames in metres, K [n_im,3,3]; both indexed by `gt.infos.batch_im_id`.  `depth` may just as well be
+                the depth of a `Panda3dSceneRenderer.render_scenes` call: then the occluders are the other objects of a synthetic scene.
+    Every row's canvas*canvas tiles are rendered, BOP_DEPTH_BYTES (256 MiB) of depth maps at a time.  A row with a non-finite pose is not
+    handed to the rasteriser (a placeholder is rendered) and gives counts and boxes of -1 and NaN, as does a non-finite K.  One
+    synchronising copy at the end.
+    Known deviation: each box is blank only when its own mask is empty; `bop_toolkit` (absent here, so this is unpinned against it)
+    blanks both boxes when nothing is visible.  Silhouette pixels are this engine's fill rule."""
+    n = len(gt.infos)
+    labels = list(gt.infos["label"])
+    im = gt.infos["batch_im_id"].to_numpy().astype(np.int64)
+    dev = depth.device if depth.is_cuda else torch.device("cuda")
+    depth = depth.to(device=dev, dtype=torch.float32).contiguous()
+    K = K.to(device=dev, dtype=torch.float32)
+    if depth.dim() != 3 or K.shape != (depth.shape[0], 3, 3) or (n and (im.min() < 0 or im.max() >= depth.shape[0])):
+        raise ValueError("depth must be [n_im,H,W], K [n_im,3,3], and batch_im_id must index them")
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    n_tiles = canvas * canvas
+    im_t = torch.from_numpy(im).to(dev)
+    T = gt.poses.to(device=dev, dtype=torch.float32)
+    K_rows = K[im_t].contiguous()
+    # a non-finite pose or K is not handed to the rasteriser: a placeholder is rendered and the row's results are set to -1 / NaN
+    bad = ~(torch.isfinite(T).flatten(1).all(1) & torch.isfinite(K_rows).flatten(1).all(1))
+    place = torch.eye(4, device=dev)
+    place[2, 3] = 1.0
+    K_place = torch.tensor([[float(W), 0.0, 0.5 * W], [0.0, float(W), 0.5 * H], [0.0, 0.0, 1.0]], device=dev)
+    R = torch.where(bad[:, None, None], place, T)
+    K_tiles = tile_intrinsics(torch.where(bad[:, None, None], K_place, K_rows), canvas, (H, W))
+    im32 = im_t.to(torch.int32)
+    counts = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    boxes = torch.empty(n, 8, dtype=torch.int32, device=dev)
+    fract = torch.empty(n, dtype=torch.float32, device=dev)
+    masks = [torch.empty(n, H, W, dtype=torch.uint8, device=dev) for _ in range(2)] if return_masks else None
+    rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4 * n_tiles))
+    for r0 in range(0, n, rows_per_launch):
+        r1 = min(n, r0 + rows_per_launch)
+        tiles = renderer.render_depth([l for l in labels[r0:r1] for _ in range(n_tiles)], R[r0:r1].repeat_interleave(n_tiles, dim=0),
+                                      K_tiles[r0:r1].flatten(0, 1), (H, W)).view(r1 - r0, n_tiles, H, W)
+        out = eng.gt_info(tiles, depth, K_rows[r0:r1].contiguous(), canvas=canvas, delta=delta, im_ids=im32[r0:r1].contiguous(),
+                          with_masks=return_masks)
+        counts[r0:r1], boxes[r0:r1], fract[r0:r1] = out["counts"], out["boxes"], out["visib_fract"]
+        if return_masks:
+            masks[0][r0:r1], masks[1][r0:r1] = out["mask"], out["mask_visib"]
+    counts = torch.where(bad[:, None], torch.full_like(counts, -1), counts)
+    boxes = torch.where(bad[:, None], torch.full_like(boxes, -1), boxes)
+    fract = torch.where(bad, torch.full_like(fract, float("nan")), fract)
+    table = torch.cat([counts.double(), boxes.double(), fract.double()[:, None]], dim=1).cpu().numpy()   # the one synchronising copy
+    df = gt_info_table(table[:, :4], table[:, 4:12], table[:, 12], index=gt.infos.index)
+    if not return_masks:
+        return df
+    for m in masks:
+        m[bad] = 0
+    return df, masks[0], masks[1]
+
+
+def detections_from_gt_info(gt, info: pd.DataFrame, visib_gt_min: float = 0.0) -> PandasTensorCollection:
+    """Ground-truth detections for the pose estimator (the counterpart of the reference's make_detections_from_object_data,
+    inference/utils.py:214-225): infos `label`, `batch_im_id`, `instance_id` of the rows of `gt` that have a visible pixel and
+    visib_fract >= visib_gt_min, `bboxes` [m,4] float32 = their bbox_modal.  `info` is the table of `gt_info`, row-aligned with
+    `gt.infos`; `instance_id` is the one of `gt.infos` when it has one, else the row's position in `gt`."""
+    if len(info) != len(gt.infos):
+        raise ValueError("info must have one row per row of gt")
+    keep = (info["px_count_visib"].to_numpy() > 0) & (info["visib_fract"].to_numpy() >= float(visib_gt_min))
+    src = gt.infos.reset_index(drop=True)
+    inst = src["instance_id"].to_numpy() if "instance_id" in src else np.arange(len(src))
+    infos = pd.DataFrame(dict(label=src["label"].to_numpy()[keep], batch_im_id=src["batch_im_id"].to_numpy()[keep], instance_id=inst[keep]))
+    rows = [b for b, k in zip(info["bbox_modal"], keep) if k]
+    bboxes = torch.as_tensor(np.asarray(rows, np.float32).reshape(-1, 4))
+    return PandasTensorCollection(infos=infos, bboxes=bboxes)

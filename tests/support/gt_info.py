@@ -1,0 +1,149 @@
+"""TEST SUPPORT: ctypes wrapper of the host emulation of the ground-truth-info kernels (tests/gt_info_emul.cpp), built on first use, an
+independent float64 restatement of the definition (written from the definition, not from the arithmetic headers: it stitches the tiles
+into one canvas and looks at that) with the borderline-pixel census of `support.vsd.f64_vsd`, and the seeded cases the CPU contract test
+and the GPU test share."""
+from __future__ import annotations
+
+import ctypes as C
+import subprocess
+from pathlib import Path
+from typing import Dict, Optional
+
+import numpy as np
+
+from . import vsd as vs
+
+ROOT = Path(__file__).resolve().parent.parent.parent
+LIB = ROOT / "tests" / "_build" / "libgt_info_emul.so"
+_CSRC = ROOT / "megapose6d_amd" / "csrc"
+_SRCS = [ROOT / "tests" / "gt_info_emul.cpp", _CSRC / "gt_info_core.h", _CSRC / "vsd_core.h"]
+_lib = None
+
+ULP = vs.ULP
+BAND_ROUNDINGS = vs.BAND_ROUNDINGS    # band of a borderline pixel = 16 * 2^-24 * D_max: the derivation of tests/test_vsd_contract_cpu.py
+COUNT_NAMES = ("px_count_all", "px_count_image", "px_count_valid", "px_count_visib")
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
+            LIB.parent.mkdir(exist_ok=True)
+            tmp = LIB.with_suffix(".tmp.so")
+            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I", str(_CSRC),
+                            "-o", str(tmp), str(_SRCS[0])], check=True)
+            tmp.replace(LIB)
+        _lib = C.CDLL(str(LIB))
+        _lib.gt_info_emul.restype = None
+    return _lib
+
+
+def _p(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def gt_info(depth_gt, depth_test, K, canvas=3, delta=0.015, gt_ids=None, im_ids=None, with_masks=True) -> Dict[str, np.ndarray]:
+    """Same addressing as megapose6d_amd.engine.gt_info: depth_gt [n_gt, canvas^2, h, w], depth_test [n_im, h, w], K [b,3,3]
+    -> counts [b,4] int32, boxes [b,8] int32, visib_fract [b] float32, mask / mask_visib [b,h,w] uint8"""
+    depth_gt, depth_test, K = (np.ascontiguousarray(a, np.float32) for a in (depth_gt, depth_test, K))
+    gt_ids = None if gt_ids is None else np.ascontiguousarray(gt_ids, np.int32)
+    im_ids = None if im_ids is None else np.ascontiguousarray(im_ids, np.int32)
+    b = K.shape[0]
+    n_gt, n_tiles, h, w = depth_gt.shape
+    assert n_tiles == canvas * canvas and canvas in (1, 3) and depth_test.shape[1:] == (h, w) and K.shape == (b, 3, 3)
+    for ids, maps in ((gt_ids, depth_gt), (im_ids, depth_test)):
+        assert (maps.shape[0] >= b) if ids is None else (ids.shape == (b,) and (b == 0 or (ids.min() >= 0 and ids.max() < maps.shape[0])))
+    out = dict(counts=np.empty((b, 4), np.int32), boxes=np.empty((b, 8), np.int32), visib_fract=np.empty(b, np.float32))
+    if with_masks:
+        out["mask"], out["mask_visib"] = np.empty((b, h, w), np.uint8), np.empty((b, h, w), np.uint8)
+    load().gt_info_emul(_p(depth_gt), _p(gt_ids), _p(depth_test), _p(im_ids), _p(K), C.c_int(b), C.c_int(h), C.c_int(w), C.c_int(canvas),
+                        C.c_float(delta), _p(out["counts"]), _p(out["boxes"]), _p(out["visib_fract"]), _p(out.get("mask")), _p(out.get("mask_visib")))
+    return out
+
+
+# float64 restatement of the definition on the same fp32 inputs --------------------------------------------------------------------------
+def _extents(m: np.ndarray, x_off: int, y_off: int):
+    """inclusive [xmin, ymin, xmax, ymax] of the set pixels of m, shifted; [-1] * 4 over no pixel"""
+    ys, xs = np.nonzero(m)
+    if len(ys) == 0:
+        return [-1, -1, -1, -1]
+    return [int(xs.min()) + x_off, int(ys.min()) + y_off, int(xs.max()) + x_off, int(ys.max()) + y_off]
+
+
+def f64_gt_info(depth_gt, depth_test, K, canvas=3, delta=0.015, gt_ids=None, im_ids=None) -> Dict[str, np.ndarray]:
+    """-> counts [b,4] int64, boxes [b,8] int64, visib_fract [b], mask / mask_visib [b,h,w] bool, borderline [b] (pixels of the object
+    under an observed depth whose dist_gt - dist_test - delta lies within 16 * 2^-24 * D_max of zero: only px_count_visib and bbox_visib
+    can depend on them), near [b,h,w] bool (where they are), d_max [b]"""
+    K = np.asarray(np.asarray(K, np.float32), np.float64)
+    depth_gt = np.asarray(depth_gt, np.float32)
+    delta = float(np.float32(delta))
+    b = K.shape[0]
+    n_gt, n_tiles, h, w = depth_gt.shape
+    assert n_tiles == canvas * canvas
+    c = (canvas - 1) // 2
+    counts, boxes, fract = np.zeros((b, 4), np.int64), np.zeros((b, 8), np.int64), np.full(b, np.nan)
+    mask, mask_visib, near = (np.zeros((b, h, w), bool) for _ in range(3))
+    border, d_max = np.zeros(b, np.int64), np.zeros(b)
+    xs, ys = np.arange(w, dtype=np.float64)[None, :], np.arange(h, dtype=np.float64)[:, None]
+    for i in range(b):
+        if not np.isfinite(K[i]).all():
+            counts[i], boxes[i] = -1, -1
+            continue
+        tiles = depth_gt[i if gt_ids is None else gt_ids[i]]
+        # the whole canvas as one picture: tile (ty, tx) sits at rows ty*h .., columns tx*w ..; image pixel (0, 0) is canvas pixel (c*w, c*h)
+        whole = np.block([[tiles[ty * canvas + tx] for tx in range(canvas)] for ty in range(canvas)]) > 0
+        image = whole[c * h:(c + 1) * h, c * w:(c + 1) * w]
+        u = (xs + 0.5 - K[i, 0, 2]) / K[i, 0, 0]
+        v = (ys + 0.5 - K[i, 1, 2]) / K[i, 1, 1]
+        r = np.sqrt(u * u + v * v + 1.0)
+        z_test = np.asarray(depth_test[i if im_ids is None else im_ids[i]], np.float64)
+        z_test = np.where(np.isfinite(z_test) & (z_test >= 0), z_test, 0.0)
+        d_gt, d_test = np.asarray(tiles[c * canvas + c], np.float64) * r, z_test * r
+        d_max[i] = max(d_gt.max(), d_test.max())
+        observed = d_test > 0
+        vis = image & (~observed | (d_gt - d_test <= delta))
+        near[i] = image & observed & (np.abs(d_gt - d_test - delta) <= BAND_ROUNDINGS * ULP * d_max[i])
+        border[i] = near[i].sum()
+        counts[i] = [whole.sum(), image.sum(), (image & observed).sum(), vis.sum()]
+        fract[i] = 0.0 if counts[i, 0] == 0 else counts[i, 3] / counts[i, 0]
+        boxes[i, :4] = _extents(whole, -c * w, -c * h)
+        boxes[i, 4:] = _extents(vis, 0, 0)
+        mask[i], mask_visib[i] = image, vis
+    return dict(counts=counts, boxes=boxes, visib_fract=fract, mask=mask, mask_visib=mask_visib, borderline=border, near=near, d_max=d_max)
+
+
+def visib_box_range(r: Dict[str, np.ndarray], i: int):
+    """row i of f64_gt_info's result -> (inner, outer): bbox_visib without any borderline pixel and with every one of them.  A bound on
+    which the two agree has no borderline pixel as its unique extreme."""
+    return _extents(r["mask_visib"][i] & ~r["near"][i], 0, 0), _extents(r["mask_visib"][i] | r["near"][i], 0, 0)
+
+
+# seeded cases shared by the CPU contract test and the GPU test ----------------------------------------------------------------------------
+def case(seed, b, h, w, canvas, n_gt=None, n_im=None, share=False, variant=None) -> Dict[str, np.ndarray]:
+    """`support.vsd.scene`'s ground-truth maps as centre tiles and its observed frames; for canvas 3 eight outer tiles made of the same
+    blob, shifted and cut by a half-plane (two of them left empty).  variant "empty_centre": nothing in the image itself;
+    "seam": the blob runs over the seam between the left tile and the centre tile (image columns -1 and 0 are both covered)."""
+    s = vs.scene(seed, b, h, w, n_im=n_im, n_gt=n_gt, share=share)
+    rng = np.random.RandomState(seed + 7919)
+    gts = s["gt"]
+    n, centre = gts.shape[0], (canvas * canvas - 1) // 2
+    tiles = np.zeros((n, canvas * canvas, h, w), np.float32)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for g in range(n):
+        for t in range(canvas * canvas):
+            if t == centre:
+                tiles[g, t] = gts[g]
+            elif t not in (0, 8):
+                moved = np.roll(np.roll(gts[g], rng.randint(-h // 3, h // 3 + 1), axis=0), rng.randint(-w // 3, w // 3 + 1), axis=1)
+                keep = (xx * rng.uniform(-1, 1) + yy * rng.uniform(-1, 1)) <= rng.uniform(-0.2, 0.4) * max(h, w)
+                tiles[g, t] = np.where(keep, moved, 0.0)
+    if variant == "empty_centre":
+        tiles[:, centre] = 0.0
+    elif variant == "seam":
+        assert canvas == 3
+        rows = slice(h // 4, h - h // 4)
+        z = gts[:, h // 2, w // 2][:, None, None]
+        tiles[:, centre, rows, :2] = z
+        tiles[:, centre - 1] = 0.0
+        tiles[:, centre - 1, rows, w - 3:] = z
+    return dict(gt=tiles, test=s["test"], K=s["K"], gt_ids=s["gt_ids"], im_ids=s["im_ids"], canvas=canvas)
