@@ -578,6 +578,42 @@ int mp_gt_info(const float* d_depth_gt /*[n_gt,canvas*canvas,h,w]*/, const int32
                void* d_workspace, size_t workspace_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* BOP's greedy matching of pose estimates to ground truths (what the reference does in    */
+/* pandas: evaluation/meters/utils.py:51-83 get_top_n_ids, :120-152 match_poses on          */
+/* cand[cand.error < theta]), every (group, error column, threshold) problem in one launch   */
+/* (csrc/bop_match.hip; contract in csrc/bop_match_core.h).  A group is one (image, label);  */
+/* an estimate or a ground truth belongs to one group.  THE INDEX the caller builds:         */
+/*   candidates sorted by (group, walk order of their estimate, gt_row), where a group's      */
+/*   estimates are walked by decreasing score, ties by ascending pred_row:                    */
+/*     d_errs [C,E], d_cand_gt [C] = gt_row, d_cand_lgt [C] = the number of that ground truth  */
+/*     inside its group, 0 .. d_group_n_gt[g] - 1 by ascending gt_row;                         */
+/*   listed estimates (those with a candidate) in the same order:                             */
+/*     d_est_row [n_est] = pred_row, d_est_off [n_est+1] = first candidate of each;            */
+/*   groups: d_group_est_off [n_groups+1] = first listed estimate of each, d_group_n_gt        */
+/*     [n_groups], d_group_taken_off [n_groups+1] = running sum of ceil(d_group_n_gt / 32)     */
+/*     (n_taken_words = its last entry), d_n_top [n_groups] (or NULL: all 0),                  */
+/*     d_thr [n_groups,E,n_theta] float64.                                                     */
+/* The index is the caller's responsibility: it is not range-checked.                         */
+/* ------------------------------------------------------------------------------------ */
+/* what mp_bop_match was built for: E <= max_errors, n_theta <= max_thetas; a group with at most mask_bits ground truths and walked
+   candidates * E <= stage_floats takes the fast path (any other group the general one, with the same results). */
+int mp_bop_match_limits(int* max_errors, int* max_thetas, int* mask_bits, int* stage_floats);
+/* bytes of device scratch mp_bop_match needs (0 for arguments it rejects). */
+size_t mp_bop_match_workspace_bytes(int n_taken_words, int E, int n_theta);
+/* d_match [P,E,n_theta] = for problem (group, e, k), walking the group's first n_top estimates (0: all) in the index's order, each
+   estimate takes, among its candidates whose ground truth no earlier estimate of the walk took and with (double)err < thr[group,e,k]
+   (strict, float64; never for NaN), the one of the smallest error, the first in gt_row order on an exact tie; -1 for no match, for an
+   estimate without candidates and for one cut by n_top.  E, n_theta in 1..16.  P == 0 is a successful no-op, C == 0 (or no listed
+   estimate, or no group) writes -1 everywhere and launches nothing; any bad argument (a null pointer where one is needed, a negative
+   count, E or n_theta out of range, a workspace too small) returns non-zero before anything is launched. */
+int mp_bop_match(const float* d_errs /*[C,E]*/, const int32_t* d_cand_gt /*[C]*/, const int32_t* d_cand_lgt /*[C]*/,
+                 const int32_t* d_est_row /*[n_est]*/, const int32_t* d_est_off /*[n_est+1]*/,
+                 const int32_t* d_group_est_off /*[n_groups+1]*/, const int32_t* d_group_n_gt /*[n_groups]*/,
+                 const int32_t* d_group_taken_off /*[n_groups+1]*/, const int32_t* d_n_top /*[n_groups] or NULL*/,
+                 const double* d_thr /*[n_groups,E,n_theta]*/, int P, int C, int n_est, int n_groups, int n_taken_words, int E,
+                 int n_theta, int32_t* d_match /*[P,E,n_theta]*/, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

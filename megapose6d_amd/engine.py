@@ -940,6 +940,58 @@ def gt_info(depth_gt: torch.Tensor, depth_test: torch.Tensor, K: torch.Tensor, c
 
 
 # --------------------------------------------------------------------------- #
+# BOP's greedy matching (evaluation): csrc/bop_match.hip
+BOP_MATCH_MAX_ERRORS = 16            # E
+BOP_MATCH_MAX_THETAS = 16            # n_theta
+BOP_MATCH_MASK_BITS = 64             # fast path: ground truths of a group
+BOP_MATCH_STAGE_FLOATS = 4096        # fast path: walked candidates of a group * E
+BOP_MATCH_INDEX = ("cand_gt", "cand_lgt", "est_row", "est_off", "group_est_off", "group_n_gt", "group_taken_off")
+
+
+def bop_match_limits() -> Dict[str, int]:
+    """what the library was built for (mp_bop_match_limits); the constants above restate it"""
+    v = [C.c_int(0) for _ in range(4)]
+    check(_lib.load().mp_bop_match_limits(*[C.byref(x) for x in v]))
+    return dict(zip(("max_errors", "max_thetas", "mask_bits", "stage_floats"), (int(x.value) for x in v)))
+
+
+def bop_match(errs: torch.Tensor, index: Dict[str, torch.Tensor], thr: torch.Tensor, n_pred: int,
+              n_top: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """BOP's greedy matching (mp_bop_match).  errs [C,E] float32 in the index's candidate order; index = the int32 tensors
+    BOP_MATCH_INDEX as include/mp_engine.h lays them out plus the host int `n_taken_words` (`evaluation.bop_match_index` builds
+    them); thr [n_groups,E,n_theta] float64;
+    n_top [n_groups] int32 or None -> match [n_pred,E,n_theta] int32 (gt_row or -1).  The index is not range-checked."""
+    errs = _dev_f32(errs)
+    if errs.dim() != 2:
+        raise EngineError(f"errs must be [C,E], got {tuple(errs.shape)}")
+    dev = errs.device
+    c, e = errs.shape
+    ix = {k: _dev_i32(index[k]) for k in BOP_MATCH_INDEX}
+    thr = thr.to(device=dev, dtype=torch.float64).contiguous()
+    if thr.dim() != 3 or thr.shape[1] != e:
+        raise EngineError(f"thr must be [n_groups,{e},n_theta], got {tuple(thr.shape)}")
+    n_groups, _, n_theta = thr.shape
+    n_est = ix["est_row"].shape[0]
+    if ix["cand_gt"].shape != (c,) or ix["cand_lgt"].shape != (c,) or ix["est_off"].shape != (n_est + 1,) \
+            or ix["group_est_off"].shape != (n_groups + 1,) or ix["group_n_gt"].shape != (n_groups,) \
+            or ix["group_taken_off"].shape != (n_groups + 1,):
+        raise EngineError("the index does not fit errs [C,E] and thr [n_groups,E,n_theta]")
+    if n_top is not None:
+        n_top = _dev_i32(n_top)
+        if n_top.shape != (n_groups,):
+            raise EngineError(f"n_top must be [n_groups], got {tuple(n_top.shape)}")
+    n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
+    match = torch.empty(int(n_pred), e, n_theta, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = torch.empty(max(int(lib.mp_bop_match_workspace_bytes(n_words, e, n_theta)), 256), dtype=torch.uint8, device=dev)
+    check(lib.mp_bop_match(errs.data_ptr(), ix["cand_gt"].data_ptr(), ix["cand_lgt"].data_ptr(), ix["est_row"].data_ptr(),
+                           ix["est_off"].data_ptr(), ix["group_est_off"].data_ptr(), ix["group_n_gt"].data_ptr(),
+                           ix["group_taken_off"].data_ptr(), _ptr(n_top), thr.data_ptr(), int(n_pred), c, n_est, n_groups, n_words, e, n_theta,
+                           match.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return match
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

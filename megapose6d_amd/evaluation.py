@@ -5,7 +5,10 @@ The arithmetic of the reference's evaluation side -- src/megapose/evaluation/uti
 as launches of csrc/pose_error.hip -- and the three pose errors of the BOP challenge 2019, whose recalls average to the "BOP score"
 the reference's tables report: VSD (csrc/vsd.hip, on depth renders of `Panda3dBatchRenderer.render_depth`), MSSD and MSPD
 (`bop_errors`, `bop_recall`) -- and the annotation BOP calls gt info (csrc/gt_info.hip: visibility fraction, masks, modal and
-amodal boxes; `gt_info`, `detections_from_gt_info`), which the reference reads from a BOP dataset's files.  Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
+amodal boxes; `gt_info`, `detections_from_gt_info`), which the reference reads from a BOP dataset's files -- and the step that joins
+detections that carry scores to ground-truth instances, BOP's greedy matching (csrc/bop_match.hip; evaluation/meters/utils.py:51-152
+get_top_n_ids, add_valid_gt, get_candidate_matches, match_poses): `bop_candidates`, `bop_candidate_errors`, `bop_match`, `bop_scores`.
+Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
 
 Where this departs from the reference, on purpose:
   * symmetric objects are evaluated on ALL their model points, not on the seven stand-in points of `create_default_object_pts`
@@ -22,7 +25,7 @@ Where this departs from the reference, on purpose:
 from __future__ import annotations
 
 import re
-from typing import Dict, Optional, Sequence
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -177,6 +180,22 @@ def _vsd_names(taus) -> list:
     return [f"vsd_{t:.2f}" for t in taus]
 
 
+def _bop_frames(depth: torch.Tensor, K: torch.Tensor, im: np.ndarray, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the observed frames and their intrinsics on the device, checked against the rows' batch_im_id"""
+    depth = depth.to(device=dev, dtype=torch.float32).contiguous()
+    K = K.to(device=dev, dtype=torch.float32)
+    if depth.dim() != 3 or K.shape != (depth.shape[0], 3, 3) or (len(im) and (im.min() < 0 or im.max() >= depth.shape[0])):
+        raise ValueError("depth must be [n_im,H,W], K [n_im,3,3], and batch_im_id must index them")
+    return depth, K
+
+
+def _placeholder_pose(dev) -> torch.Tensor:
+    """what is rendered in the place of a non-finite pose: the object one metre down the optical axis"""
+    place = torch.eye(4, device=dev)
+    place[2, 3] = 1.0
+    return place
+
+
 def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, gt_index=None, delta: float = 0.015,
                taus: Optional[Sequence[float]] = None) -> pd.DataFrame:
     """The three BOP 2019 errors of `pred.poses` -> a DataFrame aligned with `pred.infos`: vsd_0.05 ... vsd_0.50 (one per tau), mssd
@@ -195,10 +214,7 @@ def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
     if gt_index.shape != (n,) or (n and (gt_index.min() < 0 or gt_index.max() >= len(gt.infos))):
         raise ValueError("gt_index must name one row of `gt` per prediction")
     im = pred.infos["batch_im_id"].to_numpy().astype(np.int64)
-    depth = depth.to(device=dev, dtype=torch.float32).contiguous()
-    K = K.to(device=dev, dtype=torch.float32)
-    if depth.dim() != 3 or K.shape != (depth.shape[0], 3, 3) or (n and (im.min() < 0 or im.max() >= depth.shape[0])):
-        raise ValueError("depth must be [n_im,H,W], K [n_im,3,3], and batch_im_id must index them")
+    depth, K = _bop_frames(depth, K, im, dev)
     H, W = int(depth.shape[1]), int(depth.shape[2])
     im_t = torch.from_numpy(im).to(dev)
     T_pred = pred.poses.to(device=dev, dtype=torch.float32).contiguous()
@@ -213,8 +229,7 @@ def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
     diam_t = torch.tensor(diam_rows, dtype=torch.float32, device=dev)
     # a non-finite pose is not handed to the rasteriser: a placeholder is rendered and the row's errors are set to NaN
     bad = ~(torch.isfinite(T_pred).flatten(1).all(1) & torch.isfinite(T_gt).flatten(1).all(1))
-    place = torch.eye(4, device=dev)
-    place[2, 3] = 1.0
+    place = _placeholder_pose(dev)
     R_pred = torch.where(bad[:, None, None], place, T_pred)
     R_gt = torch.where(bad[:, None, None], place, T_gt)
     rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
@@ -390,3 +405,261 @@ def detections_from_gt_info(gt, info: pd.DataFrame, visib_gt_min: float = 0.0) -
     rows = [b for b, k in zip(info["bbox_modal"], keep) if k]
     bboxes = torch.as_tensor(np.asarray(rows, np.float32).reshape(-1, 4))
     return PandasTensorCollection(infos=infos, bboxes=bboxes)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# BOP's matching of estimates to ground truths: candidates, their errors, the greedy matching, the scores
+# --------------------------------------------------------------------------------------------------------------------------------
+BOP_THETAS_PX = tuple(range(5, 51, 5))      # thresholds of correctness of MSPD, pixels at an image width of 640
+
+
+def _valid_mask(valid, index, n: int) -> np.ndarray:
+    if valid is None:
+        return np.ones(n, np.bool_)
+    valid = valid.reindex(index).to_numpy() if isinstance(valid, pd.Series) else np.asarray(valid)
+    if valid.dtype != np.bool_ or valid.shape != (n,):
+        raise ValueError("valid must be one boolean per row of the ground truth")
+    return valid
+
+
+def bop_candidates(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, valid=None, keys=("batch_im_id", "label")) -> pd.DataFrame:
+    """evaluation/meters/utils.py:107-117 get_candidate_matches(only_valids=True), on the host as a pandas merge -> a DataFrame
+    `pred_id`, `gt_id`, `group_id` (int64; positions in the two tables) of every (estimate, ground truth) pair that agrees on `keys`
+    and whose ground truth is valid.  Rows come in the order of `pred_infos`, then of `gt_infos`; a group is one value of `keys`,
+    numbered in order of first appearance.
+      valid  one boolean per row of `gt_infos` (array, or Series indexed like it): the targets, e.g. `gt_info(...)["visib_fract"] >= 0.1`
+             (add_valid_gt, utils.py:86-104); default all."""
+    keys = list(keys)
+    valid = _valid_mask(valid, gt_infos.index, len(gt_infos))
+    p = pred_infos[keys].reset_index(drop=True)
+    p["pred_id"] = np.arange(len(p), dtype=np.int64)
+    g = gt_infos[keys].reset_index(drop=True)
+    g["gt_id"] = np.arange(len(g), dtype=np.int64)
+    cand = p.merge(g[valid], on=keys, how="inner")
+    group = cand.groupby(keys, sort=False).ngroup().to_numpy().astype(np.int64) if len(cand) else np.zeros(0, np.int64)
+    return pd.DataFrame(dict(pred_id=cand["pred_id"].to_numpy().astype(np.int64), gt_id=cand["gt_id"].to_numpy().astype(np.int64), group_id=group))
+
+
+def bop_candidate_errors(pred, gt, cand: pd.DataFrame, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, delta: float = 0.015,
+                         taus: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """The three BOP 2019 errors of every candidate of `cand` (`bop_candidates`): estimate `pred_id` of `pred` against ground truth
+    `gt_id` of `gt` -> a device tensor [C, n_tau + 2] float32: VSD per tau, MSSD in metres, MSPD in pixels (the columns of
+    `bop_errors`).  Arguments as `bop_errors`; the frame and the object of a candidate are those of its estimate.  Every distinct
+    estimate and every distinct ground truth is rendered once, each under its own label and its own frame's K, estimates
+    BOP_DEPTH_BYTES of depth maps at a time.  A non-finite pose gives NaN on its candidates (a placeholder is rendered).  Nothing
+    synchronises."""
+    dev = meshes.points.device
+    taus = [float(t) for t in (BOP_TAUS if taus is None else taus)]
+    pid, gid = cand["pred_id"].to_numpy().astype(np.int64), cand["gt_id"].to_numpy().astype(np.int64)
+    n = len(pid)
+    if n and (pid.min() < 0 or pid.max() >= len(pred.infos) or gid.min() < 0 or gid.max() >= len(gt.infos)):
+        raise ValueError("cand must name rows of `pred` and of `gt`")
+    labels_pred, labels_gt = list(pred.infos["label"]), list(gt.infos["label"])
+    im_pred = pred.infos["batch_im_id"].to_numpy().astype(np.int64)
+    im_gt = gt.infos["batch_im_id"].to_numpy().astype(np.int64)
+    depth, K = _bop_frames(depth, K, np.concatenate([im_pred, im_gt]), dev)
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    if n == 0:
+        return torch.empty(0, len(taus) + 2, dtype=torch.float32, device=dev)
+    T_pred = pred.poses.to(device=dev, dtype=torch.float32).contiguous()
+    T_gt = gt.poses.to(device=dev, dtype=torch.float32).contiguous()
+    pid_t, gid_t = torch.from_numpy(pid).to(dev), torch.from_numpy(gid).to(dev)
+    labels = [labels_pred[i] for i in pid]
+    im32 = torch.from_numpy(im_pred[pid].astype(np.int32)).to(dev)
+    K_rows = K[im32.long()].contiguous()
+    ids, n_points, n_sym = _mesh_tables(meshes, labels, dev)
+    Tp, Tg = T_pred[pid_t].contiguous(), T_gt[gid_t].contiguous()
+    e3 = eng.pose_error_sym(Tp, Tg, meshes.symmetries, n_sym, meshes.points, mesh_ids=ids, n_points=n_points, reduce=eng.POSE_ERROR_MAX,
+                            with_errs=False)
+    e2 = eng.pose_error_mspd(Tp, Tg, meshes.symmetries, n_sym, meshes.points, K_rows, mesh_ids=ids, n_points=n_points, with_errs=False)
+    diam = _diameters(meshes)
+    diam_t = torch.tensor([diam[l] for l in labels], dtype=torch.float32, device=dev)
+    # a non-finite pose is not handed to the rasteriser: a placeholder is rendered and its candidates' errors are set to NaN
+    bad_pred, bad_gt = ~torch.isfinite(T_pred).flatten(1).all(1), ~torch.isfinite(T_gt).flatten(1).all(1)
+    place = _placeholder_pose(dev)
+    R_pred = torch.where(bad_pred[:, None, None], place, T_pred)
+    R_gt = torch.where(bad_gt[:, None, None], place, T_gt)
+    rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
+    u_gt, inv_gt = np.unique(gid, return_inverse=True)
+    u_pred, inv_pred = np.unique(pid, return_inverse=True)
+    K_gt = K[torch.from_numpy(im_gt[u_gt]).to(dev)]
+    K_pred = K[torch.from_numpy(im_pred[u_pred]).to(dev)]
+    u_gt_t, u_pred_t = torch.from_numpy(u_gt).to(dev), torch.from_numpy(u_pred).to(dev)
+    depth_gt = torch.empty(len(u_gt), H, W, dtype=torch.float32, device=dev)
+    for r0 in range(0, len(u_gt), rows_per_launch):
+        r1 = min(len(u_gt), r0 + rows_per_launch)
+        depth_gt[r0:r1] = renderer.render_depth([labels_gt[i] for i in u_gt[r0:r1]], R_gt[u_gt_t[r0:r1]], K_gt[r0:r1], (H, W))
+    # candidates in the order of their estimate, so that a portion of estimates is a run of candidates
+    order = np.argsort(inv_pred, kind="stable")
+    est_sorted = inv_pred[order]
+    gt_ids = torch.from_numpy(inv_gt.astype(np.int32)).to(dev)
+    est_ids = torch.from_numpy(inv_pred.astype(np.int32)).to(dev)
+    order_t = torch.from_numpy(order).to(dev)
+    vsd_errs = torch.empty(n, len(taus), dtype=torch.float32, device=dev)
+    for r0 in range(0, len(u_pred), rows_per_launch):
+        r1 = min(len(u_pred), r0 + rows_per_launch)
+        depth_est = renderer.render_depth([labels_pred[i] for i in u_pred[r0:r1]], R_pred[u_pred_t[r0:r1]], K_pred[r0:r1], (H, W))
+        rows = order_t[int(np.searchsorted(est_sorted, r0)):int(np.searchsorted(est_sorted, r1))]
+        vsd_errs[rows] = eng.vsd(depth_est, depth_gt, depth, K_rows[rows].contiguous(), diam_t[rows].contiguous(), delta=delta, taus=taus,
+                                 est_ids=(est_ids[rows] - r0).contiguous(), gt_ids=gt_ids[rows].contiguous(), im_ids=im32[rows].contiguous(),
+                                 with_counts=False)["errs"]
+    bad = bad_pred[pid_t] | bad_gt[gid_t]
+    vsd_errs = torch.where(bad[:, None], torch.full_like(vsd_errs, float("nan")), vsd_errs)
+    return torch.cat([vsd_errs, e3["err"][:, None], e2["err"][:, None]], dim=1)
+
+
+def bop_match_index(pred_id, gt_id, group_id, scores, n_groups: Optional[int] = None) -> Dict[str, object]:
+    """The index `engine.bop_match` takes (include/mp_engine.h), on the host: `order` [C] int64 = the candidates sorted by (group,
+    decreasing score of their estimate, pred_id, gt_id), then the int32 arrays `engine.BOP_MATCH_INDEX` over that order and the int
+    `n_taken_words`.  scores [P], finite.  An estimate or a ground truth in two groups is refused."""
+    pid, gid, grp = (np.asarray(a).astype(np.int64) for a in (pred_id, gt_id, group_id))
+    scores = np.asarray(scores, np.float64)
+    if scores.ndim != 1 or not np.isfinite(scores).all():
+        raise ValueError("scores must be one finite number per estimate")
+    if not (pid.shape == gid.shape == grp.shape) or pid.ndim != 1:
+        raise ValueError("pred_id, gt_id and group_id must be three arrays of one length")
+    c = len(pid)
+    if c and (pid.min() < 0 or pid.max() >= len(scores) or gid.min() < 0 or gid.max() >= 2 ** 31 - 1 or grp.min() < 0):
+        raise ValueError("pred_id must index scores; gt_id and group_id must not be negative")
+    n_groups = (int(grp.max()) + 1 if c else 0) if n_groups is None else int(n_groups)
+    if c and grp.max() >= n_groups:
+        raise ValueError(f"group_id reaches {int(grp.max())} with {n_groups} groups")
+    order = np.lexsort((gid, pid, -scores[pid], grp))
+    pid, gid, grp = pid[order], gid[order], grp[order]
+    new_est = np.ones(c, np.bool_)
+    new_est[1:] = (pid[1:] != pid[:-1]) | (grp[1:] != grp[:-1])
+    est_first = np.flatnonzero(new_est)
+    est_row, est_grp = pid[est_first], grp[est_first]
+    # the ground truths of each group, numbered by ascending gt_id
+    span = (int(gid.max()) + 1) if c else 1
+    u_key, lgt = np.unique(grp * span + gid, return_inverse=True)
+    u_grp = u_key // span
+    n_gt = np.bincount(u_grp, minlength=n_groups)
+    if len(np.unique(est_row)) != len(est_row) or len(np.unique(u_key % span)) != len(u_key):
+        raise ValueError("an estimate or a ground truth belongs to more than one group")
+    lgt = lgt - np.concatenate([[0], np.cumsum(n_gt)])[grp]
+    words = np.concatenate([[0], np.cumsum((n_gt + 31) // 32)])
+    if c >= 2 ** 31 - 1 or words[-1] >= 2 ** 31 - 1:
+        raise ValueError("too many candidates for an int32 index")
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)   # noqa: E731
+    return dict(order=order, cand_gt=i32(gid), cand_lgt=i32(lgt), est_row=i32(est_row), est_off=i32(np.append(est_first, c)),
+                group_est_off=i32(np.searchsorted(est_grp, np.arange(n_groups + 1))), group_n_gt=i32(n_gt), group_taken_off=i32(words),
+                n_taken_words=int(words[-1]))
+
+
+def bop_match(cand: pd.DataFrame, errs: torch.Tensor, scores, thresholds, n_top=None) -> torch.Tensor:
+    """BOP's greedy matching (evaluation/meters/utils.py:120-152 match_poses on cand[cand.error < theta], after :51-83 get_top_n_ids),
+    every (group, error column, threshold) at once on the device (csrc/bop_match.hip; the contract is csrc/bop_match_core.h).
+      cand        the table of `bop_candidates` (`pred_id`, `gt_id`, `group_id`)
+      errs        [C,E] float32 on the device, one row per row of `cand` (`bop_candidate_errors`)
+      scores      [P], one finite number per estimate: a group's estimates are walked by decreasing score, ties by ascending pred_id
+      thresholds  [n_groups,E,n_theta] float64; candidate c is admissible for (e, k) when (double)errs[c,e] < thresholds[group,e,k]
+      n_top       None or 0: every estimate; an int: the first n_top of each group; an array [n_groups]: per group (0 = every)
+    -> match [P,E,n_theta] int32 on the device: the gt_id the estimate was given, or -1.  Nothing synchronises."""
+    if not errs.is_cuda or errs.dim() != 2 or errs.shape[0] != len(cand):
+        raise ValueError("errs must be a device tensor [C,E] with one row per candidate")
+    dev = errs.device
+    thr = torch.as_tensor(thresholds)
+    if thr.dim() != 3 or thr.shape[1] != errs.shape[1] or thr.dtype != torch.float64:
+        raise ValueError(f"thresholds must be float64 [n_groups,{errs.shape[1]},n_theta]")
+    n_groups = int(thr.shape[0])
+    index = bop_match_index(cand["pred_id"].to_numpy(), cand["gt_id"].to_numpy(), cand["group_id"].to_numpy(), scores, n_groups)
+    if n_top is not None:
+        n_top = np.asarray(n_top)
+        if n_top.ndim == 0 and np.issubdtype(n_top.dtype, np.integer):
+            n_top = np.full(n_groups, int(n_top))
+        if n_top.shape != (n_groups,) or not np.issubdtype(n_top.dtype, np.integer) or (n_groups and n_top.min() < 0):
+            raise ValueError("n_top must be None, an int >= 0 or one int >= 0 per group")
+        index["n_top"] = n_top.astype(np.int32)
+    # one host-to-device copy for the whole index
+    names = [k for k in eng.BOP_MATCH_INDEX + ("n_top",) if k in index]
+    flat = torch.from_numpy(np.concatenate([index[k] for k in names])).to(dev)
+    on_dev, at = {"n_taken_words": index["n_taken_words"]}, 0
+    for k in names:
+        on_dev[k] = flat[at:at + len(index[k])]
+        at += len(index[k])
+    errs_sorted = errs.to(torch.float32)[torch.from_numpy(index["order"]).to(dev)]
+    return eng.bop_match(errs_sorted, on_dev, thr.to(dev), len(np.asarray(scores)), n_top=on_dev.get("n_top"))
+
+
+def bop_thresholds(diameters, n_tau: int = len(BOP_TAUS), image_width: int = 640) -> np.ndarray:
+    """diameters [n_groups] (metres, of each group's object) -> the thresholds of correctness [n_groups, n_tau + 2, 10] float64 of the
+    columns of `bop_candidate_errors`, built by the numpy expressions of `bop_recall`: BOP_THRESHOLDS for each VSD column, theta *
+    diameter for MSSD, theta_px * image_width / 640 for MSPD."""
+    diameters = np.asarray(diameters, np.float64)
+    thetas = np.asarray(BOP_THRESHOLDS, np.float64)
+    thetas_px = np.arange(5, 51, 5).astype(np.float64) * (float(image_width) / 640.0)
+    thr = np.empty((len(diameters), n_tau + 2, len(thetas)), np.float64)
+    thr[:, :n_tau, :] = thetas[None, None, :]
+    thr[:, n_tau, :] = thetas[None, :] * diameters[:, None]
+    thr[:, n_tau + 1, :] = thetas_px[None, :]
+    return thr
+
+
+def bop_match_recall(match: np.ndarray, n_targets: int) -> Dict[str, float]:
+    """match [P, n_tau + 2, n_theta] of `bop_match` on the host -> BOP's average recalls: the share of (target, tau, theta) / (target,
+    theta) with a matched ground truth.  A ground truth is matched at most once per problem, so the matches of a problem count its
+    matched targets; the targets are all valid ground truths, with a candidate or not.  Averaged as `bop_recall` averages."""
+    match = np.asarray(match)
+    if match.ndim != 3 or match.shape[1] < 3 or n_targets <= 0:
+        raise ValueError("bop_match_recall needs match [P, n_tau + 2, n_theta] and at least one target")
+    n_tau, n_theta = match.shape[1] - 2, match.shape[2]
+    hit = match >= 0
+    ar_vsd = float(hit[:, :n_tau, :].sum() / (n_targets * n_tau * n_theta))
+    ar_mssd = float(hit[:, n_tau, :].sum() / (n_targets * n_theta))
+    ar_mspd = float(hit[:, n_tau + 1, :].sum() / (n_targets * n_theta))
+    return {"ar_vsd": ar_vsd, "ar_mssd": ar_mssd, "ar_mspd": ar_mspd, "ar": (ar_vsd + ar_mssd + ar_mspd) / 3.0}
+
+
+def bop_n_top(n_top, group_n_gt: np.ndarray) -> np.ndarray:
+    """the three forms of `bop_scores`' n_top -> one int32 per group: "targets" = the group's number of valid ground truths (BOP 2019's
+    inst_count; get_top_n_ids(targets=...)), an int > 0 = that count, None or 0 = every estimate (0)"""
+    group_n_gt = np.asarray(group_n_gt, np.int32)
+    if n_top is None:
+        return np.zeros_like(group_n_gt)
+    if isinstance(n_top, str):
+        if n_top != "targets":
+            raise ValueError(f"n_top {n_top!r} is not 'targets', an int or None")
+        return group_n_gt.copy()
+    if isinstance(n_top, (bool, np.bool_)) or not isinstance(n_top, (int, np.integer)) or n_top < 0:
+        raise ValueError(f"n_top {n_top!r} is not 'targets', an int >= 0 or None")
+    return np.full_like(group_n_gt, int(n_top))
+
+
+def bop_scores(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, valid=None, n_top="targets", score_key: str = "score",
+               image_width: int = 640, keys=("batch_im_id", "label"), delta: float = 0.015, return_matches: bool = False,
+               matches_at: Tuple[str, int] = ("mssd", 0)):
+    """BOP 2019 scores of estimates that carry scores (`pred.infos[score_key]`) against the ground truths of their (image, label),
+    several or none of either -> {ar_vsd, ar_mssd, ar_mspd, ar, n_targets}: candidates (`bop_candidates`), their errors
+    (`bop_candidate_errors`), the greedy matching at every threshold (`bop_match` under `bop_thresholds`), and per error the share of
+    (valid ground truth, threshold) that got an estimate.  The denominator counts every valid ground truth, with a candidate or not.
+      valid       one boolean per row of `gt` (default all): the targets
+      n_top       "targets": a group's estimates are cut to its number of valid ground truths; an int > 0: to that count; None / 0: not cut
+      matches_at  with return_matches, the (column, k) whose matched pairs are also returned as a DataFrame `pred_id`, `gt_id`:
+                  column one of vsd_0.05 ... vsd_0.50, mssd, mspd; k the index of the threshold
+    Other arguments as `bop_errors`.  One synchronising copy at the end."""
+    valid = _valid_mask(valid, gt.infos.index, len(gt.infos))
+    n_targets = int(valid.sum())
+    if n_targets == 0:
+        raise ValueError("bop_scores needs at least one valid ground truth")
+    names = _vsd_names(BOP_TAUS) + ["mssd", "mspd"]
+    if return_matches and (matches_at[0] not in names or not 0 <= int(matches_at[1]) < len(BOP_THRESHOLDS)):
+        raise ValueError(f"matches_at {matches_at!r} is not (one of {names}, an index below {len(BOP_THRESHOLDS)})")
+    scores = pred.infos[score_key].to_numpy().astype(np.float64)
+    cand = bop_candidates(pred.infos, gt.infos, valid=valid, keys=keys)
+    errs = bop_candidate_errors(pred, gt, cand, meshes, renderer, depth, K, delta=delta)
+    grp = cand["group_id"].to_numpy()
+    n_groups = int(grp.max()) + 1 if len(cand) else 0
+    first = np.full(n_groups, -1, np.int64)
+    first[grp[::-1]] = np.arange(len(cand))[::-1]                    # a group's first candidate
+    labels = pred.infos["label"].to_numpy()[cand["pred_id"].to_numpy()[first]]
+    diam = _diameters(meshes)
+    thr = bop_thresholds([diam[l] for l in labels], len(BOP_TAUS), image_width)
+    group_n_gt = cand.groupby("group_id")["gt_id"].nunique().reindex(np.arange(n_groups)).to_numpy() if n_groups else np.zeros(0)
+    match = bop_match(cand, errs, scores, thr, n_top=bop_n_top(n_top, group_n_gt)).cpu().numpy()   # the one synchronising copy
+    out = dict(bop_match_recall(match, n_targets), n_targets=n_targets)
+    if not return_matches:
+        return out
+    col = match[:, names.index(matches_at[0]), int(matches_at[1])]
+    rows = np.flatnonzero(col >= 0)
+    return out, pd.DataFrame(dict(pred_id=rows.astype(np.int64), gt_id=col[rows].astype(np.int64)))
