@@ -42,6 +42,17 @@ struct ProfScope {
 };
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// wave-wide butterflies: every lane ends with the same bits
+__device__ __forceinline__ float wave_sum_all(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+__device__ __forceinline__ float wave_max_all(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
 
 // XCD-aware bijective remap of a linear workgroup id (8 XCDs, round-robin dispatch):
 // physical id p runs on XCD p % 8; give each XCD a contiguous chunk of logical ids so that

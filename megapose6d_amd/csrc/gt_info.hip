@@ -2,28 +2,28 @@
 // the modal box and the two masks, per row.
 //
 // The definition and its fp32 arithmetic are gt_info_core.h (on top of vsd_core.h), shared with the host emulation of the tests; this
-// file adds the work distribution, the way vsd.hip does for VSD.  Every per-row result but the final division is an integer count or a
+// file adds the work distribution, on the walk of depth_walk.h that vsd.hip uses too.  Every per-row result but the final division is an integer count or a
 // minimum / maximum, so neither the grid nor the order in which workgroups arrive can change a bit.
 //
 //   gt_info_init_kernel      the row's accumulators in the workspace: counters 0, extents "untouched"
-//   gt_info_count_kernel     grid (row, tile of the canvas, strip of image rows), 4 waves.  A wave walks image rows, a lane owns four
-//                            consecutive x of each 256-pixel chunk; 16-byte loads (and 4-byte mask stores) when the width and the bases
-//                            allow, else guarded scalar accesses with the same results.  A chunk in which no lane has a positive depth
-//                            is skipped after its load.  An OUTER tile takes only the > 0 test and the extents: no ray, no square root,
-//                            no read of the frame.  The CENTRE tile has v*v in an LDS table and u*u in registers, as vsd_count_kernel.
+//   gt_info_count_kernel     grid (row, tile of the canvas, strip of image rows), 4 waves, the walk of depth_walk.h: a wave walks image
+//                            rows, a lane owns four consecutive x of each 256-pixel chunk; 16-byte loads (and 4-byte mask stores) when
+//                            the width and the bases allow, else guarded scalar accesses with the same results.  A chunk in which no
+//                            lane has a positive depth is skipped after its load.  An OUTER tile takes only the > 0 test and the
+//                            extents: no ray, no square root, no read of the frame.  The CENTRE tile has the walk's v*v table and u*u
+//                            registers.
 //                            Predicates are reduced per wave by ballot + population count, x extents from the first / last set bit of the
 //                            same ballots (scalar registers), per workgroup through LDS, then one integer atomicAdd per non-zero counter
 //                            and one atomicMin / atomicMax per touched bound.
 //   gt_info_finalize_kernel  one thread per row: accumulators -> counts, boxes, visib_fract (-1 / NaN for an invalid row)
 #include "common.h"
+#include "depth_walk.h"
 #include "gt_info_core.h"
 
 namespace mp {
 
 using gti::kRowInts;
 using vsd::kMaxSide;
-
-constexpr int kGtiChunks = kMaxSide / 256;   // 256-pixel chunks of an image row
 
 __global__ __launch_bounds__(256) void gt_info_init_kernel(int32_t* __restrict__ acc, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -50,21 +50,6 @@ __device__ __forceinline__ void gti_store_mask(uint8_t* __restrict__ M, size_t a
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (x0 + k < w) M[at + x0 + k] = v[k] ? 255 : 0;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void gti_load4(const float* __restrict__ P, size_t off, int x0, int w, float (&d)[4]) {
-  d[0] = d[1] = d[2] = d[3] = 0.f;
-  if (VEC) {
-    if (x0 < w) {   // w % 4 == 0: the four pixels are inside together
-      const float4 q = *reinterpret_cast<const float4*>(P + off + x0);
-      d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (x0 + k < w) d[k] = P[off + x0 + k];
   }
 }
 
@@ -100,10 +85,10 @@ __global__ __launch_bounds__(256) void gt_info_count_kernel(const float* __restr
     for (int y = y0 + wave; y < y1; y += 4) {
       const size_t off = (size_t)y * w;
 #pragma unroll
-      for (int c = 0; c < kGtiChunks; ++c) {
+      for (int c = 0; c < dw::kChunks; ++c) {
         if (c * 256 >= w) break;   // uniform
         float g[4];
-        gti_load4<VEC>(G, off, c * 256 + lane * 4, w, g);
+        dw::load4<VEC>(G, off, c * 256 + lane * 4, w, g);
         if (__ballot(gti::is_obj(g[0]) || gti::is_obj(g[1]) || gti::is_obj(g[2]) || gti::is_obj(g[3])) == 0) continue;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -116,35 +101,26 @@ __global__ __launch_bounds__(256) void gt_info_count_kernel(const float* __restr
       }
     }
   } else {
-    for (int i = threadIdx.x; i < y1 - y0; i += 256) {
-      const float v = vsd::ray_v(Kr, y0 + i);
-      vv_s[i] = v * v;
-    }
+    dw::fill_vv(Kr, y0, y1, vv_s);
     __syncthreads();
-    float uu[kGtiChunks][4];
-#pragma unroll
-    for (int c = 0; c < kGtiChunks; ++c)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float u = vsd::ray_u(Kr, c * 256 + lane * 4 + k);
-        uu[c][k] = u * u;
-      }
+    float uu[dw::kChunks][4];
+    dw::fill_uu(Kr, lane, uu);
     const float* T = depth_test + (size_t)(im_ids ? im_ids[row] : row) * hw;
     for (int y = y0 + wave; y < y1; y += 4) {
       const float vv = vv_s[y - y0];
       const size_t off = (size_t)y * w;
 #pragma unroll
-      for (int c = 0; c < kGtiChunks; ++c) {
+      for (int c = 0; c < dw::kChunks; ++c) {
         if (c * 256 >= w) break;   // uniform
         const int x0 = c * 256 + lane * 4;
         float g[4], t[4];
-        gti_load4<VEC>(G, off, x0, w, g);
+        dw::load4<VEC>(G, off, x0, w, g);
         if (__ballot(gti::is_obj(g[0]) || gti::is_obj(g[1]) || gti::is_obj(g[2]) || gti::is_obj(g[3])) == 0) {   // in neither mask
           if (M) gti_store_mask<VEC>(M, off, x0, w, false, false, false, false);
           if (MV) gti_store_mask<VEC>(MV, off, x0, w, false, false, false, false);
           continue;
         }
-        gti_load4<VEC>(T, off, x0, w, t);
+        dw::load4<VEC>(T, off, x0, w, t);
         bool obj[4], vis[4];
         bool any_vis = false;
 #pragma unroll
@@ -215,15 +191,13 @@ __global__ __launch_bounds__(256) void gt_info_finalize_kernel(const float* __re
   fract[row] = ok ? gti::visib_fract(a[gti::kVisib], a[gti::kAll]) : vsd::quiet_nan();
 }
 
-static inline size_t gti_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace mp
 
 using namespace mp;
 
 extern "C" size_t mp_gt_info_workspace_bytes(int b) {
   if (b < 0) return 0;
-  return gti_align256((size_t)b * kRowInts * sizeof(int32_t)) + 256;
+  return align256((size_t)b * kRowInts * sizeof(int32_t)) + 256;
 }
 
 extern "C" int mp_gt_info(const float* d_depth_gt, const int32_t* d_gt_ids, const float* d_depth_test, const int32_t* d_im_ids, int n_gt, int n_im,
@@ -242,25 +216,20 @@ extern "C" int mp_gt_info(const float* d_depth_gt, const int32_t* d_gt_ids, cons
   MP_REQUIRE((d_gt_ids || n_gt >= b) && (d_im_ids || n_im >= b), "mp_gt_info: fewer maps than rows and no ids");
   MP_REQUIRE(workspace_bytes >= mp_gt_info_workspace_bytes(b), "mp_gt_info: workspace too small");
   const int n_tiles = canvas * canvas;
-  int strips = split > 0 ? split : ceil_div(4096, (long)b * n_tiles);   // a few thousand workgroups when rows and tiles cannot give them
-  const int max_strips = ceil_div(h, 4);                                  // at least one image row per wave
-  strips = strips < 1 ? 1 : (strips > max_strips ? max_strips : strips);
-  const int rps = ceil_div(h, strips);
-  strips = ceil_div(h, rps);
-  const bool vec = (w % 4 == 0) && (((uintptr_t)d_depth_gt | (uintptr_t)d_depth_test) % 16 == 0) &&
-                   (((uintptr_t)d_mask | (uintptr_t)d_mask_visib) % 4 == 0);
+  const dw::Strips st = dw::strips_of(split, 4096, (long)b * n_tiles, h);   // a few thousand workgroups when rows and tiles cannot give them
+  const bool vec = dw::vec_ok(w, {d_depth_gt, d_depth_test}, {d_mask, d_mask_visib});
   int32_t* acc = (int32_t*)d_workspace;
   hipStream_t s = (hipStream_t)stream;
   const double n_masks = (d_mask ? 1.0 : 0.0) + (d_mask_visib ? 1.0 : 0.0);
   ProfScope prof("gt_info", 0.0, (double)b * h * w * (4.0 * n_tiles + 4.0 + n_masks), s);
   hipLaunchKernelGGL(gt_info_init_kernel, dim3(ceil_div((long)b * kRowInts, 256)), dim3(256), 0, s, acc, b * kRowInts);
   MP_CHECK_HIP(hipGetLastError());
-  const dim3 grid(b, n_tiles, strips);
+  const dim3 grid(b, n_tiles, st.strips);
   if (vec)
-    hipLaunchKernelGGL(gt_info_count_kernel<true>, grid, dim3(256), 0, s, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, h, w, canvas, rps, delta,
+    hipLaunchKernelGGL(gt_info_count_kernel<true>, grid, dim3(256), 0, s, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, h, w, canvas, st.rows_per_strip, delta,
                        acc, d_mask, d_mask_visib);
   else
-    hipLaunchKernelGGL(gt_info_count_kernel<false>, grid, dim3(256), 0, s, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, h, w, canvas, rps, delta,
+    hipLaunchKernelGGL(gt_info_count_kernel<false>, grid, dim3(256), 0, s, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, h, w, canvas, st.rows_per_strip, delta,
                        acc, d_mask, d_mask_visib);
   MP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(gt_info_finalize_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, s, d_K, b, acc, d_counts, d_boxes, d_visib_fract);

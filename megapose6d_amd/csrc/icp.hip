@@ -63,7 +63,7 @@ __global__ void icp_target_normals(const float* __restrict__ depth, const float*
 }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  v = wave_sum_all(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) red[wave] = v;

@@ -56,10 +56,6 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
   return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
 
 // extents of R*p over a mesh's (padded) point set: one block per (mesh, rotation)
 __global__ __launch_bounds__(256) void init_extents_kernel(const float* __restrict__ pts, int n_pts, const float* __restrict__ R,
@@ -76,7 +72,7 @@ __global__ __launch_bounds__(256) void init_extents_kernel(const float* __restri
     xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
     ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
   }
-  xmin = wave_min(xmin); xmax = wave_max(xmax); ymin = wave_min(ymin); ymax = wave_max(ymax);
+  xmin = wave_min(xmin); xmax = wave_max_all(xmax); ymin = wave_min(ymin); ymax = wave_max_all(ymax);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red[wave][0] = xmin; red[wave][1] = xmax; red[wave][2] = ymin; red[wave][3] = ymax; }
   __syncthreads();
@@ -222,7 +218,7 @@ __global__ __launch_bounds__(256) void pose_prepare_kernel(
     umin = fminf(umin, u); umax = fmaxf(umax, u);
     vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
   }
-  umin = wave_min(umin); umax = wave_max(umax); vmin = wave_min(vmin); vmax = wave_max(vmax);
+  umin = wave_min(umin); umax = wave_max_all(umax); vmin = wave_min(vmin); vmax = wave_max_all(vmax);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red[wave][0] = umin; red[wave][1] = umax; red[wave][2] = vmin; red[wave][3] = vmax; }
   __syncthreads();

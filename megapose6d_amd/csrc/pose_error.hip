@@ -8,9 +8,9 @@
 // transformed once and every pair lives in registers only.  The arithmetic of one element is pose_error_core.h (shared with the host
 // emulation of the tests); this file adds the work distribution and the deterministic reductions.
 //
-//   sym_partial_kernel   (a) one wave per 256-point chunk of a row, all symmetries: per (row, symmetry, chunk) sum and max of the norms
+//   sym_partial_kernel   (a) one wave per 256-point chunk of a row, all symmetries: per (row, symmetry, chunk) sum and max of the distances;
+//                            a template over the distance: SpaceMetric (3D norm: ADD, MSSD) or PixelMetric (between projections: MSPD)
 //   sym_finalize_kernel  (a) one workgroup per row: chunk partials -> errs[s], arg-min, T_gt_sym, optional difference vectors
-//   mspd_partial_kernel  (a') sym_partial_kernel with the norm taken between projections (MSPD); finalized by sym_finalize_kernel
 //   nn_pairs_kernel      (b) one workgroup per (row, 1024 ground-truth points, range of predicted points): running (d2, k), merged by
 //                            a 64-bit atomic minimum on (bits(d2) << 32 | k)
 //   nn_finalize_kernel   (b) one workgroup per row: assignment -> difference vectors, mean and max of their norms
@@ -23,15 +23,6 @@ namespace mp {
 using pe::kChunk;
 using pe::kMaxSym;
 using pe::kPerLane;
-
-__device__ __forceinline__ float wave_sum_all(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);   // butterfly: every lane ends with the same bits
-  return v;
-}
-__device__ __forceinline__ float wave_max_all(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
 
 // lane-strided sum / max of n values, then the butterfly: the one order in which chunk partials are combined
 __device__ __forceinline__ float chunks_sum(const float* __restrict__ part, int n, int stride, int lane) {
@@ -48,33 +39,57 @@ __device__ __forceinline__ float chunks_max(const float* __restrict__ part, int 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // (a) symmetry-set error
 // ---------------------------------------------------------------------------------------------------------------------------------
+// What the two forms of the error differ in: the 12 floats kept per pose, what a lane keeps per point, and the distance.
+struct SpaceMetric {   // 3D: the pose itself, the transformed point, the norm of the difference
+  static constexpr int kKeep = 3;
+  __device__ SpaceMetric(const float*, int) {}
+  __device__ void matrix(const float* T, float* M) const {
+    for (int k = 0; k < 12; ++k) M[k] = T[k];
+  }
+  __device__ static void point(const float* M, float x, float y, float z, float* q) { pe::apply(M, x, y, z, q[0], q[1], q[2]); }
+  __device__ static float dist(const float* q, const float* g) { return sqrtf(pe::norm2(g[0] - q[0], g[1] - q[1], g[2] - q[2])); }
+};
+struct PixelMetric {   // projected (MSPD): P = K T (the projection of the rigid launch), the pixel position, the pixel distance
+  static constexpr int kKeep = 2;
+  float Kr[9];
+  __device__ PixelMetric(const float* K, int row) {
+    for (int k = 0; k < 9; ++k) Kr[k] = K[(size_t)row * 9 + k];
+  }
+  __device__ void matrix(const float* T, float* M) const { pe::proj_matrix(Kr, T, M); }
+  __device__ static void point(const float* M, float x, float y, float z, float* q) { pe::project(M, x, y, z, q[0], q[1]); }
+  __device__ static float dist(const float* q, const float* g) { return pe::pixel_dist(q[0], q[1], g[0], g[1]); }
+};
+
 // grid (b, wgs_per_row); wave w of workgroup y takes chunks (4y + w), (4y + w) + 4 wgs_per_row, ...: which wave computes a chunk never
-// changes the chunk's partial, so every grid gives the same bits.
+// changes the chunk's partial, so every grid gives the same bits.  LDS keeps the metric's matrix of T_gt Sym_s per symmetry.
+template <class Metric>
 __global__ __launch_bounds__(256) void sym_partial_kernel(const float* __restrict__ T_pred, const float* __restrict__ T_gt,
                                                           const float* __restrict__ syms, const int32_t* __restrict__ n_sym, int S_max,
-                                                          const float* __restrict__ points, int n_pts_stride,
+                                                          const float* __restrict__ K, const float* __restrict__ points, int n_pts_stride,
                                                           const int32_t* __restrict__ mesh_ids, const int32_t* __restrict__ n_points,
                                                           int n_pts, int n_chunks, float* __restrict__ partial) {
-  __shared__ float Tgs[kMaxSym * 12];
+  __shared__ float Mgs[kMaxSym * 12];
   const int row = blockIdx.x, mesh = mesh_ids[row];
   const int ns = syms ? (n_sym ? min(n_sym[mesh], S_max) : S_max) : S_max;
   const int nv = n_points ? min(n_points[mesh], n_pts) : n_pts;
+  const Metric metric(K, row);
   for (int s = threadIdx.x; s < ns; s += 256) {
-    float O[16];
+    float O[16], Mg[12];
     if (syms) {
       pe::compose(T_gt + (size_t)row * 16, syms + ((size_t)mesh * S_max + s) * 16, O);
     } else {
       for (int k = 0; k < 12; ++k) O[k] = T_gt[((size_t)row * S_max + s) * 16 + k];
     }
-    for (int k = 0; k < 12; ++k) Tgs[s * 12 + k] = O[k];
+    metric.matrix(O, Mg);
+    for (int k = 0; k < 12; ++k) Mgs[s * 12 + k] = Mg[k];
   }
   __syncthreads();
-  float Tp[12];
-  for (int k = 0; k < 12; ++k) Tp[k] = T_pred[(size_t)row * 16 + k];
+  float Mp[12];
+  metric.matrix(T_pred + (size_t)row * 16, Mp);
   const float* P = points + (size_t)mesh * n_pts_stride * 3;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int c = blockIdx.y * 4 + wave; c < n_chunks; c += gridDim.y * 4) {
-    float px[kPerLane], py[kPerLane], pz[kPerLane], qx[kPerLane], qy[kPerLane], qz[kPerLane];
+    float px[kPerLane], py[kPerLane], pz[kPerLane], q[kPerLane][Metric::kKeep];
     bool ok[kPerLane];
 #pragma unroll
     for (int p = 0; p < kPerLane; ++p) {
@@ -82,16 +97,16 @@ __global__ __launch_bounds__(256) void sym_partial_kernel(const float* __restric
       ok[p] = j < nv;
       const int jj = ok[p] ? j : 0;
       px[p] = P[3 * jj]; py[p] = P[3 * jj + 1]; pz[p] = P[3 * jj + 2];
-      pe::apply(Tp, px[p], py[p], pz[p], qx[p], qy[p], qz[p]);
+      Metric::point(Mp, px[p], py[p], pz[p], q[p]);
     }
     for (int s = 0; s < ns; ++s) {
-      const float* G = Tgs + s * 12;
+      const float* G = Mgs + s * 12;
       float sum = 0.f, mx = 0.f;
 #pragma unroll
       for (int p = 0; p < kPerLane; ++p) {
-        float gx, gy, gz;
-        pe::apply(G, px[p], py[p], pz[p], gx, gy, gz);
-        const float n = sqrtf(pe::norm2(gx - qx[p], gy - qy[p], gz - qz[p]));
+        float g[Metric::kKeep];
+        Metric::point(G, px[p], py[p], pz[p], g);
+        const float n = Metric::dist(q[p], g);
         sum = sum + (ok[p] ? n : 0.f);
         mx = fmaxf(mx, ok[p] ? n : 0.f);
       }
@@ -177,67 +192,6 @@ __global__ __launch_bounds__(256) void sym_finalize_kernel(const float* __restri
       dx = gx - qx; dy = gy - qy; dz = gz - qz;
     }
     D[3 * j] = dx; D[3 * j + 1] = dy; D[3 * j + 2] = dz;   // the padded tail is zero
-  }
-}
-
-// the projected sibling of sym_partial_kernel (MSPD): the same chunks, the same partial layout, the norm taken between the two pixel
-// positions pe::proj_dist gives under P = K T (the projection of the rigid launch).  LDS keeps P_s = K (T_gt Sym_s) per symmetry.
-__global__ __launch_bounds__(256) void mspd_partial_kernel(const float* __restrict__ T_pred, const float* __restrict__ T_gt,
-                                                           const float* __restrict__ syms, const int32_t* __restrict__ n_sym, int S_max,
-                                                           const float* __restrict__ K, const float* __restrict__ points, int n_pts_stride,
-                                                           const int32_t* __restrict__ mesh_ids, const int32_t* __restrict__ n_points,
-                                                           int n_pts, int n_chunks, float* __restrict__ partial) {
-  __shared__ float Pgs[kMaxSym * 12];
-  const int row = blockIdx.x, mesh = mesh_ids[row];
-  const int ns = syms ? (n_sym ? min(n_sym[mesh], S_max) : S_max) : S_max;
-  const int nv = n_points ? min(n_points[mesh], n_pts) : n_pts;
-  float Kr[9];
-  for (int k = 0; k < 9; ++k) Kr[k] = K[(size_t)row * 9 + k];
-  for (int s = threadIdx.x; s < ns; s += 256) {
-    float O[16], Pg[12];
-    if (syms) {
-      pe::compose(T_gt + (size_t)row * 16, syms + ((size_t)mesh * S_max + s) * 16, O);
-    } else {
-      for (int k = 0; k < 12; ++k) O[k] = T_gt[((size_t)row * S_max + s) * 16 + k];
-    }
-    pe::proj_matrix(Kr, O, Pg);
-    for (int k = 0; k < 12; ++k) Pgs[s * 12 + k] = Pg[k];
-  }
-  __syncthreads();
-  float Pp[12];
-  pe::proj_matrix(Kr, T_pred + (size_t)row * 16, Pp);
-  const float* P = points + (size_t)mesh * n_pts_stride * 3;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c = blockIdx.y * 4 + wave; c < n_chunks; c += gridDim.y * 4) {
-    float px[kPerLane], py[kPerLane], pz[kPerLane], qu[kPerLane], qv[kPerLane];
-    bool ok[kPerLane];
-#pragma unroll
-    for (int p = 0; p < kPerLane; ++p) {
-      const int j = c * kChunk + p * 64 + lane;
-      ok[p] = j < nv;
-      const int jj = ok[p] ? j : 0;
-      px[p] = P[3 * jj]; py[p] = P[3 * jj + 1]; pz[p] = P[3 * jj + 2];
-      pe::project(Pp, px[p], py[p], pz[p], qu[p], qv[p]);
-    }
-    for (int s = 0; s < ns; ++s) {
-      const float* G = Pgs + s * 12;
-      float sum = 0.f, mx = 0.f;
-#pragma unroll
-      for (int p = 0; p < kPerLane; ++p) {
-        float gu, gv;
-        pe::project(G, px[p], py[p], pz[p], gu, gv);
-        const float n = pe::pixel_dist(qu[p], qv[p], gu, gv);
-        sum = sum + (ok[p] ? n : 0.f);
-        mx = fmaxf(mx, ok[p] ? n : 0.f);
-      }
-      sum = wave_sum_all(sum);
-      mx = wave_max_all(mx);
-      if (lane == 0) {
-        float* o = partial + (((size_t)row * S_max + s) * n_chunks + c) * 2;
-        o[0] = sum;
-        o[1] = mx;
-      }
-    }
   }
 }
 
@@ -402,7 +356,6 @@ __global__ __launch_bounds__(256) void rigid_kernel(const float* __restrict__ T_
 }
 
 static inline int n_chunks_of(int n_pts) { return (n_pts + kChunk - 1) / kChunk; }
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace mp
 
@@ -415,27 +368,33 @@ extern "C" size_t mp_pose_error_workspace_bytes(int b, int n_pts, int S_max) {
   return align256(sym > nn ? sym : nn) + 256;
 }
 
-extern "C" int mp_pose_error_sym(const float* d_T_pred, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
-                                 const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts,
-                                 int b, int reduce, int split, float* d_err, float* d_err_alt, int32_t* d_idx, float* d_T_gt_sym,
-                                 float* d_errs, float* d_diffs, void* d_workspace, size_t workspace_bytes, mp_stream stream) {
-  MP_REQUIRE(d_T_pred && d_T_gt && d_points && d_mesh_ids && d_err && d_idx && d_workspace, "mp_pose_error_sym: null pointer");
-  MP_REQUIRE(n_pts >= 1 && n_pts <= n_pts_stride && b >= 0, "mp_pose_error_sym: bad sizes (n_pts %d, stride %d, b %d)", n_pts, n_pts_stride, b);
-  MP_REQUIRE(S_max >= 1 && S_max <= kMaxSym, "mp_pose_error_sym: S_max %d outside [1, %d]", S_max, kMaxSym);
-  MP_REQUIRE(reduce == MP_POSE_ERROR_MEAN || reduce == MP_POSE_ERROR_MAX, "mp_pose_error_sym: unknown reduce %d", reduce);
-  MP_REQUIRE(split >= 0, "mp_pose_error_sym: split < 0");
-  MP_REQUIRE(workspace_bytes >= mp_pose_error_workspace_bytes(b, n_pts, S_max), "mp_pose_error_sym: workspace too small");
+// both symmetry-set entries: `name` is the entry's (messages; without its mp_ prefix, the profiler row), d_K null = the 3D form
+static int pose_error_sym_launch(const char* name, const float* d_T_pred, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym,
+                                 int S_max, const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points,
+                                 int n_pts, int b, int reduce, int split, const float* d_K, float* d_err, float* d_err_alt, int32_t* d_idx,
+                                 float* d_T_gt_sym, float* d_errs, float* d_diffs, void* d_workspace, size_t workspace_bytes, mp_stream stream) {
+  MP_REQUIRE(d_T_pred && d_T_gt && d_points && d_mesh_ids && d_err && d_idx && d_workspace, "%s: null pointer", name);
+  MP_REQUIRE(n_pts >= 1 && n_pts <= n_pts_stride && b >= 0, "%s: bad sizes (n_pts %d, stride %d, b %d)", name, n_pts, n_pts_stride, b);
+  MP_REQUIRE(S_max >= 1 && S_max <= kMaxSym, "%s: S_max %d outside [1, %d]", name, S_max, kMaxSym);
+  MP_REQUIRE(reduce == MP_POSE_ERROR_MEAN || reduce == MP_POSE_ERROR_MAX, "%s: unknown reduce %d", name, reduce);
+  MP_REQUIRE(split >= 0, "%s: split < 0", name);
+  MP_REQUIRE(workspace_bytes >= mp_pose_error_workspace_bytes(b, n_pts, S_max), "%s: workspace too small", name);
   if (b == 0) return MP_OK;
   const int nch = n_chunks_of(n_pts);
   const int max_wgs = ceil_div(nch, 4);
   int wgs = split > 0 ? split : ceil_div(1024, b);   // ~4 workgroups per CU when the rows alone cannot give them
   wgs = wgs < 1 ? 1 : (wgs > max_wgs ? max_wgs : wgs);
-  MP_REQUIRE(wgs <= 65535, "mp_pose_error_sym: split too large");
+  MP_REQUIRE(wgs <= 65535, "%s: split too large", name);
   float* part = (float*)d_workspace;
-  ProfScope prof("pose_error_sym", 0.0, (double)b * n_pts * 12.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(sym_partial_kernel, dim3(b, wgs), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max,
-                     d_points, n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, part);
+  ProfScope prof(name + 3, 0.0, (double)b * n_pts * 12.0, (hipStream_t)stream);
+  if (d_K)
+    hipLaunchKernelGGL(sym_partial_kernel<PixelMetric>, dim3(b, wgs), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym,
+                       S_max, d_K, d_points, n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, part);
+  else
+    hipLaunchKernelGGL(sym_partial_kernel<SpaceMetric>, dim3(b, wgs), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym,
+                       S_max, d_K, d_points, n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, part);
   MP_CHECK_HIP(hipGetLastError());
+  // the chunk partials have one layout: the same finalize picks the symmetry
   hipLaunchKernelGGL(sym_finalize_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points,
                      n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, reduce == MP_POSE_ERROR_MAX ? 1 : 0, part, d_err, d_err_alt, d_idx,
                      d_T_gt_sym, d_errs, d_diffs);
@@ -443,33 +402,23 @@ extern "C" int mp_pose_error_sym(const float* d_T_pred, const float* d_T_gt, con
   return MP_OK;
 }
 
+extern "C" int mp_pose_error_sym(const float* d_T_pred, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
+                                 const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts,
+                                 int b, int reduce, int split, float* d_err, float* d_err_alt, int32_t* d_idx, float* d_T_gt_sym,
+                                 float* d_errs, float* d_diffs, void* d_workspace, size_t workspace_bytes, mp_stream stream) {
+  return pose_error_sym_launch("mp_pose_error_sym", d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points, n_pts_stride, d_mesh_ids, d_n_points,
+                               n_pts, b, reduce, split, nullptr, d_err, d_err_alt, d_idx, d_T_gt_sym, d_errs, d_diffs, d_workspace,
+                               workspace_bytes, stream);
+}
+
 extern "C" int mp_pose_error_mspd(const float* d_T_pred, const float* d_T_gt, const float* d_symmetries, const int32_t* d_n_sym, int S_max,
                                   const float* d_points, int n_pts_stride, const int32_t* d_mesh_ids, const int32_t* d_n_points, int n_pts,
                                   int b, int reduce, int split, const float* d_K, float* d_err, float* d_err_alt, int32_t* d_idx,
                                   float* d_T_gt_sym, float* d_errs, void* d_workspace, size_t workspace_bytes, mp_stream stream) {
-  MP_REQUIRE(d_T_pred && d_T_gt && d_points && d_mesh_ids && d_K && d_err && d_idx && d_workspace, "mp_pose_error_mspd: null pointer");
-  MP_REQUIRE(n_pts >= 1 && n_pts <= n_pts_stride && b >= 0, "mp_pose_error_mspd: bad sizes (n_pts %d, stride %d, b %d)", n_pts, n_pts_stride, b);
-  MP_REQUIRE(S_max >= 1 && S_max <= kMaxSym, "mp_pose_error_mspd: S_max %d outside [1, %d]", S_max, kMaxSym);
-  MP_REQUIRE(reduce == MP_POSE_ERROR_MEAN || reduce == MP_POSE_ERROR_MAX, "mp_pose_error_mspd: unknown reduce %d", reduce);
-  MP_REQUIRE(split >= 0, "mp_pose_error_mspd: split < 0");
-  MP_REQUIRE(workspace_bytes >= mp_pose_error_workspace_bytes(b, n_pts, S_max), "mp_pose_error_mspd: workspace too small");
-  if (b == 0) return MP_OK;
-  const int nch = n_chunks_of(n_pts);
-  const int max_wgs = ceil_div(nch, 4);
-  int wgs = split > 0 ? split : ceil_div(1024, b);
-  wgs = wgs < 1 ? 1 : (wgs > max_wgs ? max_wgs : wgs);
-  MP_REQUIRE(wgs <= 65535, "mp_pose_error_mspd: split too large");
-  float* part = (float*)d_workspace;
-  ProfScope prof("pose_error_mspd", 0.0, (double)b * n_pts * 12.0, (hipStream_t)stream);
-  hipLaunchKernelGGL(mspd_partial_kernel, dim3(b, wgs), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_K,
-                     d_points, n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, part);
-  MP_CHECK_HIP(hipGetLastError());
-  // the chunk partials have the layout of the 3D launch: the same finalize picks the symmetry (no difference vectors)
-  hipLaunchKernelGGL(sym_finalize_kernel, dim3(b), dim3(256), 0, (hipStream_t)stream, d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points,
-                     n_pts_stride, d_mesh_ids, d_n_points, n_pts, nch, reduce == MP_POSE_ERROR_MAX ? 1 : 0, part, d_err, d_err_alt, d_idx,
-                     d_T_gt_sym, d_errs, (float*)nullptr);
-  MP_CHECK_HIP(hipGetLastError());
-  return MP_OK;
+  MP_REQUIRE(d_K, "mp_pose_error_mspd: null pointer");
+  return pose_error_sym_launch("mp_pose_error_mspd", d_T_pred, d_T_gt, d_symmetries, d_n_sym, S_max, d_points, n_pts_stride, d_mesh_ids, d_n_points,
+                               n_pts, b, reduce, split, d_K, d_err, d_err_alt, d_idx, d_T_gt_sym, d_errs, nullptr, d_workspace, workspace_bytes,
+                               stream);
 }
 
 extern "C" int mp_pose_error_nn(const float* d_T_pred, const float* d_T_gt, const float* d_points, int n_pts_stride,

@@ -4,13 +4,14 @@
 // the tests; this file adds the work distribution.  Every per-row result but the final division is an integer count, so neither the
 // grid nor the order in which workgroups arrive can change a bit.
 //
-//   vsd_count_kernel     grid (row, strip of image rows), 4 waves.  A wave walks image rows (v*v comes from a per-strip LDS table), a
-//                        lane owns four consecutive x of each 256-pixel chunk (its u*u are computed once and kept); 16-byte loads when
-//                        the width and the bases allow, else guarded scalar loads with the same counts.  A chunk in which neither
-//                        render has a positive depth is skipped (it cannot be visible).  The 2 + n_tau predicates are reduced per wave
-//                        by ballot + population count, per workgroup through LDS, then one integer atomicAdd per counter.
+//   vsd_count_kernel     grid (row, strip of image rows), 4 waves, the walk of depth_walk.h (shared with gt_info.hip): strips, the v*v
+//                        table, the u*u registers, the four-pixel loads (16-byte when the width and the bases allow, else guarded
+//                        scalar loads with the same counts).  A chunk in which neither render has a positive depth is skipped (it
+//                        cannot be visible).  The 2 + n_tau predicates are reduced per wave by ballot + population count, per
+//                        workgroup through LDS, then one integer atomicAdd per counter.
 //   vsd_finalize_kernel  one thread per row: counts -> errs (NaN / -1 for an invalid row)
 #include "common.h"
+#include "depth_walk.h"
 #include "vsd_core.h"
 
 namespace mp {
@@ -19,8 +20,6 @@ using vsd::kMaxSide;
 using vsd::kMaxTau;
 
 struct VsdTaus { float v[kMaxTau]; };
-
-constexpr int kVsdChunks = kMaxSide / 256;   // 256-pixel chunks of an image row
 
 template <int NT, bool VEC>
 __global__ __launch_bounds__(256) void vsd_count_kernel(const float* __restrict__ depth_est, const int32_t* __restrict__ est_ids,
@@ -37,23 +36,14 @@ __global__ __launch_bounds__(256) void vsd_count_kernel(const float* __restrict_
   const float diam = diameter[row];
   if (!vsd::row_valid(Kr, diam)) return;   // uniform over the workgroup; the finalize kernel writes NaN / -1
   const int y0 = blockIdx.y * rows_per_strip, y1 = min(h, y0 + rows_per_strip);
-  for (int i = threadIdx.x; i < y1 - y0; i += 256) {
-    const float v = vsd::ray_v(Kr, y0 + i);
-    vv_s[i] = v * v;
-  }
+  dw::fill_vv(Kr, y0, y1, vv_s);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float thr[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) thr[t] = t < n_tau ? vsd::threshold(taus.v[t], diam, normalized) : vsd::quiet_nan();   // NaN: never far
-  float uu[kVsdChunks][4];
-#pragma unroll
-  for (int c = 0; c < kVsdChunks; ++c)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float u = vsd::ray_u(Kr, c * 256 + lane * 4 + k);
-      uu[c][k] = u * u;
-    }
+  float uu[dw::kChunks][4];
+  dw::fill_uu(Kr, lane, uu);
   const size_t hw = (size_t)h * w;
   const float* E = depth_est + (size_t)(est_ids ? est_ids[row] : row) * hw;
   const float* G = depth_gt + (size_t)(gt_ids ? gt_ids[row] : row) * hw;
@@ -65,24 +55,13 @@ __global__ __launch_bounds__(256) void vsd_count_kernel(const float* __restrict_
     const float vv = vv_s[y - y0];
     const size_t off = (size_t)y * w;
 #pragma unroll
-    for (int c = 0; c < kVsdChunks; ++c) {
+    for (int c = 0; c < dw::kChunks; ++c) {
       if (c * 256 >= w) break;   // uniform
       const int x0 = c * 256 + lane * 4;
-      float e[4] = {0.f, 0.f, 0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f}, t[4] = {0.f, 0.f, 0.f, 0.f};
-      if (VEC) {
-        if (x0 < w) {   // w % 4 == 0: the four pixels are inside together
-          const float4 e4 = *reinterpret_cast<const float4*>(E + off + x0);
-          const float4 g4 = *reinterpret_cast<const float4*>(G + off + x0);
-          const float4 t4 = *reinterpret_cast<const float4*>(T + off + x0);
-          e[0] = e4.x; e[1] = e4.y; e[2] = e4.z; e[3] = e4.w;
-          g[0] = g4.x; g[1] = g4.y; g[2] = g4.z; g[3] = g4.w;
-          t[0] = t4.x; t[1] = t4.y; t[2] = t4.z; t[3] = t4.w;
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (x0 + k < w) { e[k] = E[off + x0 + k]; g[k] = G[off + x0 + k]; t[k] = T[off + x0 + k]; }
-      }
+      float e[4], g[4], t[4];
+      dw::load4<VEC>(E, off, x0, w, e);
+      dw::load4<VEC>(G, off, x0, w, g);
+      dw::load4<VEC>(T, off, x0, w, t);
       // a depth that is not > 0 gives a distance that is not > 0: such a pixel is in neither mask
       const bool any = e[0] > 0.f || e[1] > 0.f || e[2] > 0.f || e[3] > 0.f || g[0] > 0.f || g[1] > 0.f || g[2] > 0.f || g[3] > 0.f;
       if (__ballot(any) == 0) continue;
@@ -124,8 +103,6 @@ __global__ __launch_bounds__(256) void vsd_finalize_kernel(const float* __restri
     for (int k = 0; k < 2 + n_tau; ++k) counts[(size_t)row * (2 + n_tau) + k] = ok ? c[k] : -1;
 }
 
-static inline size_t vsd_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 template <int NT>
 static void vsd_launch(bool vec, dim3 grid, hipStream_t s, const float* e, const int32_t* ei, const float* g, const int32_t* gi, const float* t,
                        const int32_t* ti, const float* K, const float* diam, int h, int w, int rps, float delta, const VsdTaus& taus, int n_tau,
@@ -144,7 +121,7 @@ using namespace mp;
 
 extern "C" size_t mp_vsd_workspace_bytes(int b, int n_tau) {
   if (b < 0 || n_tau < 1 || n_tau > kMaxTau) return 0;
-  return vsd_align256((size_t)b * (2 + n_tau) * sizeof(int32_t)) + 256;
+  return align256((size_t)b * (2 + n_tau) * sizeof(int32_t)) + 256;
 }
 
 extern "C" int mp_vsd(const float* d_depth_est, const int32_t* d_est_ids, const float* d_depth_gt, const int32_t* d_gt_ids,
@@ -163,20 +140,16 @@ extern "C" int mp_vsd(const float* d_depth_est, const int32_t* d_est_ids, const 
   // without ids the maps are row-aligned: there must be one per row
   MP_REQUIRE((d_est_ids || n_est >= b) && (d_gt_ids || n_gt >= b) && (d_im_ids || n_im >= b), "mp_vsd: fewer maps than rows and no ids");
   MP_REQUIRE(workspace_bytes >= mp_vsd_workspace_bytes(b, n_tau), "mp_vsd: workspace too small");
-  int strips = split > 0 ? split : ceil_div(4096, b);   // a few thousand workgroups when the rows alone cannot give them
-  const int max_strips = ceil_div(h, 4);                 // at least one image row per wave
-  strips = strips < 1 ? 1 : (strips > max_strips ? max_strips : strips);
-  const int rps = ceil_div(h, strips);
-  strips = ceil_div(h, rps);
+  const dw::Strips st = dw::strips_of(split, 4096, b, h);   // a few thousand workgroups when the rows alone cannot give them
   VsdTaus taus;
   for (int t = 0; t < kMaxTau; ++t) taus.v[t] = t < n_tau ? h_taus[t] : 0.f;
-  const bool vec = (w % 4 == 0) && (((uintptr_t)d_depth_est | (uintptr_t)d_depth_gt | (uintptr_t)d_depth_test) % 16 == 0);
+  const bool vec = dw::vec_ok(w, {d_depth_est, d_depth_gt, d_depth_test});
   int32_t* counters = (int32_t*)d_workspace;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("vsd", 0.0, (double)b * h * w * 12.0, s);
   MP_CHECK_HIP(hipMemsetAsync(counters, 0, (size_t)b * (2 + n_tau) * sizeof(int32_t), s));
-  const dim3 grid(b, strips);
-#define MP_VSD_ARGS vec, grid, s, d_depth_est, d_est_ids, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, d_diameter, h, w, rps, delta, taus, n_tau, \
+  const dim3 grid(b, st.strips);
+#define MP_VSD_ARGS vec, grid, s, d_depth_est, d_est_ids, d_depth_gt, d_gt_ids, d_depth_test, d_im_ids, d_K, d_diameter, h, w, st.rows_per_strip, delta, taus, n_tau, \
                     normalized ? 1 : 0, counters
   if (n_tau <= 1) vsd_launch<1>(MP_VSD_ARGS);
   else if (n_tau <= 4) vsd_launch<4>(MP_VSD_ARGS);

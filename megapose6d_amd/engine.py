@@ -49,6 +49,11 @@ def _dev_i32(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
+def _workspace(n_bytes: int, device) -> torch.Tensor:
+    """a launch's scratch of at least n_bytes (never empty: the entries refuse a null workspace)"""
+    return torch.empty(max(int(n_bytes), 256), dtype=torch.uint8, device=device)
+
+
 def clock_probe(ms_target: float = 20.0) -> Dict[str, float]:
     """Effective shader clock (MHz) under fp32-MFMA load and the probe loop's own TFLOP/s (synchronises; mp_clock_probe)."""
     mhz, tf = C.c_double(0), C.c_double(0)
@@ -730,18 +735,19 @@ def _pose_error_points(points: torch.Tensor, mesh_ids, n_points, b: int):
 
 
 def pose_error_workspace(b: int, n_pts: int, S_max: int, device) -> torch.Tensor:
-    n = int(_lib.load().mp_pose_error_workspace_bytes(b, n_pts, S_max))
-    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+    return _workspace(_lib.load().mp_pose_error_workspace_bytes(b, n_pts, S_max), device)
 
 
-def pose_error_sym(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Optional[torch.Tensor], n_sym: Optional[torch.Tensor],
-                   points: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None,
-                   reduce: int = POSE_ERROR_MEAN, split: int = 0, with_errs: bool = True, with_diffs: bool = False,
-                   with_alt: bool = False) -> Dict[str, torch.Tensor]:
-    """Symmetry-set error (mp_pose_error_sym).  `symmetries` [n_mesh,S,4,4] + `n_sym` [n_mesh]: T_gt [b,4,4] is composed with them;
-    `symmetries` None: T_gt holds the candidates [b,S,4,4].  -> err, idx, T_gt_sym (+ errs [b,S], diffs [b,N,3], err_alt)."""
+def _pose_error_sym_set(entry, T_pred, T_gt, symmetries, n_sym, points, mesh_ids, n_points, reduce, split, with_errs, with_alt,
+                        K=None, with_diffs=None) -> Dict[str, torch.Tensor]:
+    """what mp_pose_error_sym and mp_pose_error_mspd (`entry`) share: checks, outputs, workspace.  K: only the projected entry takes it;
+    with_diffs: only the 3D entry has the argument (None = it has not)."""
     T_pred, T_gt = _dev_f32(T_pred), _dev_f32(T_gt)
     b = T_pred.shape[0]
+    if K is not None:
+        K = _dev_f32(K)
+        if K.shape != (b, 3, 3):
+            raise EngineError(f"K must be [b,3,3], got {tuple(K.shape)}")
     points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
     if symmetries is not None:
         symmetries = _dev_f32(symmetries)
@@ -764,11 +770,22 @@ def pose_error_sym(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Optiona
     if with_alt:
         out["err_alt"] = torch.empty(b, **f)
     ws = pose_error_workspace(b, n_pts, S, dev)
-    check(_lib.load().mp_pose_error_sym(T_pred.data_ptr(), T_gt.data_ptr(), _ptr(symmetries), _ptr(n_sym),
-                                        S, points.data_ptr(), n_pts, mesh_ids.data_ptr(), _ptr(n_points), n_pts, b, int(reduce), int(split),
-                                        out["err"].data_ptr(), _ptr(out.get("err_alt")), out["idx"].data_ptr(), out["T_gt_sym"].data_ptr(),
-                                        _ptr(out.get("errs")), _ptr(out.get("diffs")), ws.data_ptr(), ws.numel(), _stream()))
+    # the two signatures differ in one argument each: K before the outputs, diffs after them
+    check(entry(T_pred.data_ptr(), T_gt.data_ptr(), _ptr(symmetries), _ptr(n_sym), S, points.data_ptr(), n_pts, mesh_ids.data_ptr(),
+                _ptr(n_points), n_pts, b, int(reduce), int(split), *([] if K is None else [K.data_ptr()]), out["err"].data_ptr(),
+                _ptr(out.get("err_alt")), out["idx"].data_ptr(), out["T_gt_sym"].data_ptr(), _ptr(out.get("errs")),
+                *([] if with_diffs is None else [_ptr(out.get("diffs"))]), ws.data_ptr(), ws.numel(), _stream()))
     return out
+
+
+def pose_error_sym(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Optional[torch.Tensor], n_sym: Optional[torch.Tensor],
+                   points: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None, n_points: Optional[torch.Tensor] = None,
+                   reduce: int = POSE_ERROR_MEAN, split: int = 0, with_errs: bool = True, with_diffs: bool = False,
+                   with_alt: bool = False) -> Dict[str, torch.Tensor]:
+    """Symmetry-set error (mp_pose_error_sym).  `symmetries` [n_mesh,S,4,4] + `n_sym` [n_mesh]: T_gt [b,4,4] is composed with them;
+    `symmetries` None: T_gt holds the candidates [b,S,4,4].  -> err, idx, T_gt_sym (+ errs [b,S], diffs [b,N,3], err_alt)."""
+    return _pose_error_sym_set(_lib.load().mp_pose_error_sym, T_pred, T_gt, symmetries, n_sym, points, mesh_ids, n_points, reduce, split,
+                               with_errs, with_alt, with_diffs=bool(with_diffs))
 
 
 def pose_error_nn(T_pred: torch.Tensor, T_gt: torch.Tensor, points: torch.Tensor, mesh_ids: Optional[torch.Tensor] = None,
@@ -817,35 +834,20 @@ def pose_error_mspd(T_pred: torch.Tensor, T_gt: torch.Tensor, symmetries: Option
                     reduce: int = POSE_ERROR_MAX, split: int = 0, with_errs: bool = True, with_alt: bool = False) -> Dict[str, torch.Tensor]:
     """Projected symmetry-set error (mp_pose_error_mspd; reduce = max is BOP's MSPD, in pixels).  Arguments as `pose_error_sym` plus
     K [b,3,3] -> err, idx, T_gt_sym (+ errs [b,S], err_alt)."""
-    T_pred, T_gt, K = _dev_f32(T_pred), _dev_f32(T_gt), _dev_f32(K)
-    b = T_pred.shape[0]
-    if K.shape != (b, 3, 3):
-        raise EngineError(f"K must be [b,3,3], got {tuple(K.shape)}")
-    points, mesh_ids, n_points = _pose_error_points(points, mesh_ids, n_points, b)
-    if symmetries is not None:
-        symmetries = _dev_f32(symmetries)
-        S = symmetries.shape[1]
-        if T_gt.shape != (b, 4, 4):
-            raise EngineError(f"T_gt must be [b,4,4], got {tuple(T_gt.shape)}")
-    else:
-        if T_gt.dim() != 4 or T_gt.shape[0] != b:
-            raise EngineError(f"candidate poses must be [b,S,4,4], got {tuple(T_gt.shape)}")
-        S = T_gt.shape[1]
-    n_sym = None if symmetries is None or n_sym is None else _dev_i32(n_sym)
-    n_pts = points.shape[1]
-    dev = T_pred.device
-    f = dict(dtype=torch.float32, device=dev)
-    out = dict(err=torch.empty(b, **f), idx=torch.empty(b, dtype=torch.int32, device=dev), T_gt_sym=torch.empty(b, 4, 4, **f))
-    if with_errs:
-        out["errs"] = torch.empty(b, S, **f)
-    if with_alt:
-        out["err_alt"] = torch.empty(b, **f)
-    ws = pose_error_workspace(b, n_pts, S, dev)
-    check(_lib.load().mp_pose_error_mspd(T_pred.data_ptr(), T_gt.data_ptr(), _ptr(symmetries), _ptr(n_sym), S, points.data_ptr(), n_pts,
-                                         mesh_ids.data_ptr(), _ptr(n_points), n_pts, b, int(reduce), int(split), K.data_ptr(),
-                                         out["err"].data_ptr(), _ptr(out.get("err_alt")), out["idx"].data_ptr(), out["T_gt_sym"].data_ptr(),
-                                         _ptr(out.get("errs")), ws.data_ptr(), ws.numel(), _stream()))
-    return out
+    return _pose_error_sym_set(_lib.load().mp_pose_error_mspd, T_pred, T_gt, symmetries, n_sym, points, mesh_ids, n_points, reduce, split,
+                               with_errs, with_alt, K=K)
+
+
+def _row_ids(name: str, ids: Optional[torch.Tensor], maps: torch.Tensor, b: int) -> Optional[torch.Tensor]:
+    """the optional map index of each of b rows: None needs one map per row, else int32 [b] on the device"""
+    if ids is None:
+        if maps.shape[0] < b:
+            raise EngineError(f"without {name} the maps are per row: need {b}, got {maps.shape[0]}")
+        return None
+    ids = _dev_i32(ids)
+    if ids.shape != (b,):
+        raise EngineError(f"{name} must be [b], got {tuple(ids.shape)}")
+    return ids
 
 
 # --------------------------------------------------------------------------- #
@@ -869,16 +871,7 @@ def vsd(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: torch.Tenso
     if K.shape != (b, 3, 3) or diameter.shape != (b,):
         raise EngineError(f"K must be [b,3,3] and diameter [b], got {tuple(K.shape)}, {tuple(diameter.shape)}")
     h, w = depth_est.shape[1:]
-    ids = []
-    for name, i, maps in (("est_ids", est_ids, depth_est), ("gt_ids", gt_ids, depth_gt), ("im_ids", im_ids, depth_test)):
-        if i is None:
-            if maps.shape[0] < b:
-                raise EngineError(f"without {name} the maps are per row: need {b}, got {maps.shape[0]}")
-        else:
-            i = _dev_i32(i)
-            if i.shape != (b,):
-                raise EngineError(f"{name} must be [b], got {tuple(i.shape)}")
-        ids.append(i)
+    ids = [_row_ids("est_ids", est_ids, depth_est, b), _row_ids("gt_ids", gt_ids, depth_gt, b), _row_ids("im_ids", im_ids, depth_test, b)]
     taus = [float(t) for t in (VSD_TAUS if taus is None else taus)]
     n_tau = len(taus)
     h_taus = (C.c_float * max(n_tau, 1))(*taus)
@@ -887,7 +880,7 @@ def vsd(depth_est: torch.Tensor, depth_gt: torch.Tensor, depth_test: torch.Tenso
     if with_counts:
         out["counts"] = torch.empty(b, 2 + n_tau, dtype=torch.int32, device=dev)
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.mp_vsd_workspace_bytes(b, n_tau)), 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mp_vsd_workspace_bytes(b, n_tau), dev)
     check(lib.mp_vsd(depth_est.data_ptr(), _ptr(ids[0]), depth_gt.data_ptr(), _ptr(ids[1]), depth_test.data_ptr(), _ptr(ids[2]),
                      depth_est.shape[0], depth_gt.shape[0], depth_test.shape[0], K.data_ptr(), diameter.data_ptr(), b, h, w, float(delta),
                      C.cast(h_taus, C.c_void_p), n_tau, int(bool(normalized_by_diameter)), int(split), out["errs"].data_ptr(),
@@ -914,16 +907,7 @@ def gt_info(depth_gt: torch.Tensor, depth_test: torch.Tensor, K: torch.Tensor, c
     if K.shape != (b, 3, 3):
         raise EngineError(f"K must be [b,3,3], got {tuple(K.shape)}")
     h, w = depth_test.shape[1:]
-    ids = []
-    for name, i, maps in (("gt_ids", gt_ids, depth_gt), ("im_ids", im_ids, depth_test)):
-        if i is None:
-            if maps.shape[0] < b:
-                raise EngineError(f"without {name} the maps are per row: need {b}, got {maps.shape[0]}")
-        else:
-            i = _dev_i32(i)
-            if i.shape != (b,):
-                raise EngineError(f"{name} must be [b], got {tuple(i.shape)}")
-        ids.append(i)
+    ids = [_row_ids("gt_ids", gt_ids, depth_gt, b), _row_ids("im_ids", im_ids, depth_test, b)]
     dev = K.device
     out = dict(counts=torch.empty(b, 4, dtype=torch.int32, device=dev), boxes=torch.empty(b, 8, dtype=torch.int32, device=dev),
                visib_fract=torch.empty(b, dtype=torch.float32, device=dev))
@@ -931,7 +915,7 @@ def gt_info(depth_gt: torch.Tensor, depth_test: torch.Tensor, K: torch.Tensor, c
         out["mask"] = torch.empty(b, h, w, dtype=torch.uint8, device=dev)
         out["mask_visib"] = torch.empty(b, h, w, dtype=torch.uint8, device=dev)
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.mp_gt_info_workspace_bytes(b)), 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mp_gt_info_workspace_bytes(b), dev)
     check(lib.mp_gt_info(depth_gt.data_ptr(), _ptr(ids[0]), depth_test.data_ptr(), _ptr(ids[1]), depth_gt.shape[0], depth_test.shape[0],
                          K.data_ptr(), b, h, w, int(canvas), float(delta), int(split), out["counts"].data_ptr(), out["boxes"].data_ptr(),
                          out["visib_fract"].data_ptr(), _ptr(out.get("mask")), _ptr(out.get("mask_visib")), ws.data_ptr(), ws.numel(),
@@ -983,7 +967,7 @@ def bop_match(errs: torch.Tensor, index: Dict[str, torch.Tensor], thr: torch.Ten
     n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
     match = torch.empty(int(n_pred), e, n_theta, dtype=torch.int32, device=dev)
     lib = _lib.load()
-    ws = torch.empty(max(int(lib.mp_bop_match_workspace_bytes(n_words, e, n_theta)), 256), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib.mp_bop_match_workspace_bytes(n_words, e, n_theta), dev)
     check(lib.mp_bop_match(errs.data_ptr(), ix["cand_gt"].data_ptr(), ix["cand_lgt"].data_ptr(), ix["est_row"].data_ptr(),
                            ix["est_off"].data_ptr(), ix["group_est_off"].data_ptr(), ix["group_n_gt"].data_ptr(),
                            ix["group_taken_off"].data_ptr(), _ptr(n_top), thr.data_ptr(), int(n_pred), c, n_est, n_groups, n_words, e, n_theta,

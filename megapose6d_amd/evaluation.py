@@ -139,6 +139,7 @@ def summary(df: pd.DataFrame) -> Dict[str, float]:
 # --------------------------------------------------------------------------------------------------------------------------------
 BOP_TAUS = eng.VSD_TAUS                     # VSD misalignment tolerances, fractions of the diameter
 BOP_THRESHOLDS = eng.VSD_TAUS               # thresholds of correctness of the VSD error and of MSSD / diameter
+BOP_THETAS_PX = tuple(range(5, 51, 5))      # thresholds of correctness of MSPD, pixels at an image width of 640
 BOP_DEPTH_BYTES = 256 << 20                 # bytes of estimate depth maps `bop_errors` holds at once
 
 
@@ -196,6 +197,82 @@ def _placeholder_pose(dev) -> torch.Tensor:
     return place
 
 
+def _thetas_px(image_width) -> np.ndarray:
+    return np.asarray(BOP_THETAS_PX, np.float64) * (float(image_width) / 640.0)
+
+
+def _valid_mask(valid, index, n: int, what: str = "the ground truth") -> np.ndarray:
+    if valid is None:
+        return np.ones(n, np.bool_)
+    valid = valid.reindex(index).to_numpy() if isinstance(valid, pd.Series) else np.asarray(valid)
+    if valid.dtype != np.bool_ or valid.shape != (n,):
+        raise ValueError(f"valid must be one boolean per row of {what}")
+    return valid
+
+
+def _bop_pair_errors(pred, gt, pid: np.ndarray, gid: np.ndarray, gt_labels, gt_im: np.ndarray, meshes, renderer, depth: torch.Tensor,
+                     K: torch.Tensor, delta: float, taus, gt_blank_with: Optional[np.ndarray] = None):
+    """The three BOP 2019 errors of the pairs (estimate pid[i] of `pred`, ground truth gid[i] of `gt`), int64 arrays [n]; the object and the
+    frame of a pair are those of its estimate; depth, K as `_bop_frames` returns them.  Every distinct estimate is rendered once under its
+    own label and frame, BOP_DEPTH_BYTES of depth maps at a time; the j-th distinct ground truth (in the order of np.unique(gid)) once
+    under the label gt_labels[j] and the K of frame gt_im[j], in launches of the same size.  A non-finite pose is not handed to the
+    rasteriser (a placeholder is rendered) and gives NaN on its pairs; with gt_blank_with (one pair per distinct ground truth) the
+    placeholder also stands for a ground truth whose named pair has a non-finite estimate.
+    -> vsd [n,n_tau] float32, the dicts of pose_error_sym (MSSD) and pose_error_mspd.  Nothing synchronises."""
+    dev = meshes.points.device
+    n = len(pid)
+    H, W = int(depth.shape[1]), int(depth.shape[2])
+    labels_pred = list(pred.infos["label"])
+    im_pred = pred.infos["batch_im_id"].to_numpy().astype(np.int64)
+    T_pred = pred.poses.to(device=dev, dtype=torch.float32).contiguous()
+    T_gt = gt.poses.to(device=dev, dtype=torch.float32).contiguous()
+    pid_t, gid_t = torch.from_numpy(pid).to(dev), torch.from_numpy(gid).to(dev)
+    labels = [labels_pred[i] for i in pid]
+    im32 = torch.from_numpy(im_pred[pid].astype(np.int32)).to(dev)
+    K_rows = K[im32.long()].contiguous()
+    ids, n_points, n_sym = _mesh_tables(meshes, labels, dev)
+    Tp, Tg = T_pred[pid_t].contiguous(), T_gt[gid_t].contiguous()
+    e3 = eng.pose_error_sym(Tp, Tg, meshes.symmetries, n_sym, meshes.points, mesh_ids=ids, n_points=n_points, reduce=eng.POSE_ERROR_MAX,
+                            with_errs=False)
+    e2 = eng.pose_error_mspd(Tp, Tg, meshes.symmetries, n_sym, meshes.points, K_rows, mesh_ids=ids, n_points=n_points, with_errs=False)
+    diam = _diameters(meshes)
+    diam_t = torch.tensor([diam[l] for l in labels], dtype=torch.float32, device=dev)
+    bad_pred, bad_gt = ~torch.isfinite(T_pred).flatten(1).all(1), ~torch.isfinite(T_gt).flatten(1).all(1)
+    rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
+    u_gt, inv_gt = np.unique(gid, return_inverse=True)
+    u_pred, inv_pred = np.unique(pid, return_inverse=True)
+    u_gt_t, u_pred_t = torch.from_numpy(u_gt).to(dev), torch.from_numpy(u_pred).to(dev)
+    blank_gt = bad_gt[u_gt_t]
+    if gt_blank_with is not None:
+        blank_gt = blank_gt | bad_pred[pid_t[torch.from_numpy(gt_blank_with).to(dev)]]
+    place = _placeholder_pose(dev)
+    R_pred = torch.where(bad_pred[u_pred_t, None, None], place, T_pred[u_pred_t])
+    R_gt = torch.where(blank_gt[:, None, None], place, T_gt[u_gt_t])
+    K_gt = K[torch.from_numpy(np.asarray(gt_im, np.int64)).to(dev)]
+    K_pred = K[torch.from_numpy(im_pred[u_pred]).to(dev)]
+    depth_gt = torch.empty(len(u_gt), H, W, dtype=torch.float32, device=dev)
+    for r0 in range(0, len(u_gt), rows_per_launch):
+        r1 = min(len(u_gt), r0 + rows_per_launch)
+        depth_gt[r0:r1] = renderer.render_depth(list(gt_labels[r0:r1]), R_gt[r0:r1], K_gt[r0:r1], (H, W))
+    # pairs in the order of their estimate, so that a portion of estimates is a run of pairs
+    order = np.argsort(inv_pred, kind="stable")
+    est_sorted = inv_pred[order]
+    gt_ids = torch.from_numpy(inv_gt.astype(np.int32)).to(dev)
+    est_ids = torch.from_numpy(inv_pred.astype(np.int32)).to(dev)
+    order_t = torch.from_numpy(order).to(dev)
+    vsd_errs = torch.empty(n, len(taus), dtype=torch.float32, device=dev)
+    for r0 in range(0, len(u_pred), rows_per_launch):
+        r1 = min(len(u_pred), r0 + rows_per_launch)
+        depth_est = renderer.render_depth([labels_pred[i] for i in u_pred[r0:r1]], R_pred[r0:r1], K_pred[r0:r1], (H, W))
+        rows = order_t[int(np.searchsorted(est_sorted, r0)):int(np.searchsorted(est_sorted, r1))]
+        vsd_errs[rows] = eng.vsd(depth_est, depth_gt, depth, K_rows[rows].contiguous(), diam_t[rows].contiguous(), delta=delta, taus=taus,
+                                 est_ids=(est_ids[rows] - r0).contiguous(), gt_ids=gt_ids[rows].contiguous(), im_ids=im32[rows].contiguous(),
+                                 with_counts=False)["errs"]
+    bad = bad_pred[pid_t] | bad_gt[gid_t]
+    vsd_errs = torch.where(bad[:, None], torch.full_like(vsd_errs, float("nan")), vsd_errs)
+    return vsd_errs, e3, e2
+
+
 def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, gt_index=None, delta: float = 0.015,
                taus: Optional[Sequence[float]] = None) -> pd.DataFrame:
     """The three BOP 2019 errors of `pred.poses` -> a DataFrame aligned with `pred.infos`: vsd_0.05 ... vsd_0.50 (one per tau), mssd
@@ -215,46 +292,18 @@ def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
         raise ValueError("gt_index must name one row of `gt` per prediction")
     im = pred.infos["batch_im_id"].to_numpy().astype(np.int64)
     depth, K = _bop_frames(depth, K, im, dev)
-    H, W = int(depth.shape[1]), int(depth.shape[2])
-    im_t = torch.from_numpy(im).to(dev)
-    T_pred = pred.poses.to(device=dev, dtype=torch.float32).contiguous()
-    T_gt = gt.poses.to(device=dev, dtype=torch.float32)[torch.from_numpy(gt_index).to(dev)].contiguous()
-    K_rows = K[im_t].contiguous()
-    ids, n_points, n_sym = _mesh_tables(meshes, labels, dev)
-    e3 = eng.pose_error_sym(T_pred, T_gt, meshes.symmetries, n_sym, meshes.points, mesh_ids=ids, n_points=n_points, reduce=eng.POSE_ERROR_MAX,
-                            with_errs=False)
-    e2 = eng.pose_error_mspd(T_pred, T_gt, meshes.symmetries, n_sym, meshes.points, K_rows, mesh_ids=ids, n_points=n_points, with_errs=False)
-    diam = _diameters(meshes)
-    diam_rows = [diam[l] for l in labels]
-    diam_t = torch.tensor(diam_rows, dtype=torch.float32, device=dev)
-    # a non-finite pose is not handed to the rasteriser: a placeholder is rendered and the row's errors are set to NaN
-    bad = ~(torch.isfinite(T_pred).flatten(1).all(1) & torch.isfinite(T_gt).flatten(1).all(1))
-    place = _placeholder_pose(dev)
-    R_pred = torch.where(bad[:, None, None], place, T_pred)
-    R_gt = torch.where(bad[:, None, None], place, T_gt)
-    rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
-    uniq, first, inv = np.unique(gt_index, return_index=True, return_inverse=True)
-    first_t = torch.from_numpy(first).to(dev)
-    depth_gt = torch.empty(len(uniq), H, W, dtype=torch.float32, device=dev)
-    for r0 in range(0, len(uniq), rows_per_launch):
-        sel = first[r0:r0 + rows_per_launch]
-        depth_gt[r0:r0 + len(sel)] = renderer.render_depth([labels[i] for i in sel], R_gt[first_t[r0:r0 + len(sel)]], K_rows[first_t[r0:r0 + len(sel)]], (H, W))
-    inv_t = torch.from_numpy(inv.astype(np.int32)).to(dev)
-    im32 = im_t.to(torch.int32)
-    vsd_errs = torch.empty(n, len(taus), dtype=torch.float32, device=dev)
-    for r0 in range(0, n, rows_per_launch):
-        r1 = min(n, r0 + rows_per_launch)
-        depth_est = renderer.render_depth(labels[r0:r1], R_pred[r0:r1], K_rows[r0:r1], (H, W))
-        vsd_errs[r0:r1] = eng.vsd(depth_est, depth_gt, depth, K_rows[r0:r1].contiguous(), diam_t[r0:r1].contiguous(), delta=delta, taus=taus,
-                                  gt_ids=inv_t[r0:r1].contiguous(), im_ids=im32[r0:r1].contiguous(), with_counts=False)["errs"]
-    vsd_errs = torch.where(bad[:, None], torch.full_like(vsd_errs, float("nan")), vsd_errs)
+    # a ground truth is rendered as the first estimate that names it sees it: under that estimate's label and K
+    first = np.unique(gt_index, return_index=True)[1]
+    vsd_errs, e3, e2 = _bop_pair_errors(pred, gt, np.arange(n, dtype=np.int64), gt_index, [labels[i] for i in first], im[first], meshes,
+                                           renderer, depth, K, delta, taus, gt_blank_with=first)
     table = torch.cat([vsd_errs.double(), e3["err"].double()[:, None], e2["err"].double()[:, None], e3["idx"].double()[:, None],
                        e2["idx"].double()[:, None]], dim=1).cpu().numpy()   # the one synchronising copy
     names = _vsd_names(taus)
     df = pd.DataFrame({c: table[:, k] for k, c in enumerate(names + ["mssd", "mspd"])}, index=pred.infos.index)
     df["sym_id_mssd"] = table[:, -2].astype(np.int64)
     df["sym_id_mspd"] = table[:, -1].astype(np.int64)
-    df["diameter"] = diam_rows
+    diam = _diameters(meshes)
+    df["diameter"] = [diam[l] for l in labels]
     return df
 
 
@@ -265,10 +314,7 @@ def bop_recall(df: pd.DataFrame, image_width: int = 640, valid=None) -> Dict[str
       valid  optional boolean mask (array, or Series indexed like `df`) of the rows that are targets, e.g. `gt_info(...)["visib_fract"]
              >= 0.1` taken at each row's ground truth (evaluation/meters/utils.py:86-104); the recalls are those of `df[valid]`."""
     if valid is not None:
-        valid = valid.reindex(df.index).to_numpy() if isinstance(valid, pd.Series) else np.asarray(valid)
-        if valid.dtype != np.bool_ or valid.shape != (len(df),):
-            raise ValueError("valid must be one boolean per row of the table")
-        df = df[valid]
+        df = df[_valid_mask(valid, df.index, len(df), "the table")]
     thetas = np.asarray(BOP_THRESHOLDS, np.float64)
     cols = [c for c in df.columns if re.fullmatch(r"vsd_\d+\.\d+", c)]
     if not cols or len(df) == 0:
@@ -276,7 +322,7 @@ def bop_recall(df: pd.DataFrame, image_width: int = 640, valid=None) -> Dict[str
     e_vsd = df[cols].to_numpy(np.float64)
     ar_vsd = float((e_vsd[:, :, None] < thetas[None, None, :]).mean())
     ar_mssd = float((df["mssd"].to_numpy(np.float64)[:, None] < thetas[None, :] * df["diameter"].to_numpy(np.float64)[:, None]).mean())
-    thetas_px = np.arange(5, 51, 5).astype(np.float64) * (float(image_width) / 640.0)
+    thetas_px = _thetas_px(image_width)
     ar_mspd = float((df["mspd"].to_numpy(np.float64)[:, None] < thetas_px[None, :]).mean())
     return {"ar_vsd": ar_vsd, "ar_mssd": ar_mssd, "ar_mspd": ar_mspd, "ar": (ar_vsd + ar_mssd + ar_mspd) / 3.0}
 
@@ -348,10 +394,7 @@ def gt_info(gt, renderer, depth: torch.Tensor, K: torch.Tensor, delta: float = 0
     labels = list(gt.infos["label"])
     im = gt.infos["batch_im_id"].to_numpy().astype(np.int64)
     dev = depth.device if depth.is_cuda else torch.device("cuda")
-    depth = depth.to(device=dev, dtype=torch.float32).contiguous()
-    K = K.to(device=dev, dtype=torch.float32)
-    if depth.dim() != 3 or K.shape != (depth.shape[0], 3, 3) or (n and (im.min() < 0 or im.max() >= depth.shape[0])):
-        raise ValueError("depth must be [n_im,H,W], K [n_im,3,3], and batch_im_id must index them")
+    depth, K = _bop_frames(depth, K, im, dev)
     H, W = int(depth.shape[1]), int(depth.shape[2])
     n_tiles = canvas * canvas
     im_t = torch.from_numpy(im).to(dev)
@@ -359,8 +402,7 @@ def gt_info(gt, renderer, depth: torch.Tensor, K: torch.Tensor, delta: float = 0
     K_rows = K[im_t].contiguous()
     # a non-finite pose or K is not handed to the rasteriser: a placeholder is rendered and the row's results are set to -1 / NaN
     bad = ~(torch.isfinite(T).flatten(1).all(1) & torch.isfinite(K_rows).flatten(1).all(1))
-    place = torch.eye(4, device=dev)
-    place[2, 3] = 1.0
+    place = _placeholder_pose(dev)
     K_place = torch.tensor([[float(W), 0.0, 0.5 * W], [0.0, float(W), 0.5 * H], [0.0, 0.0, 1.0]], device=dev)
     R = torch.where(bad[:, None, None], place, T)
     K_tiles = tile_intrinsics(torch.where(bad[:, None, None], K_place, K_rows), canvas, (H, W))
@@ -410,18 +452,6 @@ def detections_from_gt_info(gt, info: pd.DataFrame, visib_gt_min: float = 0.0) -
 # --------------------------------------------------------------------------------------------------------------------------------
 # BOP's matching of estimates to ground truths: candidates, their errors, the greedy matching, the scores
 # --------------------------------------------------------------------------------------------------------------------------------
-BOP_THETAS_PX = tuple(range(5, 51, 5))      # thresholds of correctness of MSPD, pixels at an image width of 640
-
-
-def _valid_mask(valid, index, n: int) -> np.ndarray:
-    if valid is None:
-        return np.ones(n, np.bool_)
-    valid = valid.reindex(index).to_numpy() if isinstance(valid, pd.Series) else np.asarray(valid)
-    if valid.dtype != np.bool_ or valid.shape != (n,):
-        raise ValueError("valid must be one boolean per row of the ground truth")
-    return valid
-
-
 def bop_candidates(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, valid=None, keys=("batch_im_id", "label")) -> pd.DataFrame:
     """evaluation/meters/utils.py:107-117 get_candidate_matches(only_valids=True), on the host as a pandas merge -> a DataFrame
     `pred_id`, `gt_id`, `group_id` (int64; positions in the two tables) of every (estimate, ground truth) pair that agrees on `keys`
@@ -454,57 +484,14 @@ def bop_candidate_errors(pred, gt, cand: pd.DataFrame, meshes, renderer, depth: 
     n = len(pid)
     if n and (pid.min() < 0 or pid.max() >= len(pred.infos) or gid.min() < 0 or gid.max() >= len(gt.infos)):
         raise ValueError("cand must name rows of `pred` and of `gt`")
-    labels_pred, labels_gt = list(pred.infos["label"]), list(gt.infos["label"])
+    labels_gt = list(gt.infos["label"])
     im_pred = pred.infos["batch_im_id"].to_numpy().astype(np.int64)
     im_gt = gt.infos["batch_im_id"].to_numpy().astype(np.int64)
     depth, K = _bop_frames(depth, K, np.concatenate([im_pred, im_gt]), dev)
-    H, W = int(depth.shape[1]), int(depth.shape[2])
     if n == 0:
         return torch.empty(0, len(taus) + 2, dtype=torch.float32, device=dev)
-    T_pred = pred.poses.to(device=dev, dtype=torch.float32).contiguous()
-    T_gt = gt.poses.to(device=dev, dtype=torch.float32).contiguous()
-    pid_t, gid_t = torch.from_numpy(pid).to(dev), torch.from_numpy(gid).to(dev)
-    labels = [labels_pred[i] for i in pid]
-    im32 = torch.from_numpy(im_pred[pid].astype(np.int32)).to(dev)
-    K_rows = K[im32.long()].contiguous()
-    ids, n_points, n_sym = _mesh_tables(meshes, labels, dev)
-    Tp, Tg = T_pred[pid_t].contiguous(), T_gt[gid_t].contiguous()
-    e3 = eng.pose_error_sym(Tp, Tg, meshes.symmetries, n_sym, meshes.points, mesh_ids=ids, n_points=n_points, reduce=eng.POSE_ERROR_MAX,
-                            with_errs=False)
-    e2 = eng.pose_error_mspd(Tp, Tg, meshes.symmetries, n_sym, meshes.points, K_rows, mesh_ids=ids, n_points=n_points, with_errs=False)
-    diam = _diameters(meshes)
-    diam_t = torch.tensor([diam[l] for l in labels], dtype=torch.float32, device=dev)
-    # a non-finite pose is not handed to the rasteriser: a placeholder is rendered and its candidates' errors are set to NaN
-    bad_pred, bad_gt = ~torch.isfinite(T_pred).flatten(1).all(1), ~torch.isfinite(T_gt).flatten(1).all(1)
-    place = _placeholder_pose(dev)
-    R_pred = torch.where(bad_pred[:, None, None], place, T_pred)
-    R_gt = torch.where(bad_gt[:, None, None], place, T_gt)
-    rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
-    u_gt, inv_gt = np.unique(gid, return_inverse=True)
-    u_pred, inv_pred = np.unique(pid, return_inverse=True)
-    K_gt = K[torch.from_numpy(im_gt[u_gt]).to(dev)]
-    K_pred = K[torch.from_numpy(im_pred[u_pred]).to(dev)]
-    u_gt_t, u_pred_t = torch.from_numpy(u_gt).to(dev), torch.from_numpy(u_pred).to(dev)
-    depth_gt = torch.empty(len(u_gt), H, W, dtype=torch.float32, device=dev)
-    for r0 in range(0, len(u_gt), rows_per_launch):
-        r1 = min(len(u_gt), r0 + rows_per_launch)
-        depth_gt[r0:r1] = renderer.render_depth([labels_gt[i] for i in u_gt[r0:r1]], R_gt[u_gt_t[r0:r1]], K_gt[r0:r1], (H, W))
-    # candidates in the order of their estimate, so that a portion of estimates is a run of candidates
-    order = np.argsort(inv_pred, kind="stable")
-    est_sorted = inv_pred[order]
-    gt_ids = torch.from_numpy(inv_gt.astype(np.int32)).to(dev)
-    est_ids = torch.from_numpy(inv_pred.astype(np.int32)).to(dev)
-    order_t = torch.from_numpy(order).to(dev)
-    vsd_errs = torch.empty(n, len(taus), dtype=torch.float32, device=dev)
-    for r0 in range(0, len(u_pred), rows_per_launch):
-        r1 = min(len(u_pred), r0 + rows_per_launch)
-        depth_est = renderer.render_depth([labels_pred[i] for i in u_pred[r0:r1]], R_pred[u_pred_t[r0:r1]], K_pred[r0:r1], (H, W))
-        rows = order_t[int(np.searchsorted(est_sorted, r0)):int(np.searchsorted(est_sorted, r1))]
-        vsd_errs[rows] = eng.vsd(depth_est, depth_gt, depth, K_rows[rows].contiguous(), diam_t[rows].contiguous(), delta=delta, taus=taus,
-                                 est_ids=(est_ids[rows] - r0).contiguous(), gt_ids=gt_ids[rows].contiguous(), im_ids=im32[rows].contiguous(),
-                                 with_counts=False)["errs"]
-    bad = bad_pred[pid_t] | bad_gt[gid_t]
-    vsd_errs = torch.where(bad[:, None], torch.full_like(vsd_errs, float("nan")), vsd_errs)
+    u_gt = np.unique(gid)
+    vsd_errs, e3, e2 = _bop_pair_errors(pred, gt, pid, gid, [labels_gt[i] for i in u_gt], im_gt[u_gt], meshes, renderer, depth, K, delta, taus)
     return torch.cat([vsd_errs, e3["err"][:, None], e2["err"][:, None]], dim=1)
 
 
@@ -588,7 +575,7 @@ def bop_thresholds(diameters, n_tau: int = len(BOP_TAUS), image_width: int = 640
     diameter for MSSD, theta_px * image_width / 640 for MSPD."""
     diameters = np.asarray(diameters, np.float64)
     thetas = np.asarray(BOP_THRESHOLDS, np.float64)
-    thetas_px = np.arange(5, 51, 5).astype(np.float64) * (float(image_width) / 640.0)
+    thetas_px = _thetas_px(image_width)
     thr = np.empty((len(diameters), n_tau + 2, len(thetas)), np.float64)
     thr[:, :n_tau, :] = thetas[None, None, :]
     thr[:, n_tau, :] = thetas[None, :] * diameters[:, None]

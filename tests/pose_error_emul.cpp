@@ -1,6 +1,7 @@
 // TEST SUPPORT: host emulation of the pose-error kernels (megapose6d_amd/csrc/pose_error.hip) built from the same per-element arithmetic
 // (pose_error_core.h).  Same arguments as the C ABI, on host arrays; the reductions over points accumulate in double and round once
-// (the kernels' own order is compared with a tolerance).  Built by tests/support/pose_error.py with -ffp-contract=off.
+// (the kernels' own order is compared with a tolerance); a maximum has no order, so the max forms are held bit for bit.  Built by
+// tests/support/pose_error.py with -ffp-contract=off.
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -14,9 +15,32 @@ static inline int valid_points(const int32_t* n_points, int mesh, int n_pts) {
   return n_points ? (n_points[mesh] < n_pts ? n_points[mesh] : n_pts) : n_pts;
 }
 
-extern "C" void pose_error_emul_sym(const float* T_pred, const float* T_gt, const float* syms, const int32_t* n_sym, int S_max,
-                                    const float* points, int n_pts_stride, const int32_t* mesh_ids, const int32_t* n_points, int n_pts, int b,
-                                    int reduce_max, float* err, float* err_alt, int32_t* idx, float* T_gt_sym, float* errs, float* diffs) {
+// the distance of one point under the prediction and under a candidate ground truth: in space (ADD, MSSD) or between projections (MSPD)
+struct SpaceDist {
+  const float* Tp;
+  float G[16];
+  SpaceDist(const float*, const float* T_pred) : Tp(T_pred) {}
+  void candidate(const float* Gs) { for (int k = 0; k < 16; ++k) G[k] = Gs[k]; }
+  float operator()(float x, float y, float z) const {
+    float qx, qy, qz, gx, gy, gz;
+    pe::apply(Tp, x, y, z, qx, qy, qz);
+    pe::apply(G, x, y, z, gx, gy, gz);
+    return sqrtf(pe::norm2(gx - qx, gy - qy, gz - qz));
+  }
+};
+struct PixelDist {
+  const float* K;
+  float Pp[12], Pg[12];
+  PixelDist(const float* K_row, const float* T_pred) : K(K_row) { pe::proj_matrix(K, T_pred, Pp); }
+  void candidate(const float* Gs) { pe::proj_matrix(K, Gs, Pg); }
+  float operator()(float x, float y, float z) const { return pe::proj_dist(Pp, Pg, x, y, z); }
+};
+
+// one row loop for both: the symmetry set, the mean (accumulated in double) and the maximum over the points, the arg-min
+template <class Dist>
+static void sym_rows(const float* T_pred, const float* T_gt, const float* syms, const int32_t* n_sym, int S_max, const float* points,
+                     int n_pts_stride, const int32_t* mesh_ids, const int32_t* n_points, int n_pts, int b, int reduce_max, const float* K,
+                     float* err, float* err_alt, int32_t* idx, float* T_gt_sym, float* errs, float* diffs) {
   const float inf = std::numeric_limits<float>::infinity();
   for (int row = 0; row < b; ++row) {
     const int mesh = mesh_ids[row];
@@ -26,6 +50,7 @@ extern "C" void pose_error_emul_sym(const float* T_pred, const float* T_gt, cons
     const float* P = points + (size_t)mesh * n_pts_stride * 3;
     bool ok = pe::pose_finite(Tp);
     if (syms) ok = ok && pe::pose_finite(T_gt + (size_t)row * 16);
+    Dist dist(K ? K + (size_t)row * 9 : nullptr, Tp);
     float best = inf, best_alt = inf;
     int bi = -1;
     float Tw[16];
@@ -38,14 +63,12 @@ extern "C" void pose_error_emul_sym(const float* T_pred, const float* T_gt, cons
         } else {
           for (int k = 0; k < 16; ++k) G[k] = T_gt[((size_t)row * S_max + s) * 16 + k];
         }
+        dist.candidate(G);
         const bool ok_s = ok && (syms || pe::pose_finite(G));
         double sum = 0.0;
         float mx = 0.f;
         for (int j = 0; j < nv; ++j) {
-          float qx, qy, qz, gx, gy, gz;
-          pe::apply(Tp, P[3 * j], P[3 * j + 1], P[3 * j + 2], qx, qy, qz);
-          pe::apply(G, P[3 * j], P[3 * j + 1], P[3 * j + 2], gx, gy, gz);
-          const float n = sqrtf(pe::norm2(gx - qx, gy - qy, gz - qz));
+          const float n = dist(P[3 * j], P[3 * j + 1], P[3 * j + 2]);
           sum += (double)n;
           mx = fmaxf(mx, n);
         }
@@ -77,6 +100,21 @@ extern "C" void pose_error_emul_sym(const float* T_pred, const float* T_gt, cons
       }
     }
   }
+}
+
+extern "C" void pose_error_emul_sym(const float* T_pred, const float* T_gt, const float* syms, const int32_t* n_sym, int S_max,
+                                    const float* points, int n_pts_stride, const int32_t* mesh_ids, const int32_t* n_points, int n_pts, int b,
+                                    int reduce_max, float* err, float* err_alt, int32_t* idx, float* T_gt_sym, float* errs, float* diffs) {
+  sym_rows<SpaceDist>(T_pred, T_gt, syms, n_sym, S_max, points, n_pts_stride, mesh_ids, n_points, n_pts, b, reduce_max, nullptr, err, err_alt,
+                      idx, T_gt_sym, errs, diffs);
+}
+
+// the projected form (MSPD; mp_pose_error_mspd): no difference vectors
+extern "C" void mspd_emul(const float* T_pred, const float* T_gt, const float* syms, const int32_t* n_sym, int S_max, const float* points,
+                          int n_pts_stride, const int32_t* mesh_ids, const int32_t* n_points, int n_pts, int b, int reduce_max, const float* K,
+                          float* err, float* err_alt, int32_t* idx, float* T_gt_sym, float* errs) {
+  sym_rows<PixelDist>(T_pred, T_gt, syms, n_sym, S_max, points, n_pts_stride, mesh_ids, n_points, n_pts, b, reduce_max, K, err, err_alt, idx,
+                      T_gt_sym, errs, nullptr);
 }
 
 extern "C" void pose_error_emul_nn(const float* T_pred, const float* T_gt, const float* points, int n_pts_stride, const int32_t* mesh_ids,

@@ -4,43 +4,26 @@ table: no index, no sorted copy, sets of taken ground truths); and the seeded ca
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent.parent
-LIB = ROOT / "tests" / "_build" / "libbop_match_emul.so"
-GOLDEN = ROOT / "tests" / "golden" / "bop_match.npz"
-_CSRC = ROOT / "megapose6d_amd" / "csrc"
-_SRCS = [ROOT / "tests" / "bop_match_emul.cpp", _CSRC / "bop_match_core.h"]
-_lib = None
+from .emul import CSRC, TESTS, _p, build
+
+GOLDEN = TESTS / "golden" / "bop_match.npz"
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
-            LIB.parent.mkdir(exist_ok=True)
-            tmp = LIB.with_suffix(".tmp.so")
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-I", str(_CSRC), "-o", str(tmp),
-                            str(_SRCS[0])], check=True)
-            tmp.replace(LIB)
-        _lib = C.CDLL(str(LIB))
-        _lib.bop_match_emul.restype = C.c_int
-        _lib.bop_match_emul_limits.restype = None
-    return _lib
+    lib = build("bop_match_emul", [TESTS / "bop_match_emul.cpp", CSRC / "bop_match_core.h"], fma=False)
+    lib.bop_match_emul.restype = C.c_int
+    lib.bop_match_emul_limits.restype = None
+    return lib
 
 
 def limits() -> Dict[str, int]:
     v = (C.c_int * 4)()
     load().bop_match_emul_limits(v)
     return dict(zip(("max_errors", "max_thetas", "mask_bits", "stage_floats"), (int(x) for x in v)))
-
-
-def _p(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def emul_index(errs_sorted, index, thr, n_pred, n_top=None) -> np.ndarray:

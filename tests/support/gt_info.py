@@ -5,19 +5,12 @@ and the GPU test share."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict
 
 import numpy as np
 
 from . import vsd as vs
-
-ROOT = Path(__file__).resolve().parent.parent.parent
-LIB = ROOT / "tests" / "_build" / "libgt_info_emul.so"
-_CSRC = ROOT / "megapose6d_amd" / "csrc"
-_SRCS = [ROOT / "tests" / "gt_info_emul.cpp", _CSRC / "gt_info_core.h", _CSRC / "vsd_core.h"]
-_lib = None
+from .emul import CSRC, TESTS, _p, build
 
 ULP = vs.ULP
 BAND_ROUNDINGS = vs.BAND_ROUNDINGS    # band of a borderline pixel = 16 * 2^-24 * D_max: the derivation of tests/test_vsd_contract_cpu.py
@@ -25,21 +18,9 @@ COUNT_NAMES = ("px_count_all", "px_count_image", "px_count_valid", "px_count_vis
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
-            LIB.parent.mkdir(exist_ok=True)
-            tmp = LIB.with_suffix(".tmp.so")
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I", str(_CSRC),
-                            "-o", str(tmp), str(_SRCS[0])], check=True)
-            tmp.replace(LIB)
-        _lib = C.CDLL(str(LIB))
-        _lib.gt_info_emul.restype = None
-    return _lib
-
-
-def _p(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    lib = build("gt_info_emul", [TESTS / "gt_info_emul.cpp", CSRC / "gt_info_core.h", CSRC / "vsd_core.h"])
+    lib.gt_info_emul.restype = None
+    return lib
 
 
 def gt_info(depth_gt, depth_test, K, canvas=3, delta=0.015, gt_ids=None, im_ids=None, with_masks=True) -> Dict[str, np.ndarray]:

@@ -1,47 +1,22 @@
-"""TEST SUPPORT: ctypes wrapper of the host emulation of the pose-error kernels (tests/pose_error_emul.cpp), built on first use, the
+"""TEST SUPPORT: ctypes wrapper of the host emulation of the pose-error kernels (tests/pose_error_emul.cpp; support/emul.py builds it), the
 float64 restatement the emulation is held to, and the derived distance bound."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent.parent
-LIB = ROOT / "tests" / "_build" / "libpose_error_emul.so"
-_SRCS = [ROOT / "tests" / "pose_error_emul.cpp", ROOT / "megapose6d_amd" / "csrc" / "pose_error_core.h"]
-_lib = None
+from .emul import CSRC, TESTS, _f32, _i32, _p, build
 
 ULP = 2.0 ** -24
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
-            LIB.parent.mkdir(exist_ok=True)
-            tmp = LIB.with_suffix(".tmp.so")
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I",
-                            str(ROOT / "megapose6d_amd" / "csrc"), "-o", str(tmp), str(_SRCS[0])], check=True)
-            tmp.replace(LIB)
-        _lib = C.CDLL(str(LIB))
-        for n in ("pose_error_emul_sym", "pose_error_emul_nn", "pose_error_emul_rigid"):
-            getattr(_lib, n).restype = None
-    return _lib
-
-
-def _p(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a):
-    return None if a is None else np.ascontiguousarray(a, np.float32)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32)
+    lib = build("pose_error_emul", [TESTS / "pose_error_emul.cpp", CSRC / "pose_error_core.h"])
+    for n in ("pose_error_emul_sym", "mspd_emul", "pose_error_emul_nn", "pose_error_emul_rigid"):
+        getattr(lib, n).restype = None
+    return lib
 
 
 def _points(points, mesh_ids, b):
@@ -53,8 +28,9 @@ def _points(points, mesh_ids, b):
     return points, _i32(mesh_ids)
 
 
-def sym(T_pred, T_gt, symmetries, n_sym, points, mesh_ids=None, n_points=None, reduce_max=False, with_diffs=True) -> Dict[str, np.ndarray]:
-    """Same addressing as megapose6d_amd.engine.pose_error_sym (symmetries None: T_gt = candidates [b,S,4,4])."""
+def sym(T_pred, T_gt, symmetries, n_sym, points, mesh_ids=None, n_points=None, reduce_max=False, with_diffs=True, K=None) -> Dict[str, np.ndarray]:
+    """Same addressing as megapose6d_amd.engine.pose_error_sym (symmetries None: T_gt = candidates [b,S,4,4]); with K [b,3,3] as
+    engine.pose_error_mspd: the distances are taken between projections, and there are no difference vectors."""
     T_pred, T_gt, symmetries = _f32(T_pred), _f32(T_gt), _f32(symmetries)
     b = T_pred.shape[0]
     points, mesh_ids = _points(points, mesh_ids, b)
@@ -63,6 +39,13 @@ def sym(T_pred, T_gt, symmetries, n_sym, points, mesh_ids=None, n_points=None, r
     n = points.shape[1]
     out = dict(err=np.empty(b, np.float32), err_alt=np.empty(b, np.float32), idx=np.empty(b, np.int32), T_gt_sym=np.empty((b, 4, 4), np.float32),
                errs=np.empty((b, S), np.float32))
+    if K is not None:
+        K = _f32(K)
+        assert K.shape == (b, 3, 3)
+        load().mspd_emul(_p(T_pred), _p(T_gt), _p(symmetries), _p(n_sym), C.c_int(S), _p(points), C.c_int(n), _p(mesh_ids), _p(n_points),
+                                    C.c_int(n), C.c_int(b), C.c_int(int(reduce_max)), _p(K), _p(out["err"]), _p(out["err_alt"]), _p(out["idx"]),
+                                    _p(out["T_gt_sym"]), _p(out["errs"]))
+        return out
     if with_diffs:
         out["diffs"] = np.empty((b, n, 3), np.float32)
     load().pose_error_emul_sym(_p(T_pred), _p(T_gt), _p(symmetries), _p(n_sym), C.c_int(S), _p(points), C.c_int(n), _p(mesh_ids), _p(n_points),

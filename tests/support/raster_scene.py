@@ -2,31 +2,18 @@
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 from typing import Dict, List, Sequence
 
 import numpy as np
 
-ROOT = Path(__file__).resolve().parent.parent.parent
-LIB = ROOT / "tests" / "_build" / "libraster_scene_emul.so"
-_SRCS = [ROOT / "tests" / "raster_scene_emul.cpp", ROOT / "tests" / "raster_emul.cpp", ROOT / "megapose6d_amd" / "csrc" / "raster_core.h",
-         ROOT / "megapose6d_amd" / "csrc" / "raster_scene_core.h"]
-_lib = None
+from .emul import CSRC, TESTS, build
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
-            LIB.parent.mkdir(exist_ok=True)
-            tmp = LIB.with_suffix(".tmp.so")
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I",
-                            str(ROOT / "megapose6d_amd" / "csrc"), "-I", str(ROOT / "tests"), "-o", str(tmp), str(_SRCS[0])], check=True)
-            tmp.replace(LIB)
-        _lib = C.CDLL(str(LIB))
-        _lib.raster_scene_emul_render.restype = None
-    return _lib
+    lib = build("raster_scene_emul", [TESTS / "raster_scene_emul.cpp", TESTS / "raster_emul.cpp", CSRC / "raster_core.h",
+                                      CSRC / "raster_scene_core.h"])
+    lib.raster_scene_emul_render.restype = None
+    return lib
 
 
 def render(meshes: Sequence[Dict[str, np.ndarray]], obj_off: Sequence[int], mesh_ids: Sequence[int], TCO: np.ndarray, K: np.ndarray,

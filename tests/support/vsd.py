@@ -4,19 +4,12 @@ borderline-pixel census and the derived MSPD bound the emulation is held to."""
 from __future__ import annotations
 
 import ctypes as C
-import subprocess
-from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict
 
 import numpy as np
 
 from . import pose_error as _pe
-
-ROOT = Path(__file__).resolve().parent.parent.parent
-LIB = ROOT / "tests" / "_build" / "libvsd_emul.so"
-_CSRC = ROOT / "megapose6d_amd" / "csrc"
-_SRCS = [ROOT / "tests" / "vsd_emul.cpp", _CSRC / "vsd_core.h", _CSRC / "pose_error_core.h"]
-_lib = None
+from .emul import CSRC, TESTS, _f32, _i32, _p, build
 
 ULP = 2.0 ** -24
 BAND_ROUNDINGS = 16          # band of a borderline pixel = 16 * 2^-24 * D_max (derived in tests/test_vsd_contract_cpu.py)
@@ -24,30 +17,9 @@ DEFAULT_TAUS = tuple(np.arange(0.05, 0.51, 0.05))
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not LIB.is_file() or LIB.stat().st_mtime < max(s.stat().st_mtime for s in _SRCS):
-            LIB.parent.mkdir(exist_ok=True)
-            tmp = LIB.with_suffix(".tmp.so")
-            subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I", str(_CSRC),
-                            "-o", str(tmp), str(_SRCS[0])], check=True)
-            tmp.replace(LIB)
-        _lib = C.CDLL(str(LIB))
-        for n in ("vsd_emul", "mspd_emul"):
-            getattr(_lib, n).restype = None
-    return _lib
-
-
-def _p(a: Optional[np.ndarray]):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a):
-    return None if a is None else np.ascontiguousarray(a, np.float32)
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, np.int32)
+    lib = build("vsd_emul", [TESTS / "vsd_emul.cpp", CSRC / "vsd_core.h"])
+    lib.vsd_emul.restype = None
+    return lib
 
 
 def vsd(depth_est, depth_gt, depth_test, K, diameter, delta=0.015, taus=DEFAULT_TAUS, normalized=True, est_ids=None, gt_ids=None,
@@ -69,21 +41,7 @@ def vsd(depth_est, depth_gt, depth_test, K, diameter, delta=0.015, taus=DEFAULT_
 
 def mspd(T_pred, T_gt, symmetries, n_sym, points, K, mesh_ids=None, n_points=None, reduce_max=True) -> Dict[str, np.ndarray]:
     """Same addressing as megapose6d_amd.engine.pose_error_mspd (symmetries None: T_gt = candidates [b,S,4,4])."""
-    T_pred, T_gt, symmetries, K, points = _f32(T_pred), _f32(T_gt), _f32(symmetries), _f32(K), _f32(points)
-    b = T_pred.shape[0]
-    assert points.ndim == 3 and points.shape[2] == 3 and K.shape == (b, 3, 3)
-    if mesh_ids is None:
-        assert points.shape[0] == b
-        mesh_ids = np.arange(b)
-    mesh_ids, n_sym, n_points = _i32(mesh_ids), _i32(n_sym), _i32(n_points)
-    S = symmetries.shape[1] if symmetries is not None else T_gt.shape[1]
-    n = points.shape[1]
-    out = dict(err=np.empty(b, np.float32), err_alt=np.empty(b, np.float32), idx=np.empty(b, np.int32), T_gt_sym=np.empty((b, 4, 4), np.float32),
-               errs=np.empty((b, S), np.float32))
-    load().mspd_emul(_p(T_pred), _p(T_gt), _p(symmetries), _p(n_sym), C.c_int(S), _p(points), C.c_int(n), _p(mesh_ids), _p(n_points), C.c_int(n),
-                     C.c_int(b), C.c_int(int(reduce_max)), _p(K), _p(out["err"]), _p(out["err_alt"]), _p(out["idx"]), _p(out["T_gt_sym"]),
-                     _p(out["errs"]))
-    return out
+    return _pe.sym(T_pred, T_gt, symmetries, n_sym, points, mesh_ids, n_points, reduce_max=reduce_max, with_diffs=False, K=K)
 
 
 # float64 restatement of the definitions on the same fp32 inputs ---------------------------------------------------------------------

@@ -3,25 +3,16 @@ kernels' own order: tile binning, lane coverage incl. the 32-bit path, shading t
 independent oracle (oracle/raster.c) -- bit for bit, on crop-like views, MSAA 1 / 4, near-plane clipping, textures with per-pixel
 LOD, point lights, large triangles, the list-overflow fallback and arbitrary list order."""
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-LIB = ROOT / "tests" / "_build" / "libraster_emul.so"
+from support.emul import CSRC, TESTS, build
 
 
 @pytest.fixture(scope="module")
 def emul():
-    src = ROOT / "tests" / "raster_emul.cpp"
-    core = ROOT / "megapose6d_amd" / "csrc" / "raster_core.h"
-    if not LIB.is_file() or LIB.stat().st_mtime < max(src.stat().st_mtime, core.stat().st_mtime):
-        LIB.parent.mkdir(exist_ok=True)
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fno-fast-math", "-shared", "-fPIC", "-I",
-                        str(core.parent), "-o", str(LIB), str(src)], check=True)
-    lib = C.CDLL(str(LIB))
+    lib = build("raster_emul", [TESTS / "raster_emul.cpp", CSRC / "raster_core.h"])
     lib.raster_emul_render.restype = None
     return lib
 
