@@ -614,6 +614,42 @@ int mp_bop_match(const float* d_errs /*[C,E]*/, const int32_t* d_cand_gt /*[C]*/
                  int n_theta, int32_t* d_match /*[P,E,n_theta]*/, void* d_workspace, size_t workspace_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* BOP's 2D detection and 2D segmentation scores (COCO average precision): the pixel counts */
+/* behind the mask IoU of every (detection, ground truth) candidate, and COCO's greedy       */
+/* matching (pycocotools' COCOeval.evaluateImg with iscrowd = 0 and one area range) at every  */
+/* IoU threshold in one launch (csrc/det_ap.hip; contract in csrc/det_ap_core.h).  The        */
+/* accumulation to AP / AR is host arithmetic (evaluation.coco_accumulate).                   */
+/* ------------------------------------------------------------------------------------ */
+/* Masks are bytes; a pixel is set when its byte is non-zero (a bool tensor's 0 / 1, mp_gt_info's 0 / 255, anything else).
+   d_counts[c] = {pixels set in both d_pred_masks[d_cand_pred[c]] and d_gt_masks[d_cand_gt[c]], pixels set in the former, pixels set in
+   the latter}; a candidate whose index is outside [0, P) or [0, G) reads nothing and gives -1 -1 -1.  H * W in 1 .. 2^31 - 1 (a count fits
+   an int32; mask offsets are size_t), C <= 2^23 per call.  16-byte loads when H * W is a multiple of 16 and both tensors are 16-byte
+   aligned, else byte loads with the same results.  split = 0 picks the number of slices a mask is cut into; > 0 forces it (integer sums:
+   any value gives the same bits).  d_counts is zeroed on `stream` inside the call; there is no scratch.  C == 0 is a successful no-op;
+   any other bad argument (a null pointer, a negative count, H * W out of range, candidates without masks) returns non-zero before
+   anything is launched. */
+int mp_mask_pair_counts(const uint8_t* d_pred_masks /*[P,H,W]*/, const uint8_t* d_gt_masks /*[G,H,W]*/,
+                        const int32_t* d_cand_pred /*[C]*/, const int32_t* d_cand_gt /*[C]*/, int P, int G, int C, int H, int W, int split,
+                        int32_t* d_counts /*[C,3]: intersection, area pred, area gt*/, mp_stream stream);
+/* bytes of device scratch mp_det_match needs (0 for arguments it rejects). */
+size_t mp_det_match_workspace_bytes(int n_taken_words, int n_theta);
+/* THE INDEX is mp_bop_match's, unchanged.  d_match [P,n_theta] = for problem (group, k), walking the group's first n_top estimates (0:
+   all) in the index's order, each estimate looks at its candidates whose ground truth no earlier estimate of the walk took and whose
+   d_iou >= min(d_thr[k], 1 - 1e-10) (float64; never for NaN): first at those with d_gt_ignore[gt_row] == 0, taking the largest IoU, the
+   LAST in gt_row order on an exact tie; only if there is none, the same among those with d_gt_ignore != 0.  A taken ground truth, ignored
+   or not, stays taken.  -1 for no match, for an estimate without candidates and for one cut by n_top.  n_theta in 1..16.  P == 0 is a
+   successful no-op, C == 0 (or no listed estimate, or no group) writes -1 everywhere and launches nothing; any bad argument (a null
+   pointer where one is needed, a negative count, n_theta out of range, a workspace too small) returns non-zero before anything is
+   launched.  The index is not range-checked. */
+int mp_det_match(const double* d_iou /*[C], the index's order*/, const int32_t* d_cand_gt /*[C]*/, const int32_t* d_cand_lgt /*[C]*/,
+                 const int32_t* d_est_row /*[n_est]*/, const int32_t* d_est_off /*[n_est+1]*/,
+                 const int32_t* d_group_est_off /*[n_groups+1]*/, const int32_t* d_group_n_gt /*[n_groups]*/,
+                 const int32_t* d_group_taken_off /*[n_groups+1]*/, const int32_t* d_n_top /*[n_groups] or NULL*/,
+                 const uint8_t* d_gt_ignore /*[G]*/, const double* d_thr /*[n_theta]*/, int P, int C, int n_est, int n_groups,
+                 int n_taken_words, int n_theta, int32_t* d_match /*[P,n_theta]*/, void* d_workspace, size_t workspace_bytes,
+                 mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

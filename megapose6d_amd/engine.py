@@ -976,6 +976,80 @@ def bop_match(errs: torch.Tensor, index: Dict[str, torch.Tensor], thr: torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# BOP's detection / segmentation scores (evaluation): csrc/det_ap.hip
+DET_MATCH_MAX_THETAS = 16            # n_theta
+MASK_PAIR_MAX_PAIRS = 1 << 23        # candidates of one mp_mask_pair_counts call
+
+
+def _dev_bytes(name: str, t: torch.Tensor) -> torch.Tensor:
+    """a uint8 or bool device tensor as uint8, through a view: no copy unless it is not contiguous"""
+    if not t.is_cuda:
+        raise EngineError("engine tensors must live on the GPU")
+    if t.dtype == torch.bool:
+        t = t.contiguous().view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise EngineError(f"{name} must be uint8 or bool, got {t.dtype}")
+    return t.contiguous()
+
+
+def mask_pair_counts(pred_masks: torch.Tensor, gt_masks: torch.Tensor, cand_pred: torch.Tensor, cand_gt: torch.Tensor,
+                     split: int = 0) -> torch.Tensor:
+    """Pixel counts of mask pairs (mp_mask_pair_counts).  pred_masks [P,H,W], gt_masks [G,H,W] uint8 or bool (a pixel is set when its
+    byte is non-zero; taken through a uint8 view, no copy); cand_pred, cand_gt [C] int32 -> counts [C,3] int32: intersection, area of
+    pred_masks[cand_pred[c]], area of gt_masks[cand_gt[c]]; -1 -1 -1 for a candidate whose index is out of range.  More than
+    MASK_PAIR_MAX_PAIRS candidates go in several launches."""
+    pred_masks, gt_masks = _dev_bytes("pred_masks", pred_masks), _dev_bytes("gt_masks", gt_masks)
+    if pred_masks.dim() != 3 or gt_masks.dim() != 3 or pred_masks.shape[1:] != gt_masks.shape[1:]:
+        raise EngineError(f"masks must be [P,H,W] and [G,H,W], got {tuple(pred_masks.shape)}, {tuple(gt_masks.shape)}")
+    cand_pred, cand_gt = _dev_i32(cand_pred), _dev_i32(cand_gt)
+    if cand_pred.dim() != 1 or cand_pred.shape != cand_gt.shape:
+        raise EngineError(f"cand_pred and cand_gt must be [C], got {tuple(cand_pred.shape)}, {tuple(cand_gt.shape)}")
+    c = cand_pred.shape[0]
+    h, w = pred_masks.shape[1:]
+    counts = torch.empty(c, 3, dtype=torch.int32, device=pred_masks.device)
+    lib = _lib.load()
+    for c0 in range(0, max(c, 1), MASK_PAIR_MAX_PAIRS):
+        n = min(c, c0 + MASK_PAIR_MAX_PAIRS) - c0
+        check(lib.mp_mask_pair_counts(pred_masks.data_ptr(), gt_masks.data_ptr(), cand_pred[c0:].data_ptr(), cand_gt[c0:].data_ptr(),
+                                      pred_masks.shape[0], gt_masks.shape[0], n, h, w, int(split), counts[c0:].data_ptr(), _stream()))
+    return counts
+
+
+def det_match(iou: torch.Tensor, index: Dict[str, torch.Tensor], gt_ignore: torch.Tensor, thr: torch.Tensor, n_pred: int,
+              n_top: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """COCO's greedy matching (mp_det_match).  iou [C] float64 in the index's candidate order; index as `bop_match` takes it;
+    gt_ignore [G] uint8 or bool, indexed by gt_row; thr [n_theta] float64; n_top [n_groups] int32 or None -> match [n_pred,n_theta]
+    int32 (gt_row or -1).  Neither the index nor the gt_rows against gt_ignore are range-checked."""
+    if not iou.is_cuda:
+        raise EngineError("engine tensors must live on the GPU")
+    dev = iou.device
+    iou = iou.to(torch.float64).contiguous()
+    thr = thr.to(device=dev, dtype=torch.float64).contiguous()
+    if iou.dim() != 1 or thr.dim() != 1:
+        raise EngineError(f"iou must be [C] and thr [n_theta], got {tuple(iou.shape)}, {tuple(thr.shape)}")
+    c, n_theta = iou.shape[0], thr.shape[0]
+    ix = {k: _dev_i32(index[k]) for k in BOP_MATCH_INDEX}
+    gt_ignore = _dev_bytes("gt_ignore", gt_ignore)
+    n_est, n_groups = ix["est_row"].shape[0], ix["group_n_gt"].shape[0]
+    if ix["cand_gt"].shape != (c,) or ix["cand_lgt"].shape != (c,) or ix["est_off"].shape != (n_est + 1,) \
+            or ix["group_est_off"].shape != (n_groups + 1,) or ix["group_taken_off"].shape != (n_groups + 1,) or gt_ignore.dim() != 1:
+        raise EngineError("the index does not fit iou [C]")
+    if n_top is not None:
+        n_top = _dev_i32(n_top)
+        if n_top.shape != (n_groups,):
+            raise EngineError(f"n_top must be [n_groups], got {tuple(n_top.shape)}")
+    n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
+    match = torch.empty(int(n_pred), n_theta, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = _workspace(lib.mp_det_match_workspace_bytes(n_words, n_theta), dev)
+    check(lib.mp_det_match(iou.data_ptr(), ix["cand_gt"].data_ptr(), ix["cand_lgt"].data_ptr(), ix["est_row"].data_ptr(),
+                           ix["est_off"].data_ptr(), ix["group_est_off"].data_ptr(), ix["group_n_gt"].data_ptr(),
+                           ix["group_taken_off"].data_ptr(), _ptr(n_top), gt_ignore.data_ptr(), thr.data_ptr(), int(n_pred), c, n_est, n_groups,
+                           n_words, n_theta, match.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return match
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

@@ -8,6 +8,9 @@ the reference's tables report: VSD (csrc/vsd.hip, on depth renders of `Panda3dBa
 amodal boxes; `gt_info`, `detections_from_gt_info`), which the reference reads from a BOP dataset's files -- and the step that joins
 detections that carry scores to ground-truth instances, BOP's greedy matching (csrc/bop_match.hip; evaluation/meters/utils.py:51-152
 get_top_n_ids, add_valid_gt, get_candidate_matches, match_poses): `bop_candidates`, `bop_candidate_errors`, `bop_match`, `bop_scores`.
+-- and the scores of BOP's 2D detection and 2D segmentation tasks, COCO average precision of scored boxes and masks against `gt_info`'s
+modal boxes and visible masks (csrc/det_ap.hip: the pixel counts of mask pairs, COCO's greedy matching; the reference has no such meter):
+`mask_iou`, `box_iou`, `coco_match`, `coco_accumulate`, `bop_detection_scores`.
 Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
 
 Where this departs from the reference, on purpose:
@@ -21,6 +24,8 @@ Where this departs from the reference, on purpose:
     "bop19", step cost);
   * `gt_info` blanks each box only when its own mask is empty; `bop_toolkit` (absent, so unpinned) blanks both boxes when nothing is
     visible.  Its silhouette pixels are this engine's fill rule, as for VSD.
+  * the detection scores are unpinned against `pycocotools` and `bop_toolkit` (both absent); a ground truth's `ignore` flag is the
+    caller's (stock `pycocotools` overwrites it with `iscrowd`), and a NaN IoU never matches.
 """
 from __future__ import annotations
 
@@ -650,3 +655,201 @@ def bop_scores(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
     col = match[:, names.index(matches_at[0]), int(matches_at[1])]
     rows = np.flatnonzero(col >= 0)
     return out, pd.DataFrame(dict(pred_id=rows.astype(np.int64), gt_id=col[rows].astype(np.int64)))
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# BOP's 2D detection / 2D segmentation scores: COCO average precision over IoU 0.50:0.05:0.95
+# --------------------------------------------------------------------------------------------------------------------------------
+COCO_IOU_THRS = np.linspace(0.5, 0.95, 10)       # pycocotools' Params.iouThrs
+COCO_REC_THRS = np.linspace(0.0, 1.0, 101)       # pycocotools' Params.recThrs
+
+
+def _cand_rows(cand, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`cand` (the table of `bop_candidates`, or a pair of arrays / tensors pred_id, gt_id) -> two int64 device tensors [C]"""
+    pid, gid = (cand["pred_id"].to_numpy(), cand["gt_id"].to_numpy()) if isinstance(cand, pd.DataFrame) else cand
+    return tuple(torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).to(device=dev, dtype=torch.int64) for a in (pid, gid))
+
+
+def mask_iou(pred_masks: torch.Tensor, gt_masks: torch.Tensor, cand) -> torch.Tensor:
+    """Mask IoU of every candidate -> float64 [C] on the device.  pred_masks [P,H,W], gt_masks [G,H,W] on the device, uint8 or bool (a
+    pixel is set when its byte is non-zero: `Detector` masks are bool, `gt_info` masks 0 / 255; both go through a uint8 view, no copy);
+    cand = the table of `bop_candidates`, or (pred_id, gt_id).  The counts are csrc/det_ap.hip's (`engine.mask_pair_counts`: inter,
+    area_p, area_g, integers); IoU = inter / (area_p + area_g - inter) as one float64 division in torch, 0 where the union is 0.  A
+    candidate that names no mask is refused by the kernel (counts of -1) and gives NaN, which never matches.  Nothing synchronises."""
+    dev = pred_masks.device
+    pid, gid = _cand_rows(cand, dev)
+    counts = eng.mask_pair_counts(pred_masks, gt_masks, pid.to(torch.int32), gid.to(torch.int32)).to(torch.float64)
+    inter, union = counts[:, 0], counts[:, 1] + counts[:, 2] - counts[:, 0]
+    iou = torch.where(union > 0, inter / union, torch.zeros_like(inter))
+    return torch.where(counts[:, 0] < 0, torch.full_like(iou, float("nan")), iou)
+
+
+def box_iou(pred_boxes: torch.Tensor, gt_boxes: torch.Tensor, cand) -> torch.Tensor:
+    """Box IoU of every candidate -> float64 [C] on the device of `pred_boxes`; torch elementwise ops in float64.  Boxes are [x1, y1, x2,
+    y2] with w = x2 - x1 and no +1 (COCO's rule on [x, y, w, h]; it agrees with `bbox_visib`'s w = xmax - xmin of `bbox_modal`).  With p
+    = pred_boxes[pred_id] and g = gt_boxes[gt_id] as float64, in this order:
+      iw = clamp(min(p.x2, g.x2) - max(p.x1, g.x1), min=0);  ih = clamp(min(p.y2, g.y2) - max(p.y1, g.y1), min=0);  inter = iw * ih
+      area_p = (p.x2 - p.x1) * (p.y2 - p.y1);  area_g = (g.x2 - g.x1) * (g.y2 - g.y1);  union = (area_p + area_g) - inter
+      iou = inter / union, 0 where union <= 0."""
+    dev = pred_boxes.device
+    pid, gid = _cand_rows(cand, dev)
+    p, g = pred_boxes.to(torch.float64)[pid], gt_boxes.to(device=dev, dtype=torch.float64)[gid]
+    iw = (torch.minimum(p[:, 2], g[:, 2]) - torch.maximum(p[:, 0], g[:, 0])).clamp(min=0)
+    ih = (torch.minimum(p[:, 3], g[:, 3]) - torch.maximum(p[:, 1], g[:, 1])).clamp(min=0)
+    inter = iw * ih
+    area_p = (p[:, 2] - p[:, 0]) * (p[:, 3] - p[:, 1])
+    area_g = (g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1])
+    union = (area_p + area_g) - inter
+    return torch.where(union > 0, inter / union, torch.zeros_like(inter))
+
+
+def coco_match(cand: pd.DataFrame, iou: torch.Tensor, scores, gt_ignore, iou_thrs=COCO_IOU_THRS, n_top=100) -> torch.Tensor:
+    """COCO's greedy matching of detections to ground truths (COCOeval.evaluateImg with iscrowd = 0 and one area range), every (group,
+    IoU threshold) at once on the device (csrc/det_ap.hip; the contract is csrc/det_ap_core.h).
+      cand       the table of `bop_candidates(valid=None)`: ignored ground truths take part
+      iou        [C] float64 on the device, one per row of `cand` (`mask_iou`, `box_iou`)
+      scores     [P], one finite number per detection: a group's detections are walked by decreasing score, ties by ascending pred_id
+      gt_ignore  [G] booleans (host or device), indexed by gt_id
+      iou_thrs   [T] float64, T in 1..16; the bar of threshold t is min(t, 1 - 1e-10)
+      n_top      COCO's maxDets: the first n_top detections of each group take part (None or 0: all)
+    -> match [P,T] int32 on the device: the gt_id the detection was given (an ignored one only where no other was admissible), or -1.
+    One host-to-device copy of the index; nothing synchronises."""
+    if not iou.is_cuda or iou.dim() != 1 or iou.shape[0] != len(cand) or iou.dtype != torch.float64:
+        raise ValueError("iou must be a float64 device tensor [C] with one entry per candidate")
+    dev = iou.device
+    thr = np.asarray(iou_thrs, np.float64)
+    if thr.ndim != 1 or not 1 <= len(thr) <= eng.DET_MATCH_MAX_THETAS:
+        raise ValueError(f"iou_thrs must be 1 .. {eng.DET_MATCH_MAX_THETAS} thresholds")
+    if n_top is not None and (isinstance(n_top, (bool, np.bool_)) or not isinstance(n_top, (int, np.integer)) or n_top < 0):
+        raise ValueError(f"n_top {n_top!r} is not an int >= 0 or None")
+    ign = torch.as_tensor(gt_ignore)
+    if ign.dtype != torch.bool or ign.dim() != 1 or (len(cand) and int(cand["gt_id"].max()) >= ign.shape[0]):
+        raise ValueError("gt_ignore must be one boolean per ground truth")
+    index = bop_match_index(cand["pred_id"].to_numpy(), cand["gt_id"].to_numpy(), cand["group_id"].to_numpy(), scores)
+    n_groups = len(index["group_n_gt"])
+    index["n_top"] = np.full(n_groups, int(n_top or 0), np.int32)
+    # one host-to-device copy for the whole index: the int32 arrays, padded to an even count, then the order (int64) and the thresholds
+    # (float64) as pairs of int32
+    names = list(eng.BOP_MATCH_INDEX + ("n_top",))
+    n32 = sum(len(index[k]) for k in names)
+    parts = [index[k] for k in names] + [np.zeros(n32 % 2, np.int32), index["order"].astype(np.int64).view(np.int32), thr.view(np.int32)]
+    flat = torch.from_numpy(np.concatenate(parts)).to(dev)
+    on_dev, at = {"n_taken_words": index["n_taken_words"]}, 0
+    for k in names:
+        on_dev[k] = flat[at:at + len(index[k])]
+        at += len(index[k])
+    at += n32 % 2
+    order = flat[at:at + 2 * len(index["order"])].view(torch.int64)
+    thr_dev = flat[at + 2 * len(index["order"]):].view(torch.float64)
+    return eng.det_match(iou[order], on_dev, ign.to(dev), thr_dev, len(np.asarray(scores)), n_top=on_dev["n_top"])
+
+
+def coco_kept(pred_infos: pd.DataFrame, scores, n_top=100, keys=("batch_im_id", "label")) -> np.ndarray:
+    """COCO's maxDets on the host -> one boolean per detection: whether it is among the first n_top of its (image, label) by decreasing
+    score, ties by ascending row (None or 0: all are).  The cut `coco_match` makes inside a group, and the same cut for the detections
+    whose (image, label) has no ground truth and therefore no group."""
+    scores = np.asarray(scores, np.float64)
+    n = len(pred_infos)
+    if scores.shape != (n,):
+        raise ValueError("scores must be one number per detection")
+    if not n_top or n == 0:
+        return np.ones(n, np.bool_)
+    grp = pred_infos.reset_index(drop=True).groupby(list(keys), sort=False).ngroup().to_numpy()
+    order = np.lexsort((np.arange(n), -scores, grp))
+    g = grp[order]
+    run_start = np.flatnonzero(np.concatenate([[True], g[1:] != g[:-1]]))
+    rank = np.arange(n) - np.repeat(run_start, np.diff(np.append(run_start, n)))
+    kept = np.empty(n, np.bool_)
+    kept[order] = rank < int(n_top)
+    return kept
+
+
+def coco_accumulate(match, scores, pred_labels, gt_labels, gt_ignore, n_top_kept, iou_thrs=COCO_IOU_THRS) -> Dict[str, object]:
+    """COCOeval.accumulate and summarize, restated on the host in numpy float64, for one area range and one maxDets.
+      match [P,T] int32 of `coco_match` (a device tensor is copied: the one synchronising copy); scores [P]; pred_labels [P], gt_labels
+      [G]; gt_ignore [G] booleans; n_top_kept [P] booleans (`coco_kept`); iou_thrs [T].
+    Per label and threshold: the kept detections of all images are taken by decreasing score, ties by ascending pred row.  One matched
+    to an ignored ground truth is neither true nor false positive; an unmatched kept one is a false positive (also one whose (image,
+    label) has no ground truth at all, and so no candidate); one cut by n_top is dropped.  npig = the label's ground truths that are not
+    ignored; a label with npig == 0 is left out.  With tp, fp the running sums: recall = tp / npig, precision = tp / (tp + fp +
+    np.spacing(1)); the precision envelope is made monotone from the right and sampled at np.linspace(0, 1, 101) with searchsorted(side=
+    "left"), 0 beyond the last recall.  The samples are stored as COCO stores them, precision [T,101,K] and recall [T,K] (its last value
+    per threshold, 0 without detections) over the K labels that are left, by ascending label.
+    -> AP = np.mean(precision), AP50 / AP75 = np.mean(precision[t]) at the threshold closest to 0.5 / 0.75 (within 1e-9; else -1), AR =
+    np.mean(recall), AP_per_label = {label: np.mean(precision[:, :, k])}, labels = the K labels.  Without any label left every score is
+    -1, as in COCO."""
+    if torch.is_tensor(match):
+        match = match.cpu().numpy()
+    match = np.asarray(match)
+    scores, thr = np.asarray(scores, np.float64), np.asarray(iou_thrs, np.float64)
+    pred_labels, gt_labels = np.asarray(pred_labels), np.asarray(gt_labels)
+    gt_ignore, kept = np.asarray(gt_ignore), np.asarray(n_top_kept)
+    P, T = len(scores), len(thr)
+    if match.shape != (P, T) or pred_labels.shape != (P,) or kept.shape != (P,) or kept.dtype != np.bool_:
+        raise ValueError("match must be [P,T] with one score, one label and one kept flag per detection and one threshold per column")
+    if gt_ignore.dtype != np.bool_ or gt_ignore.shape != gt_labels.shape or (match.size and match.max() >= len(gt_labels)):
+        raise ValueError("gt_ignore must be one boolean per ground truth, and match must name ground truths")
+    labels = [l for l in np.unique(gt_labels) if np.count_nonzero(~gt_ignore[gt_labels == l]) > 0]
+    K, R = len(labels), len(COCO_REC_THRS)
+    precision, recall = np.zeros((T, R, K)), np.zeros((T, K))
+    for k, label in enumerate(labels):
+        npig = np.count_nonzero(~gt_ignore[gt_labels == label])
+        rows = np.flatnonzero((pred_labels == label) & kept)
+        rows = rows[np.lexsort((rows, -scores[rows]))]
+        m = match[rows]
+        matched = m >= 0
+        to_ignored = matched & gt_ignore[np.clip(m, 0, None)]
+        tp_sum = np.cumsum(matched & ~to_ignored, axis=0).astype(np.float64)
+        fp_sum = np.cumsum(~matched, axis=0).astype(np.float64)
+        for t in range(T):
+            tp, fp = tp_sum[:, t], fp_sum[:, t]
+            nd = len(tp)
+            rc = tp / npig
+            pr = tp / (fp + tp + np.spacing(1))
+            recall[t, k] = rc[-1] if nd else 0.0
+            pr = np.maximum.accumulate(pr[::-1])[::-1]
+            at = np.searchsorted(rc, COCO_REC_THRS, side="left")
+            inside = at < nd
+            precision[t, inside, k] = pr[at[inside]]
+    if K == 0:
+        return dict(AP=-1.0, AP50=-1.0, AP75=-1.0, AR=-1.0, AP_per_label={}, labels=[])
+
+    def at_thr(value):
+        t = np.flatnonzero(np.abs(thr - value) < 1e-9)
+        return float(np.mean(precision[t[0]])) if len(t) else -1.0
+
+    return dict(AP=float(np.mean(precision)), AP50=at_thr(0.5), AP75=at_thr(0.75), AR=float(np.mean(recall)),
+                AP_per_label={l: float(np.mean(precision[:, :, k])) for k, l in enumerate(labels)}, labels=labels)
+
+
+def bop_detection_scores(pred, gt, info: pd.DataFrame, iou_type: str = "bbox", gt_masks: Optional[torch.Tensor] = None,
+                         visib_gt_min: float = 0.1, n_top: int = 100, score_key: str = "score", keys=("batch_im_id", "label")):
+    """The scores of BOP's 2D detection ("bbox") and 2D segmentation ("segm") tasks: COCO AP over IoU 0.50:0.05:0.95, AP50, AP75, AR and
+    per-label AP (the dict of `coco_accumulate`).
+      pred      detections as `Detector.get_detections(output_masks=True)` returns them: infos `label`, `batch_im_id`, `score`; `bboxes`
+                [P,4] xyxy ("bbox") or `masks` [P,H,W] bool / uint8 on the device ("segm")
+      gt        the ground truths (`infos` with `label`, `batch_im_id`); info  the table of `gt_info`, row-aligned with `gt.infos`
+      gt_masks  "segm": `gt_info(return_masks=True)`'s mask_visib [G,H,W] on the device; "bbox" scores against `bbox_modal`
+    A ground truth is ignored when visib_fract < visib_gt_min or px_count_visib == 0; ignored ground truths take part in the matching
+    (`bop_candidates(valid=None)`), so a detection of one is neither true nor false positive.  n_top is COCO's maxDets per (image, label).
+    One synchronising copy (the match table).
+    Unpinned against pycocotools and bop_toolkit (both absent here).  Known deviation: stock pycocotools overwrites a ground truth's
+    `ignore` with `iscrowd`; here the caller's flag is honoured."""
+    if iou_type not in ("bbox", "segm"):
+        raise ValueError(f"iou_type {iou_type!r} is not 'bbox' or 'segm'")
+    if len(info) != len(gt.infos):
+        raise ValueError("info must have one row per row of gt")
+    scores = pred.infos[score_key].to_numpy().astype(np.float64)
+    cand = bop_candidates(pred.infos, gt.infos, valid=None, keys=keys)
+    gt_ignore = (info["visib_fract"].to_numpy() < float(visib_gt_min)) | (info["px_count_visib"].to_numpy() == 0)
+    if iou_type == "segm":
+        if gt_masks is None or not gt_masks.is_cuda or gt_masks.shape[0] != len(gt.infos):
+            raise ValueError("iou_type 'segm' needs gt_masks [G,H,W] on the device")
+        iou = mask_iou(pred.masks.to(gt_masks.device), gt_masks, cand)
+    else:
+        boxes = pred.bboxes if pred.bboxes.is_cuda else pred.bboxes.cuda()
+        gt_boxes = torch.as_tensor(np.asarray(list(info["bbox_modal"]), np.float64).reshape(-1, 4))
+        iou = box_iou(boxes, gt_boxes, cand)
+    match = coco_match(cand, iou, scores, gt_ignore, n_top=n_top)
+    kept = coco_kept(pred.infos, scores, n_top=n_top, keys=keys)
+    return coco_accumulate(match, scores, pred.infos["label"].to_numpy(), gt.infos["label"].to_numpy(), gt_ignore, kept)
