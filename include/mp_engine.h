@@ -650,6 +650,28 @@ int mp_det_match(const double* d_iou /*[C], the index's order*/, const int32_t* 
                  mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* BOP's model info: the exact diameter of a point set (the largest distance between two of */
+/* its points: `diameter` of a BOP dataset's models_info.json, bop_toolkit's calc_model_info */
+/* / calc_pts_diameter, an O(N^2) maximum) and its axis-aligned bounds                       */
+/* (csrc/model_info.hip; contract in csrc/model_info_core.h).                                */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_model_info needs (0 for arguments it rejects: n_obj < 1, an object without points, a bad tile, more than
+   2^31 - 1 jobs).  h_n_points [n_obj] is host memory. */
+size_t mp_model_info_scratch_bytes(int n_obj, const int32_t* h_n_points, int tile);
+/* For object o, over rows 0 .. n_points[o] - 1 of d_points[o] (the rows beyond are padding and are never read): d_d2[o] = the largest
+   squared distance between two points, fmaf(dz, dz, fmaf(dy, dy, dx * dx)) on fp32 differences; d_pair[o] = the two rows (i <= j) that
+   reach it, on equal distances the pair with the lowest i, then the lowest j; d_bounds[o] = min x y z, then size x y z (max - min).  The
+   result is the maximum of a total order, so no tile, grid or arrival order changes a bit.  One point gives 0 and (0, 0).  An object with
+   a NaN or infinite coordinate gives NaN, (-1, -1), NaN and leaves the other objects alone.  d_n_points (device) and h_n_points (host)
+   hold the same n_obj counts, each in 1 .. stride.  tile = the j points of one LDS stage: 0 the library's choice, else a multiple of 64
+   in 64 .. 1024 (a forced tile also shortens the chunk of a job, so that a few hundred points reach every path).  Two launches on
+   `stream`, no atomics; the prefix array of job counts (n_obj + 1 entries) is copied from pageable host memory.  Any bad argument
+   returns non-zero before anything is launched. */
+int mp_model_info(const float* d_points /*[n_obj,stride,3]*/, int stride, const int32_t* d_n_points /*[n_obj]*/,
+                  const int32_t* h_n_points /*[n_obj], host*/, int n_obj, int tile, void* d_scratch, float* d_d2 /*[n_obj]*/,
+                  int32_t* d_pair /*[n_obj,2]*/, float* d_bounds /*[n_obj,6]*/, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

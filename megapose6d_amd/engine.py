@@ -1050,6 +1050,41 @@ def det_match(iou: torch.Tensor, index: Dict[str, torch.Tensor], gt_ignore: torc
 
 
 # --------------------------------------------------------------------------- #
+# BOP's model info (evaluation): csrc/model_info.hip
+MODEL_INFO_TILE_STEP = 64            # a forced tile is a multiple of this ...
+MODEL_INFO_MAX_TILE = 1024           # ... and at most this
+
+
+def model_info(points: torch.Tensor, n_points, tile: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The exact diameter and the bounds of point sets (mp_model_info).  points [n_obj,stride,3] float32 on the device; n_points
+    [n_obj] (host ints, an array or a tensor: the launch needs them on both sides), each in 1 .. stride: the rows beyond are padding and
+    are never read; tile = the j points of one LDS stage (0: the library's choice; a multiple of 64 up to 1024 forces it, for tests)
+    -> d2 [n_obj] float32 (the largest squared distance), pair [n_obj,2] int32 (the rows that reach it, i <= j, lowest i then lowest j
+    on equal distances), bounds [n_obj,6] float32 (min x y z, size x y z).  An object with a non-finite coordinate gives NaN, -1 -1,
+    NaN.  Nothing synchronises (a tensor of n_points is read back before the launch)."""
+    points = _dev_f32(points)
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise EngineError(f"points must be [n_obj,stride,3], got {tuple(points.shape)}")
+    n_obj, stride = int(points.shape[0]), int(points.shape[1])
+    h_n = np.ascontiguousarray(n_points.cpu().numpy() if isinstance(n_points, torch.Tensor) else n_points).astype(np.int32)
+    if h_n.shape != (n_obj,) or n_obj < 1 or h_n.min() < 1 or h_n.max() > stride:
+        raise EngineError(f"n_points must be [n_obj] with every count in 1 .. {stride}")
+    dev = points.device
+    d_n = torch.from_numpy(h_n).to(dev)
+    lib = _lib.load()
+    n_bytes = lib.mp_model_info_scratch_bytes(n_obj, h_n.ctypes.data, int(tile))
+    if n_bytes == 0:
+        raise EngineError(f"model_info: tile {tile} is not 0 or a multiple of {MODEL_INFO_TILE_STEP} up to {MODEL_INFO_MAX_TILE}, or too many jobs")
+    ws = _workspace(n_bytes, dev)
+    d2 = torch.empty(n_obj, dtype=torch.float32, device=dev)
+    pair = torch.empty(n_obj, 2, dtype=torch.int32, device=dev)
+    bounds = torch.empty(n_obj, 6, dtype=torch.float32, device=dev)
+    check(lib.mp_model_info(points.data_ptr(), stride, d_n.data_ptr(), h_n.ctypes.data, n_obj, int(tile), ws.data_ptr(), d2.data_ptr(),
+                            pair.data_ptr(), bounds.data_ptr(), _stream()))
+    return d2, pair, bounds
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

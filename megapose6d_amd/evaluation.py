@@ -11,6 +11,9 @@ get_top_n_ids, add_valid_gt, get_candidate_matches, match_poses): `bop_candidate
 -- and the scores of BOP's 2D detection and 2D segmentation tasks, COCO average precision of scored boxes and masks against `gt_info`'s
 modal boxes and visible masks (csrc/det_ap.hip: the pixel counts of mask pairs, COCO's greedy matching; the reference has no such meter):
 `mask_iou`, `box_iou`, `coco_match`, `coco_accumulate`, `bop_detection_scores`.
+-- and BOP's model info (csrc/model_info.hip: the exact diameter, the largest distance between two model points, and the bounds;
+bop_toolkit's calc_model_info): `model_info`, `bop_models_info`, `save_models_info`, `load_models_info`, and the `diameters=` keyword
+that scales every threshold by it instead of the default box diagonal.
 Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
 
 Where this departs from the reference, on purpose:
@@ -26,6 +29,8 @@ Where this departs from the reference, on purpose:
     visible.  Its silhouette pixels are this engine's fill rule, as for VSD.
   * the detection scores are unpinned against `pycocotools` and `bop_toolkit` (both absent); a ground truth's `ignore` flag is the
     caller's (stock `pycocotools` overwrites it with `iscrowd`), and a NaN IoU never matches.
+  * the default diameter is the diagonal of the bounding box (the reference's ModelNet meter), which is never smaller than BOP's;
+    `diameters="exact"` or a models_info.json gives BOP's.  `model_info` is unpinned against `bop_toolkit` (absent).
 """
 from __future__ import annotations
 
@@ -79,12 +84,37 @@ def _diameters(meshes) -> Dict[str, float]:
     return cache
 
 
-def pose_errors(pred, gt, meshes, K: Optional[torch.Tensor] = None, nearest: bool = True) -> pd.DataFrame:
+def resolve_diameters(meshes, diameters, labels) -> Dict[str, float]:
+    """The `diameters=` keyword of `pose_errors`, `bop_errors`, `bop_candidate_errors` and `bop_scores` -> {label: metres} covering
+    `labels`.  None: the diagonal of the axis-aligned bounding box (modelnet_meters.py:72-73, the default); "exact": BOP's diameter,
+    the largest distance between two model points (`model_info(meshes)`, computed once and kept on `meshes`); a mapping label ->
+    metres, e.g. from `load_models_info`: a label of `labels` it lacks raises KeyError, a value that is not positive and finite
+    ValueError."""
+    if diameters is None:
+        return _diameters(meshes)
+    if isinstance(diameters, str):
+        if diameters != "exact":
+            raise ValueError(f"diameters {diameters!r} is not None, 'exact' or a mapping from label to metres")
+        info = getattr(meshes, "_model_info", None)
+        if info is None:
+            info = model_info(meshes)
+            object.__setattr__(meshes, "_model_info", info)
+        diameters = info["diameter"].to_dict()
+    out = {}
+    for label in dict.fromkeys(labels):
+        d = float(diameters[label])            # KeyError for a label the mapping lacks
+        if not (np.isfinite(d) and d > 0.0):
+            raise ValueError(f"the diameter of {label!r} is {d}: it must be positive and finite")
+        out[label] = d
+    return out
+
+
+def pose_errors(pred, gt, meshes, K: Optional[torch.Tensor] = None, nearest: bool = True, diameters=None) -> pd.DataFrame:
     """Errors of `pred.poses` against `gt.poses`, row by row (`pred.infos.label` names the object; `meshes` is a BatchedMeshes on the
     device) -> a DataFrame aligned with `pred.infos`:
       add (mean over ALL model points), add_sym (the minimum of that over the object's symmetry set), mssd (the same with max),
       adds (nearest neighbour; only with nearest=True), sym_id, trans_err / rot_err_deg (against the closest symmetric ground truth),
-      proj_error (with K [B,3,3]), diameter."""
+      proj_error (with K [B,3,3]), diameter (of `diameters`: None the box diagonal, "exact" BOP's, or a mapping; `resolve_diameters`)."""
     dev = meshes.points.device
     T_pred, T_gt = pred.poses.to(dev), gt.poses.to(dev)
     labels = list(pred.infos["label"])
@@ -103,7 +133,7 @@ def pose_errors(pred, gt, meshes, K: Optional[torch.Tensor] = None, nearest: boo
     table = torch.stack([cols[n].double() for n in names] + [sym["idx"].double()], dim=1).cpu().numpy()   # the one synchronising copy
     df = pd.DataFrame({n: table[:, k] for k, n in enumerate(names)}, index=pred.infos.index)
     df.insert(names.index("trans_err"), "sym_id", table[:, -1].astype(np.int64))
-    diam = _diameters(meshes)
+    diam = resolve_diameters(meshes, diameters, labels)
     df["diameter"] = [diam[l] for l in labels]
     return df
 
@@ -216,13 +246,14 @@ def _valid_mask(valid, index, n: int, what: str = "the ground truth") -> np.ndar
 
 
 def _bop_pair_errors(pred, gt, pid: np.ndarray, gid: np.ndarray, gt_labels, gt_im: np.ndarray, meshes, renderer, depth: torch.Tensor,
-                     K: torch.Tensor, delta: float, taus, gt_blank_with: Optional[np.ndarray] = None):
+                     K: torch.Tensor, delta: float, taus, gt_blank_with: Optional[np.ndarray] = None, diameters=None):
     """The three BOP 2019 errors of the pairs (estimate pid[i] of `pred`, ground truth gid[i] of `gt`), int64 arrays [n]; the object and the
     frame of a pair are those of its estimate; depth, K as `_bop_frames` returns them.  Every distinct estimate is rendered once under its
     own label and frame, BOP_DEPTH_BYTES of depth maps at a time; the j-th distinct ground truth (in the order of np.unique(gid)) once
     under the label gt_labels[j] and the K of frame gt_im[j], in launches of the same size.  A non-finite pose is not handed to the
     rasteriser (a placeholder is rendered) and gives NaN on its pairs; with gt_blank_with (one pair per distinct ground truth) the
-    placeholder also stands for a ground truth whose named pair has a non-finite estimate.
+    placeholder also stands for a ground truth whose named pair has a non-finite estimate.  diameters as `resolve_diameters` takes it
+    (the VSD tolerance is tau * diameter).
     -> vsd [n,n_tau] float32, the dicts of pose_error_sym (MSSD) and pose_error_mspd.  Nothing synchronises."""
     dev = meshes.points.device
     n = len(pid)
@@ -240,7 +271,7 @@ def _bop_pair_errors(pred, gt, pid: np.ndarray, gid: np.ndarray, gt_labels, gt_i
     e3 = eng.pose_error_sym(Tp, Tg, meshes.symmetries, n_sym, meshes.points, mesh_ids=ids, n_points=n_points, reduce=eng.POSE_ERROR_MAX,
                             with_errs=False)
     e2 = eng.pose_error_mspd(Tp, Tg, meshes.symmetries, n_sym, meshes.points, K_rows, mesh_ids=ids, n_points=n_points, with_errs=False)
-    diam = _diameters(meshes)
+    diam = resolve_diameters(meshes, diameters, labels)
     diam_t = torch.tensor([diam[l] for l in labels], dtype=torch.float32, device=dev)
     bad_pred, bad_gt = ~torch.isfinite(T_pred).flatten(1).all(1), ~torch.isfinite(T_gt).flatten(1).all(1)
     rows_per_launch = max(1, BOP_DEPTH_BYTES // (H * W * 4))
@@ -279,12 +310,14 @@ def _bop_pair_errors(pred, gt, pid: np.ndarray, gid: np.ndarray, gt_labels, gt_i
 
 
 def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, gt_index=None, delta: float = 0.015,
-               taus: Optional[Sequence[float]] = None) -> pd.DataFrame:
+               taus: Optional[Sequence[float]] = None, diameters=None) -> pd.DataFrame:
     """The three BOP 2019 errors of `pred.poses` -> a DataFrame aligned with `pred.infos`: vsd_0.05 ... vsd_0.50 (one per tau), mssd
     (metres, over the symmetry set, all model points), mspd (pixels), sym_id_mssd, sym_id_mspd, diameter.
       renderer  a Panda3dBatchRenderer of the same objects (its `render_depth`: one sample at each pixel centre)
       depth     [n_im,H,W] observed frames in metres, K [n_im,3,3]; both indexed by `pred.infos.batch_im_id`
       gt_index  row of `gt` each prediction is measured against (default: row-aligned)
+      diameters None (the box diagonal), "exact" (BOP's diameter) or a mapping label -> metres (`resolve_diameters`): the VSD tolerance
+                tau * diameter and the `diameter` column
     Every distinct ground-truth row is rendered once, whatever the number of estimates that share it; estimates are rendered
     BOP_DEPTH_BYTES (256 MiB) of depth maps at a time (ground-truth renders in launches of the same size).  A row with a non-finite
     pose gives NaN in every error column.  One synchronising copy at the end."""
@@ -300,14 +333,14 @@ def bop_errors(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
     # a ground truth is rendered as the first estimate that names it sees it: under that estimate's label and K
     first = np.unique(gt_index, return_index=True)[1]
     vsd_errs, e3, e2 = _bop_pair_errors(pred, gt, np.arange(n, dtype=np.int64), gt_index, [labels[i] for i in first], im[first], meshes,
-                                           renderer, depth, K, delta, taus, gt_blank_with=first)
+                                           renderer, depth, K, delta, taus, gt_blank_with=first, diameters=diameters)
     table = torch.cat([vsd_errs.double(), e3["err"].double()[:, None], e2["err"].double()[:, None], e3["idx"].double()[:, None],
                        e2["idx"].double()[:, None]], dim=1).cpu().numpy()   # the one synchronising copy
     names = _vsd_names(taus)
     df = pd.DataFrame({c: table[:, k] for k, c in enumerate(names + ["mssd", "mspd"])}, index=pred.infos.index)
     df["sym_id_mssd"] = table[:, -2].astype(np.int64)
     df["sym_id_mspd"] = table[:, -1].astype(np.int64)
-    diam = _diameters(meshes)
+    diam = resolve_diameters(meshes, diameters, labels)
     df["diameter"] = [diam[l] for l in labels]
     return df
 
@@ -476,7 +509,7 @@ def bop_candidates(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, valid=None,
 
 
 def bop_candidate_errors(pred, gt, cand: pd.DataFrame, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, delta: float = 0.015,
-                         taus: Optional[Sequence[float]] = None) -> torch.Tensor:
+                         taus: Optional[Sequence[float]] = None, diameters=None) -> torch.Tensor:
     """The three BOP 2019 errors of every candidate of `cand` (`bop_candidates`): estimate `pred_id` of `pred` against ground truth
     `gt_id` of `gt` -> a device tensor [C, n_tau + 2] float32: VSD per tau, MSSD in metres, MSPD in pixels (the columns of
     `bop_errors`).  Arguments as `bop_errors`; the frame and the object of a candidate are those of its estimate.  Every distinct
@@ -496,7 +529,8 @@ def bop_candidate_errors(pred, gt, cand: pd.DataFrame, meshes, renderer, depth: 
     if n == 0:
         return torch.empty(0, len(taus) + 2, dtype=torch.float32, device=dev)
     u_gt = np.unique(gid)
-    vsd_errs, e3, e2 = _bop_pair_errors(pred, gt, pid, gid, [labels_gt[i] for i in u_gt], im_gt[u_gt], meshes, renderer, depth, K, delta, taus)
+    vsd_errs, e3, e2 = _bop_pair_errors(pred, gt, pid, gid, [labels_gt[i] for i in u_gt], im_gt[u_gt], meshes, renderer, depth, K, delta, taus,
+                                        diameters=diameters)
     return torch.cat([vsd_errs, e3["err"][:, None], e2["err"][:, None]], dim=1)
 
 
@@ -620,7 +654,7 @@ def bop_n_top(n_top, group_n_gt: np.ndarray) -> np.ndarray:
 
 def bop_scores(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor, valid=None, n_top="targets", score_key: str = "score",
                image_width: int = 640, keys=("batch_im_id", "label"), delta: float = 0.015, return_matches: bool = False,
-               matches_at: Tuple[str, int] = ("mssd", 0)):
+               matches_at: Tuple[str, int] = ("mssd", 0), diameters=None):
     """BOP 2019 scores of estimates that carry scores (`pred.infos[score_key]`) against the ground truths of their (image, label),
     several or none of either -> {ar_vsd, ar_mssd, ar_mspd, ar, n_targets}: candidates (`bop_candidates`), their errors
     (`bop_candidate_errors`), the greedy matching at every threshold (`bop_match` under `bop_thresholds`), and per error the share of
@@ -629,6 +663,8 @@ def bop_scores(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
       n_top       "targets": a group's estimates are cut to its number of valid ground truths; an int > 0: to that count; None / 0: not cut
       matches_at  with return_matches, the (column, k) whose matched pairs are also returned as a DataFrame `pred_id`, `gt_id`:
                   column one of vsd_0.05 ... vsd_0.50, mssd, mspd; k the index of the threshold
+      diameters   None (the box diagonal), "exact" (BOP's diameter) or a mapping label -> metres (`resolve_diameters`): the VSD
+                  tolerance tau * diameter and the MSSD thresholds theta * diameter
     Other arguments as `bop_errors`.  One synchronising copy at the end."""
     valid = _valid_mask(valid, gt.infos.index, len(gt.infos))
     n_targets = int(valid.sum())
@@ -639,13 +675,13 @@ def bop_scores(pred, gt, meshes, renderer, depth: torch.Tensor, K: torch.Tensor,
         raise ValueError(f"matches_at {matches_at!r} is not (one of {names}, an index below {len(BOP_THRESHOLDS)})")
     scores = pred.infos[score_key].to_numpy().astype(np.float64)
     cand = bop_candidates(pred.infos, gt.infos, valid=valid, keys=keys)
-    errs = bop_candidate_errors(pred, gt, cand, meshes, renderer, depth, K, delta=delta)
+    errs = bop_candidate_errors(pred, gt, cand, meshes, renderer, depth, K, delta=delta, diameters=diameters)
     grp = cand["group_id"].to_numpy()
     n_groups = int(grp.max()) + 1 if len(cand) else 0
     first = np.full(n_groups, -1, np.int64)
     first[grp[::-1]] = np.arange(len(cand))[::-1]                    # a group's first candidate
     labels = pred.infos["label"].to_numpy()[cand["pred_id"].to_numpy()[first]]
-    diam = _diameters(meshes)
+    diam = resolve_diameters(meshes, diameters, labels)
     thr = bop_thresholds([diam[l] for l in labels], len(BOP_TAUS), image_width)
     group_n_gt = cand.groupby("group_id")["gt_id"].nunique().reindex(np.arange(n_groups)).to_numpy() if n_groups else np.zeros(0)
     match = bop_match(cand, errs, scores, thr, n_top=bop_n_top(n_top, group_n_gt)).cpu().numpy()   # the one synchronising copy
@@ -853,3 +889,87 @@ def bop_detection_scores(pred, gt, info: pd.DataFrame, iou_type: str = "bbox", g
     match = coco_match(cand, iou, scores, gt_ignore, n_top=n_top)
     kept = coco_kept(pred.infos, scores, n_top=n_top, keys=keys)
     return coco_accumulate(match, scores, pred.infos["label"].to_numpy(), gt.infos["label"].to_numpy(), gt_ignore, kept)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# BOP's model info: the exact diameter and the bounds of every object (models_info.json)
+# --------------------------------------------------------------------------------------------------------------------------------
+MODEL_INFO_COLUMNS = ("diameter", "min_x", "min_y", "min_z", "size_x", "size_y", "size_z", "pt_i", "pt_j")
+
+
+def model_info_table(labels, pair, bounds, pts_i, pts_j) -> pd.DataFrame:
+    """The host side of `model_info`: pair [n,2] and bounds [n,6] as the kernel gives them, pts_i / pts_j [n,3] the two fp32 points it
+    named -> a DataFrame indexed by label with MODEL_INFO_COLUMNS.  `diameter` is the float64 distance of the two fp32 points, not the
+    square root of the kernel's fp32 d2; an object the kernel refused (pair -1 -1) has NaN."""
+    pair = np.asarray(pair, np.int64).reshape(-1, 2)
+    bounds = np.asarray(bounds, np.float32).reshape(-1, 6).astype(np.float64)
+    a, b = np.asarray(pts_i, np.float32).astype(np.float64), np.asarray(pts_j, np.float32).astype(np.float64)
+    diameter = np.sqrt(((a - b) ** 2).sum(1))
+    diameter[pair[:, 0] < 0] = np.nan
+    cols = {"diameter": diameter}
+    for k, name in enumerate(MODEL_INFO_COLUMNS[1:7]):
+        cols[name] = bounds[:, k]
+    cols["pt_i"], cols["pt_j"] = pair[:, 0], pair[:, 1]
+    return pd.DataFrame(cols, index=pd.Index(list(labels), name="label"))
+
+
+def model_info(meshes, tile: int = 0) -> pd.DataFrame:
+    """What bop_toolkit's calc_model_info writes to models_info.json, for every object of `meshes` (a BatchedMeshes on the device), in
+    metres: `diameter` = the largest distance between two model points (calc_pts_diameter's O(N^2) maximum, one launch of
+    csrc/model_info.hip over all objects), min_* / size_* = the axis-aligned bounds, pt_i <= pt_j = the rows of `meshes.points` that
+    are the farthest apart (on equal fp32 distances the lowest pt_i, then the lowest pt_j).  -> a DataFrame indexed by label.  tile
+    as `engine.model_info` takes it.  One synchronising copy."""
+    labels = list(meshes.labels)
+    pts = meshes.points
+    n_points = np.asarray([meshes.infos[l]["n_points"] for l in labels], np.int32)
+    _, pair, bounds = eng.model_info(pts, n_points, tile=tile)
+    rows = torch.arange(len(labels), device=pts.device)
+    ends = pts[rows[:, None], pair.long().clamp(min=0)]                                       # [n,2,3]
+    table = torch.cat([pair.double(), bounds.double(), ends.flatten(1).double()], dim=1).cpu().numpy()   # the one synchronising copy
+    return model_info_table(labels, table[:, :2], table[:, 2:8], table[:, 8:11], table[:, 11:14])
+
+
+def _bop_obj_key(label):
+    """the key of an object in models_info.json: BOP's integer id where the label carries one ("obj_000005" or "5" -> 5)"""
+    m = re.fullmatch(r"(?:obj_)?(\d+)", str(label))
+    return int(m.group(1)) if m else label
+
+
+def bop_models_info(info: pd.DataFrame, scale: float = 1000.0) -> Dict[object, Dict[str, float]]:
+    """The table of `model_info` -> the dict bop_toolkit saves as models_info.json: {obj_id: {diameter, min_x, min_y, min_z, size_x,
+    size_y, size_z}}, every length times `scale` (BOP's files are in millimetres), keyed by the integer id where the label has one
+    ("obj_000005" -> 5), else by the label.  No symmetry fields: generating them is not built."""
+    out = {}
+    for label, row in info.iterrows():
+        key = _bop_obj_key(label)
+        if key in out:
+            raise ValueError(f"two labels give the object key {key!r}")
+        out[key] = {name: float(row[name]) * float(scale) for name in MODEL_INFO_COLUMNS[:7]}
+    return out
+
+
+def save_models_info(path, info, scale: float = 1000.0) -> None:
+    """Write models_info.json: `info` the table of `model_info` (scaled by `scale` through `bop_models_info`) or a dict that is
+    already BOP's (written as it is)."""
+    import json
+
+    data = bop_models_info(info, scale) if isinstance(info, pd.DataFrame) else info
+    with open(path, "w") as f:
+        json.dump({str(k): v for k, v in data.items()}, f, indent=2, sort_keys=True)
+
+
+def load_models_info(path, scale: float = 0.001, label_format: str = "obj_{:06d}", return_info: bool = False):
+    """Read a BOP models_info.json -> {label: diameter in metres}, what the `diameters=` keyword takes.  An integer key becomes
+    label_format.format(id) (the reference's "obj_000005", bop_object_datasets.py:40), any other key is the label itself; `scale`
+    turns the file's unit into metres.  With return_info also the file's dict, keyed by label, every field as it is in the file
+    (symmetries_discrete, symmetries_continuous: kept, not interpreted)."""
+    import json
+
+    with open(path) as f:
+        data = json.load(f)
+    diameters, infos = {}, {}
+    for key, fields in data.items():
+        label = label_format.format(int(key)) if re.fullmatch(r"\d+", str(key)) else str(key)
+        diameters[label] = float(fields["diameter"]) * float(scale)
+        infos[label] = fields
+    return (diameters, infos) if return_info else diameters
