@@ -36,16 +36,16 @@ typedef void* mp_stream; /* hipStream_t */
 int mp_version(void);
 const char* mp_last_error(void);
 /* Per-launch HIP-event profiler: between begin/end every instrumented kernel launch is bracketed by hipEvents recorded on
- * its launch stream.  mp_profile_query aggregates by kernel name: number of launches, summed duration (ms), and the summed
- * ALGORITHMIC flops / bytes of those launches (DESIGN.md states each kernel's per-unit figures).  Returns 1 past the end. */
+ * its launch stream.  mp_profile_query_ex aggregates by kernel name (idx enumerates the distinct names): number of launches, summed
+ * duration (ms), and the summed ALGORITHMIC flops / bytes of those launches (DESIGN.md states each kernel's per-unit figures).  Returns 1
+ * past the end. */
 int mp_profile_begin(void);
 int mp_profile_end(void);
 int mp_profile_active(void); /* 1 between begin and end */
-int mp_profile_query(int idx, char* name, int name_len, int64_t* launches, double* total_ms, double* total_flops,
-                     double* total_bytes);
-/* the same + the FLOPs the launches EXECUTED on the matrix pipe (= the algorithmic figure for the direct kernels; 16/36 of it for the
+/* Besides those, the FLOPs the launches EXECUTED on the matrix pipe (= the algorithmic figure for the direct kernels; 16/36 of it for the
  * fp32 Winograd kernel; 9 bf16 piece products per Winograd multiplication / 3 or 9 per stem multiplication for the exact-piece kernels)
- * and the dense peak (TFLOP/s) of the pipe they run on (157.3 fp32 MFMA, 2500 bf16 MFMA): executed / time / peak = MFMA utilisation */
+ * and the dense peak (TFLOP/s) of the pipe they run on (157.3 fp32 MFMA, 2500 bf16 MFMA): executed / time / peak = MFMA utilisation.
+ * Every output pointer may be NULL. */
 int mp_profile_query_ex(int idx, char* name, int name_len, int64_t* launches, double* total_ms, double* total_flops,
                         double* total_bytes, double* total_executed_flops, double* peak_tflops);
 
@@ -314,12 +314,11 @@ int mp_conv3x3_wino_bf16_nhwc(const mp_conv_desc* desc, const void* d_u_pieces, 
 int mp_xrec_elements(int n_f32, int n_u8);
 int mp_conv_stem_supported(int KS, int n_f32, int n_u8);
 size_t mp_conv_stem_packed_bytes(int KS, int n_f32, int n_u8, int Cout);
-int mp_conv_stem_pack_weights(const float* h_w_oihw, int Cout, int Cin, int KS, int n_f32, const float* h_scale /*[Cout] or NULL*/,
-                              void* h_packed);
-/* the same for a record whose fp32-kind channels are not the leading ones: input channel c (< 32) is fp32-kind iff bit c of f32_mask is
- * set (an RGBD refiner: crop rgb + crop depth + one rendered depth per view = 0x8102040F for 32 channels, 4 views) */
-int mp_conv_stem_pack_weights_mask(const float* h_w_oihw, int Cout, int Cin, int KS, uint32_t f32_mask, const float* h_scale,
-                                   void* h_packed);
+/* the piece blob of a record: input channel c (< 32) is fp32-kind iff bit c of f32_mask is set -- (1u << n_f32) - 1u when the fp32-kind
+ * channels are the n_f32 leading ones; an RGBD refiner: crop rgb + crop depth + one rendered depth per view = 0x8102040F for 32
+ * channels, 4 views */
+int mp_conv_stem_pack_weights_mask(const float* h_w_oihw, int Cout, int Cin, int KS, uint32_t f32_mask,
+                                   const float* h_scale /*[Cout] or NULL*/, void* h_packed);
 int mp_conv_stem_xrec(const mp_conv_desc* desc, const void* d_packed, int n_f32, mp_stream stream);
 /* the same with the 3x3 / stride-2 / pad-1 max pool that follows the stem (models/torchvision_resnet.py:216) fused into the epilogue:
  * d_ypool = padded NHWC [N, (Ho-1)/2+1, (Wo-1)/2+1, Cout] with border pool_border; desc->relu must be set; desc->d_y may be NULL (the stem
@@ -373,12 +372,10 @@ typedef struct {
   int64_t numel;
 } mp_named_tensor;
 
-/* state_dict layout = the reference checkpoints' (SURVEY.md App. F): backbone.*, pose_fc.*, */
-/* views_logits_head.*.  head: 0 = pose_fc (9 outputs), 1 = views_logits_head (n_views).     */
-int mp_backbone_create(int kind, int c_in, int head_kind, int n_head_out, const mp_named_tensor* h_state,
-                       int n_tensors, mp_backbone** out);
-/* the same with the WideResNet width multiplier of `resnet34_width=N` (training/pose_models_cfg.py:114-116, models/wide_resnet.py:62:
- * stage widths 64N .. 512N, features 512N); width = 1 for the released models */
+/* state_dict layout = the reference checkpoints' (SURVEY.md, appendix F): backbone.*, pose_fc.*, views_logits_head.*.  head: 0 = pose_fc
+ * (9 outputs), 1 = views_logits_head (n_views).  width = the WideResNet width multiplier of `resnet34_width=N`
+ * (training/pose_models_cfg.py:114-116, models/wide_resnet.py:62: stage widths 64N .. 512N, features 512N); width = 1 for the released
+ * models */
 int mp_backbone_create_wide(int kind, int width, int c_in, int head_kind, int n_head_out, const mp_named_tensor* state, int n_tensors,
                             mp_backbone** out);
 int mp_backbone_destroy(mp_backbone* bb);
@@ -398,21 +395,15 @@ int mp_backbone_forward(mp_backbone* bb, const float* d_x, int batch, int h, int
 int mp_backbone_forward_f16(mp_backbone* bb, const void* d_x_half, int batch, int h, int w, float* d_out,
                             float* d_sigmoid, float* d_feat, void* d_workspace, size_t workspace_bytes,
                             mp_stream stream);
-/* the same forward on the bf16 stem RECORDS the rasteriser writes with MP_RASTER_XREC (n_f32 fp32-kind channels first, all other   */
-/* input channels 8-bit integers): only the stem convolution differs (mp_conv_stem_xrec: exact bf16 pieces, 16x the fp32 MFMA rate). */
-/* mp_backbone_xrec_elements: record length in bf16 elements for this backbone (packs the piece blob on first use), 0 = the stem has   */
-/* no such form (records outside 16..48 elements): use mp_backbone_forward.  The tensor has the geometry    */
-/* of the fp32 input (border mp_backbone_input_border()) with records of that many bf16 elements per pixel.                            */
-/* PRECONDITION of every mp_backbone_forward_xrec*: mp_backbone_xrec_elements / mp_backbone_xrec_prepare was called for that mask before   */
-/* (once, outside stream capture): the forwards only look the blob up and fail with MP_ERR_INVALID if it is missing -- they never allocate. */
-int mp_backbone_xrec_elements(mp_backbone* bb, int n_f32);
-int mp_backbone_forward_xrec(mp_backbone* bb, const void* d_xrec, int n_f32, int batch, int h, int w, float* d_out,
-                             float* d_sigmoid, float* d_feat, void* d_workspace, size_t workspace_bytes,
-                             mp_stream stream);
-/* ... with the fp32-kind channels given as a mask (bit c = input channel c; depth channels of an RGBD model).  mp_backbone_xrec_prepare
- * packs and uploads the stem's piece blob for that mask (host work + a synchronous copy: call it once, outside stream capture, from one
- * thread) and returns the record length (0 = no exact-piece form); mp_backbone_forward_xrec_mask only uses a prepared blob and fails if
- * there is none -- it never allocates. */
+/* the same forward on the bf16 stem RECORDS the rasteriser writes with MP_RASTER_XREC (the fp32-kind channels first, all other
+ * input channels 8-bit integers): only the stem convolution differs (mp_conv_stem_xrec: exact bf16 pieces, 16x the fp32 MFMA rate).
+ * The fp32-kind channels are given as a mask (bit c = input channel c: (1u << n_f32) - 1u for n_f32 leading ones; also the depth
+ * channels of an RGBD model).  mp_backbone_xrec_prepare packs and uploads the stem's piece blob for that mask (host work + a
+ * synchronous copy) and returns the record length in bf16 elements for this backbone, 0 = the stem has no such form (records outside
+ * 16..48 elements): use mp_backbone_forward.  The tensor has the geometry of the fp32 input (border mp_backbone_input_border()) with
+ * records of that many bf16 elements per pixel.
+ * PRECONDITION of every mp_backbone_forward_xrec_*: mp_backbone_xrec_prepare was called for that mask before (once, outside stream
+ * capture, from one thread): the forwards only look the blob up and fail with MP_ERR_INVALID if it is missing -- they never allocate. */
 int mp_backbone_xrec_prepare(mp_backbone* bb, uint32_t f32_mask);
 int mp_backbone_forward_xrec_mask(mp_backbone* bb, const void* d_xrec, uint32_t f32_mask, int batch, int h, int w, float* d_out,
                                   float* d_sigmoid, float* d_feat, void* d_workspace, size_t workspace_bytes,
@@ -451,21 +442,17 @@ int mp_init_poses_from_boxes(const float* d_boxes /*[b,4]*/, const float* d_K /*
 /* (lib3d/multiview.py:197-234), | MP_MV_REMOVE_TCO (remove_TCO_rendering: the TCO view is not in the list and KV_crop[:,0] is  */
 /* NOT replaced by K_crop, models/pose_rigid.py:551-552), | MP_MV_INPLANE (views_inplane_rotations: every view 4x, rotated by   */
 /* 0/90/180/270 degrees about the optical axis, multiview.py:236-245).  V must equal mp_pose_multiview_n_views(multiview).       */
-/* mp_pose_prepare_ex additionally returns K_crop of crop_inputs ([b,3,3], what update_pose consumes) in d_K_main (may be NULL). */
+/* d_K_main (may be NULL) additionally receives K_crop of crop_inputs ([b,3,3], what update_pose consumes).                    */
 #define MP_MV_REMOVE_TCO 256
 #define MP_MV_INPLANE 512
 int mp_pose_multiview_n_views(int multiview);
-int mp_pose_prepare_ex(const float* d_TCO_in, const float* d_K, const int32_t* d_mesh_ids, const float* d_points, int n_pts_stride,
-                       int n_pts_main, int n_pts_views, int b, int V, int multiview, int im_h, int im_w, int out_h, int out_w, float lamb,
-                       float* d_TCO_n, float* d_tCR, float* d_TCV_O, float* d_KV_crop, float* d_boxes_rend, float* d_boxes_crop,
-                       float* d_K_main /*[b,3,3] or NULL*/, mp_stream stream);
-int mp_pose_prepare(const float* d_TCO_in /*[b,4,4]*/, const float* d_K /*[b,3,3]*/,
-                    const int32_t* d_mesh_ids, const float* d_points /*[n_mesh,n_pts,3] sampled*/,
-                    int n_pts_stride, int n_pts_main, int n_pts_views, int b, int V, int multiview,
-                    int im_h, int im_w, int out_h, int out_w, float lamb,
-                    float* d_TCO_n /*[b,4,4]*/, float* d_tCR /*[b,3]*/, float* d_TCV_O /*[b,V,4,4]*/,
-                    float* d_KV_crop /*[b,V,3,3]*/, float* d_boxes_rend /*[b,4]*/,
-                    float* d_boxes_crop /*[b,4]*/, mp_stream stream);
+int mp_pose_prepare_ex(const float* d_TCO_in /*[b,4,4]*/, const float* d_K /*[b,3,3]*/,
+                       const int32_t* d_mesh_ids, const float* d_points /*[n_mesh,n_pts,3] sampled*/,
+                       int n_pts_stride, int n_pts_main, int n_pts_views, int b, int V, int multiview,
+                       int im_h, int im_w, int out_h, int out_w, float lamb,
+                       float* d_TCO_n /*[b,4,4]*/, float* d_tCR /*[b,3]*/, float* d_TCV_O /*[b,V,4,4]*/,
+                       float* d_KV_crop /*[b,V,3,3]*/, float* d_boxes_rend /*[b,4]*/,
+                       float* d_boxes_crop /*[b,4]*/, float* d_K_main /*[b,3,3] or NULL*/, mp_stream stream);
 
 /* models/pose_rigid.py:305-312 update_pose + lib3d/cosypose_ops.py:33-58                    */
 int mp_pose_update(const float* d_TCO /*[b,4,4]*/, const float* d_K_crop /*[b,3,3] (stride 9*kstride)*/,
@@ -475,7 +462,7 @@ int mp_pose_update(const float* d_TCO /*[b,4,4]*/, const float* d_K_crop /*[b,3,
 /* ------------------------------------------------------------------------------------ */
 /* Pose errors (evaluation): the arithmetic between two pose tables and a mesh, fused so    */
 /* that no point pair is stored (csrc/pose_error.hip; contract in csrc/pose_error_core.h).  */
-/* Points are addressed as in mp_pose_prepare: row i reads mesh d_mesh_ids[i] of d_points   */
+/* Points are addressed as in mp_pose_prepare_ex: row i reads mesh d_mesh_ids[i] of d_points */
 /* [n_mesh, n_pts_stride, 3] and averages its first min(d_n_points[mesh], n_pts) points     */
 /* (d_n_points NULL: all n_pts), so BatchedMeshes.points with mesh ids and a per-row        */
 /* [b,N,3] tensor (ids 0..b-1) both fit.  Outputs sized by n_pts have a zero / -1 tail.     */

@@ -89,7 +89,6 @@ SIGNATURES = {
     "mp_profile_begin": (_i, []),
     "mp_profile_end": (_i, []),
     "mp_profile_active": (_i, []),
-    "mp_profile_query": (_i, [_i, C.c_char_p, _i, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mp_profile_query_ex": (_i, [_i, C.c_char_p, _i, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mp_device_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.c_char_p, _i]),
@@ -136,7 +135,6 @@ SIGNATURES = {
     "mp_xrec_elements": (_i, [_i, _i]),
     "mp_conv_stem_supported": (_i, [_i, _i, _i]),
     "mp_conv_stem_packed_bytes": (_sz, [_i, _i, _i, _i]),
-    "mp_conv_stem_pack_weights": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mp_conv_stem_pack_weights_mask": (_i, [_vp, _i, _i, _i, _u32, _vp, _vp]),
     "mp_conv_stem_sparse_chunks": (_i, [_i, _i, _i]),
     "mp_conv_stem_sparse_packed_bytes": (_sz, [_i, _i, _i, _i]),
@@ -148,7 +146,6 @@ SIGNATURES = {
     "mp_maxpool3x3s2": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "mp_bn_relu_nhwc": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mp_pool_fc_heads": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "mp_backbone_create": (_i, [_i, _i, _i, _i, C.POINTER(NamedTensor), _i, C.POINTER(_vp)]),
     "mp_backbone_create_wide": (_i, [_i, _i, _i, _i, _i, C.POINTER(NamedTensor), _i, C.POINTER(_vp)]),
     "mp_backbone_destroy": (_i, [_vp]),
     "mp_backbone_input_channels_padded": (_i, [_vp]),
@@ -157,8 +154,6 @@ SIGNATURES = {
     "mp_backbone_workspace_reset": (_i, [_vp, _vp]),
     "mp_backbone_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_backbone_forward_f16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mp_backbone_xrec_elements": (_i, [_vp, _i]),
-    "mp_backbone_forward_xrec": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_backbone_xrec_prepare": (_i, [_vp, _u32]),
     "mp_backbone_forward_xrec_mask": (_i, [_vp, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_backbone_forward_xrec_sparse": (_i, [_vp, _vp, _u32, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -166,8 +161,6 @@ SIGNATURES = {
     "mp_normalize_T": (_i, [_vp, _i, _vp, _vp]),
     "mp_init_extents": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "mp_init_poses_from_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),
-    "mp_pose_prepare": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp,
-                             _vp]),
     "mp_pose_multiview_n_views": (_i, [_i]),
     "mp_pose_prepare_ex": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_pose_error_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -229,11 +229,6 @@ Geometry geometry(const mp_backbone* bb, int h, int w) {
 
 }  // namespace
 
-extern "C" int mp_backbone_create(int kind, int c_in, int head_kind, int n_head_out, const mp_named_tensor* st, int n_tensors,
-                                  mp_backbone** out) {
-  return mp_backbone_create_wide(kind, 1, c_in, head_kind, n_head_out, st, n_tensors, out);
-}
-
 extern "C" int mp_backbone_create_wide(int kind, int width, int c_in, int head_kind, int n_head_out, const mp_named_tensor* st, int n_tensors,
                                        mp_backbone** out) {
   MP_REQUIRE(out && st && n_tensors > 0, "mp_backbone_create: bad arguments");
@@ -376,13 +371,6 @@ extern "C" int mp_backbone_xrec_prepare(mp_backbone* bb, uint32_t f32_mask) {
   return mp_xrec_elements(n_f32, n_u8);
 }
 
-static uint32_t leading_mask(int n_f32) { return n_f32 >= 32 ? 0xFFFFFFFFu : n_f32 <= 0 ? 0u : (1u << n_f32) - 1u; }
-
-extern "C" int mp_backbone_xrec_elements(mp_backbone* bb, int n_f32) {
-  if (!bb || n_f32 < 0 || n_f32 > bb->c_in) return 0;
-  return mp_backbone_xrec_prepare(bb, leading_mask(n_f32));
-}
-
 // x_mode: 0 = fp32 padded NHWC, 1 = binary16 elements (MP_RASTER_F16), 2 = bf16 stem records whose fp32-kind channels are f32_mask (MP_RASTER_XREC)
 static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, uint32_t f32_mask, int batch, int h, int w, float* d_out, float* d_sigmoid,
                                  float* d_feat, void* d_ws, size_t ws_bytes, mp_stream stream, const unsigned char* d_tile_flags = nullptr) {
@@ -428,7 +416,7 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
       if (sp_it != bb->stem_blobs_sparse.end()) d_sparse_blob = sp_it->second;
     }
     MP_REQUIRE(d_stem_pieces != nullptr, "mp_backbone_forward_xrec: no piece blob for the fp32-kind channel mask 0x%x of this %d-channel stem: "
-               "call mp_backbone_xrec_prepare / mp_backbone_xrec_elements first (it returns 0 if the stem has no exact-piece form)", f32_mask, bb->c_in);
+               "call mp_backbone_xrec_prepare first (it returns 0 if the stem has no exact-piece form)", f32_mask, bb->c_in);
     const int n_f32 = __builtin_popcount(f32_mask);
     mp_conv_desc d;
     memset(&d, 0, sizeof(d));
@@ -501,12 +489,6 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
 extern "C" int mp_backbone_forward(mp_backbone* bb, const float* d_x, int batch, int h, int w, float* d_out, float* d_sigmoid,
                                    float* d_feat, void* d_ws, size_t ws_bytes, mp_stream stream) {
   return backbone_forward_impl(bb, d_x, 0, 0, batch, h, w, d_out, d_sigmoid, d_feat, d_ws, ws_bytes, stream);
-}
-
-extern "C" int mp_backbone_forward_xrec(mp_backbone* bb, const void* d_xrec, int n_f32, int batch, int h, int w, float* d_out, float* d_sigmoid,
-                                        float* d_feat, void* d_ws, size_t ws_bytes, mp_stream stream) {
-  MP_REQUIRE(bb && n_f32 >= 0 && n_f32 <= 32, "mp_backbone_forward_xrec: bad arguments");
-  return backbone_forward_impl(bb, (const float*)d_xrec, 2, leading_mask(n_f32), batch, h, w, d_out, d_sigmoid, d_feat, d_ws, ws_bytes, stream);
 }
 
 extern "C" int mp_backbone_forward_xrec_mask(mp_backbone* bb, const void* d_xrec, uint32_t f32_mask, int batch, int h, int w, float* d_out,

@@ -387,12 +387,7 @@ extern "C" size_t mp_conv_stem_packed_bytes(int KS, int n_f32, int n_u8, int Cou
 // packed[cb][wave][step][piece][lane][e]: lane = (cout = cb*64 + wave*16 + (lane & 15), slice group lane >> 4), slice s = 4 step + group
 // = (kh, kw, chunk q of the pixel record), element e of the chunk = record slot 8q + e -> input channel; piece = w1 | w2 | w3 of
 // w * scale (* 1/255 for the integer channels, one rounding of the exact product)
-extern "C" int mp_conv_stem_pack_weights(const float* w, int Cout, int Cin, int KS, int n_f32, const float* scale, void* packed) {
-  MP_REQUIRE(n_f32 >= 0 && n_f32 <= 32 && n_f32 <= Cin, "mp_conv_stem_pack_weights: bad n_f32");
-  return mp_conv_stem_pack_weights_mask(w, Cout, Cin, KS, n_f32 >= 32 ? 0xFFFFFFFFu : (1u << n_f32) - 1u, scale, packed);
-}
-
-// the general record: input channel c is fp32-kind (three pieces) iff bit c of f32_mask is set -- e.g. an RGBD refiner's depth channels
+// The record: input channel c is fp32-kind (three pieces) iff bit c of f32_mask is set -- e.g. an RGBD refiner's depth channels
 // (observation depth + one rendered depth per view) -- and sits, in channel order, in front of the integer channels:
 //   [x1,x2,x3 of every fp32-kind channel | k of every integer channel | zero padding]
 // q_walk = record chunks per pixel the kernel's slice walk visits: Q for the dense walk; the chunks that hold fp32-kind pieces for the

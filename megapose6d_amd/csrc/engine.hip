@@ -62,11 +62,6 @@ extern "C" int mp_profile_end(void) {
 }
 extern "C" int mp_profile_active(void) { return mp::g_prof_on ? 1 : 0; }
 // Aggregated by kernel name.  idx enumerates distinct names; returns 1 when idx is past the end.
-extern "C" int mp_profile_query(int idx, char* name, int name_len, int64_t* launches, double* total_ms, double* total_flops,
-                                double* total_bytes) {
-  return mp_profile_query_ex(idx, name, name_len, launches, total_ms, total_flops, total_bytes, nullptr, nullptr);
-}
-
 extern "C" int mp_profile_query_ex(int idx, char* name, int name_len, int64_t* launches, double* total_ms, double* total_flops,
                                    double* total_bytes, double* total_executed_flops, double* peak_tflops) {
   std::map<std::string, int> order;

@@ -366,14 +366,6 @@ extern "C" int mp_pose_prepare_ex(const float* d_TCO_in, const float* d_K, const
   return MP_OK;
 }
 
-extern "C" int mp_pose_prepare(const float* d_TCO_in, const float* d_K, const int32_t* d_mesh_ids, const float* d_points,
-                               int n_pts_stride, int n_pts_main, int n_pts_views, int b, int V, int multiview, int im_h,
-                               int im_w, int out_h, int out_w, float lamb, float* d_TCO_n, float* d_tCR, float* d_TCV_O,
-                               float* d_KV_crop, float* d_boxes_rend, float* d_boxes_crop, mp_stream stream) {
-  return mp_pose_prepare_ex(d_TCO_in, d_K, d_mesh_ids, d_points, n_pts_stride, n_pts_main, n_pts_views, b, V, multiview, im_h, im_w, out_h,
-                            out_w, lamb, d_TCO_n, d_tCR, d_TCV_O, d_KV_crop, d_boxes_rend, d_boxes_crop, nullptr, stream);
-}
-
 extern "C" int mp_pose_update(const float* d_TCO, const float* d_K_crop, int k_stride_floats, const float* d_out9,
                               const float* d_tCR, int b, float* d_TCO_out, mp_stream stream) {
   MP_REQUIRE(d_TCO && d_K_crop && d_out9 && d_tCR && d_TCO_out && k_stride_floats >= 9, "mp_pose_update: bad arguments");

@@ -962,6 +962,13 @@ extern "C" int mp_raster_prof_read(unsigned long long* out16, int reset) {
 }
 #endif
 
+static CropArgs crop_args(const float* d_images, int images_nhwc4, int C, int H, int W, const int32_t* d_im_ids, const float* d_boxes, int c0) {
+  CropArgs crop;
+  crop.images = d_images; crop.im_ids = d_im_ids; crop.boxes = d_boxes;
+  crop.C = C; crop.H = H; crop.W = W; crop.c0 = c0; crop.nhwc4 = images_nhwc4 ? 1 : 0;
+  return crop;
+}
+
 extern "C" int mp_raster_render(const mp_mesh_db* db, const int32_t* d_mesh_ids, const float* d_TCO, const float* d_K,
                                 int n_views, int h, int w, uint32_t flags, const mp_lights* lights, float* d_out,
                                 int64_t stride_v, int views_per_item, int64_t stride_view, int64_t stride_y, int64_t stride_x,
@@ -980,9 +987,7 @@ extern "C" int mp_raster_render_crop(const mp_mesh_db* db, const int32_t* d_mesh
                                      const int32_t* d_im_ids, const float* d_boxes, int c0_crop, mp_stream stream) {
   MP_REQUIRE(d_images && d_im_ids && d_boxes && n_im > 0 && (C == 3 || C == 4) && H > 0 && W > 0 && c0_crop >= 0,
              "mp_raster_render_crop: bad crop arguments");
-  CropArgs crop;
-  crop.images = d_images; crop.im_ids = d_im_ids; crop.boxes = d_boxes;
-  crop.C = C; crop.H = H; crop.W = W; crop.c0 = c0_crop; crop.nhwc4 = images_nhwc4 ? 1 : 0;
+  const CropArgs crop = crop_args(d_images, images_nhwc4, C, H, W, d_im_ids, d_boxes, c0_crop);
   return raster_render_impl(db, d_mesh_ids, d_TCO, d_K, n_views, h, w, flags, lights, d_out, stride_v, views_per_item, stride_view, stride_y,
                             stride_x, c_rgb, c_normals, c_depth, d_ws, ws_bytes, stream, crop);
 }
@@ -995,9 +1000,7 @@ extern "C" int mp_raster_render_xrec(const mp_mesh_db* db, const int32_t* d_mesh
                                      mp_stream stream) {
   MP_REQUIRE(d_images && d_im_ids && d_boxes && n_im > 0 && (C == 3 || C == 4) && H > 0 && W > 0, "mp_raster_render_xrec: bad crop arguments");
   MP_REQUIRE(f32_mask != 0u, "mp_raster_render_xrec: empty fp32-kind channel mask");
-  CropArgs crop;
-  crop.images = d_images; crop.im_ids = d_im_ids; crop.boxes = d_boxes;
-  crop.C = C; crop.H = H; crop.W = W; crop.c0 = 0; crop.nhwc4 = images_nhwc4 ? 1 : 0;
+  const CropArgs crop = crop_args(d_images, images_nhwc4, C, H, W, d_im_ids, d_boxes, 0);
   return raster_render_impl(db, d_mesh_ids, d_TCO, d_K, n_views, h, w, (flags | MP_RASTER_XREC) & ~MP_RASTER_F16, lights, (float*)d_out_records,
                             stride_v, views_per_item, stride_view, stride_y, stride_x, c_rgb, c_normals, c_depth, d_ws, ws_bytes, stream, crop,
                             f32_mask, d_tCR, depth_mode);

@@ -33,25 +33,54 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _dev_f32(t: torch.Tensor) -> torch.Tensor:
+def _dev(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """`t` as a contiguous device tensor of `dtype` (itself if it already is one)"""
     if not t.is_cuda:
         raise EngineError("engine tensors must live on the GPU")
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.to(torch.float32).contiguous()
+    if t.dtype != dtype or not t.is_contiguous():
+        t = t.to(dtype).contiguous()
     return t
+
+
+def _dev_f32(t: torch.Tensor) -> torch.Tensor:
+    return _dev(t, torch.float32)
 
 
 def _dev_i32(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise EngineError("engine tensors must live on the GPU")
-    if t.dtype != torch.int32 or not t.is_contiguous():
-        t = t.to(torch.int32).contiguous()
-    return t
+    return _dev(t, torch.int32)
 
 
 def _workspace(n_bytes: int, device) -> torch.Tensor:
     """a launch's scratch of at least n_bytes (never empty: the entries refuse a null workspace)"""
     return torch.empty(max(int(n_bytes), 256), dtype=torch.uint8, device=device)
+
+
+class _Handle:
+    """Owner of one C handle: `_destroy` names the entry that frees it; it runs once, from close() or at collection."""
+    _destroy = ""
+    handle = None
+
+    def close(self):
+        if self.handle:
+            getattr(_lib.load(), self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _named_tensors(state_dict: Dict[str, torch.Tensor]):
+    """The floating-point tensors of a state dict as the mp_named_tensor array of a create call -> (array, items); the array points
+    into the names and host arrays of `items`: keep that referenced until the call has returned."""
+    items = [(k.encode(), np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32)) for k, v in state_dict.items()
+             if torch.is_tensor(v) and v.dtype.is_floating_point]
+    arr = (NamedTensor * len(items))()
+    for i, (k, a) in enumerate(items):
+        arr[i] = NamedTensor(k, a.ctypes.data, a.size)
+    return arr, items
 
 
 def clock_probe(ms_target: float = 20.0) -> Dict[str, float]:
@@ -120,10 +149,11 @@ def device_info() -> Tuple[int, int, str]:
 
 
 # --------------------------------------------------------------------------- #
-class MeshDB:
+class MeshDB(_Handle):
     """Device-resident meshes (mp_mesh_db).  `meshes`: list of dicts with float32 arrays
     vertices [V,3] (metres), normals [V,3], colors [V,3] in [0,1], int32 faces [T,3]; optionally uvs [T,3,2] and
     texture_mips (list of uint32 [h_l, w_l] RGBA8 levels) for UV-textured objects."""
+    _destroy = "mp_mesh_db_destroy"
 
     def __init__(self, meshes: Sequence[Dict[str, np.ndarray]]):
         lib = _lib.load()
@@ -163,17 +193,6 @@ class MeshDB:
         if ws is None or ws.numel() < need or ws.device != torch.device(device):
             self._ws[slot] = ws = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
         return ws
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().mp_mesh_db_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def make_lights(ambient=(1.0, 1.0, 1.0), point_dirs=(), point_colors=(), point_offsets=None) -> Lights:
@@ -218,6 +237,10 @@ def raster_render(db: MeshDB, mesh_ids: torch.Tensor, TCO: torch.Tensor, K: torc
     # a bfloat16 `out` = the stem RECORDS of the exact-piece stem convolution (MP_RASTER_XREC; strides / offset in bf16 elements)
     flags = (flags | RASTER_XREC) if out.dtype == torch.bfloat16 else (flags & ~RASTER_XREC)
     ws = db.workspace(n, h, w, out.device, slot)
+    # what the three entries share, in call order (args[7] = flags); the crop forms append theirs
+    args = [db.handle, mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(), n, h, w, flags, C.byref(lights),
+            out.data_ptr() + es * out_offset_floats, stride_v, views_per_item, stride_view, stride_y, stride_x, c_rgb, c_normals, c_depth,
+            ws.data_ptr(), ws.numel()]
     if crop is not None:
         images, im_ids, boxes, c0 = crop
         if isinstance(images, PackedObservation):
@@ -228,24 +251,17 @@ def raster_render(db: MeshDB, mesh_ids: torch.Tensor, TCO: torch.Tensor, K: torc
             n_im, Cc, H, W = images.shape
         im_ids, boxes = _dev_i32(im_ids), _dev_f32(boxes)
         assert boxes.shape[0] * views_per_item == n and im_ids.shape[0] == boxes.shape[0]
+        args += [images.data_ptr(), nhwc4, n_im, Cc, H, W, im_ids.data_ptr(), boxes.data_ptr()]
         if xrec is not None:   # records with depth channels: (f32_mask, tCR [n_items, 3], depth mode) -> mp_raster_render_xrec
             assert out.dtype == torch.bfloat16 and c0 == 0
             f32_mask, tCR, depth_mode = xrec
             tCR = _dev_f32(tCR) if tCR is not None else None
-            check(lib.mp_raster_render_xrec(db.handle, mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(), n, h, w, flags & ~RASTER_XREC,
-                                            C.byref(lights), out.data_ptr() + es * out_offset_floats, stride_v, views_per_item, stride_view,
-                                            stride_y, stride_x, c_rgb, c_normals, c_depth, ws.data_ptr(), ws.numel(), images.data_ptr(), nhwc4,
-                                            n_im, Cc, H, W, im_ids.data_ptr(), boxes.data_ptr(), int(f32_mask) & 0xFFFFFFFF, _ptr(tCR),
-                                            int(depth_mode), _stream()))
+            args[7] = flags & ~RASTER_XREC   # (the entry sets that flag itself)
+            check(lib.mp_raster_render_xrec(*args, int(f32_mask) & 0xFFFFFFFF, _ptr(tCR), int(depth_mode), _stream()))
             return
-        check(lib.mp_raster_render_crop(db.handle, mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(), n, h, w, flags, C.byref(lights),
-                                        out.data_ptr() + es * out_offset_floats, stride_v, views_per_item, stride_view, stride_y, stride_x,
-                                        c_rgb, c_normals, c_depth, ws.data_ptr(), ws.numel(), images.data_ptr(), nhwc4, n_im, Cc, H, W,
-                                        im_ids.data_ptr(), boxes.data_ptr(), c0, _stream()))
+        check(lib.mp_raster_render_crop(*args, c0, _stream()))
         return
-    check(lib.mp_raster_render(db.handle, mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(), n, h, w, flags, C.byref(lights),
-                               out.data_ptr() + es * out_offset_floats, stride_v, views_per_item, stride_view, stride_y, stride_x, c_rgb,
-                               c_normals, c_depth, ws.data_ptr(), ws.numel(), _stream()))
+    check(lib.mp_raster_render(*args, _stream()))
 
 
 def lights_array(rigs: Sequence[Lights], device) -> torch.Tensor:
@@ -323,15 +339,35 @@ def padded_view(buf: torch.Tensor, n: int, h: int, w: int, c: int, border: int) 
     return full[:, border : border + h, border : border + w, :]
 
 
+def _pack_weights(entry, w_oihw: np.ndarray, scale: Optional[np.ndarray], n_out: int, dtype, *dims) -> np.ndarray:
+    """What the weight packers share: `w_oihw` as a contiguous fp32 array, the optional `scale` as one (None: NULL), a blob of `n_out`
+    elements of `dtype` (the size the library states) and the call entry(w, *dims, scale, blob)."""
+    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
+    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
+    out = np.empty(n_out, dtype=dtype)
+    check(entry(w.ctypes.data, *dims, None if sc is None else sc.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _conv_desc(x: Optional[int], N: int, H: int, W: int, Cp: int, in_border: int, Cout: int, K: int, stride: int, pad: int,
+               y: Optional[int] = None, out_border: int = 0, bias=None, residual=None, relu: bool = False, y_act=None, act_scale=None,
+               act_shift=None) -> ConvDesc:
+    """mp_conv_desc with its input, geometry, output and epilogue groups filled (x, y: device addresses or None, the rest optional
+    tensors); the weights and every other field stay zero for the caller to set."""
+    d = ConvDesc()
+    d.d_x, d.N, d.H, d.W, d.C, d.in_border = x, N, H, W, Cp, in_border
+    d.d_bias = _ptr(bias)
+    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, K, K, stride, pad
+    d.d_y, d.out_border, d.d_residual, d.relu = y, out_border, _ptr(residual), int(relu)
+    d.d_y_act, d.d_act_scale, d.d_act_shift = _ptr(y_act), _ptr(act_scale), _ptr(act_shift)
+    return d
+
+
 def conv_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
-    n = lib.mp_conv_packed_floats(cin_p, Cout, KH, KW)
-    out = np.empty(n, dtype=np.float32)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_pack_weights(w.ctypes.data, Cout, Cin, KH, KW, cin_p, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    Cout, Cin, KH, KW = np.shape(w_oihw)
+    return _pack_weights(lib.mp_conv_pack_weights, w_oihw, scale, lib.mp_conv_packed_floats(cin_p, Cout, KH, KW), np.float32,
+                         Cout, Cin, KH, KW, cin_p)
 
 
 def conv2d_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int, w_packed: torch.Tensor,
@@ -341,30 +377,22 @@ def conv2d_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int
                 splitk_ws: Optional[torch.Tensor] = None) -> None:
     """`splitk_ws` (fp32 scratch): lets launches whose tile grid cannot fill the chip split the K loop (deterministic two-pass).
     A float16 `x` (same padded-NHWC geometry) selects the half-precision input path (mp_conv_desc.x_f16; Cout <= 64 only)."""
-    lib = _lib.load()
-    d = ConvDesc()
     assert x.dtype in (torch.float32, torch.float16)
-    d.x_f16 = int(x.dtype == torch.float16)
+    d = _conv_desc(x.data_ptr(), N, H, W, Cp, in_border, Cout, K, stride, pad, _ptr(y), out_border, bias, residual, relu, y_act, act_scale,
+                   act_shift)
+    d.d_w, d.x_f16 = w_packed.data_ptr(), int(x.dtype == torch.float16)
     if splitk_ws is not None:
         d.d_splitk_ws, d.splitk_ws_floats = splitk_ws.data_ptr(), splitk_ws.numel()
-    d.d_x, d.N, d.H, d.W, d.C, d.in_border = x.data_ptr(), N, H, W, Cp, in_border
-    d.d_w, d.d_bias = w_packed.data_ptr(), _ptr(bias)
-    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, K, K, stride, pad
-    d.d_y, d.out_border, d.d_residual, d.relu = _ptr(y), out_border, _ptr(residual), int(relu)
-    d.d_y_act, d.d_act_scale, d.d_act_shift = _ptr(y_act), _ptr(act_scale), _ptr(act_shift)
-    check(lib.mp_conv2d_nhwc(C.byref(d), _stream()))
+    check(_lib.load().mp_conv2d_nhwc(C.byref(d), _stream()))
 
 
 def conv_bf16x9_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     """direct-convolution weights (scale folded as in conv_pack_weights) split into three exact bf16 pieces, MFMA fragment order
     (mp_conv_bf16x9_pack_weights); uint8 blob for conv2d_bf16x9_nhwc"""
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
-    out = np.empty(lib.mp_conv_bf16x9_packed_bytes(cin_p, Cout, KH, KW), dtype=np.uint8)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_bf16x9_pack_weights(w.ctypes.data, Cout, Cin, KH, KW, cin_p, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    Cout, Cin, KH, KW = np.shape(w_oihw)
+    return _pack_weights(lib.mp_conv_bf16x9_pack_weights, w_oihw, scale, lib.mp_conv_bf16x9_packed_bytes(cin_p, Cout, KH, KW), np.uint8,
+                         Cout, Cin, KH, KW, cin_p)
 
 
 def conv2d_bf16x9_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int, w_pieces: torch.Tensor,
@@ -373,25 +401,19 @@ def conv2d_bf16x9_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_bord
                        act_scale: Optional[torch.Tensor] = None, act_shift: Optional[torch.Tensor] = None) -> None:
     """conv2d_nhwc on the bf16 MFMA through exact operand pieces (mp_conv2d_bf16x9_nhwc): always one single-pass launch;
     `w_pieces` = conv_bf16x9_pack_weights(...) on the device.  Needs Cp % 16 == 0 and K * Cp % 32 == 0."""
-    d = ConvDesc()
-    d.d_x, d.N, d.H, d.W, d.C, d.in_border = x.data_ptr(), N, H, W, Cp, in_border
-    d.d_w, d.d_bias = w_pieces.data_ptr(), _ptr(bias)
-    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, K, K, stride, pad
-    d.d_y, d.out_border, d.d_residual, d.relu = _ptr(y), out_border, _ptr(residual), int(relu)
-    d.d_y_act, d.d_act_scale, d.d_act_shift = _ptr(y_act), _ptr(act_scale), _ptr(act_shift)
+    d = _conv_desc(x.data_ptr(), N, H, W, Cp, in_border, Cout, K, stride, pad, _ptr(y), out_border, bias, residual, relu, y_act, act_scale,
+                   act_shift)
+    d.d_w = w_pieces.data_ptr()
     check(_lib.load().mp_conv2d_bf16x9_nhwc(C.byref(d), w_pieces.data_ptr(), _stream()))
 
 
 def conv_wino_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     """Winograd-transformed weights U = G g G^T of a 3x3 layer in MFMA fragment order (mp_conv_wino_pack_weights)"""
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
+    Cout, Cin, KH, KW = np.shape(w_oihw)
     assert KH == 3 and KW == 3
-    out = np.empty(lib.mp_conv_wino_packed_floats(cin_p, Cout), dtype=np.float32)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_wino_pack_weights(w.ctypes.data, Cout, Cin, cin_p, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    return _pack_weights(lib.mp_conv_wino_pack_weights, w_oihw, scale, lib.mp_conv_wino_packed_floats(cin_p, Cout), np.float32,
+                         Cout, Cin, cin_p)
 
 
 def conv3x3_wino_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_border: int, u_packed: torch.Tensor,
@@ -400,12 +422,8 @@ def conv3x3_wino_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_borde
                       act_scale: Optional[torch.Tensor] = None, act_shift: Optional[torch.Tensor] = None) -> None:
     """Fused Winograd F(2x2, 3x3) form of a 3x3 / stride-1 / pad-1 convolution (mp_conv3x3_wino_nhwc).  `x` must carry
     (W + 2 * in_border + 1) * Cp floats of readable slack behind the tensor when H or W is odd."""
-    d = ConvDesc()
-    d.d_x, d.N, d.H, d.W, d.C, d.in_border = x.data_ptr(), N, H, W, Cp, in_border
-    d.d_bias = _ptr(bias)
-    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, 3, 3, 1, 1
-    d.d_y, d.out_border, d.d_residual, d.relu = _ptr(y), out_border, _ptr(residual), int(relu)
-    d.d_y_act, d.d_act_scale, d.d_act_shift = _ptr(y_act), _ptr(act_scale), _ptr(act_shift)
+    d = _conv_desc(x.data_ptr(), N, H, W, Cp, in_border, Cout, 3, 1, 1, _ptr(y), out_border, bias, residual, relu, y_act, act_scale,
+                   act_shift)   # (d_w stays unset: the transformed weights are an argument of their own)
     if u_packed.dtype == torch.uint8:   # the three-bf16-piece blob: the exact-piece kernel (mp_conv3x3_wino_bf16_nhwc)
         check(_lib.load().mp_conv3x3_wino_bf16_nhwc(C.byref(d), u_packed.data_ptr(), _stream()))
         return
@@ -415,23 +433,17 @@ def conv3x3_wino_nhwc(x: torch.Tensor, N: int, H: int, W: int, Cp: int, in_borde
 def conv_wino_eligible(N: int, H: int, W: int, Cp: int, in_border: int, Cout: int, out_border: int, n_cu: int) -> bool:
     """True if the backbone would run this 3x3 / stride-1 / pad-1 layer on a Winograd kernel (mp_conv_wino_eligible): channel counts
     that tile, tensors small enough for 32-bit byte offsets, and a grid of at least a quarter of `n_cu` workgroups"""
-    d = ConvDesc()
-    d.N, d.H, d.W, d.C, d.in_border = N, H, W, Cp, in_border
-    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, 3, 3, 1, 1
-    d.out_border = out_border
+    d = _conv_desc(None, N, H, W, Cp, in_border, Cout, 3, 1, 1, None, out_border)
     return bool(_lib.load().mp_conv_wino_eligible(C.byref(d), n_cu))
 
 
 def conv_wino_bf16_pack_weights(w_oihw: np.ndarray, cin_p: int, scale: Optional[np.ndarray] = None) -> np.ndarray:
     """U = G g G^T of a 3x3 layer split into three exact bf16 pieces, MFMA fragment order (mp_conv_wino_bf16_pack_weights); uint8 blob"""
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
+    Cout, Cin, KH, KW = np.shape(w_oihw)
     assert KH == 3 and KW == 3
-    out = np.empty(lib.mp_conv_wino_bf16_packed_bytes(cin_p, Cout), dtype=np.uint8)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_wino_bf16_pack_weights(w.ctypes.data, Cout, Cin, cin_p, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    return _pack_weights(lib.mp_conv_wino_bf16_pack_weights, w_oihw, scale, lib.mp_conv_wino_bf16_packed_bytes(cin_p, Cout), np.uint8,
+                         Cout, Cin, cin_p)
 
 
 def conv_wino_bf16_telemetry(on: bool) -> bool:
@@ -461,18 +473,15 @@ def leading_mask(n_f32: int) -> int:
 
 def conv_stem_pack_weights(w_oihw: np.ndarray, n_f32: int, scale: Optional[np.ndarray] = None, f32_mask: Optional[int] = None) -> np.ndarray:
     """three exact bf16 pieces of every stem weight (BN scale and, for the integer channels, 1/255 folded in) in MFMA fragment order
-    (mp_conv_stem_pack_weights[_mask]); the first `n_f32` input channels -- or, with `f32_mask`, the channels whose bit is set -- are
+    (mp_conv_stem_pack_weights_mask); the first `n_f32` input channels -- or, with `f32_mask`, the channels whose bit is set -- are
     fp32-kind, the others 8-bit integers.  Returns a uint8 blob."""
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
+    Cout, Cin, KH, KW = np.shape(w_oihw)
     assert KH == KW
     mask = leading_mask(n_f32) if f32_mask is None else int(f32_mask)
     nf = bin(mask).count("1")
-    out = np.empty(lib.mp_conv_stem_packed_bytes(KH, nf, Cin - nf, Cout), dtype=np.uint8)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_stem_pack_weights_mask(w.ctypes.data, Cout, Cin, KH, mask, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    return _pack_weights(lib.mp_conv_stem_pack_weights_mask, w_oihw, scale, lib.mp_conv_stem_packed_bytes(KH, nf, Cin - nf, Cout), np.uint8,
+                         Cout, Cin, KH, mask)
 
 
 def xrec_elements(n_f32: int, n_u8: int) -> int:
@@ -483,15 +492,11 @@ def conv_stem_pack_weights_sparse(w_oihw: np.ndarray, n_f32: int, scale: Optiona
     """the piece blob of the stem's BACKGROUND-TILE walk (only the record chunks that hold fp32-kind pieces; mp_conv_stem_pack_weights_sparse);
     None if this record has no such form (nothing to skip)"""
     lib = _lib.load()
-    w = np.ascontiguousarray(w_oihw, dtype=np.float32)
-    Cout, Cin, KH, KW = w.shape
+    Cout, Cin, KH, KW = np.shape(w_oihw)
     n = lib.mp_conv_stem_sparse_packed_bytes(KH, n_f32, Cin - n_f32, Cout)
     if n == 0:
         return None
-    out = np.empty(n, dtype=np.uint8)
-    sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float32)
-    check(lib.mp_conv_stem_pack_weights_sparse(w.ctypes.data, Cout, Cin, KH, n_f32, None if sc is None else sc.ctypes.data, out.ctypes.data))
-    return out
+    return _pack_weights(lib.mp_conv_stem_pack_weights_sparse, w_oihw, scale, n, np.uint8, Cout, Cin, KH, n_f32)
 
 
 def conv_stem_bg_stats(reset: bool = True) -> Tuple[float, float]:
@@ -509,11 +514,8 @@ def conv_stem_xrec(xrec: torch.Tensor, N: int, H: int, W: int, c_real: int, n_f3
     output is written too (mp_conv_stem_xrec_pool; `y` may then be None); with `w_sparse` + `tile_flags` (uint8 [N, ceil(H/8), ceil(W/8)],
     0 = the tile's integer channels are all 0) workgroups over background take the short walk (mp_conv_stem_xrec_sparse)"""
     assert xrec.dtype == torch.bfloat16 and w_pieces.dtype == torch.uint8
-    d = ConvDesc()
-    d.d_x, d.N, d.H, d.W, d.C, d.c_real, d.in_border = xrec.data_ptr(), N, H, W, (c_real + 3) // 4 * 4, c_real, in_border
-    d.d_bias = _ptr(bias)
-    d.Cout, d.KH, d.KW, d.stride, d.pad = Cout, K, K, 2, pad
-    d.d_y, d.out_border, d.relu = _ptr(y), out_border, int(relu)
+    d = _conv_desc(xrec.data_ptr(), N, H, W, (c_real + 3) // 4 * 4, in_border, Cout, K, 2, pad, _ptr(y), out_border, bias, relu=relu)
+    d.c_real = c_real
     if w_sparse is not None and tile_flags is not None:
         assert tile_flags.dtype == torch.uint8 and tile_flags.is_cuda and w_sparse.dtype == torch.uint8
         check(_lib.load().mp_conv_stem_xrec_sparse(C.byref(d), w_pieces.data_ptr(), w_sparse.data_ptr(), n_f32, tile_flags.data_ptr(),
@@ -529,12 +531,9 @@ def conv2d_plan(N: int, H: int, W: int, Cp: int, in_border: int, Cout: int, K: i
                 ws_floats: int = 0, x_f16: bool = False) -> Dict[str, int]:
     """How mp_conv2d_nhwc would lay this launch out on `n_cu` CUs (host-only, no GPU work): mode 0 single pass, 1 every tile
     split along K, 2 full rounds + split-K tail (half-precision inputs always run single pass)."""
-    d = ConvDesc()
-    d.x_f16 = int(x_f16)
     dummy = 0x1000  # the planner only tests pointers for NULL
-    d.d_x, d.N, d.H, d.W, d.C, d.in_border = dummy, N, H, W, Cp, in_border
-    d.d_w, d.Cout, d.KH, d.KW, d.stride, d.pad = dummy, Cout, K, K, stride, pad
-    d.d_y, d.out_border = dummy, 1
+    d = _conv_desc(dummy, N, H, W, Cp, in_border, Cout, K, stride, pad, dummy, 1)
+    d.d_w, d.x_f16 = dummy, int(x_f16)
     if ws_floats:
         d.d_splitk_ws, d.splitk_ws_floats = dummy, ws_floats
     out = (C.c_int32 * 5)()
@@ -558,8 +557,9 @@ def pool_fc_heads(x, N, H, W, Cc, in_border, fc_w, fc_b, n_feat, head_w, head_b,
                                        head_b.data_ptr(), n_out, _ptr(feat), out.data_ptr(), _ptr(sigmoid), _stream()))
 
 
-class Backbone:
+class Backbone(_Handle):
     """mp_backbone: whole CNN + head resident on the device, one call per forward."""
+    _destroy = "mp_backbone_destroy"
 
     def __init__(self, kind: str, c_in: int, head: str, n_out: int, state_dict: Dict[str, torch.Tensor]):
         lib = _lib.load()
@@ -569,17 +569,7 @@ class Backbone:
         if kind not in BACKBONE_KINDS:
             raise EngineError(f"unknown backbone '{kind}' (pose_models_cfg.py:106-118 supports {list(BACKBONE_KINDS)} and resnet34_width=N)")
         self.width = width
-        keep = []
-        items = []
-        for k, v in state_dict.items():
-            if not torch.is_tensor(v) or not v.dtype.is_floating_point:
-                continue
-            a = np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32)
-            keep.append(a)
-            items.append((k.encode(), a))
-        arr = (NamedTensor * len(items))()
-        for i, (k, a) in enumerate(items):
-            arr[i] = NamedTensor(k, a.ctypes.data, a.size)
+        arr, items = _named_tensors(state_dict)   # (`items` owns what `arr` points into)
         h = C.c_void_p()
         check(lib.mp_backbone_create_wide(BACKBONE_KINDS[kind], width, c_in, 0 if head == "pose" else 1, n_out, arr, len(items), C.byref(h)))
         self.handle = h
@@ -638,17 +628,6 @@ class Backbone:
             return
         fn = lib.mp_backbone_forward_f16 if x.dtype == torch.float16 else lib.mp_backbone_forward
         check(fn(self.handle, x.data_ptr(), batch, h, w, out.data_ptr(), _ptr(sigmoid), _ptr(feat), ws.data_ptr(), ws.numel(), _stream()))
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().mp_backbone_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # --------------------------------------------------------------------------- #
@@ -939,6 +918,28 @@ def bop_match_limits() -> Dict[str, int]:
     return dict(zip(("max_errors", "max_thetas", "mask_bits", "stage_floats"), (int(x.value) for x in v)))
 
 
+def _match_index(index: Dict[str, torch.Tensor], c: int, n_groups: Optional[int], checked: Sequence[str], misfit: str,
+                 n_top: Optional[torch.Tensor]):
+    """What bop_match and det_match share: the BOP_MATCH_INDEX tensors as int32 on the device, the shapes of those named in `checked`
+    (any other shape: EngineError(misfit)), n_top [n_groups] and the host int `n_taken_words`; n_groups None = as many as group_n_gt has
+    -> (index, its seven device addresses in call order, n_top, n_est, n_groups, n_words).  Keep `index` referenced until the launch is
+    enqueued: the addresses point into it."""
+    ix = {k: _dev_i32(index[k]) for k in BOP_MATCH_INDEX}
+    n_est = ix["est_row"].shape[0]
+    if n_groups is None:
+        n_groups = ix["group_n_gt"].shape[0]
+    shape = dict(cand_gt=(c,), cand_lgt=(c,), est_off=(n_est + 1,), group_est_off=(n_groups + 1,), group_n_gt=(n_groups,),
+                 group_taken_off=(n_groups + 1,))
+    if any(ix[k].shape != shape[k] for k in checked):
+        raise EngineError(misfit)
+    if n_top is not None:
+        n_top = _dev_i32(n_top)
+        if n_top.shape != (n_groups,):
+            raise EngineError(f"n_top must be [n_groups], got {tuple(n_top.shape)}")
+    n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
+    return ix, [ix[k].data_ptr() for k in BOP_MATCH_INDEX], n_top, n_est, n_groups, n_words
+
+
 def bop_match(errs: torch.Tensor, index: Dict[str, torch.Tensor], thr: torch.Tensor, n_pred: int,
               n_top: Optional[torch.Tensor] = None) -> torch.Tensor:
     """BOP's greedy matching (mp_bop_match).  errs [C,E] float32 in the index's candidate order; index = the int32 tensors
@@ -950,27 +951,16 @@ def bop_match(errs: torch.Tensor, index: Dict[str, torch.Tensor], thr: torch.Ten
         raise EngineError(f"errs must be [C,E], got {tuple(errs.shape)}")
     dev = errs.device
     c, e = errs.shape
-    ix = {k: _dev_i32(index[k]) for k in BOP_MATCH_INDEX}
     thr = thr.to(device=dev, dtype=torch.float64).contiguous()
     if thr.dim() != 3 or thr.shape[1] != e:
         raise EngineError(f"thr must be [n_groups,{e},n_theta], got {tuple(thr.shape)}")
     n_groups, _, n_theta = thr.shape
-    n_est = ix["est_row"].shape[0]
-    if ix["cand_gt"].shape != (c,) or ix["cand_lgt"].shape != (c,) or ix["est_off"].shape != (n_est + 1,) \
-            or ix["group_est_off"].shape != (n_groups + 1,) or ix["group_n_gt"].shape != (n_groups,) \
-            or ix["group_taken_off"].shape != (n_groups + 1,):
-        raise EngineError("the index does not fit errs [C,E] and thr [n_groups,E,n_theta]")
-    if n_top is not None:
-        n_top = _dev_i32(n_top)
-        if n_top.shape != (n_groups,):
-            raise EngineError(f"n_top must be [n_groups], got {tuple(n_top.shape)}")
-    n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
+    ix, ix_ptrs, n_top, n_est, n_groups, n_words = _match_index(
+        index, c, n_groups, BOP_MATCH_INDEX[:2] + BOP_MATCH_INDEX[3:], "the index does not fit errs [C,E] and thr [n_groups,E,n_theta]", n_top)
     match = torch.empty(int(n_pred), e, n_theta, dtype=torch.int32, device=dev)
     lib = _lib.load()
     ws = _workspace(lib.mp_bop_match_workspace_bytes(n_words, e, n_theta), dev)
-    check(lib.mp_bop_match(errs.data_ptr(), ix["cand_gt"].data_ptr(), ix["cand_lgt"].data_ptr(), ix["est_row"].data_ptr(),
-                           ix["est_off"].data_ptr(), ix["group_est_off"].data_ptr(), ix["group_n_gt"].data_ptr(),
-                           ix["group_taken_off"].data_ptr(), _ptr(n_top), thr.data_ptr(), int(n_pred), c, n_est, n_groups, n_words, e, n_theta,
+    check(lib.mp_bop_match(errs.data_ptr(), *ix_ptrs, _ptr(n_top), thr.data_ptr(), int(n_pred), c, n_est, n_groups, n_words, e, n_theta,
                            match.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return match
 
@@ -983,13 +973,12 @@ MASK_PAIR_MAX_PAIRS = 1 << 23        # candidates of one mp_mask_pair_counts cal
 
 def _dev_bytes(name: str, t: torch.Tensor) -> torch.Tensor:
     """a uint8 or bool device tensor as uint8, through a view: no copy unless it is not contiguous"""
-    if not t.is_cuda:
-        raise EngineError("engine tensors must live on the GPU")
+    t = _dev(t, t.dtype)
     if t.dtype == torch.bool:
-        t = t.contiguous().view(torch.uint8)
+        t = t.view(torch.uint8)
     if t.dtype != torch.uint8:
         raise EngineError(f"{name} must be uint8 or bool, got {t.dtype}")
-    return t.contiguous()
+    return t
 
 
 def mask_pair_counts(pred_masks: torch.Tensor, gt_masks: torch.Tensor, cand_pred: torch.Tensor, cand_gt: torch.Tensor,
@@ -1020,31 +1009,22 @@ def det_match(iou: torch.Tensor, index: Dict[str, torch.Tensor], gt_ignore: torc
     """COCO's greedy matching (mp_det_match).  iou [C] float64 in the index's candidate order; index as `bop_match` takes it;
     gt_ignore [G] uint8 or bool, indexed by gt_row; thr [n_theta] float64; n_top [n_groups] int32 or None -> match [n_pred,n_theta]
     int32 (gt_row or -1).  Neither the index nor the gt_rows against gt_ignore are range-checked."""
-    if not iou.is_cuda:
-        raise EngineError("engine tensors must live on the GPU")
+    iou = _dev(iou, torch.float64)
     dev = iou.device
-    iou = iou.to(torch.float64).contiguous()
     thr = thr.to(device=dev, dtype=torch.float64).contiguous()
     if iou.dim() != 1 or thr.dim() != 1:
         raise EngineError(f"iou must be [C] and thr [n_theta], got {tuple(iou.shape)}, {tuple(thr.shape)}")
     c, n_theta = iou.shape[0], thr.shape[0]
-    ix = {k: _dev_i32(index[k]) for k in BOP_MATCH_INDEX}
     gt_ignore = _dev_bytes("gt_ignore", gt_ignore)
-    n_est, n_groups = ix["est_row"].shape[0], ix["group_n_gt"].shape[0]
-    if ix["cand_gt"].shape != (c,) or ix["cand_lgt"].shape != (c,) or ix["est_off"].shape != (n_est + 1,) \
-            or ix["group_est_off"].shape != (n_groups + 1,) or ix["group_taken_off"].shape != (n_groups + 1,) or gt_ignore.dim() != 1:
-        raise EngineError("the index does not fit iou [C]")
-    if n_top is not None:
-        n_top = _dev_i32(n_top)
-        if n_top.shape != (n_groups,):
-            raise EngineError(f"n_top must be [n_groups], got {tuple(n_top.shape)}")
-    n_words = int(index["n_taken_words"])            # a host int (= group_taken_off[-1]): nothing is read back here
+    misfit = "the index does not fit iou [C]"
+    if gt_ignore.dim() != 1:
+        raise EngineError(misfit)
+    ix, ix_ptrs, n_top, n_est, n_groups, n_words = _match_index(
+        index, c, None, ("cand_gt", "cand_lgt", "est_off", "group_est_off", "group_taken_off"), misfit, n_top)
     match = torch.empty(int(n_pred), n_theta, dtype=torch.int32, device=dev)
     lib = _lib.load()
     ws = _workspace(lib.mp_det_match_workspace_bytes(n_words, n_theta), dev)
-    check(lib.mp_det_match(iou.data_ptr(), ix["cand_gt"].data_ptr(), ix["cand_lgt"].data_ptr(), ix["est_row"].data_ptr(),
-                           ix["est_off"].data_ptr(), ix["group_est_off"].data_ptr(), ix["group_n_gt"].data_ptr(),
-                           ix["group_taken_off"].data_ptr(), _ptr(n_top), gt_ignore.data_ptr(), thr.data_ptr(), int(n_pred), c, n_est, n_groups,
+    check(lib.mp_det_match(iou.data_ptr(), *ix_ptrs, _ptr(n_top), gt_ignore.data_ptr(), thr.data_ptr(), int(n_pred), c, n_est, n_groups,
                            n_words, n_theta, match.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return match
 
@@ -1127,9 +1107,10 @@ def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch
 
 
 # --------------------------------------------------------------------------- #
-class DetectorNet:
+class DetectorNet(_Handle):
     """mp_detector: the Mask R-CNN (ResNet-50 + FPN) detection graph resident on the device, one call per image batch
     (csrc/detector.hip).  `state_dict` uses torchvision's keys (= a checkpoint of the reference's DetectorMaskRCNN)."""
+    _destroy = "mp_detector_destroy"
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], n_classes: int, min_size: int, max_size: int, **overrides):
         lib = _lib.load()
@@ -1143,16 +1124,7 @@ class DetectorNet:
                 cur[:] = list(v)
             else:
                 setattr(self.cfg, k, v)
-        keep, items = [], []
-        for k, v in state_dict.items():
-            if not torch.is_tensor(v) or not v.dtype.is_floating_point:
-                continue
-            a = np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float32)
-            keep.append(a)
-            items.append((k.encode(), a))
-        arr = (NamedTensor * len(items))()
-        for i, (k, a) in enumerate(items):
-            arr[i] = NamedTensor(k, a.ctypes.data, a.size)
+        arr, items = _named_tensors(state_dict)   # (`items` owns what `arr` points into)
         h = C.c_void_p()
         check(lib.mp_detector_create(C.byref(self.cfg), arr, len(items), C.byref(h)))
         self.handle = h
@@ -1214,14 +1186,3 @@ class DetectorNet:
         if rs.value > 1:
             return flat.view(s[0], rs.value)[:, : s[1]].contiguous()
         return flat.view(s[0], s[1])
-
-    def close(self):
-        if getattr(self, "handle", None):
-            _lib.load().mp_detector_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

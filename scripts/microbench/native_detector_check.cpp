@@ -443,7 +443,7 @@ static int time_case(int n, int H, int W, int C) {
     char name[128];
     int64_t launches;
     double ms, fl, by;
-    if (mp_profile_query(i, name, sizeof(name), &launches, &ms, &fl, &by) == 1) break;
+    if (mp_profile_query_ex(i, name, sizeof(name), &launches, &ms, &fl, &by, nullptr, nullptr) == 1) break;
     printf("    %-44s %4ld launches %8.3f ms  %7.1f TFLOP/s\n", name, (long)launches, ms, ms > 0 ? fl / ms / 1e9 : 0.0);
   }
   std::vector<int32_t> hc(n);

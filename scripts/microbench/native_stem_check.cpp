@@ -91,7 +91,7 @@ static int run_case(const Case& s, int* n_bad) {
   std::vector<float> packed(mp_conv_packed_floats(Cp, s.Cout, s.KS, s.KS));
   std::vector<unsigned char> pk(mp_conv_stem_packed_bytes(s.KS, s.n_f32, s.n_u8, s.Cout));
   MP_OKAY(mp_conv_pack_weights(w.data(), s.Cout, Cin, s.KS, s.KS, Cp, scl.data(), packed.data()));
-  MP_OKAY(mp_conv_stem_pack_weights(w.data(), s.Cout, Cin, s.KS, s.n_f32, scl.data(), pk.data()));
+  MP_OKAY(mp_conv_stem_pack_weights_mask(w.data(), s.Cout, Cin, s.KS, (1u << s.n_f32) - 1u, scl.data(), pk.data()));
   float *d_x, *d_w, *d_b, *d_y0, *d_y1, *d_sk;
   unsigned short* d_xr;
   unsigned char* d_pk;

@@ -169,6 +169,29 @@ def test_bad_arguments_are_refused_before_any_launch():
         eng.bop_match(errs, dict(t, n_taken_words=index["n_taken_words"], est_off=t["est_off"][:-1]), thr, P)
 
 
+def test_smallest_index_and_the_misfits_the_wrapper_refuses_itself():
+    """2 groups, 3 candidates, 2 estimates, E = 1, n_theta = 2: the table of the emulation; an est_off one element short and an n_top of
+    [n_groups + 1] are refused by the wrapper with its own texts (not the library's "mp_engine error"), i.e. before any launch."""
+    from megapose6d_amd import engine as eng
+    from megapose6d_amd import evaluation as ev
+
+    c = bm.case(4, [(1, 2), (1, 1)], 1, 2, nan_share=0.0)
+    assert len(c["pred_id"]) == 3 and len(c["scores"]) == 2 and c["thr"].shape == (2, 1, 2)
+    ref = _check(c)
+    assert ref.shape == (2, 1, 2) and (ref >= 0).any() and (ref < 0).any()
+    index = ev.bop_match_index(c["pred_id"], c["gt_id"], c["group_id"], c["scores"], 2)
+    t = dict({k: _dev(index[k]) for k in eng.BOP_MATCH_INDEX}, n_taken_words=index["n_taken_words"])
+    errs, thr = _dev(np.ascontiguousarray(c["errs"][index["order"]], np.float32)), _dev(c["thr"])
+    assert np.array_equal(eng.bop_match(errs, t, thr, 2, n_top=_dev(np.ones(2, np.int32))).cpu().numpy(),
+                          bm.emul_index(c["errs"][index["order"]], index, c["thr"], 2, [1, 1]))
+    with pytest.raises(eng.EngineError) as short:
+        eng.bop_match(errs, dict(t, est_off=t["est_off"][:-1]), thr, 2)
+    assert str(short.value) == "the index does not fit errs [C,E] and thr [n_groups,E,n_theta]"
+    with pytest.raises(eng.EngineError) as top:
+        eng.bop_match(errs, t, thr, 2, n_top=_dev(np.ones(3, np.int32)))
+    assert str(top.value) == "n_top must be [n_groups], got (3,)"
+
+
 # --------------------------------------------------------------------------------------------------------------------------------
 # end to end
 # --------------------------------------------------------------------------------------------------------------------------------

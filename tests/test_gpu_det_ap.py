@@ -185,6 +185,30 @@ def test_match_bad_arguments_are_refused_before_any_launch():
             ev.coco_match(**args)
 
 
+def test_smallest_index_and_the_misfits_the_wrapper_refuses_itself():
+    """2 groups, 3 candidates, 2 estimates, n_theta = 2: the table of the emulation; an est_off one element short and an n_top of
+    [n_groups + 1] are refused by the wrapper with its own texts (not the library's "mp_engine error"), i.e. before any launch."""
+    from megapose6d_amd import engine as eng
+    from megapose6d_amd import evaluation as ev
+
+    c = da.case(6, [(1, 2), (1, 1)], nan_share=0.0)
+    thr2 = np.array([0.5, 0.75])
+    assert len(c["pred_id"]) == 3 and len(c["scores"]) == 2
+    ref = _check(c, thr2)
+    assert ref.shape == (2, 2) and (ref >= 0).any() and (ref < 0).any()
+    index = ev.bop_match_index(c["pred_id"], c["gt_id"], c["group_id"], c["scores"])
+    t = dict({k: _dev(index[k]) for k in eng.BOP_MATCH_INDEX}, n_taken_words=index["n_taken_words"])
+    iou, thr, ign = _dev(c["iou"][index["order"]]), _dev(thr2), _dev(c["gt_ignore"].astype(np.uint8))
+    assert np.array_equal(eng.det_match(iou, t, ign, thr, 2, n_top=_dev(np.ones(2, np.int32))).cpu().numpy(),
+                          da.emul_index(c["iou"][index["order"]], index, c["gt_ignore"], thr2, 2, [1, 1]))
+    with pytest.raises(eng.EngineError) as short:
+        eng.det_match(iou, dict(t, est_off=t["est_off"][:-1]), ign, thr, 2)
+    assert str(short.value) == "the index does not fit iou [C]"
+    with pytest.raises(eng.EngineError) as top:
+        eng.det_match(iou, t, ign, thr, 2, n_top=_dev(np.ones(3, np.int32)))
+    assert str(top.value) == "n_top must be [n_groups], got (3,)"
+
+
 # --------------------------------------------------------------------------------------------------------------------------------
 # end to end
 # --------------------------------------------------------------------------------------------------------------------------------

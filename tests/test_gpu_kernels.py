@@ -190,6 +190,28 @@ def test_exact_piece_kernels_at_the_ends_of_the_fp32_range(eng, name, sx, sw, ke
     assert err < CONV_TOL * scale + 1e-37, (name, kernel, err, scale)
 
 
+def test_handles_are_destroyed_once_and_close_is_idempotent(eng, monkeypatch):
+    """MeshDB (one 4-vertex, 2-triangle mesh) and Backbone (the resnet18 logits state dict): close() twice, then del -- the second close
+    is a no-op, nothing raises, and the library's destroy entry ran once per handle."""
+    from megapose6d_amd import _lib
+    from tests.support import synthetic as syn
+
+    lib, calls = _lib.load(), []
+    for name in ("mp_mesh_db_destroy", "mp_backbone_destroy"):
+        monkeypatch.setattr(lib, name, lambda h, real=getattr(lib, name), name=name: (calls.append(name), real(h))[1])
+    v = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32) * 0.1
+    quad = {"vertices": v, "normals": np.tile(np.float32([0, 0, 1]), (4, 1)), "colors": np.full((4, 3), 0.5, np.float32),
+            "faces": np.array([[0, 1, 2], [0, 2, 3]], np.int32)}
+    db = eng.MeshDB([quad])
+    bb = eng.Backbone("resnet18", 9, "logits", 1, syn.make_state_dict("resnet18", 9, "logits", 1, seed=5))
+    assert db.handle and bb.handle and db.n == 1 and db.max_vertices == 4
+    for obj, name in ((db, "mp_mesh_db_destroy"), (bb, "mp_backbone_destroy")):
+        assert obj.close() is None and obj.handle is None and calls.count(name) == 1
+        assert obj.close() is None and obj.handle is None and calls.count(name) == 1
+    del db, bb
+    assert calls == ["mp_mesh_db_destroy", "mp_backbone_destroy"]
+
+
 def test_backbone_takes_the_winograd_path_at_full_batch(eng):
     """a 576-row forward runs its 3x3 / stride-1 layers on the Winograd kernel (profiler row present), a 2-row forward stays on the direct
     kernel's split-K path (grid too small), and both agree with each other on the rows they share"""

@@ -1,4 +1,4 @@
-"""-m gpu: the exact-piece bf16 stem path (csrc/conv_stem.hip + MP_RASTER_XREC + mp_backbone_forward_xrec).
+"""-m gpu: the exact-piece bf16 stem path (csrc/conv_stem.hip + MP_RASTER_XREC + mp_backbone_forward_xrec_mask).
 
 What it replaces: the first convolution behind `self.backbone(x)` (reference src/megapose/models/torchvision_resnet.py:213-216,
 models/wide_resnet.py:65-67) fed by the renders `uint8 / 255` of panda3d_batch_renderer.py:261-274.  Statements checked here:

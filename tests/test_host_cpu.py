@@ -111,6 +111,41 @@ def test_conv_weight_packing_layout():
     assert p[0, 0, 0, 9] == 0 and p[0, n_chunks - 1, 0, 31] == 0  # padded channel / K tail
 
 
+def test_weight_packers_coerce_weights_and_scale_alike():
+    """All six weight packers of engine.py, on the smallest layer each accepts, give the same blob bit for bit for scale=None and a scale
+    of ones, for a float64 Fortran-ordered `w` and its contiguous fp32 copy, and for a strided scale and its contiguous copy.  (The
+    6-channel stem record has no background-tile form -- its packer returns None for every input alike -- so that packer also runs on
+    the pipeline's 3 + 27 channels.)"""
+    from megapose6d_amd import engine as eng
+
+    rs = np.random.RandomState(3)
+    w3, w7, w7_30 = rs.randn(64, 16, 3, 3), rs.randn(64, 6, 7, 7), rs.randn(64, 30, 7, 7)       # float64
+    packers = [("conv_pack_weights", w3, lambda w, sc: eng.conv_pack_weights(w, 16, sc), np.float32),
+               ("conv_bf16x9_pack_weights", w3, lambda w, sc: eng.conv_bf16x9_pack_weights(w, 16, sc), np.uint8),
+               ("conv_wino_pack_weights", w3, lambda w, sc: eng.conv_wino_pack_weights(w, 16, sc), np.float32),
+               ("conv_wino_bf16_pack_weights", w3, lambda w, sc: eng.conv_wino_bf16_pack_weights(w, 16, sc), np.uint8),
+               ("conv_stem_pack_weights", w7, lambda w, sc: eng.conv_stem_pack_weights(w, 3, sc), np.uint8),
+               ("conv_stem_pack_weights (mask)", w7, lambda w, sc: eng.conv_stem_pack_weights(w, 0, sc, f32_mask=0b101010), np.uint8),
+               ("conv_stem_pack_weights_sparse", w7, lambda w, sc: eng.conv_stem_pack_weights_sparse(w, 3, sc), None),
+               ("conv_stem_pack_weights_sparse 3+27", w7_30, lambda w, sc: eng.conv_stem_pack_weights_sparse(w, 3, sc), np.uint8)]
+    longer = (rs.rand(128) + 0.5).astype(np.float32)
+    assert not longer[::2].flags.c_contiguous
+    for name, w64, pack, dtype in packers:
+        w32 = np.ascontiguousarray(w64, dtype=np.float32)
+        wf = np.asfortranarray(w64)
+        assert wf.dtype == np.float64 and wf.flags.f_contiguous and not wf.flags.c_contiguous and not np.array_equal(w32, w64)
+        ref = pack(w32, None)
+        pairs = [(ref, pack(w32, np.ones(64, np.float32))), (pack(wf, longer[:64]), pack(w32, longer[:64])),
+                 (pack(w32, longer[::2]), pack(w32, longer[::2].copy()))]
+        if dtype is None:
+            assert ref is None and all(a is None and b is None for a, b in pairs), name
+            continue
+        assert ref.dtype == dtype and ref.ndim == 1 and ref.size > 0 and ref.any(), name
+        for k, (a, b) in enumerate(pairs):
+            assert a.dtype == b.dtype == dtype and a.shape == b.shape == ref.shape and a.tobytes() == b.tobytes(), (name, k)
+        assert pairs[1][1].tobytes() != ref.tobytes(), name    # (the scale is not ignored)
+
+
 def test_tensor_collection_semantics():
     from megapose6d_amd.tcoll import PandasTensorCollection, concatenate
 
