@@ -13,18 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "conv_layer.h"
 
 namespace mp {
-
-struct ConvLayer {
-  int Cin, Cin_p, Cout, K, stride, pad;
-  float* d_w = nullptr;   // packed fp32 weights
-  float* d_u = nullptr;   // Winograd-transformed weights of an eligible 3x3 / stride-1 layer: fp32 (conv_wino.hip, MP_CONV_WINO=1) ...
-  void* d_ub = nullptr;   // ... or split into three exact bf16 pieces (conv_wino_bf16.hip, the default)
-  void* d_wb = nullptr;   // the direct weights split into three exact bf16 pieces (conv_bf16x9.hip) of an eligible non-Winograd layer
-  float* d_b = nullptr;  // folded BN shift (may be null)
-};
 
 struct BnAct {  // unfoldable pre-activation BN: relu(x*scale + shift)
   float* d_scale = nullptr;
@@ -66,143 +57,37 @@ struct mp_backbone {
 
 namespace {
 
-typedef std::map<std::string, std::pair<const float*, int64_t>> StateMap;
-
-int upload(mp_backbone* bb, const std::vector<float>& h, float** d) {
-  MP_CHECK_HIP(hipMalloc(d, h.size() * sizeof(float)));
-  MP_CHECK_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-  bb->allocs.push_back(*d);
-  return MP_OK;
-}
-
-const float* find(const StateMap& sm, const std::string& k, int64_t numel) {
-  auto it = sm.find(k);
-  if (it == sm.end()) {
-    set_error("mp_backbone_create: missing state_dict key '%s'", k.c_str());
-    return nullptr;
-  }
-  if (it->second.second != numel) {
-    set_error("mp_backbone_create: key '%s' has %ld elements, expected %ld", k.c_str(), (long)it->second.second, (long)numel);
-    return nullptr;
-  }
-  return it->second.first;
-}
-
-// eval BatchNorm -> per-channel (scale, shift)
-int bn_affine(const StateMap& sm, const std::string& prefix, int C, std::vector<float>& scale, std::vector<float>& shift) {
-  const float* g = find(sm, prefix + ".weight", C);
-  const float* b = find(sm, prefix + ".bias", C);
-  const float* m = find(sm, prefix + ".running_mean", C);
-  const float* v = find(sm, prefix + ".running_var", C);
-  if (!g || !b || !m || !v) return MP_ERR_INVALID;
-  scale.resize(C);
-  shift.resize(C);
-  for (int c = 0; c < C; ++c) {
-    const float s = g[c] / sqrtf(v[c] + 1e-5f);
-    scale[c] = s;
-    shift[c] = b[c] - m[c] * s;
-  }
-  return MP_OK;
-}
+const char* const WHO = "mp_backbone_create";
 
 int make_conv(mp_backbone* bb, const StateMap& sm, const std::string& wkey, const std::string& bnkey /* "" = none */, int Cin,
               int Cin_p, int Cout, int K, int stride, int pad, ConvLayer* L) {
-  L->Cin = Cin; L->Cin_p = Cin_p; L->Cout = Cout; L->K = K; L->stride = stride; L->pad = pad;
-  const float* w = find(sm, wkey, (int64_t)Cout * Cin * K * K);
+  const float* w = find(sm, wkey, (int64_t)Cout * Cin * K * K, WHO);
   if (!w) return MP_ERR_INVALID;
-  std::vector<float> scale, shift;
-  if (!bnkey.empty()) {
-    int rc = bn_affine(sm, bnkey, Cout, scale, shift);
-    if (rc) return rc;
-  }
-  int rc;
-  if (L == &bb->stem) {
-    bb->stem_w_host.assign(w, w + (size_t)Cout * Cin * K * K);
-    bb->stem_scale_host = scale;
-  }
-  std::vector<float> packed(mp_conv_packed_floats(Cin_p, Cout, K, K));
-  rc = mp_conv_pack_weights(w, Cout, Cin, K, K, Cin_p, bnkey.empty() ? nullptr : scale.data(), packed.data());
-  if (rc) return rc;
-  rc = upload(bb, packed, &L->d_w);
   // 3x3 / stride-1 layers of the residual stages also get their Winograd F(2x2, 3x3) form.  MP_CONV_WINO: 2 (default) = the bf16x9
   // exact-piece kernel, 1 = the fp32-MFMA kernel, 0 = keep the direct kernel
   static const int wino_mode = getenv("MP_CONV_WINO") ? atoi(getenv("MP_CONV_WINO")) : 2;
-  if (!rc && wino_mode != 0 && K == 3 && stride == 1 && pad == 1 && Cin_p % 16 == 0 && Cout % 64 == 0) {
-    if (wino_mode == 1) {
-      std::vector<float> u(mp_conv_wino_packed_floats(Cin_p, Cout));
-      rc = mp_conv_wino_pack_weights(w, Cout, Cin, Cin_p, bnkey.empty() ? nullptr : scale.data(), u.data());
-      if (!rc) rc = upload(bb, u, &L->d_u);
-    } else {
-      std::vector<float> u((mp_conv_wino_bf16_packed_bytes(Cin_p, Cout) + 3) / 4);
-      rc = mp_conv_wino_bf16_pack_weights(w, Cout, Cin, Cin_p, bnkey.empty() ? nullptr : scale.data(), u.data());
-      float* d = nullptr;
-      if (!rc) rc = upload(bb, u, &d);
-      L->d_ub = d;
-    }
+  unsigned forms = wino_mode == 0 ? 0u : wino_mode == 1 ? CONV_FORM_WINO_F32 : CONV_FORM_WINO_BF16;
+  if (L == &bb->stem) {   // the stem's exact-piece form is packed per record layout (mp_backbone_xrec_prepare) from the host copies
+    bb->stem_w_host.assign(w, w + (size_t)Cout * Cin * K * K);
+    std::vector<float> shift;
+    if (!bnkey.empty() && bn_affine(sm, bnkey, Cout, WHO, bb->stem_scale_host, shift)) return MP_ERR_INVALID;
+  } else if (bb->direct_bf16) {
+    // the other 3x3 / 1x1 layers of the residual stages (stride 2: layer{2,3,4}.0.conv1 / .downsample) also get the exact-piece direct form
+    forms |= CONV_FORM_DIRECT_BF16;
   }
-  // the other 3x3 / 1x1 layers of the residual stages (stride 2: layer{2,3,4}.0.conv1 / .downsample) also get the exact-piece direct form
-  if (!rc && bb->direct_bf16 && L != &bb->stem && !L->d_u && !L->d_ub && (K == 1 || K == 3) && Cin_p % 16 == 0 && (K * Cin_p) % 32 == 0 &&
-      Cout % 64 == 0) {
-    std::vector<float> wb((mp_conv_bf16x9_packed_bytes(Cin_p, Cout, K, K) + 3) / 4);
-    rc = mp_conv_bf16x9_pack_weights(w, Cout, Cin, K, K, Cin_p, bnkey.empty() ? nullptr : scale.data(), wb.data());
-    float* d = nullptr;
-    if (!rc) rc = upload(bb, wb, &d);
-    L->d_wb = d;
-  }
-  if (rc) return rc;
-  if (!bnkey.empty()) {
-    rc = upload(bb, shift, &L->d_b);
-    if (rc) return rc;
-  }
-  return MP_OK;
+  return make_conv_layer(bb->allocs, sm, WHO, w, bnkey, nullptr, 0, Cin, Cin_p, Cout, K, stride, pad, forms, L);
 }
 
 int make_bnact(mp_backbone* bb, const StateMap& sm, const std::string& bnkey, int C, BnAct* a) {
   std::vector<float> scale, shift;
-  int rc = bn_affine(sm, bnkey, C, scale, shift);
+  int rc = bn_affine(sm, bnkey, C, WHO, scale, shift);
   if (rc) return rc;
-  rc = upload(bb, scale, &a->d_scale);
+  rc = upload(bb->allocs, scale, &a->d_scale);
   if (rc) return rc;
-  return upload(bb, shift, &a->d_shift);
+  return upload(bb->allocs, shift, &a->d_shift);
 }
 
 constexpr size_t SPLITK_WS_FLOATS = 12u << 20;  // 48 MB of split-K scratch at the end of the workspace (>= 512 tiles of 128 x 128)
-
-int run_conv(const mp_backbone* bb, const ConvLayer& L, const float* x, int N, int H, int W, int in_border, float* y, int out_border,
-             const float* res, int relu, float* y_act, const BnAct* act, hipStream_t s, float* splitk_ws = nullptr, bool x_f16 = false) {
-  mp_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x_f16 = x_f16 ? 1 : 0;
-  d.d_x = x; d.N = N; d.H = H; d.W = W; d.C = L.Cin_p; d.c_real = L.Cin; d.in_border = in_border;
-  d.d_w = L.d_w; d.d_bias = L.d_b; d.Cout = L.Cout; d.KH = L.K; d.KW = L.K; d.stride = L.stride; d.pad = L.pad;
-  d.d_y = y; d.out_border = out_border; d.d_residual = res; d.relu = relu;
-  d.d_y_act = y_act;
-  if (y_act) { d.d_act_scale = act->d_scale; d.d_act_shift = act->d_shift; }
-  d.d_splitk_ws = splitk_ws;
-  d.splitk_ws_floats = splitk_ws ? (int64_t)SPLITK_WS_FLOATS : 0;
-  if ((L.d_u || L.d_ub || L.d_wb) && !x_f16) {
-    static int n_cu = 0, n_cu_dev = -1, lds_ok = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (n_cu_dev != dev) {
-      if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) n_cu = 256;
-      int lds = 0;   // the Winograd kernels take 128.5 KB of LDS per workgroup (gfx950: 160 KB per CU); a part with less keeps the direct kernel
-      lds_ok = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && lds >= 132 * 1024;
-      n_cu_dev = dev;
-    }
-    if ((L.d_u || L.d_ub) && lds_ok && mp_conv_wino_eligible(&d, n_cu))   // (the workspace buffers carry the read slack the Winograd kernels need)
-      return L.d_ub ? mp_conv3x3_wino_bf16_nhwc(&d, L.d_ub, s) : mp_conv3x3_wino_nhwc(&d, L.d_u, s);
-    // exact-piece direct kernel unless the fp32 kernel's plan splits every tile along K (small grids: mode 1).  A "whole rounds + split-K
-    // tail" plan (mode 2) runs as ONE single-pass launch here: on the bf16 pipe its extra, partly filled round costs less than the split tail.
-    if (L.d_wb) {
-      int32_t plan[5] = {0, 1, 0, 0, 0};
-      const int rc = mp_conv2d_plan(&d, n_cu, plan);
-      if (rc) return rc;
-      if (plan[0] != 1) return mp_conv2d_bf16x9_nhwc(&d, L.d_wb, s);
-    }
-  }
-  return mp_conv2d_nhwc(&d, s);
-}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // (+ one padded row + one pixel of slack: the Winograd kernel reads -- and discards -- that much past an odd-sized tensor)
@@ -288,18 +173,18 @@ extern "C" int mp_backbone_create_wide(int kind, int width, int c_in, int head_k
     }
   }
   if (!bb->wide) {
-    const float* fw = find(sm, B + "fc.weight", 512 * 512);
-    const float* fb = find(sm, B + "fc.bias", 512);
+    const float* fw = find(sm, B + "fc.weight", 512 * 512, WHO);
+    const float* fb = find(sm, B + "fc.bias", 512, WHO);
     if (!fw || !fb) { mp_backbone_destroy(bb); return MP_ERR_INVALID; }
-    MP_TRY(upload(bb, std::vector<float>(fw, fw + 512 * 512), &bb->d_fc_w));
-    MP_TRY(upload(bb, std::vector<float>(fb, fb + 512), &bb->d_fc_b));
+    MP_TRY(upload(bb->allocs, std::vector<float>(fw, fw + 512 * 512), &bb->d_fc_w));
+    MP_TRY(upload(bb->allocs, std::vector<float>(fb, fb + 512), &bb->d_fc_b));
   }
   const std::string H = head_kind == 0 ? "pose_fc" : "views_logits_head";
-  const float* hw = find(sm, H + ".weight", (int64_t)n_head_out * NF);
-  const float* hb = find(sm, H + ".bias", n_head_out);
+  const float* hw = find(sm, H + ".weight", (int64_t)n_head_out * NF, WHO);
+  const float* hb = find(sm, H + ".bias", n_head_out, WHO);
   if (!hw || !hb) { mp_backbone_destroy(bb); return MP_ERR_INVALID; }
-  MP_TRY(upload(bb, std::vector<float>(hw, hw + (size_t)n_head_out * NF), &bb->d_head_w));
-  MP_TRY(upload(bb, std::vector<float>(hb, hb + n_head_out), &bb->d_head_b));
+  MP_TRY(upload(bb->allocs, std::vector<float>(hw, hw + (size_t)n_head_out * NF), &bb->d_head_w));
+  MP_TRY(upload(bb->allocs, std::vector<float>(hb, hb + n_head_out), &bb->d_head_b));
 #undef MP_TRY
   *out = bb;
   return MP_OK;
@@ -439,7 +324,7 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
                     : mp_conv_stem_xrec(&d, d_stem_pieces, n_f32, s);
     }
   } else {
-    rc = run_conv(bb, bb->stem, d_x, batch, h, w, bb->in_border, S, 1, nullptr, 1, nullptr, nullptr, s, SK, x_f16);
+    rc = run_conv_layer(bb->stem, d_x, batch, h, w, bb->in_border, S, 1, nullptr, 1, s, SK, SPLITK_WS_FLOATS, nullptr, nullptr, nullptr, x_f16);
   }
   if (rc) return rc;
   const Block& b0 = bb->blocks[0];
@@ -457,28 +342,29 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
     const bool last = (i + 1 == nb);
     if (!bb->wide) {
       // y1 = relu(bn1(conv1(x))); idn = bn(down(x)) | x; out = relu(bn2(conv2(y1)) + idn)
-      rc = run_conv(bb, blk.conv1, A[si], batch, Hi, Wi, 1, Bf[so], 1, nullptr, 1, nullptr, nullptr, s, SK);
+      rc = run_conv_layer(blk.conv1, A[si], batch, Hi, Wi, 1, Bf[so], 1, nullptr, 1, s, SK, SPLITK_WS_FLOATS);
       if (rc) return rc;
       const float* idn = A[si];
       if (blk.has_down) {
-        rc = run_conv(bb, blk.down, A[si], batch, Hi, Wi, 1, Cf[so], 1, nullptr, 0, nullptr, nullptr, s, SK);
+        rc = run_conv_layer(blk.down, A[si], batch, Hi, Wi, 1, Cf[so], 1, nullptr, 0, s, SK, SPLITK_WS_FLOATS);
         if (rc) return rc;
         idn = Cf[so];
       }
-      rc = run_conv(bb, blk.conv2, Bf[so], batch, g.hs[so], g.ws[so], 1, A[so], 1, idn, 1, nullptr, nullptr, s, SK);
+      rc = run_conv_layer(blk.conv2, Bf[so], batch, g.hs[so], g.ws[so], 1, A[so], 1, idn, 1, s, SK, SPLITK_WS_FLOATS);
       if (rc) return rc;
     } else {
       // a = relu(bn1(x)) was produced upstream into Aact[si]; residual = down(a) | x
-      rc = run_conv(bb, blk.conv1, Aact[si], batch, Hi, Wi, 1, Bf[so], 1, nullptr, 1, nullptr, nullptr, s, SK);
+      rc = run_conv_layer(blk.conv1, Aact[si], batch, Hi, Wi, 1, Bf[so], 1, nullptr, 1, s, SK, SPLITK_WS_FLOATS);
       if (rc) return rc;
       const float* idn = A[si];
       if (blk.has_down) {
-        rc = run_conv(bb, blk.down, Aact[si], batch, Hi, Wi, 1, Cf[so], 1, nullptr, 0, nullptr, nullptr, s, SK);
+        rc = run_conv_layer(blk.down, Aact[si], batch, Hi, Wi, 1, Cf[so], 1, nullptr, 0, s, SK, SPLITK_WS_FLOATS);
         if (rc) return rc;
         idn = Cf[so];
       }
-      const BnAct* next_pre = last ? nullptr : &bb->blocks[i + 1].pre;
-      rc = run_conv(bb, blk.conv2, Bf[so], batch, g.hs[so], g.ws[so], 1, A[so], 1, idn, 0, last ? nullptr : Aact[so], next_pre, s, SK);
+      const BnAct next_pre = last ? BnAct() : bb->blocks[i + 1].pre;
+      rc = run_conv_layer(blk.conv2, Bf[so], batch, g.hs[so], g.ws[so], 1, A[so], 1, idn, 0, s, SK, SPLITK_WS_FLOATS, last ? nullptr : Aact[so],
+                          next_pre.d_scale, next_pre.d_shift);
       if (rc) return rc;
     }
   }

@@ -41,6 +41,11 @@ struct ProfScope {
   hipStream_t stream;
 };
 
+// CU count (256 if the query fails) and LDS bytes per workgroup (-1 if it fails) of the calling thread's current device, asked once per
+// device; defined in engine.hip
+int device_cu_count();
+int device_lds_bytes();
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 

@@ -625,14 +625,7 @@ extern "C" int mp_conv2d_nhwc(const mp_conv_desc* d, mp_stream stream) {
   }
   static const int splitk_on = getenv("MP_CONV_SPLITK") ? atoi(getenv("MP_CONV_SPLITK")) : 1;
   static const int tail_on = getenv("MP_CONV_TAIL") ? atoi(getenv("MP_CONV_TAIL")) : 1;
-  static int resident = 0;
-  if (!resident) {
-    int dev = 0, n_cu = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    resident = 2 * n_cu;
-  }
-  const ConvPlan plan = plan_conv(p, small, d->d_splitk_ws ? d->splitk_ws_floats : 0, resident, splitk_on != 0, tail_on != 0);
+  const ConvPlan plan = plan_conv(p, small, d->d_splitk_ws ? d->splitk_ws_floats : 0, 2 * device_cu_count(), splitk_on != 0, tail_on != 0);
   if (plan.mode == 1) {  // small grid: every tile split along K
     p.chunks_per_split = plan.chunks_per_split;
     p.k_split = plan.k_split;

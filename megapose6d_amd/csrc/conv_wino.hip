@@ -316,18 +316,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 using namespace mp;
 
-// The 3x3 / stride-1 / pad-1 layers this kernel takes: channel counts that tile (8 input channels per step, 64 output channels per
-// workgroup) and enough tiles to give every CU a workgroup (small grids stay on the direct kernel's split-K path).
-extern "C" int mp_conv_wino_eligible(const mp_conv_desc* d, int n_cu) {
-  if (!d || d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->x_f16) return 0;
-  if (d->C % WCK != 0 || d->Cout % WCOUT != 0 || d->in_border < 1) return 0;   // 16 input channels per step, 64 output channels per workgroup
-  const long tiles = (long)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2);
-  const long wgs = ((tiles + WT - 1) / WT) * (d->Cout / WCOUT);
-  // the kernels address with 32-bit byte offsets: larger tensors (wide backbones at full batch) stay on the direct kernel
+// Why a layer cannot run on the Winograd kernels (null = it can): the shapes that tile (16 input channels per step, 64 output channels
+// per workgroup) and the 32-bit byte offsets the kernels address with -- larger tensors (wide backbones at full batch) stay on the
+// direct kernel.  The one place these rules live: the launches turn the text into their error, mp_conv_wino_eligible into a "no".
+static const char* wino_unfit(const mp_conv_desc* d) {
+  if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1) return "3x3 / stride 1 / pad 1 only";
+  if (d->C % WCK != 0 || d->Cout % WCOUT != 0 || d->in_border < 1) return "C % 16, Cout % 64, in_border >= 1";
   const long Hp = d->H + 2 * d->in_border, Wp = d->W + 2 * d->in_border;
+  const long n_tiles = (long)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2);
   const long in_bytes = ((long)d->N * Hp + 2) * Wp * d->C * 4;
   const long out_elems = (long)d->N * (d->H + 2 * d->out_border) * (d->W + 2 * d->out_border) * d->Cout;
-  if (tiles >= (1L << 30) || in_bytes >= (1L << 31) || out_elems >= (1L << 29)) return 0;
+  if (n_tiles >= (1L << 30) || in_bytes >= (1L << 31) || out_elems >= (1L << 29)) return "tensor too large for 32-bit offsets";
+  return nullptr;
+}
+
+int mp::wino_make_params(const mp_conv_desc* d, WinoParams* pp, const char* who) {
+  MP_REQUIRE(d && d->d_x && (d->d_y || d->d_y_act), "%s: null pointer", who);
+  MP_REQUIRE(!d->d_y_act || (d->d_act_scale && d->d_act_shift), "%s: y_act needs scale/shift", who);
+  const char* unfit = wino_unfit(d);
+  MP_REQUIRE(!unfit, "%s: %s", who, unfit);
+  WinoParams& p = *pp;
+  p.x = d->d_x; p.u = nullptr; p.bias = d->d_bias; p.residual = d->d_residual; p.act_scale = d->d_act_scale; p.act_shift = d->d_act_shift;
+  p.y = d->d_y; p.y_act = d->d_y_act;
+  p.N = d->N; p.Ho = d->H; p.Wo = d->W;
+  p.Hp = d->H + 2 * d->in_border; p.Wp = d->W + 2 * d->in_border; p.C = d->C;
+  p.in_off = d->in_border - 1;
+  p.Cout = d->Cout;
+  p.Hop = d->H + 2 * d->out_border; p.Wop = d->W + 2 * d->out_border; p.out_border = d->out_border;
+  p.tiles_x = (d->W + 1) / 2; p.tiles_y = (d->H + 1) / 2;
+  p.n_tiles = d->N * p.tiles_x * p.tiles_y;
+  p.n_chunks = d->C / 8;
+  p.n_steps = d->C / WCK;
+  p.relu = d->relu;
+  p.n_cblocks = d->Cout / WCOUT;
+  p.out_bytes = d->N * p.Hop * p.Wop * d->Cout * 4;
+  wino_fastdiv_make((unsigned)p.tiles_x, &p.mg_tx, &p.sh_tx);
+  wino_fastdiv_make((unsigned)p.tiles_y, &p.mg_ty, &p.sh_ty);
+  wino_fastdiv_make((unsigned)p.n_cblocks, &p.mg_cb, &p.sh_cb);
+  p.n_units = (p.n_tiles + WT - 1) / WT * p.n_cblocks;
+  p.telemetry = 0;
+  return MP_OK;
+}
+
+// U = G g G^T of one (cout, cin) pair, G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], in double with the folded BN scale `s` on every
+// term, rounded once to fp32: U[f = 4a + b]
+void mp::wino_transform_weights(const float* g, double s, float* U) {
+  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
+  double t[4][3];
+  for (int a = 0; a < 4; ++a)
+    for (int k = 0; k < 3; ++k) t[a][k] = G[a][0] * g[0 * 3 + k] * s + G[a][1] * g[1 * 3 + k] * s + G[a][2] * g[2 * 3 + k] * s;
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) U[a * 4 + b] = (float)(t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2]);
+}
+
+// The 3x3 / stride-1 / pad-1 layers the Winograd kernels take: what wino_unfit lets through, fp32 input, and enough tiles to give the CUs
+// a workgroup (small grids stay on the direct kernel's split-K path).
+extern "C" int mp_conv_wino_eligible(const mp_conv_desc* d, int n_cu) {
+  if (!d || d->x_f16 || wino_unfit(d)) return 0;
+  const long tiles = (long)d->N * ((d->H + 1) / 2) * ((d->W + 1) / 2);
+  const long wgs = ((tiles + WT - 1) / WT) * (d->Cout / WCOUT);
   // Grid threshold: below it the direct kernel's split-K path takes the layer.  MP_WINO_MIN_WGS overrides it (A/B runs; see DESIGN.md 5:
   // the per-rank refiner batch of an 8-GPU run at the released K = 5 is 40 rows = 200 / 104 workgroups for the 256- / 512-channel layers)
   static const long min_wgs_env = getenv("MP_WINO_MIN_WGS") ? atol(getenv("MP_WINO_MIN_WGS")) : -1;
@@ -348,57 +395,31 @@ extern "C" int mp_conv_wino_stats(double* direct_flops, double* executed_flops, 
 
 extern "C" size_t mp_conv_wino_packed_floats(int Cin_p, int Cout) { return (size_t)16 * Cin_p * Cout; }
 
-// U = G g G^T per (cout, cin), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], computed in double, stored in MFMA fragment order:
+// U (wino_transform_weights) stored in MFMA fragment order:
 // packed[cb][chunk][f][j][lane][q] = U_f[cin = chunk*8 + (lane >> 5)*4 + q][cout = cb*64 + j*32 + (lane & 31)]
 extern "C" int mp_conv_wino_pack_weights(const float* w, int Cout, int Cin, int Cin_p, const float* scale, float* packed) {
   MP_REQUIRE(w && packed && Cin_p >= Cin && Cin_p % WCK == 0 && Cout % WCOUT == 0, "mp_conv_wino_pack_weights: bad arguments (Cin_p %% 16, Cout %% 64)");
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int n_chunks = Cin_p / 8, n_cb = Cout / WCOUT;
+  const int n_chunks = Cin_p / 8;
   memset(packed, 0, mp_conv_wino_packed_floats(Cin_p, Cout) * sizeof(float));
   for (int n = 0; n < Cout; ++n) {
-    const double s = scale ? (double)scale[n] : 1.0;
     const int cb = n / WCOUT, j = (n % WCOUT) / 32, nl = n % 32;
     for (int c = 0; c < Cin; ++c) {
-      const float* g = w + ((size_t)n * Cin + c) * 9;
-      double t[4][3], U[4][4];
-      for (int a = 0; a < 4; ++a)
-        for (int k = 0; k < 3; ++k) t[a][k] = G[a][0] * g[0 * 3 + k] * s + G[a][1] * g[1 * 3 + k] * s + G[a][2] * g[2 * 3 + k] * s;
-      for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b) U[a][b] = t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2];
+      float U[16];
+      wino_transform_weights(w + ((size_t)n * Cin + c) * 9, scale ? (double)scale[n] : 1.0, U);
       const int ch = c / 8, kq = (c % 8) / 4, q = c % 4;
       const int lane = kq * 32 + nl;
-      for (int f = 0; f < 16; ++f)
-        packed[(((((size_t)cb * n_chunks + ch) * 16 + f) * 2 + j) * 64 + lane) * 4 + q] = (float)U[f / 4][f % 4];
+      for (int f = 0; f < 16; ++f) packed[(((((size_t)cb * n_chunks + ch) * 16 + f) * 2 + j) * 64 + lane) * 4 + q] = U[f];
     }
   }
-  (void)n_cb;
   return MP_OK;
 }
 
 extern "C" int mp_conv3x3_wino_nhwc(const mp_conv_desc* d, const float* d_u, mp_stream stream) {
-  MP_REQUIRE(d && d->d_x && d_u && (d->d_y || d->d_y_act), "mp_conv3x3_wino_nhwc: null pointer");
-  MP_REQUIRE(d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1, "mp_conv3x3_wino_nhwc: 3x3 / stride 1 / pad 1 only");
-  MP_REQUIRE(d->C % WCK == 0 && d->Cout % WCOUT == 0 && d->in_border >= 1, "mp_conv3x3_wino_nhwc: C %% 16, Cout %% 64, in_border >= 1");
-  MP_REQUIRE(!d->d_y_act || (d->d_act_scale && d->d_act_shift), "mp_conv3x3_wino_nhwc: y_act needs scale/shift");
+  MP_REQUIRE(d_u, "mp_conv3x3_wino_nhwc: null pointer");
   WinoParams p;
-  p.x = d->d_x; p.u = d_u; p.bias = d->d_bias; p.residual = d->d_residual; p.act_scale = d->d_act_scale; p.act_shift = d->d_act_shift;
-  p.y = d->d_y; p.y_act = d->d_y_act;
-  p.N = d->N; p.Ho = d->H; p.Wo = d->W;
-  p.Hp = d->H + 2 * d->in_border; p.Wp = d->W + 2 * d->in_border; p.C = d->C;
-  p.in_off = d->in_border - 1;
-  p.Cout = d->Cout;
-  p.Hop = d->H + 2 * d->out_border; p.Wop = d->W + 2 * d->out_border; p.out_border = d->out_border;
-  p.tiles_x = (d->W + 1) / 2; p.tiles_y = (d->H + 1) / 2;
-  const long n_tiles = (long)d->N * p.tiles_x * p.tiles_y;
-  const long in_bytes = ((long)d->N * p.Hp + 2) * p.Wp * p.C * 4, out_elems = (long)d->N * p.Hop * p.Wop * d->Cout;
-  MP_REQUIRE(n_tiles < (1L << 30) && in_bytes < (1L << 31) && out_elems < (1L << 29), "mp_conv3x3_wino_nhwc: tensor too large for 32-bit offsets");
-  p.out_bytes = (int)(out_elems * 4);
-  p.n_tiles = (int)n_tiles;
-  p.n_chunks = d->C / 8;
-  p.n_steps = d->C / WCK;
-  p.relu = d->relu;
-  p.telemetry = 0;
-  p.n_cblocks = d->Cout / WCOUT;
+  int rc = wino_make_params(d, &p, "mp_conv3x3_wino_nhwc");
+  if (rc) return rc;
+  p.u = d_u;
   int dev = 0;
   MP_CHECK_HIP(hipGetDevice(&dev));
   static int attr_dev = -1;
@@ -406,18 +427,17 @@ extern "C" int mp_conv3x3_wino_nhwc(const mp_conv_desc* d, const float* d_u, mp_
     MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv3x3_wino_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO_LDS_BYTES));
     attr_dev = dev;
   }
-  const long n_wg = ((n_tiles + WT - 1) / WT) * p.n_cblocks;
   hipStream_t s = (hipStream_t)stream;
   // profiler row: the ALGORITHMIC work of the layer as SURVEY.md 8d defines it (2 * MACs of the direct convolution over the real
   // channels; bytes = input + weights + output once).  What the kernel EXECUTES is 16 multiplications per 2x2 tile and (cin, cout)
   // pair -- 16/36 of that for even sizes; both totals are accumulated for mp_conv_wino_stats (bench.py reports the executed rate as
   // the kernel's MFMA utilisation, which is <= 1 by construction, next to the algorithmic rate, which may exceed the matrix peak).
   const double c_real = d->c_real > 0 ? d->c_real : d->C;
-  const double direct = 2.0 * 9.0 * (double)d->N * d->H * d->W * c_real * d->Cout, executed = 2.0 * 16.0 * (double)n_tiles * c_real * d->Cout;
+  const double direct = 2.0 * 9.0 * (double)d->N * d->H * d->W * c_real * d->Cout, executed = 2.0 * 16.0 * (double)p.n_tiles * c_real * d->Cout;
   g_wino_direct += direct;
   g_wino_executed += executed;
   ProfScope prof("conv3x3_wino_f32<64t,64c>", direct, 4.0 * ((double)d->N * d->H * d->W * (d->C + d->Cout) + 16.0 * d->C * d->Cout), s, executed, 157.3);
-  hipLaunchKernelGGL(conv3x3_wino_f32, dim3((unsigned)n_wg), dim3(256), WINO_LDS_BYTES, s, p);
+  hipLaunchKernelGGL(conv3x3_wino_f32, dim3((unsigned)p.n_units), dim3(256), WINO_LDS_BYTES, s, p);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }

@@ -583,30 +583,24 @@ using namespace mp;
 
 extern "C" size_t mp_conv_wino_bf16_packed_bytes(int Cin_p, int Cout) { return (size_t)(Cout / WCOUT) * (Cin_p / WCK) * UB_STEP_BYTES; }
 
-// U = G g G^T per (cout, cin) in double, rounded once to fp32, split into three bf16 pieces, in MFMA fragment order:
+// U (wino_transform_weights: in double, rounded once to fp32) split into three bf16 pieces, in MFMA fragment order:
 // packed[cb][step][f][j][piece][lane][e] = piece of U_f[cin = step*16 + (lane >> 5)*8 + e][cout = cb*64 + j*32 + (lane & 31)]
 extern "C" int mp_conv_wino_bf16_pack_weights(const float* w, int Cout, int Cin, int Cin_p, const float* scale, void* packed_bytes) {
   MP_REQUIRE(w && packed_bytes && Cin_p >= Cin && Cin_p % WCK == 0 && Cout % WCOUT == 0,
              "mp_conv_wino_bf16_pack_weights: bad arguments (Cin_p %% 16, Cout %% 64)");
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
   const int n_steps = Cin_p / WCK;
   unsigned short* out = (unsigned short*)packed_bytes;
   memset(out, 0, mp_conv_wino_bf16_packed_bytes(Cin_p, Cout));
   for (int n = 0; n < Cout; ++n) {
-    const double s = scale ? (double)scale[n] : 1.0;
     const int cb = n / WCOUT, j = (n % WCOUT) / 32, nl = n % 32;
     for (int c = 0; c < Cin; ++c) {
-      const float* g = w + ((size_t)n * Cin + c) * 9;
-      double t[4][3], U[4][4];
-      for (int a = 0; a < 4; ++a)
-        for (int k = 0; k < 3; ++k) t[a][k] = G[a][0] * g[0 * 3 + k] * s + G[a][1] * g[1 * 3 + k] * s + G[a][2] * g[2 * 3 + k] * s;
-      for (int a = 0; a < 4; ++a)
-        for (int b = 0; b < 4; ++b) U[a][b] = t[a][0] * G[b][0] + t[a][1] * G[b][1] + t[a][2] * G[b][2];
+      float U[16];
+      wino_transform_weights(w + ((size_t)n * Cin + c) * 9, scale ? (double)scale[n] : 1.0, U);
       const int st = c / WCK, kh = (c % WCK) / 8, e = c % 8;
       const int lane = kh * 32 + nl;
       for (int f = 0; f < 16; ++f) {
         unsigned short pc[3];
-        bf16x9_split3((float)U[f / 4][f % 4], pc);
+        bf16x9_split3(U[f], pc);
         for (int piece = 0; piece < 3; ++piece)
           out[(((((size_t)(cb * n_steps + st) * 16 + f) * 2 + j) * 3 + piece) * 64 + lane) * 8 + e] = pc[piece];
       }
@@ -665,31 +659,11 @@ extern "C" int mp_conv_wino_bf16_clock(double* shader_mhz, double* cycles_per_st
 }
 
 extern "C" int mp_conv3x3_wino_bf16_nhwc(const mp_conv_desc* d, const void* d_u_pieces, mp_stream stream) {
-  MP_REQUIRE(d && d->d_x && d_u_pieces && (d->d_y || d->d_y_act), "mp_conv3x3_wino_bf16_nhwc: null pointer");
-  MP_REQUIRE(d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1, "mp_conv3x3_wino_bf16_nhwc: 3x3 / stride 1 / pad 1 only");
-  MP_REQUIRE(d->C % WCK == 0 && d->Cout % WCOUT == 0 && d->in_border >= 1, "mp_conv3x3_wino_bf16_nhwc: C %% 16, Cout %% 64, in_border >= 1");
-  MP_REQUIRE(!d->d_y_act || (d->d_act_scale && d->d_act_shift), "mp_conv3x3_wino_bf16_nhwc: y_act needs scale/shift");
+  MP_REQUIRE(d_u_pieces, "mp_conv3x3_wino_bf16_nhwc: null pointer");
   WinoParams p;
-  p.x = d->d_x; p.u = (const float*)d_u_pieces; p.bias = d->d_bias; p.residual = d->d_residual; p.act_scale = d->d_act_scale; p.act_shift = d->d_act_shift;
-  p.y = d->d_y; p.y_act = d->d_y_act;
-  p.N = d->N; p.Ho = d->H; p.Wo = d->W;
-  p.Hp = d->H + 2 * d->in_border; p.Wp = d->W + 2 * d->in_border; p.C = d->C;
-  p.in_off = d->in_border - 1;
-  p.Cout = d->Cout;
-  p.Hop = d->H + 2 * d->out_border; p.Wop = d->W + 2 * d->out_border; p.out_border = d->out_border;
-  p.tiles_x = (d->W + 1) / 2; p.tiles_y = (d->H + 1) / 2;
-  const long n_tiles = (long)d->N * p.tiles_x * p.tiles_y;
-  const long in_bytes = ((long)d->N * p.Hp + 2) * p.Wp * p.C * 4, out_elems = (long)d->N * p.Hop * p.Wop * d->Cout;
-  MP_REQUIRE(n_tiles < (1L << 30) && in_bytes < (1L << 31) && out_elems < (1L << 29), "mp_conv3x3_wino_bf16_nhwc: tensor too large for 32-bit offsets");
-  p.out_bytes = (int)(out_elems * 4);
-  p.n_tiles = (int)n_tiles;
-  p.n_chunks = d->C / 8;
-  p.n_steps = d->C / WCK;
-  wino_fastdiv_make((unsigned)p.tiles_x, &p.mg_tx, &p.sh_tx);
-  wino_fastdiv_make((unsigned)p.tiles_y, &p.mg_ty, &p.sh_ty);
-  p.relu = d->relu;
-  p.n_cblocks = d->Cout / WCOUT;
-  wino_fastdiv_make((unsigned)p.n_cblocks, &p.mg_cb, &p.sh_cb);
+  int rc = wino_make_params(d, &p, "mp_conv3x3_wino_bf16_nhwc");
+  if (rc) return rc;
+  p.u = (const float*)d_u_pieces;
   int dev = 0;
   MP_CHECK_HIP(hipGetDevice(&dev));
   static int attr_dev = -1;
@@ -704,11 +678,11 @@ extern "C" int mp_conv3x3_wino_bf16_nhwc(const mp_conv_desc* d, const void* d_u_
 #undef WB_ATTR
     attr_dev = dev;
   }
-  const long n_wg = ((n_tiles + WT - 1) / WT) * p.n_cblocks;
+  const int n_wg = p.n_units;
   hipStream_t s = (hipStream_t)stream;
   const double c_real = d->c_real > 0 ? d->c_real : d->C;
   const double direct = 2.0 * 9.0 * (double)d->N * d->H * d->W * c_real * d->Cout;
-  const double executed = 9.0 * 2.0 * 16.0 * (double)n_tiles * c_real * d->Cout;   // bf16 FLOPs: nine piece products per Winograd multiplication
+  const double executed = 9.0 * 2.0 * 16.0 * (double)p.n_tiles * c_real * d->Cout;   // bf16 FLOPs: nine piece products per Winograd multiplication
   {
     std::lock_guard<std::mutex> lock(g_wb_mu);
     g_wb_direct += direct;
@@ -719,9 +693,7 @@ extern "C" int mp_conv3x3_wino_bf16_nhwc(const mp_conv_desc* d, const void* d_u_
   const dim3 grid((unsigned)n_wg), block(256);
   // persistent form (default since round 6, MP_WINO_PERSIST=0 = one workgroup per unit): one workgroup per CU walks the units
   static const int persist_env = getenv("MP_WINO_PERSIST") ? atoi(getenv("MP_WINO_PERSIST")) : 1;
-  static int n_cu = 0;
-  if (!n_cu) { hipDeviceProp_t prop; MP_CHECK_HIP(hipGetDeviceProperties(&prop, dev)); n_cu = prop.multiProcessorCount; }
-  p.n_units = (int)n_wg;
+  const int n_cu = device_cu_count();
   bool launched = false;
 #ifdef MP_CONV_EXPERIMENTS
   const int diag = getenv("MP_WINO_DIAG") ? atoi(getenv("MP_WINO_DIAG")) : 0;

@@ -21,11 +21,10 @@
 // None of this is on the pose hot path (one call per frame set); it is bounded by the ResNet-50 convolutions (MFMA).
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "conv_layer.h"
 
 namespace mp {
 
@@ -457,18 +456,10 @@ __global__ __launch_bounds__(256) void det_mask_paste_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------------------------
 // host side: weights
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct DetConv {
-  int Cin = 0, Cin_p = 0, Cout = 0, K = 1, stride = 1, pad = 0;   // Cout = channels the kernel writes (padded heads included)
-  float* d_w = nullptr;
-  float* d_b = nullptr;
-};
-
 struct Bottleneck {
-  DetConv c1, c2, c3, down;
+  ConvLayer c1, c2, c3, down;
   bool has_down = false;
 };
-
-typedef std::map<std::string, std::pair<const float*, int64_t>> DetState;
 
 struct SpecEntry {
   std::string name;
@@ -569,10 +560,10 @@ struct DetPlan {
 struct mp_detector {
   mp_detector_config cfg;
   int C, Cpred_s, Cmask_s;   // classes; padded row strides of the predictor / mask-logit outputs
-  DetConv stem;
+  ConvLayer stem;
   std::vector<Bottleneck> blocks;
   std::vector<int> stage_of_block;
-  DetConv fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred, mask_fcn[4], mask_deconv, mask_logits;
+  ConvLayer fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred, mask_fcn[4], mask_deconv, mask_logits;
   float base_anchors[DET_LEVELS][DET_A][4];
   std::vector<void*> allocs;
   // last forward (debug taps)
@@ -587,84 +578,24 @@ constexpr size_t DET_SPLITK_FLOATS = 16u << 20;
 
 inline size_t tensor_floats(int N, int H, int W, int C, int b) { return (size_t)N * (H + 2 * b) * (W + 2 * b) * C + (size_t)(W + 2 * b) * C + 64; }
 
-int det_upload(mp_detector* d, const std::vector<float>& h, float** p) {
-  MP_CHECK_HIP(hipMalloc(p, h.size() * sizeof(float)));
-  MP_CHECK_HIP(hipMemcpy(*p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-  d->allocs.push_back(*p);
-  return MP_OK;
+const char* const WHO = "mp_detector_create";
+
+// OIHW weights (+ optional FrozenBatchNorm `bn`, + optional bias) -> the layer in its fp32 form; cout_pad > Cout appends zero output channels
+int det_make_conv(mp_detector* d, const StateMap& sm, const float* w_oihw, int Cout, int Cin, int K, int stride, int pad, const std::string& bn,
+                  const float* bias, int cout_pad, ConvLayer* L) {
+  return make_conv_layer(d->allocs, sm, WHO, w_oihw, bn, bias, cout_pad, Cin, (Cin + 3) / 4 * 4, Cout, K, stride, pad, 0u, L);
 }
 
-const float* det_find(const DetState& sm, const std::string& k, int64_t numel) {
-  auto it = sm.find(k);
-  if (it == sm.end()) {
-    set_error("mp_detector_create: missing state_dict key '%s'", k.c_str());
-    return nullptr;
-  }
-  if (it->second.second != numel) {
-    set_error("mp_detector_create: key '%s' has %ld elements, expected %ld", k.c_str(), (long)it->second.second, (long)numel);
-    return nullptr;
-  }
-  return it->second.first;
-}
-
-// OIHW weights (+ optional FrozenBatchNorm `bn`, + optional bias key) -> packed conv; cout_pad > Cout appends zero output channels
-int det_make_conv(mp_detector* d, const DetState& sm, const std::vector<float>& w_oihw, int Cout, int Cin, int K, int stride, int pad,
-                  const std::string& bn, const float* bias, int cout_pad, DetConv* L) {
-  const int Co = std::max(Cout, cout_pad);
-  L->Cin = Cin; L->Cin_p = (Cin + 3) / 4 * 4; L->Cout = Co; L->K = K; L->stride = stride; L->pad = pad;
-  std::vector<float> scale, shift(Co, 0.f);
-  bool has_shift = false;
-  if (!bn.empty()) {
-    const float* g = det_find(sm, bn + ".weight", Cout);
-    const float* b = det_find(sm, bn + ".bias", Cout);
-    const float* m = det_find(sm, bn + ".running_mean", Cout);
-    const float* v = det_find(sm, bn + ".running_var", Cout);
-    if (!g || !b || !m || !v) return MP_ERR_INVALID;
-    scale.assign(Co, 0.f);
-    for (int c = 0; c < Cout; ++c) {   // FrozenBatchNorm2d: eps = 1e-5 (ops/misc.py)
-      const float s = g[c] / sqrtf(v[c] + 1e-5f);
-      scale[c] = s;
-      shift[c] = b[c] - m[c] * s;
-    }
-    has_shift = true;
-  }
-  if (bias) {
-    for (int c = 0; c < Cout; ++c) shift[c] += bias[c];
-    has_shift = true;
-  }
-  std::vector<float> w(w_oihw);
-  w.resize((size_t)Co * Cin * K * K, 0.f);
-  std::vector<float> packed(mp_conv_packed_floats(L->Cin_p, Co, K, K));
-  int rc = mp_conv_pack_weights(w.data(), Co, Cin, K, K, L->Cin_p, scale.empty() ? nullptr : scale.data(), packed.data());
-  if (rc) return rc;
-  rc = det_upload(d, packed, &L->d_w);
-  if (rc) return rc;
-  if (has_shift) rc = det_upload(d, shift, &L->d_b);
-  return rc;
-}
-
-int det_conv_from_key(mp_detector* d, const DetState& sm, const std::string& wkey, int Cout, int Cin, int K, int stride, int pad,
-                      const std::string& bn, const std::string& bias_key, DetConv* L) {
-  const float* w = det_find(sm, wkey, (int64_t)Cout * Cin * K * K);
+int det_conv_from_key(mp_detector* d, const StateMap& sm, const std::string& wkey, int Cout, int Cin, int K, int stride, int pad,
+                      const std::string& bn, const std::string& bias_key, ConvLayer* L) {
+  const float* w = find(sm, wkey, (int64_t)Cout * Cin * K * K, WHO);
   if (!w) return MP_ERR_INVALID;
   const float* b = nullptr;
   if (!bias_key.empty()) {
-    b = det_find(sm, bias_key, Cout);
+    b = find(sm, bias_key, Cout, WHO);
     if (!b) return MP_ERR_INVALID;
   }
-  return det_make_conv(d, sm, std::vector<float>(w, w + (size_t)Cout * Cin * K * K), Cout, Cin, K, stride, pad, bn, b, 0, L);
-}
-
-int det_run_conv(const DetConv& L, const float* x, int N, int H, int W, int in_border, float* y, int out_border, const float* res, int relu,
-                 hipStream_t s, float* sk) {
-  mp_conv_desc c;
-  memset(&c, 0, sizeof(c));
-  c.d_x = x; c.N = N; c.H = H; c.W = W; c.C = L.Cin_p; c.c_real = L.Cin; c.in_border = in_border;
-  c.d_w = L.d_w; c.d_bias = L.d_b; c.Cout = L.Cout; c.KH = L.K; c.KW = L.K; c.stride = L.stride; c.pad = L.pad;
-  c.d_y = y; c.out_border = out_border; c.d_residual = res; c.relu = relu;
-  c.d_splitk_ws = sk;
-  c.splitk_ws_floats = sk ? (int64_t)DET_SPLITK_FLOATS : 0;
-  return mp_conv2d_nhwc(&c, s);
+  return det_make_conv(d, sm, w, Cout, Cin, K, stride, pad, bn, b, 0, L);
 }
 
 int det_make_plan(const mp_detector* d, int n, int H, int W, DetPlan* p) {
@@ -800,7 +731,7 @@ extern "C" int mp_detector_create(const mp_detector_config* cfg, const mp_named_
                  cfg->rpn_post_nms_top_n <= DET_MAX_SEG && cfg->box_detections_per_img >= 1 && cfg->box_detections_per_img <= DET_MAX_SEG,
              "mp_detector_create: top-n sizes must lie in [1, %d]", DET_MAX_SEG);
   for (int k = 0; k < 3; ++k) MP_REQUIRE(cfg->image_std[k] > 0.f && cfg->aspect_ratios[k] > 0.f, "mp_detector_create: bad std / aspect ratio");
-  DetState sm;
+  StateMap sm;
   for (int i = 0; i < n_tensors; ++i) sm[st[i].name] = std::make_pair(st[i].h_data, st[i].numel);
   mp_detector* d = new mp_detector();
   d->cfg = *cfg;
@@ -835,49 +766,49 @@ extern "C" int mp_detector_create(const mp_detector_config* cfg, const mp_named_
   }
   DET_TRY(det_conv_from_key(d, sm, "rpn.head.conv.weight", 256, 256, 3, 1, 1, "", "rpn.head.conv.bias", &d->rpn_conv));
   {  // cls_logits (A) + bbox_pred (4A) as ONE 1x1 convolution with 16 output channels
-    const float* wc = det_find(sm, "rpn.head.cls_logits.weight", DET_A * 256);
-    const float* bc = det_find(sm, "rpn.head.cls_logits.bias", DET_A);
-    const float* wb = det_find(sm, "rpn.head.bbox_pred.weight", 4 * DET_A * 256);
-    const float* bb = det_find(sm, "rpn.head.bbox_pred.bias", 4 * DET_A);
+    const float* wc = find(sm, "rpn.head.cls_logits.weight", DET_A * 256, WHO);
+    const float* bc = find(sm, "rpn.head.cls_logits.bias", DET_A, WHO);
+    const float* wb = find(sm, "rpn.head.bbox_pred.weight", 4 * DET_A * 256, WHO);
+    const float* bb = find(sm, "rpn.head.bbox_pred.bias", 4 * DET_A, WHO);
     if (!wc || !bc || !wb || !bb) { mp_detector_destroy(d); return MP_ERR_INVALID; }
     std::vector<float> w(16 * 256, 0.f), b(16, 0.f);
     memcpy(w.data(), wc, sizeof(float) * DET_A * 256);
     memcpy(w.data() + DET_A * 256, wb, sizeof(float) * 4 * DET_A * 256);
     memcpy(b.data(), bc, sizeof(float) * DET_A);
     memcpy(b.data() + DET_A, bb, sizeof(float) * 4 * DET_A);
-    DET_TRY(det_make_conv(d, sm, w, 16, 256, 1, 1, 0, "", b.data(), 16, &d->rpn_head));
+    DET_TRY(det_make_conv(d, sm, w.data(), 16, 256, 1, 1, 0, "", b.data(), 16, &d->rpn_head));
   }
   {  // fc6: torchvision flattens [R, 256, 7, 7] channel-major; the RoIAlign output here is [R, 7, 7, 256]
-    const float* w6 = det_find(sm, "roi_heads.box_head.fc6.weight", (int64_t)1024 * 12544);
-    const float* b6 = det_find(sm, "roi_heads.box_head.fc6.bias", 1024);
+    const float* w6 = find(sm, "roi_heads.box_head.fc6.weight", (int64_t)1024 * 12544, WHO);
+    const float* b6 = find(sm, "roi_heads.box_head.fc6.bias", 1024, WHO);
     if (!w6 || !b6) { mp_detector_destroy(d); return MP_ERR_INVALID; }
     std::vector<float> w((size_t)1024 * 12544);
     for (int o = 0; o < 1024; ++o)
       for (int c = 0; c < 256; ++c)
         for (int q = 0; q < 49; ++q) w[(size_t)o * 12544 + (size_t)q * 256 + c] = w6[(size_t)o * 12544 + (size_t)c * 49 + q];
-    DET_TRY(det_make_conv(d, sm, w, 1024, 12544, 1, 1, 0, "", b6, 0, &d->fc6));
+    DET_TRY(det_make_conv(d, sm, w.data(), 1024, 12544, 1, 1, 0, "", b6, 0, &d->fc6));
   }
   DET_TRY(det_conv_from_key(d, sm, "roi_heads.box_head.fc7.weight", 1024, 1024, 1, 1, 0, "", "roi_heads.box_head.fc7.bias", &d->fc7));
   {  // cls_score (C) + bbox_pred (4C) as one layer
-    const float* wc = det_find(sm, "roi_heads.box_predictor.cls_score.weight", (int64_t)C * 1024);
-    const float* bc = det_find(sm, "roi_heads.box_predictor.cls_score.bias", C);
-    const float* wb = det_find(sm, "roi_heads.box_predictor.bbox_pred.weight", (int64_t)4 * C * 1024);
-    const float* bb = det_find(sm, "roi_heads.box_predictor.bbox_pred.bias", 4 * C);
+    const float* wc = find(sm, "roi_heads.box_predictor.cls_score.weight", (int64_t)C * 1024, WHO);
+    const float* bc = find(sm, "roi_heads.box_predictor.cls_score.bias", C, WHO);
+    const float* wb = find(sm, "roi_heads.box_predictor.bbox_pred.weight", (int64_t)4 * C * 1024, WHO);
+    const float* bb = find(sm, "roi_heads.box_predictor.bbox_pred.bias", 4 * C, WHO);
     if (!wc || !bc || !wb || !bb) { mp_detector_destroy(d); return MP_ERR_INVALID; }
     std::vector<float> w((size_t)d->Cpred_s * 1024, 0.f), b(d->Cpred_s, 0.f);
     memcpy(w.data(), wc, sizeof(float) * C * 1024);
     memcpy(w.data() + (size_t)C * 1024, wb, sizeof(float) * 4 * C * 1024);
     memcpy(b.data(), bc, sizeof(float) * C);
     memcpy(b.data() + C, bb, sizeof(float) * 4 * C);
-    DET_TRY(det_make_conv(d, sm, w, d->Cpred_s, 1024, 1, 1, 0, "", b.data(), d->Cpred_s, &d->pred));
+    DET_TRY(det_make_conv(d, sm, w.data(), d->Cpred_s, 1024, 1, 1, 0, "", b.data(), d->Cpred_s, &d->pred));
   }
   for (int i = 0; i < 4; ++i) {
     const std::string k = "roi_heads.mask_head.mask_fcn" + std::to_string(i + 1);
     DET_TRY(det_conv_from_key(d, sm, k + ".weight", 256, 256, 3, 1, 1, "", k + ".bias", &d->mask_fcn[i]));
   }
   {  // ConvTranspose2d(256, 256, 2, 2): out[o, 2y+a, 2x+b] = sum_i in[i, y, x] W[i, o, a, b] + bias[o]  ->  1x1 conv onto (a, b, o)
-    const float* wt = det_find(sm, "roi_heads.mask_predictor.conv5_mask.weight", 256 * 256 * 4);
-    const float* bt = det_find(sm, "roi_heads.mask_predictor.conv5_mask.bias", 256);
+    const float* wt = find(sm, "roi_heads.mask_predictor.conv5_mask.weight", 256 * 256 * 4, WHO);
+    const float* bt = find(sm, "roi_heads.mask_predictor.conv5_mask.bias", 256, WHO);
     if (!wt || !bt) { mp_detector_destroy(d); return MP_ERR_INVALID; }
     std::vector<float> w((size_t)1024 * 256), b(1024);
     for (int ab = 0; ab < 4; ++ab)
@@ -885,15 +816,15 @@ extern "C" int mp_detector_create(const mp_detector_config* cfg, const mp_named_
         b[ab * 256 + o] = bt[o];
         for (int i = 0; i < 256; ++i) w[((size_t)ab * 256 + o) * 256 + i] = wt[((size_t)i * 256 + o) * 4 + ab];
       }
-    DET_TRY(det_make_conv(d, sm, w, 1024, 256, 1, 1, 0, "", b.data(), 0, &d->mask_deconv));
+    DET_TRY(det_make_conv(d, sm, w.data(), 1024, 256, 1, 1, 0, "", b.data(), 0, &d->mask_deconv));
   }
   {
-    const float* wl = det_find(sm, "roi_heads.mask_predictor.mask_fcn_logits.weight", (int64_t)C * 256);
-    const float* bl = det_find(sm, "roi_heads.mask_predictor.mask_fcn_logits.bias", C);
+    const float* wl = find(sm, "roi_heads.mask_predictor.mask_fcn_logits.weight", (int64_t)C * 256, WHO);
+    const float* bl = find(sm, "roi_heads.mask_predictor.mask_fcn_logits.bias", C, WHO);
     if (!wl || !bl) { mp_detector_destroy(d); return MP_ERR_INVALID; }
     std::vector<float> b(d->Cmask_s, 0.f);
     memcpy(b.data(), bl, sizeof(float) * C);
-    DET_TRY(det_make_conv(d, sm, std::vector<float>(wl, wl + (size_t)C * 256), C, 256, 1, 1, 0, "", b.data(), d->Cmask_s, &d->mask_logits));
+    DET_TRY(det_make_conv(d, sm, wl, C, 256, 1, 1, 0, "", b.data(), d->Cmask_s, &d->mask_logits));
   }
 #undef DET_TRY
   // anchor_utils.py generate_anchors: h_ratios = sqrt(ar), w_ratios = 1 / h_ratios, base = round([-w, -h, w, h] / 2) (float32, half to even)
@@ -950,7 +881,7 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
                        cfg.image_mean[0], cfg.image_mean[1], cfg.image_mean[2], cfg.image_std[0], cfg.image_std[1], cfg.image_std[2], F("x0"),
                        p.Hp, p.Wp, 3);
   }
-  rc = det_run_conv(d->stem, F("x0"), n, p.Hp, p.Wp, 3, F("stem"), 1, nullptr, 1, s, SK);
+  rc = run_conv_layer(d->stem, F("x0"), n, p.Hp, p.Wp, 3, F("stem"), 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
   rc = mp_maxpool3x3s2(F("stem"), n, p.Hp / 2, p.Wp / 2, 64, 1, F("pool"), 1, nullptr, nullptr, nullptr, s);
   if (rc) return rc;
@@ -963,26 +894,26 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
     const std::string S = "s" + std::to_string(st);
     const int oh = p.fh[st], ow = p.fw[st];
     float* t1 = b.has_down ? F(S + ".t1in") : F(S + ".t1");
-    rc = det_run_conv(b.c1, x, n, xh, xw, 1, t1, 1, nullptr, 1, s, SK);
+    rc = run_conv_layer(b.c1, x, n, xh, xw, 1, t1, 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
-    rc = det_run_conv(b.c2, t1, n, xh, xw, 1, F(S + ".t2"), 1, nullptr, 1, s, SK);
+    rc = run_conv_layer(b.c2, t1, n, xh, xw, 1, F(S + ".t2"), 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
     const float* idn = x;
     if (b.has_down) {
-      rc = det_run_conv(b.down, x, n, xh, xw, 1, F(S + ".d"), 1, nullptr, 0, s, SK);
+      rc = run_conv_layer(b.down, x, n, xh, xw, 1, F(S + ".d"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
       if (rc) return rc;
       idn = F(S + ".d");
     }
     float* y = (x == F(S + ".xa")) ? F(S + ".xb") : F(S + ".xa");
-    rc = det_run_conv(b.c3, F(S + ".t2"), n, oh, ow, 1, y, 1, idn, 1, s, SK);
+    rc = run_conv_layer(b.c3, F(S + ".t2"), n, oh, ow, 1, y, 1, idn, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
     x = y; xh = oh; xw = ow;
     stage_out[st] = y;
   }
   // FPN (ops/feature_pyramid_network.py): last_inner = inner[3](C5); P5 = layer[3](last_inner); going down: lateral + nearest upsample
-  rc = det_run_conv(d->fpn_inner[3], stage_out[3], n, p.fh[3], p.fw[3], 1, F("L3"), 1, nullptr, 0, s, SK);
+  rc = run_conv_layer(d->fpn_inner[3], stage_out[3], n, p.fh[3], p.fw[3], 1, F("L3"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
-  rc = det_run_conv(d->fpn_layer[3], F("L3"), n, p.fh[3], p.fw[3], 1, F("P5"), 1, nullptr, 0, s, SK);
+  rc = run_conv_layer(d->fpn_layer[3], F("L3"), n, p.fh[3], p.fw[3], 1, F("P5"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
   for (int l = 2; l >= 0; --l) {
     const std::string sl = std::to_string(l), su = std::to_string(l + 1);
@@ -992,9 +923,9 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
       hipLaunchKernelGGL(det_resize_nearest_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("L" + su), p.fh[l + 1], p.fw[l + 1], F("U" + sl),
                          p.fh[l], p.fw[l], DET_FPN_C, n, 1, 1, 0, 0);
     }
-    rc = det_run_conv(d->fpn_inner[l], stage_out[l], n, p.fh[l], p.fw[l], 1, F("L" + sl), 1, F("U" + sl), 0, s, SK);
+    rc = run_conv_layer(d->fpn_inner[l], stage_out[l], n, p.fh[l], p.fw[l], 1, F("L" + sl), 1, F("U" + sl), 0, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
-    rc = det_run_conv(d->fpn_layer[l], F("L" + sl), n, p.fh[l], p.fw[l], 1, F("P" + std::to_string(l + 2)), 1, nullptr, 0, s, SK);
+    rc = run_conv_layer(d->fpn_layer[l], F("L" + sl), n, p.fh[l], p.fw[l], 1, F("P" + std::to_string(l + 2)), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
   }
   {  // LastLevelMaxPool: F.max_pool2d(P5, 1, 2, 0)
@@ -1008,9 +939,9 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
   L.off[0] = 0;
   for (int l = 0; l < DET_LEVELS; ++l) {
     const std::string sl = std::to_string(l);
-    rc = det_run_conv(d->rpn_conv, F("P" + std::to_string(l + 2)), n, p.fh[l], p.fw[l], 1, F("rpn_t" + sl), 0, nullptr, 1, s, SK);
+    rc = run_conv_layer(d->rpn_conv, F("P" + std::to_string(l + 2)), n, p.fh[l], p.fw[l], 1, F("rpn_t" + sl), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
-    rc = det_run_conv(d->rpn_head, F("rpn_t" + sl), n, p.fh[l], p.fw[l], 0, F("rpn_h" + sl), 0, nullptr, 0, s, SK);
+    rc = run_conv_layer(d->rpn_head, F("rpn_t" + sl), n, p.fh[l], p.fw[l], 0, F("rpn_h" + sl), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
     L.head[l] = F("rpn_h" + sl);
     L.gh[l] = p.fh[l]; L.gw[l] = p.fw[l];
@@ -1058,11 +989,11 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
     hipLaunchKernelGGL(det_roi_align_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, py, reinterpret_cast<const float4*>(F("proposals")),
                        I("proposal_counts"), R, n, 7, 0, F("roi7"));
   }
-  rc = det_run_conv(d->fc6, F("roi7"), n * R, 1, 1, 0, F("fc6"), 0, nullptr, 1, s, SK);
+  rc = run_conv_layer(d->fc6, F("roi7"), n * R, 1, 1, 0, F("fc6"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
-  rc = det_run_conv(d->fc7, F("fc6"), n * R, 1, 1, 0, F("fc7"), 0, nullptr, 1, s, SK);
+  rc = run_conv_layer(d->fc7, F("fc6"), n * R, 1, 1, 0, F("fc7"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
-  rc = det_run_conv(d->pred, F("fc7"), n * R, 1, 1, 0, F("class_logits"), 0, nullptr, 0, s, SK);
+  rc = run_conv_layer(d->pred, F("fc7"), n * R, 1, 1, 0, F("class_logits"), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
   if (rc) return rc;
   hipLaunchKernelGGL(det_box_post_kernel, dim3(ceil_div((long)n * R, 256)), dim3(256), 0, s, F("class_logits"), d->Cpred_s, C,
                      reinterpret_cast<const float4*>(F("proposals")), I("proposal_counts"), R, n, (float)p.hr, (float)p.wr, cfg.box_score_thresh,
@@ -1097,13 +1028,13 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
     const float* mx = F("roi14");
     for (int i = 0; i < 4; ++i) {
       float* my = (i & 1) ? F("m_b") : F("m_a");
-      rc = det_run_conv(d->mask_fcn[i], mx, n * D, 14, 14, 1, my, 1, nullptr, 1, s, SK);
+      rc = run_conv_layer(d->mask_fcn[i], mx, n * D, 14, 14, 1, my, 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
       if (rc) return rc;
       mx = my;
     }
-    rc = det_run_conv(d->mask_deconv, mx, n * D, 14, 14, 1, F("m_up"), 0, nullptr, 1, s, SK);
+    rc = run_conv_layer(d->mask_deconv, mx, n * D, 14, 14, 1, F("m_up"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
-    rc = det_run_conv(d->mask_logits, F("m_up"), n * D * 196 * 4, 1, 1, 0, F("mask_logits"), 0, nullptr, 0, s, SK);
+    rc = run_conv_layer(d->mask_logits, F("m_up"), n * D * 196 * 4, 1, 1, 0, F("mask_logits"), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
     ProfScope prof("det_mask_paste", 0.0, (double)n * D * H * W * 4.0, s);
     hipLaunchKernelGGL(det_mask_paste_kernel, dim3(ceil_div((long)H * W, 256), n * D), dim3(256), 0, s, F("mask_logits"), d->Cmask_s,

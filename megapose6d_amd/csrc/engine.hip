@@ -1,4 +1,5 @@
 // engine.hip -- library-wide state of libmp_engine.so: error string, version, device probe.
+#include <atomic>
 #include <map>
 #include <string>
 #include <vector>
@@ -13,6 +14,23 @@ void set_error(const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
 }
+
+// one attribute of the current device, asked on the first call per device (0 = not asked yet; a race only asks twice)
+constexpr int MAX_DEVICES = 64;
+static std::atomic<int> g_n_cu[MAX_DEVICES], g_lds_bytes[MAX_DEVICES];
+static int cached_attribute(std::atomic<int>* cache, hipDeviceAttribute_t attr, int fallback) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool keep = dev >= 0 && dev < MAX_DEVICES;
+  int v = keep ? cache[dev].load(std::memory_order_relaxed) : 0;
+  if (v == 0) {
+    if (hipDeviceGetAttribute(&v, attr, dev) != hipSuccess || v <= 0) v = fallback;
+    if (keep) cache[dev].store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+int device_cu_count() { return cached_attribute(g_n_cu, hipDeviceAttributeMultiprocessorCount, 256); }
+int device_lds_bytes() { return cached_attribute(g_lds_bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, -1); }
 }  // namespace mp
 
 namespace mp {
@@ -121,9 +139,6 @@ __global__ __launch_bounds__(256) void clock_probe_kernel(float* sink, unsigned 
 extern "C" int mp_clock_probe(double ms_target, double* shader_mhz, double* mfma_tflops, mp_stream stream) {
   MP_REQUIRE(ms_target > 0.0 && ms_target <= 2000.0, "mp_clock_probe: ms_target out of range");
   hipStream_t s = (hipStream_t)stream;
-  int dev = 0, n_cu = 0;
-  MP_CHECK_HIP(hipGetDevice(&dev));
-  MP_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
   float* sink = nullptr;
   unsigned long long* clk = nullptr;
   MP_CHECK_HIP(hipMalloc(&sink, sizeof(float)));
@@ -133,7 +148,7 @@ extern "C" int mp_clock_probe(double ms_target, double* shader_mhz, double* mfma
   MP_CHECK_HIP(hipEventCreate(&e1));
   // 32 MFMAs of 64 cycles per iteration and wave, two waves per SIMD: 4096 cycles per iteration at full rate
   const int iters = (int)(ms_target * 1e-3 * 2.4e9 / 4096.0) + 1;
-  const int grid = 2 * n_cu;
+  const int grid = 2 * mp::device_cu_count();
   int rc = MP_OK;
   float ms = 0.f;
   unsigned long long h[2] = {0, 0};
@@ -163,7 +178,7 @@ extern "C" int mp_device_info(int* n_cus, int* lds_bytes, char* arch_name, int a
   MP_CHECK_HIP(hipGetDevice(&dev));
   hipDeviceProp_t prop;
   MP_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
-  if (n_cus) *n_cus = prop.multiProcessorCount;
+  if (n_cus) *n_cus = mp::device_cu_count();
   if (lds_bytes) *lds_bytes = (int)prop.sharedMemPerBlock;
   if (arch_name && arch_name_len > 0) {
     strncpy(arch_name, prop.gcnArchName, arch_name_len - 1);

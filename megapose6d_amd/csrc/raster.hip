@@ -930,12 +930,7 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
     });
   }
   if (compact) {   // the pairs no view reaches: background + crop, strided over the light list, four waves per SIMD
-    static int n_cu = 0;
-    if (n_cu == 0) {
-      int dev = 0;
-      MP_CHECK_HIP(hipGetDevice(&dev));
-      MP_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int n_cu = device_cu_count();
     const size_t lds_l = (size_t)TILE_WAVES * (((size_t)64 * run_lds * sizeof(float) + 15) & ~(size_t)15);
     const long long n_res = std::min<long long>((long long)n_cu * 8, std::max<long long>(1, ((long long)n_items * lay.n_tiles + TILE_WAVES - 1) / TILE_WAVES));
     ProfScope prof_l(f16 ? "raster_tiles_light/f16" : xrec ? "raster_tiles_light/xrec" : "raster_tiles_light", 0.0, 0.0, s);

@@ -36,6 +36,11 @@ struct WinoParams {
   int telemetry;        // != 0: every 64th workgroup adds its clock readings to the kernel's telemetry counters (mp_conv_wino_bf16_telemetry)
 };
 
+// mp_conv_desc -> WinoParams (argument checks, the 32-bit limits, every field but `u`; telemetry off); defined in conv_wino.hip
+int wino_make_params(const mp_conv_desc* d, WinoParams* p, const char* who);
+// the 16 values U[f] = (G g G^T)[f / 4][f % 4] * s of one (cout, cin) pair's 3x3 weights `g`; defined in conv_wino.hip
+void wino_transform_weights(const float* g, double s, float* U);
+
 __device__ __forceinline__ float4 buf4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));

@@ -410,3 +410,23 @@ def test_two_forwards_are_bit_identical():
         assert torch.equal(v, again[k]), k
     for w, v in run.tap.items():
         assert torch.equal(v, run.net.debug_tensor(w).cpu()), w
+
+
+def test_detector_convolutions_stay_on_the_fp32_kernel():
+    """every convolution of a detector forward runs on the fp32-MFMA direct kernel: the detector's layers are packed in that form only,
+    so no Winograd launch is counted and every convolution row of the profiler is conv_nhwc_f32_mfma (conv_splitk_reduce is the second
+    pass of that kernel's split-K launches)"""
+    from megapose6d_amd import engine as eng
+
+    run = _run("batch2")
+    eng.conv_wino_stats(reset=True)
+    eng.conv_wino_bf16_stats(reset=True)
+    eng.profile_begin()
+    try:
+        run.net.forward(run.images.cuda())
+    finally:
+        prof = eng.profile_end()
+    assert eng.conv_wino_stats()[0] == 0.0 and eng.conv_wino_bf16_stats()[0] == 0.0
+    convs = [k for k in prof if k.startswith("conv") and k != "conv_splitk_reduce"]
+    assert convs and all(k.startswith("conv_nhwc_f32_mfma") for k in convs), sorted(prof)
+    assert sum(int(prof[k]["launches"]) for k in convs) >= 80, prof   # the forward has 80 convolution layers (53 ResNet-50, 8 FPN, 10 RPN, 3 box head, 6 mask head)
