@@ -208,6 +208,9 @@ int mp_raster_render_scene(const mp_mesh_db* db, int n_cams, const int32_t* h_ob
 /* Crop: replaces lib3d/cropping.py:113-144 crop_images (torchvision.ops.roi_align,       */
 /* sampling_ratio=4, aligned=False) incl. the RGBD validity rule (:131-142), reading the  */
 /* observation by batch_im_id (no per-row gather, pose_estimator.py:389).                 */
+/* C is 3 or 4; 0 <= b <= 65535 (one grid row per box; b = 0 launches nothing), anything  */
+/* else is MP_ERR_INVALID, nothing launched.  d_im_ids are NOT range-checked: every id    */
+/* must lie in [0, n_im) and every box must be finite.                                    */
 /* ------------------------------------------------------------------------------------ */
 int mp_crop_roi_align(const float* d_images /*[n_im,C,H,W] NCHW*/, int n_im, int C, int H, int W,
                       const int32_t* d_im_ids /*[b]*/, const float* d_boxes /*[b,4] x1,y1,x2,y2*/, int b,
