@@ -16,9 +16,8 @@ coarse logits are all-gathered (RCCL), every rank computes the same top-K, refin
 from __future__ import annotations
 
 import time
-from collections import defaultdict
 from pathlib import Path
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, List, Optional, Tuple
 
 import numpy as np
 import pandas as pd
@@ -73,6 +72,42 @@ class _Timer:
 
     def elapsed(self) -> float:
         return time.time() - self.t0
+
+
+class _StageClock(_Timer):
+    """Fences and wall clock of one stage (the "timing" block of PoseEstimator has the semantics)."""
+
+    def __init__(self, cuda_timer: bool):
+        self.cuda_timer = cuda_timer
+        if cuda_timer:
+            torch.cuda.synchronize()
+        super().__init__()
+
+    def stop(self, render_time: float, event_sets, timing_str: bool = True) -> dict:
+        """-> the stage's render_time / model_time / time (/ timing_str); `render_time` = the host enqueue time, reported without the timer"""
+        model_time = 0.0
+        if self.cuda_timer:
+            torch.cuda.synchronize()
+            render_time, model_time = PoseEstimator._sum_events(event_sets)
+        elapsed = self.elapsed()
+        times = {"render_time": render_time, "model_time": model_time, "time": elapsed}
+        if timing_str:
+            times["timing_str"] = f"time: {elapsed:.2f}, model_time: {model_time:.2f}, render_time: {render_time:.2f}"
+        return times
+
+
+# One refiner row of the stage's all-gather, per iteration: (name in the returned collection, floats, trailing shape)
+_REFINER_ROW = (("poses", 16, (4, 4)), ("poses_input", 16, (4, 4)), ("K_crop", 9, (3, 3)), ("boxes_rend", 4, (4,)), ("boxes_crop", 4, (4,)),
+                ("pose_out", 9, (9,)))
+_REFINER_ROW_WIDTH = sum(width for _, width, _ in _REFINER_ROW)
+assert _REFINER_ROW_WIDTH == 58
+
+
+def _refiner_row_fields(o) -> dict:
+    """the tensors of one PosePredictorOutput that go into its rows of `_REFINER_ROW`"""
+    pose_out = o.network_outputs["pose"] if "pose" in o.network_outputs else torch.zeros(o.TCO_output.shape[0], 9, device=o.TCO_output.device)
+    return {"poses": o.TCO_output, "poses_input": o.TCO_input, "K_crop": o.K_crop, "boxes_rend": o.boxes_rend, "boxes_crop": o.boxes_crop,
+            "pose_out": pose_out}
 
 
 class PoseEstimator(torch.nn.Module):
@@ -170,15 +205,54 @@ class PoseEstimator(torch.nn.Module):
             self._extents = eng.init_extents(self.mesh_db.points, self._SO3_grid)
         return self._extents
 
+    def _is_sharded(self) -> bool:
+        return self.distributed and mpdist.world_size() > 1
+
     def _shard(self, n: int) -> np.ndarray:
-        if self.distributed and mpdist.world_size() > 1:
-            return mpdist.shard_indices(n, mpdist.rank(), mpdist.world_size())
-        return np.arange(n)
+        return mpdist.shard_indices(n, mpdist.rank(), mpdist.world_size()) if self._is_sharded() else np.arange(n)
 
     def _gather(self, local: torch.Tensor, n: int) -> torch.Tensor:
-        if self.distributed and mpdist.world_size() > 1:
-            return mpdist.gather_rows(local, n, mpdist.rank(), mpdist.world_size())
-        return local
+        return mpdist.gather_rows(local, n, mpdist.rank(), mpdist.world_size()) if self._is_sharded() else local
+
+    def _run_chunks(self, n_rows: int, reference_bsz: int, run_chunk) -> Tuple[list, List[torch.cuda.Stream], int]:
+        """`run_chunk(rows slice, slot)` for every chunk of this rank's `n_rows` rows, chunk ci under stream ci % n_streams ->
+        (per-chunk results, streams, rows per chunk).  Call it after the stage's input tensors have been enqueued: the side
+        streams wait for them (`_plan`)."""
+        chunk, streams = self._plan(n_rows, reference_bsz)
+        results = []
+        for ci, s in enumerate(range(0, n_rows, chunk)):
+            slot = ci % len(streams)
+            with torch.cuda.stream(streams[slot]):
+                results.append(run_chunk(slice(s, min(s + chunk, n_rows)), slot))
+        return results, streams, chunk
+
+    def _row_tables(self, observation: ObservationTensor, infos: pd.DataFrame, poses: torch.Tensor):
+        """Index tables of a stage over pose rows -> (labels of this rank's rows, K_all [R,3,3], and K / poses / image ids of this
+        rank's rows).  The labels stay host copies: no D2H read-back inside the chunk loop."""
+        device = observation.images.device
+        labels_all = infos["label"].tolist()
+        rows_h = self._shard(len(labels_all))
+        im_all = torch.as_tensor(infos["batch_im_id"].values.astype(np.int32), device=device)
+        rows = torch.as_tensor(rows_h, device=device, dtype=torch.long)
+        poses = poses.to(device=device, dtype=torch.float32)
+        K_all = observation.K[im_all.long()].float()
+        return [labels_all[i] for i in rows_h], K_all, K_all[rows], poses[rows], im_all[rows]
+
+    def _coarse_pass(self, observation: ObservationTensor, labels: List[str], K_rows: torch.Tensor, poses_rows: torch.Tensor,
+                     im_rows: torch.Tensor, cuda_timer: bool, return_debug_data: bool):
+        """The coarse model over this rank's rows, in chunks -> (logits [rows,1], scores [rows,1], debug data (crops / renders
+        [rows,C,h,w], or empty), host render time, event sets, number of chunks).  An empty shard gives zero-row tensors."""
+        def run(sl: slice, slot: int):
+            return self.coarse_model.forward_coarse(images=observation.images, K=K_rows[sl], labels=labels[sl], TCO_input=poses_rows[sl],
+                                                    cuda_timer=cuda_timer, return_debug_data=return_debug_data, im_ids=im_rows[sl],
+                                                    slot=slot, defer_timing=True)
+        outs, streams, _ = self._run_chunks(len(labels), self.bsz_images, run)
+        keys = ("logits", "scores") + (("images_crop", "renders") if return_debug_data else ())
+        parts = {k: [o[k] for o in outs] for k in keys}
+        self._join(streams, [t for k in keys for t in parts[k]])
+        logits, scores = (torch.cat(parts[k]) if outs else torch.zeros(0, 1, device=K_rows.device) for k in keys[:2])
+        debug_data = {k: torch.cat(parts[k]) for k in keys[2:]}
+        return logits, scores, debug_data, sum((o["render_time"] for o in outs), 0.0), [o["events"] for o in outs], len(outs)
 
     # -- timing ---------------------------------------------------------------------------------------------------
     # Reference semantics (pose_estimator.py:274-275, 422-423; training/utils.py:224-264): `model_time` is a CUDA-event time that is
@@ -198,21 +272,15 @@ class PoseEstimator(torch.nn.Module):
             m += dm
         return r, m
 
-    def _is_sharded(self) -> bool:
-        return self.distributed and mpdist.world_size() > 1
-
     # -- coarse ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward_coarse_model(self, observation: ObservationTensor, detections: DetectionsType, cuda_timer: bool = False,
                              return_debug_data: bool = False) -> Tuple[PoseEstimatesType, dict]:
-        if cuda_timer:
-            torch.cuda.synchronize()
-        start = time.time()
+        clock = _StageClock(cuda_timer)
         assert_detections_valid(detections)
         if return_debug_data and self._is_sharded():
             raise NotImplementedError("return_debug_data with distributed=True: crops/renders are shard-local (rows rank::world); "
                                       "run the debug call on one rank with distributed=False")
-        coarse = self.coarse_model
         device = observation.images.device
         B, M = len(detections), self._SO3_grid.shape[0]
         df = detections.infos
@@ -233,133 +301,70 @@ class PoseEstimator(torch.nn.Module):
         K_rows = observation.K[im_of_row.long()].float()
         TCO_local = eng.init_poses_from_boxes(bboxes_all[det_of_row], K_rows, det_mesh[det_of_row], rot_of_row, self._SO3_grid,
                                               self._grid_extents())
-        logits_l, scores_l = [], []
-        crops, renders, event_sets = [], [], []
-        render_time = model_time = 0.0
-        chunk, streams = self._plan(rows_h.size, self.bsz_images)   # after the inputs above are enqueued: side streams wait for them
-        n_batches = 0
-        for ci, s in enumerate(range(0, rows_h.size, chunk)):
-            sl = slice(s, min(s + chunk, rows_h.size))
-            labels_ = [labels_det[i] for i in det_h[sl]]
-            slot = ci % len(streams)
-            with torch.cuda.stream(streams[slot]):
-                out_ = coarse.forward_coarse(images=observation.images, K=K_rows[sl], labels=labels_, TCO_input=TCO_local[sl],
-                                             cuda_timer=cuda_timer, return_debug_data=return_debug_data, im_ids=im_of_row[sl], slot=slot,
-                                             defer_timing=True)
-            render_time += out_["render_time"]
-            event_sets.append(out_["events"])
-            logits_l.append(out_["logits"])
-            scores_l.append(out_["scores"])
-            if return_debug_data:
-                crops.append(out_["images_crop"])
-                renders.append(out_["renders"])
-            n_batches += 1
-        self._join(streams, logits_l + scores_l + crops + renders)
-        packed = torch.cat([TCO_local.flatten(1), torch.cat(logits_l), torch.cat(scores_l)], dim=1)  # [rows, 18]
-        packed = self._gather(packed, n)
+        # after the inputs above are enqueued: side streams wait for them
+        logits, scores, debug_data, render_time, event_sets, n_batches = self._coarse_pass(
+            observation, [labels_det[i] for i in det_h], K_rows, TCO_local, im_of_row, cuda_timer, return_debug_data)
+        packed = self._gather(torch.cat([TCO_local.flatten(1), logits, scores], dim=1), n)  # [rows, 18]
         TCO = packed[:, :16].reshape(n, 4, 4).contiguous()
         logits = packed[:, 16].reshape(B, M)
         scores = packed[:, 17].reshape(B, M)
         bboxes = bboxes_all[torch.arange(n, device=device) // M]
-        debug_data = dict()
-        if return_debug_data:
-            ic, rr = torch.cat(crops), torch.cat(renders)
-            debug_data = {"images_crop": ic.reshape([B, M, -1, *ic.shape[-2:]]), "renders": rr.reshape([B, M, -1, *rr.shape[-2:]])}
+        debug_data = {k: v.reshape([B, M, -1, *v.shape[-2:]]) for k, v in debug_data.items()}
         host = torch.stack([logits.flatten(), scores.flatten()]).cpu().numpy()  # the stage's single D2H sync
         df_h["coarse_logit"] = host[0]
         df_h["coarse_score"] = host[1]
-        if cuda_timer:
-            torch.cuda.synchronize()
-            render_time, model_time = self._sum_events(event_sets)
-        elapsed = time.time() - start
-        timing_str = f"time: {elapsed:.2f}, model_time: {model_time:.2f}, render_time: {render_time:.2f}"
-        extra_data = {"render_time": render_time, "model_time": model_time, "time": elapsed, "logits": logits, "scores": scores,
-                      "TCO": TCO.reshape([B, M, 4, 4]), "debug": debug_data, "n_batches": n_batches, "timing_str": timing_str}
+        extra_data = {**clock.stop(render_time, event_sets), "logits": logits, "scores": scores, "TCO": TCO.reshape([B, M, 4, 4]),
+                      "debug": debug_data, "n_batches": n_batches}
         return PandasTensorCollection(df_h, poses=TCO, bboxes=bboxes), extra_data
 
     # -- refiner --------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward_refiner(self, observation: ObservationTensor, data_TCO_input: PoseEstimatesType, n_iterations: int = 5,
                         keep_all_outputs: bool = False, cuda_timer: bool = False, **refiner_kwargs) -> Tuple[dict, dict]:
-        if cuda_timer:
-            torch.cuda.synchronize()
-        start = time.time()
+        clock = _StageClock(cuda_timer)
         assert self.refiner_model is not None
         if keep_all_outputs and self._is_sharded():
             raise NotImplementedError("keep_all_outputs with distributed=True: the per-batch outputs are shard-local")
-        device = observation.images.device
         R = data_TCO_input.poses.shape[0]
-        rows_h = self._shard(R)
         df = data_TCO_input.infos.copy()  # the reference adds these two columns to its per-batch copies (:155-156)
-        labels_all = df["label"].tolist()
-        im_h = df["batch_im_id"].values.astype(np.int32)
-        im_all = torch.as_tensor(im_h, device=device)
-        rows = torch.as_tensor(rows_h, device=device, dtype=torch.long)
-        poses_in = data_TCO_input.poses.to(device=device, dtype=torch.float32)
-        K_all = observation.K[im_all.long()].float()
-        K_rows, poses_rows, im_rows = K_all[rows], poses_in[rows], im_all[rows]
-        chunk, streams = self._plan(rows_h.size, self.bsz_objects)   # after the inputs above are enqueued (side streams wait for them)
+        labels, K_all, K_rows, poses_rows, im_rows = self._row_tables(observation, df, data_TCO_input.poses)
+
+        def run(sl: slice, slot: int):
+            return self.refiner_model(images=observation.images, K=K_rows[sl], TCO=poses_rows[sl], n_iterations=n_iterations,
+                                      labels=labels[sl], im_ids=im_rows[sl], materialize=keep_all_outputs, slot=slot,
+                                      cuda_timer=cuda_timer, **refiner_kwargs)
+        # after the inputs above are enqueued (side streams wait for them)
+        chunk_outputs, streams, chunk = self._run_chunks(len(labels), self.bsz_objects, run)
         df["refiner_batch_idx"] = np.arange(R) // chunk
         df["refiner_instance_idx"] = np.arange(R) % chunk
-        keys = ("poses", "poses_input", "K_crop", "boxes_rend", "boxes_crop", "pose_out")
-        acc: Dict[int, Dict[str, list]] = {n: {k: [] for k in keys} for n in range(1, n_iterations + 1)}
-        all_outputs = []
-        event_sets = []
-        render_time = model_time = 0.0
-        produced = []
-        for ci, s in enumerate(range(0, rows_h.size, chunk)):
-            sl = slice(s, min(s + chunk, rows_h.size))
-            labels_ = [labels_all[i] for i in rows_h[sl]]
-            slot = ci % len(streams)
-            with torch.cuda.stream(streams[slot]):
-                outputs_ = self.refiner_model(images=observation.images, K=K_rows[sl], TCO=poses_rows[sl], n_iterations=n_iterations,
-                                              labels=labels_, im_ids=im_rows[sl], materialize=keep_all_outputs, slot=slot,
-                                              cuda_timer=cuda_timer, **refiner_kwargs)
-            for o in outputs_.values():
-                produced += [o.TCO_output, o.TCO_input, o.KV_crop, o.boxes_rend, o.boxes_crop, o.renders, o.images_crop]
-                produced += list(o.network_outputs.values())
-            if keep_all_outputs:
-                all_outputs.append(outputs_)
-            for n in range(1, n_iterations + 1):
-                o = outputs_[f"iteration={n}"]
-                a = acc[n]
-                a["poses"].append(o.TCO_output)
-                a["poses_input"].append(o.TCO_input)
-                a["K_crop"].append(o.K_crop)
-                a["boxes_rend"].append(o.boxes_rend)
-                a["boxes_crop"].append(o.boxes_crop)
-                a["pose_out"].append(o.network_outputs["pose"] if "pose" in o.network_outputs else
-                                     torch.zeros(o.TCO_output.shape[0], 9, device=device))
-                render_time += o.timing_dict["render"]
-                event_sets.append(o.timing_dict.get("events"))
-        self._join(streams, produced)
+        steps = [o for outputs_ in chunk_outputs for o in outputs_.values()]   # chunk-major, iteration-minor
+        self._join(streams, [t for o in steps for t in (o.TCO_output, o.TCO_input, o.KV_crop, o.boxes_rend, o.boxes_crop, o.renders,
+                                                        o.images_crop, *o.network_outputs.values())])
         # ONE all-gather for the whole stage: the 58 floats of every iteration side by side, [rows, n_iterations * 58]
-        W = 58
-        blocks = []
-        for n in range(1, n_iterations + 1):
-            a = acc[n]
-            if rows_h.size:
-                blocks += [torch.cat(a["poses"]).flatten(1), torch.cat(a["poses_input"]).flatten(1), torch.cat(a["K_crop"]).flatten(1),
-                           torch.cat(a["boxes_rend"]), torch.cat(a["boxes_crop"]), torch.cat(a["pose_out"])]
-        packed_all = torch.cat(blocks, dim=1) if rows_h.size else torch.zeros(0, W * n_iterations, device=device)
+        W = _REFINER_ROW_WIDTH
+        if labels:
+            fields = {n: [_refiner_row_fields(outputs_[f"iteration={n}"]) for outputs_ in chunk_outputs] for n in range(1, n_iterations + 1)}
+            packed_all = torch.cat([torch.cat([f[name] for f in fields[n]]).flatten(1) for n in range(1, n_iterations + 1)
+                                    for name, _, _ in _REFINER_ROW], dim=1)
+        else:
+            packed_all = torch.zeros(0, W * n_iterations, device=observation.images.device)
         packed_all = self._gather(packed_all, R)
         preds = dict()
         pose_outputs = dict()
         for n in range(1, n_iterations + 1):
-            packed = packed_all[:, (n - 1) * W:n * W]
-            preds[f"iteration={n}"] = PandasTensorCollection(
-                df, poses=packed[:, 0:16].reshape(R, 4, 4).contiguous(), poses_input=packed[:, 16:32].reshape(R, 4, 4).contiguous(),
-                K_crop=packed[:, 32:41].reshape(R, 3, 3).contiguous(), K=K_all, boxes_rend=packed[:, 41:45].contiguous(),
-                boxes_crop=packed[:, 45:49].contiguous())
-            pose_outputs[f"iteration={n}"] = packed[:, 49:58].contiguous()
-        if cuda_timer:
-            torch.cuda.synchronize()
-            render_time, model_time = self._sum_events(event_sets)
-        elapsed = time.time() - start
+            cols, o = {}, (n - 1) * W
+            for name, width, shape in _REFINER_ROW:
+                cols[name] = packed_all[:, o:o + width].reshape(R, *shape).contiguous()
+                o += width
+                if name == "K_crop":
+                    cols["K"] = K_all   # (not gathered: every rank has it; registered after K_crop, the order callers have always seen)
+            pose_outputs[f"iteration={n}"] = cols.pop("pose_out")
+            preds[f"iteration={n}"] = PandasTensorCollection(df, **cols)
+        times = clock.stop(sum((o.timing_dict["render"] for o in steps), 0.0), [o.timing_dict.get("events") for o in steps],
+                           timing_str=False)   # (this stage reports none, like the reference's)
         # `pose_outputs` (engine extension): the refiner network's raw 9-vector per row and iteration, [R, 9] -- what the parity
         # checks compare before the pose update damps it (PosePredictorOutput.network_outputs["pose"], pose_rigid.py:50-66)
-        extra_data = {"n_iterations": n_iterations, "outputs": all_outputs, "model_time": model_time, "render_time": render_time,
-                      "time": elapsed, "pose_outputs": pose_outputs}
+        extra_data = {"n_iterations": n_iterations, "outputs": chunk_outputs if keep_all_outputs else [], **times, "pose_outputs": pose_outputs}
         return preds, extra_data
 
     # -- scoring --------------------------------------------------------------------------------------------------
@@ -367,59 +372,21 @@ class PoseEstimator(torch.nn.Module):
     def forward_scoring_model(self, observation: ObservationTensor, data_TCO: PoseEstimatesType, cuda_timer: bool = False,
                               return_debug_data: bool = False) -> Tuple[PoseEstimatesType, dict]:
         """Adds 'pose_logit' / 'pose_score' to data_TCO.infos (modifies the collection in place, :217-322)."""
-        if cuda_timer:
-            torch.cuda.synchronize()
-        start = time.time()
+        clock = _StageClock(cuda_timer)
         assert self.coarse_model is not None
         if return_debug_data and self._is_sharded():
             raise NotImplementedError("return_debug_data with distributed=True: crops/renders are shard-local (rows rank::world)")
-        device = observation.images.device
         df = data_TCO.infos
-        R = len(df)
-        labels_all = df["label"].tolist()
-        im_h = df["batch_im_id"].values.astype(np.int32)
-        rows_h = self._shard(R)
-        im_all = torch.as_tensor(im_h, device=device)
-        rows = torch.as_tensor(rows_h, device=device, dtype=torch.long)
-        poses = data_TCO.poses.to(device=device, dtype=torch.float32)
-        K_all = observation.K[im_all.long()].float()
-        K_rows, poses_rows, im_rows = K_all[rows], poses[rows], im_all[rows]
-        chunk, streams = self._plan(rows_h.size, self.bsz_images)
-        logits_l, scores_l, crops, renders, event_sets = [], [], [], [], []
-        render_time = model_time = 0.0
-        n_batches = 0
-        for ci, s in enumerate(range(0, rows_h.size, chunk)):
-            sl = slice(s, min(s + chunk, rows_h.size))
-            slot = ci % len(streams)
-            with torch.cuda.stream(streams[slot]):
-                out_ = self.coarse_model.forward_coarse(images=observation.images, K=K_rows[sl], labels=[labels_all[i] for i in rows_h[sl]],
-                                                        TCO_input=poses_rows[sl], cuda_timer=cuda_timer, return_debug_data=return_debug_data,
-                                                        im_ids=im_rows[sl], slot=slot, defer_timing=True)
-            render_time += out_["render_time"]
-            event_sets.append(out_["events"])
-            logits_l.append(out_["logits"])
-            scores_l.append(out_["scores"])
-            if return_debug_data:
-                crops.append(out_["images_crop"])
-                renders.append(out_["renders"])
-            n_batches += 1
-        self._join(streams, logits_l + scores_l + crops + renders)
-        packed = torch.cat([torch.cat(logits_l), torch.cat(scores_l)], dim=1) if rows_h.size else torch.zeros(0, 2, device=device)
-        packed = self._gather(packed, R)
+        labels, _, K_rows, poses_rows, im_rows = self._row_tables(observation, df, data_TCO.poses)
+        # after the inputs above are enqueued: side streams wait for them
+        logits, scores, debug_data, render_time, event_sets, n_batches = self._coarse_pass(
+            observation, labels, K_rows, poses_rows, im_rows, cuda_timer, return_debug_data)
+        packed = self._gather(torch.cat([logits, scores], dim=1), len(df))  # [rows, 2]
         logits, scores = packed[:, 0:1].contiguous(), packed[:, 1:2].contiguous()
-        debug_data = dict()
-        if return_debug_data:
-            debug_data = {"images_crop": torch.cat(crops), "renders": torch.cat(renders)}
         host = packed.cpu().numpy()
         df["pose_logit"] = host[:, 0]
         df["pose_score"] = host[:, 1]
-        if cuda_timer:
-            torch.cuda.synchronize()
-            render_time, model_time = self._sum_events(event_sets)
-        elapsed = time.time() - start
-        timing_str = f"time: {elapsed:.2f}, model_time: {model_time:.2f}, render_time: {render_time:.2f}"
-        extra_data = {"render_time": render_time, "model_time": model_time, "time": elapsed, "logits": logits, "scores": scores,
-                      "debug": debug_data, "n_batches": n_batches, "timing_str": timing_str}
+        extra_data = {**clock.stop(render_time, event_sets), "logits": logits, "scores": scores, "debug": debug_data, "n_batches": n_batches}
         data_TCO.infos = df
         return data_TCO, extra_data
 

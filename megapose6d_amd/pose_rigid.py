@@ -10,8 +10,8 @@ nothing synchronises.
 """
 from __future__ import annotations
 
+import math
 import os
-
 import time
 from collections import defaultdict
 from types import SimpleNamespace
@@ -90,7 +90,6 @@ class _RefinerGraph:
     """One captured refiner call of `rows` rows: n_iterations x (pose_prepare, render + crop, backbone, pose update) on static buffers."""
 
     def __init__(self, model: "PosePredictor", rows: int, n_iterations: int, slot: int, packed: "eng.PackedObservation", device):
-        V = model.n_rendered_views
         self.TCO = torch.zeros(rows, 4, 4, dtype=torch.float32, device=device)
         self.K = torch.zeros(rows, 3, 3, dtype=torch.float32, device=device)
         self.im_ids = torch.zeros(rows, dtype=torch.int32, device=device)
@@ -99,7 +98,7 @@ class _RefinerGraph:
         self.obs = eng.PackedObservation.__new__(eng.PackedObservation)
         self.obs.n_im, self.obs.C, self.obs.H, self.obs.W = packed.n_im, packed.C, packed.H, packed.W
         self.obs.data = torch.empty_like(packed.data)
-        width = sum(wd for _, wd in model._graph_widths())
+        width = sum(math.prod(shape) for _, shape in model._graph_layout())
         self.pack = torch.zeros(n_iterations, rows, width, dtype=torch.float32, device=device)
         self.graph = torch.cuda.CUDAGraph()
         self._fill = None
@@ -118,8 +117,8 @@ class _RefinerGraph:
             st = m._step(None, self.im_ids, self.K, dummy, TCO_input, want_sigmoid=False, slot=self._slot, ids=(self.pts_ids, self.ren_ids),
                          packed=self.obs)
             TCO_output = eng.pose_update(st["TCO_n"], st["K_crop"], st["out"], st["tCR"], 9)
-            torch.cat([st["TCO_n"].flatten(1), TCO_output.flatten(1), st["K_crop"].flatten(1), st["KV_crop"].flatten(1), st["boxes_rend"],
-                       st["boxes_crop"], st["out"], st["tCR"], st["TCV_O"].flatten(1)], dim=1, out=self.pack[n])
+            st["TCO_out"] = TCO_output
+            torch.cat([st[name].flatten(1) for name, _ in m._graph_layout()], dim=1, out=self.pack[n])
             TCO_input = TCO_output
 
     def run(self, TCO, K, im_ids, ids, packed) -> torch.Tensor:
@@ -280,13 +279,20 @@ class PosePredictor(nn.Module):
     def _f32_mask(self) -> int:
         """bit c set = logical input channel c is fp32-kind in a stem record (three exact bf16 pieces): the observation crop's channels
         and, for depth models, the rendered depth of every view (pose_rigid.py:395-408 channel layout); rgb / normals are 8-bit integers"""
-        nin, nper = self._n_input_channels, self._n_single_render_channels
-        mask = (1 << nin) - 1
-        if self.render_depth:
-            d0 = nin + (6 if self.render_normals else 3)
-            for v in range(self.n_rendered_views):
-                mask |= 1 << (d0 + nper * v)
-        return mask
+        return ((1 << self._n_input_channels) - 1) | sum(1 << c for c in self._depth_channels())
+
+    def _view_slots(self) -> Tuple[int, int, int]:
+        """(rgb, normals, depth): first channel of each slot of a rendered view, from the view's first channel; -1 = not rendered"""
+        return tuple(dims[0] if dims else -1 for dims in (self._render_rgb_dims, self._render_normal_dims, self._render_depth_dims))
+
+    def _views_depth_dims(self) -> List[int]:
+        """the rendered depth of every view, counted from the first rendered channel"""
+        depth = self._view_slots()[2]
+        return [self._n_single_render_channels * v + depth for v in range(self.n_rendered_views)] if depth >= 0 else []
+
+    def _depth_channels(self) -> List[int]:
+        """depth channels of the CNN input: the observation's, if any, then the rendered depth of every view"""
+        return self._input_depth_dims + [self._n_input_channels + c for c in self._views_depth_dims()]
 
     def _record_len(self) -> int:
         """bf16 elements per pixel if this model's CNN input is staged as stem records (see `stem_records`), else 0.  Depth models too
@@ -406,6 +412,7 @@ class PosePredictor(nn.Module):
         vg = max(1, (32 - nin) // nper)
         records = x.dtype == torch.bfloat16
         mode = eng.DEPTH_NORM_MODES[self.depth_normalization_type]
+        rgb, normals, depth = self._view_slots()
         for v0 in range(0, V, vg):
             v1 = min(V, v0 + vg)
             nv = v1 - v0
@@ -416,9 +423,8 @@ class PosePredictor(nn.Module):
             c0 = nin + nper * v0
             # stem records of a model with depth channels: the launch normalises them before the exact split (mp_raster_render_xrec)
             xrec = (self._f32_mask(), tCR, mode) if (records and (self.input_depth or self.render_depth)) else None
-            self.renderer.render_into(view_ids, Tg, Kg, self._lights(), (h, w), x, s_row, s_y, s_x, c0,
-                                      c0 + 3 if self.render_normals else -1,
-                                      c0 + (6 if self.render_normals else 3) if self.render_depth else -1, off,
+            self.renderer.render_into(view_ids, Tg, Kg, self._lights(), (h, w), x, s_row, s_y, s_x, c0 + rgb,
+                                      c0 + normals if normals >= 0 else -1, c0 + depth if depth >= 0 else -1, off,
                                       views_per_item=nv, stride_view=nper, slot=slot,
                                       crop=((self._packed(images) if packed is None else packed), im_ids, boxes_crop, 0) if v0 == 0 else None,
                                       xrec=xrec)
@@ -426,12 +432,7 @@ class PosePredictor(nn.Module):
         if ev is not None:
             ev[1].record()
         bb = self._backbone_engine()
-        depth_ch = []
-        if self.input_depth:
-            depth_ch.append(3)
-        if self.render_depth:
-            d0 = nin + (6 if self.render_normals else 3)
-            depth_ch += [d0 + nper * v for v in range(V)]
+        depth_ch = self._depth_channels()
         if depth_ch and mode and not records:   # (records: normalised inside the rasteriser launch)
             eng.normalize_depth(x, b, h, w, bb.in_border, bb.c_in_p, depth_ch, tCR, mode)
         n_out = bb.n_out
@@ -460,6 +461,21 @@ class PosePredictor(nn.Module):
             images = images[:, :3]  # pose_rigid.py:511-513, :669-671
         return images
 
+    def _check_rows(self, images: torch.Tensor, K: torch.Tensor, labels: List[str], TCO: torch.Tensor, im_ids: Optional[torch.Tensor]):
+        """forward / forward_coarse: checked rows -> (frames cut to the model's input channels, row -> frame ids, default one each)"""
+        images = self._prep_images(images)
+        bsz = TCO.shape[0]
+        assert TCO.shape == (bsz, 4, 4) and K.shape == (bsz, 3, 3) and len(labels) == bsz
+        if im_ids is None:
+            assert images.shape[0] == bsz
+            im_ids = torch.arange(bsz, dtype=torch.int32, device=TCO.device)
+        return images, im_ids
+
+    def _crops_and_renders(self, bsz: int, slot: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """copies of the last step's observation crops and renders [bsz,C,h,w], out of the CNN input buffer of `slot`"""
+        nin = self._n_input_channels
+        return self._nchw_view(bsz, 0, nin, slot).clone(), self._nchw_view(bsz, nin, self.backbone.n_inputs, slot).clone()
+
     # -- reference API -----------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, images: torch.Tensor, K: torch.Tensor, labels: List[str], TCO: torch.Tensor, n_iterations: int = 1,
@@ -471,13 +487,8 @@ class PosePredictor(nn.Module):
         events to `timing_dict["events"]` (resolve with `PosePredictor.step_times` after a synchronise)."""
         if random_ambient_light:
             raise NotImplementedError("random_ambient_light is a training-time augmentation")
-        images = self._prep_images(images)
-        bsz = TCO.shape[0]
-        assert TCO.shape == (bsz, 4, 4) and K.shape == (bsz, 3, 3) and len(labels) == bsz
-        device = TCO.device
-        if im_ids is None:
-            assert images.shape[0] == bsz
-            im_ids = torch.arange(bsz, dtype=torch.int32, device=device)
+        images, im_ids = self._check_rows(images, K, labels, TCO, im_ids)
+        bsz, device = TCO.shape[0], TCO.device
         if (self.predict_pose_update and 0 < bsz <= self.graph_rows and not materialize and not cuda_timer and not eng.profiling()
                 and self.render_dtype == torch.float32):
             graphed = self._forward_graphed(images, K, labels, TCO, n_iterations, im_ids, slot)
@@ -485,7 +496,6 @@ class PosePredictor(nn.Module):
                 return graphed
         outputs: Dict[str, PosePredictorOutput] = dict()
         TCO_input = TCO
-        nin = self._n_input_channels
         for n in range(n_iterations):
             st = self._step(images, im_ids, K, labels, TCO_input, want_sigmoid=False, slot=slot, events=cuda_timer)
             K_crop = st["K_crop"]   # crop_inputs' intrinsics (== KV_crop[:, 0] unless remove_TCO_rendering)
@@ -499,8 +509,7 @@ class PosePredictor(nn.Module):
                 renderings_logits = st["out"]
             renders = images_crop = None
             if materialize:
-                images_crop = self._nchw_view(bsz, 0, nin, slot).clone()
-                renders = self._nchw_view(bsz, nin, self.backbone.n_inputs, slot).clone()
+                images_crop, renders = self._crops_and_renders(bsz, slot)
             outputs[f"iteration={n + 1}"] = PosePredictorOutput(
                 renders=renders, images_crop=images_crop, TCO_input=st["TCO_n"], TCO_output=TCO_output, TCV_O_input=st["TCV_O"],
                 tCR=st["tCR"], labels=labels, K=K, K_crop=K_crop, KV_crop=st["KV_crop"], network_outputs=network_outputs,
@@ -510,10 +519,11 @@ class PosePredictor(nn.Module):
         return outputs
 
     # -- hipGraph path of small refiner calls -----------------------------------------------------------------------
-    def _graph_widths(self):
+    def _graph_layout(self):
+        """one row of a captured call's packed result, per iteration: (name, trailing shape) side by side"""
         V = self.n_rendered_views
-        return (("TCO_n", 16), ("TCO_out", 16), ("K_crop", 9), ("KV_crop", 9 * V), ("boxes_rend", 4), ("boxes_crop", 4), ("out", 9),
-                ("tCR", 3), ("TCV_O", 16 * V))
+        return (("TCO_n", (4, 4)), ("TCO_out", (4, 4)), ("K_crop", (3, 3)), ("KV_crop", (V, 3, 3)), ("boxes_rend", (4,)), ("boxes_crop", (4,)),
+                ("out", (9,)), ("tCR", (3,)), ("TCV_O", (V, 4, 4)))
 
     def _forward_graphed(self, images, K, labels, TCO, n_iterations, im_ids, slot) -> Optional[Dict[str, PosePredictorOutput]]:
         """The same call as the loop in forward(), captured once as a hipGraph (torch.cuda.CUDAGraph = hipStreamBeginCapture /
@@ -540,13 +550,13 @@ class PosePredictor(nn.Module):
         outputs: Dict[str, PosePredictorOutput] = dict()
         for n in range(n_iterations):
             f, o = {}, 0
-            for name, wd in self._graph_widths():
-                f[name] = res[n, :, o:o + wd]
+            for name, shape in self._graph_layout():
+                wd = math.prod(shape)
+                f[name] = res[n, :, o:o + wd].reshape(b, *shape)
                 o += wd
             outputs[f"iteration={n + 1}"] = PosePredictorOutput(
-                renders=None, images_crop=None, TCO_input=f["TCO_n"].reshape(b, 4, 4), TCO_output=f["TCO_out"].reshape(b, 4, 4),
-                TCV_O_input=f["TCV_O"].reshape(b, V, 4, 4), tCR=f["tCR"], labels=labels, K=K, K_crop=f["K_crop"].reshape(b, 3, 3),
-                KV_crop=f["KV_crop"].reshape(b, V, 3, 3), network_outputs={"pose": f["out"]}, boxes_rend=f["boxes_rend"],
+                renders=None, images_crop=None, TCO_input=f["TCO_n"], TCO_output=f["TCO_out"], TCV_O_input=f["TCV_O"], tCR=f["tCR"],
+                labels=labels, K=K, K_crop=f["K_crop"], KV_crop=f["KV_crop"], network_outputs={"pose": f["out"]}, boxes_rend=f["boxes_rend"],
                 boxes_crop=f["boxes_crop"], renderings_logits=torch.empty(b, V, dtype=TCO.dtype, device=device),
                 timing_dict={"render": 0.0, "events": None})
         return outputs
@@ -557,12 +567,7 @@ class PosePredictor(nn.Module):
                        im_ids: Optional[torch.Tensor] = None, slot: int = 0, defer_timing: bool = False) -> Dict[str, Any]:
         """pose_rigid.py:634-708: logits/scores [b,1] of each hypothesis."""
         assert self.predict_rendered_views_logits, "Method only valid if coarse classification model"
-        images = self._prep_images(images)
-        bsz = TCO_input.shape[0]
-        assert TCO_input.shape == (bsz, 4, 4) and K.shape == (bsz, 3, 3) and len(labels) == bsz
-        if im_ids is None:
-            assert images.shape[0] == bsz
-            im_ids = torch.arange(bsz, dtype=torch.int32, device=TCO_input.device)
+        images, im_ids = self._check_rows(images, K, labels, TCO_input, im_ids)
         st = self._step(images, im_ids, K, labels, TCO_input, want_sigmoid=True, slot=slot, events=cuda_timer, mv_mode=0)   # forward_coarse: KV_crop = K_crop (pose_rigid.py:683-685)
         # cuda_timer=True: `events` lets the caller resolve DEVICE render / model times once per stage (PoseEstimator does, after
         # its single synchronisation); a direct caller gets them here at the price of a synchronise, like the reference's
@@ -576,9 +581,7 @@ class PosePredictor(nn.Module):
             out["render_time"], out["model_time"] = self.step_times(st["events"])
             out["time"] = out["model_time"]
         if return_debug_data:
-            nin = self._n_input_channels
-            out["images_crop"] = self._nchw_view(bsz, 0, nin, slot).clone()
-            out["renders"] = self._nchw_view(bsz, nin, self.backbone.n_inputs, slot).clone()
+            out["images_crop"], out["renders"] = self._crops_and_renders(TCO_input.shape[0], slot)
         return out
 
     @torch.no_grad()
@@ -671,7 +674,7 @@ class PosePredictor(nn.Module):
             assert images.shape[1] == 4, "images must have C=4 channels if input_depth=True"
             images[:, self._input_depth_dims] = self.normalize_depth(images[:, self._input_depth_dims], tCR)
         if self.render_depth:
-            dims = [self._render_depth_dims[0] + self._n_single_render_channels * v for v in range(self.n_rendered_views)]
+            dims = self._views_depth_dims()
             renders[:, dims] = self.normalize_depth(renders[:, dims], tCR)
         return images, renders
 

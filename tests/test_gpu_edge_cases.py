@@ -196,3 +196,132 @@ def test_pose_predictor_stand_alone_helpers_match_the_fused_step():
     assert torch.equal(re2[:, other], renders[:, other])
     assert (re2[:, depth_dims] - (torch.clamp(renders[:, depth_dims] / tCR[:, 2].view(2, 1, 1, 1), 0, 2) - 1)).abs().max() < 1e-6
     assert torch.equal(images, images.clone()) and not torch.equal(re2, renders)   # inputs untouched (copies returned)
+
+
+# -- the stage scaffold of PoseEstimator: timer, debug data, kept outputs, ragged chunks on two streams -----------------------------------
+def _coarse_top2(est, obs, det):
+    """the fixture's detections with instance ids -> (detections, their 216 coarse rows, the 6 top-2 rows)"""
+    from megapose6d_amd.pose_estimator import add_instance_id
+    from megapose6d_amd.tcoll import PandasTensorCollection
+
+    det = add_instance_id(PandasTensorCollection(det.infos.copy(), bboxes=det.bboxes))
+    coarse, _ = est.forward_coarse_model(obs, det)
+    return det, coarse, est.filter_pose_estimates(coarse, top_K=2, filter_field="coarse_logit")
+
+
+def _assert_collections_equal(a, b):
+    assert list(a.tensors) == list(b.tensors)
+    for k in a.tensors:
+        assert torch.equal(a.tensors[k], b.tensors[k]), k
+
+
+def test_timed_stages_equal_untimed_stages(multi_scene):
+    """cuda_timer=True fences the stage and reports device times; it changes no result and no key of any extra_data"""
+    tmp, ds, est, obs, det = multi_scene
+    det = _coarse_top2(est, obs, det)[0]
+    runs = []
+    for timed in (False, True):
+        coarse, ce = est.forward_coarse_model(obs, det, cuda_timer=timed)
+        top = est.filter_pose_estimates(coarse, top_K=2, filter_field="coarse_logit")
+        preds, re = est.forward_refiner(obs, top, n_iterations=2, cuda_timer=timed)
+        scored, se = est.forward_scoring_model(obs, preds["iteration=2"].clone(), cuda_timer=timed)
+        runs.append((coarse, ce, preds, re, scored, se))
+    (c0, ce0, p0, re0, s0, se0), (c1, ce1, p1, re1, s1, se1) = runs
+    for e0, e1 in ((ce0, ce1), (se0, se1)):
+        assert torch.equal(e0["logits"], e1["logits"]) and torch.equal(e0["scores"], e1["scores"])
+    assert torch.equal(ce0["TCO"], ce1["TCO"])
+    _assert_collections_equal(c0, c1)
+    _assert_collections_equal(s0, s1)
+    assert sorted(p0) == sorted(p1) == ["iteration=1", "iteration=2"]
+    for k in p0:
+        assert list(p0[k].tensors) == ["poses", "poses_input", "K_crop", "K", "boxes_rend", "boxes_crop"]
+        _assert_collections_equal(p0[k], p1[k])
+        assert torch.equal(re0["pose_outputs"][k], re1["pose_outputs"][k])
+    assert s0.infos["pose_logit"].tolist() == s1.infos["pose_logit"].tolist()
+    assert c0.infos["coarse_logit"].tolist() == c1.infos["coarse_logit"].tolist()
+    for e0, e1 in ((ce0, ce1), (re0, re1), (se0, se1)):
+        assert e0["model_time"] == 0.0
+        assert e1["model_time"] > 0 and e1["render_time"] > 0
+    stage_keys = {"render_time", "model_time", "time", "logits", "scores", "debug", "n_batches", "timing_str"}
+    for e in (ce0, ce1):
+        assert set(e) == stage_keys | {"TCO"}
+    for e in (se0, se1):
+        assert set(e) == stage_keys
+    for e in (re0, re1):
+        assert set(e) == {"n_iterations", "outputs", "model_time", "render_time", "time", "pose_outputs"}
+        assert e["n_iterations"] == 2 and e["outputs"] == []
+
+
+def test_stage_debug_data_is_the_models_debug_data(multi_scene):
+    """return_debug_data=True of the coarse and scoring stages: the crops / renders of coarse_model.forward_coarse, stage-shaped"""
+    tmp, ds, est, obs, det = multi_scene
+    det, coarse, top = _coarse_top2(est, obs, det)
+    B, M = len(det), 72
+    h, w = est.coarse_model.render_size
+    n_in = est.coarse_model.backbone.n_inputs
+
+    def direct(infos, poses):
+        im = infos["batch_im_id"].values.astype(np.int64)
+        return est.coarse_model.forward_coarse(obs.images, obs.K[torch.as_tensor(im, device="cuda")].float(), infos["label"].tolist(),
+                                               poses.contiguous(), im_ids=torch.as_tensor(im.astype(np.int32), device="cuda"),
+                                               return_debug_data=True)
+
+    dbg = est.forward_coarse_model(obs, det, return_debug_data=True)[1]["debug"]
+    assert set(dbg) == {"images_crop", "renders"}
+    assert dbg["images_crop"].shape == (B, M, 3, h, w) and dbg["renders"].shape == (B, M, n_in - 3, h, w)
+    d = 2   # the detection of frame 1 (other intrinsics, the larger mesh)
+    ref = direct(coarse.infos.iloc[d * M:(d + 1) * M], coarse.poses[d * M:(d + 1) * M])
+    assert torch.equal(dbg["images_crop"][d], ref["images_crop"]) and torch.equal(dbg["renders"][d], ref["renders"])
+
+    R = len(top)
+    dbg = est.forward_scoring_model(obs, top.clone(), return_debug_data=True)[1]["debug"]
+    assert set(dbg) == {"images_crop", "renders"}
+    assert dbg["images_crop"].shape == (R, 3, h, w) and dbg["renders"].shape == (R, n_in - 3, h, w)
+    sel = np.flatnonzero(top.infos["bbox_id"].values == d)
+    assert sel.size == 2
+    ref = direct(top.infos.iloc[sel], top.poses[sel.tolist()])
+    assert torch.equal(dbg["images_crop"][sel.tolist()], ref["images_crop"]) and torch.equal(dbg["renders"][sel.tolist()], ref["renders"])
+
+
+def test_refiner_keep_all_outputs(multi_scene):
+    """keep_all_outputs=True: one dict of materialised PosePredictorOutputs per chunk, the same poses as without"""
+    tmp, ds, est, obs, det = multi_scene
+    top = _coarse_top2(est, obs, det)[2]
+    R = len(top)
+    assert R == 6
+    old = est.max_rows_per_launch
+    try:
+        est.max_rows_per_launch = 4
+        preds, extra = est.forward_refiner(obs, top, n_iterations=2, keep_all_outputs=True)
+        plain, plain_extra = est.forward_refiner(obs, top, n_iterations=2, keep_all_outputs=False)
+    finally:
+        est.max_rows_per_launch = old
+    assert len(extra["outputs"]) == 2 and plain_extra["outputs"] == []
+    for outputs_, rows in zip(extra["outputs"], (4, 2)):
+        assert sorted(outputs_) == ["iteration=1", "iteration=2"]
+        for o in outputs_.values():
+            assert o.renders is not None and o.images_crop is not None
+            assert o.renders.shape[0] == rows and o.images_crop.shape[0] == rows and o.TCO_output.shape == (rows, 4, 4)
+    for k in ("iteration=1", "iteration=2"):
+        assert preds[k].infos["refiner_batch_idx"].tolist() == (np.arange(R) // 4).tolist()
+        assert preds[k].infos["refiner_instance_idx"].tolist() == (np.arange(R) % 4).tolist()
+        assert torch.equal(preds[k].poses, plain[k].poses)
+
+
+def test_scoring_under_ragged_chunks_and_two_streams(multi_scene):
+    """9 scoring rows in chunks of 4 interleaved on two streams == one launch (the bound test_ragged_chunks_match_single_launch uses)"""
+    tmp, ds, est, obs, det = multi_scene
+    _, e1 = est.run_inference_pipeline(obs, detections=det, n_refiner_iterations=2, n_pose_hypotheses=3)
+    old = est.max_rows_per_launch, est.n_streams, est.min_rows_per_stream
+    try:
+        est.max_rows_per_launch, est.n_streams, est.min_rows_per_stream = 4, 2, 2
+        _, e2 = est.run_inference_pipeline(obs, detections=det, n_refiner_iterations=2, n_pose_hypotheses=3)
+    finally:
+        est.max_rows_per_launch, est.n_streams, est.min_rows_per_stream = old
+    l1, l2 = e1["scoring"]["data"]["logits"], e2["scoring"]["data"]["logits"]
+    R = l1.shape[0]
+    assert R == 9 and l2.shape == l1.shape == (R, 1)
+    assert e1["scoring"]["data"]["n_batches"] == 1 and e2["scoring"]["data"]["n_batches"] == -(-R // 4)
+    err = (l1 - l2).abs().max().item()
+    print(f"scoring logits, chunks of 4 on two streams vs one launch: max abs diff {err:.3e}")
+    assert err < 1e-4
