@@ -662,6 +662,32 @@ int mp_model_info(const float* d_points /*[n_obj,stride,3]*/, int stride, const 
                   int32_t* d_pair /*[n_obj,2]*/, float* d_bounds /*[n_obj,6]*/, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Points drawn uniformly over the surface of triangle meshes: the reference's              */
+/* MeshDataBase.batched(resample_n_points=n) (lib3d/rigid_mesh_database.py:100-104,          */
+/* trimesh.sample.sample_surface), on uniforms the caller supplies                           */
+/* (csrc/surface_sample.hip; contract in csrc/surface_sample_core.h).                        */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_surface_sample needs (0 for arguments it refuses: n_obj < 1, offsets that do not ascend, an object without
+   faces or with more than 2^22, a bad block or one that cuts an object into more than 2048 blocks, count < 1).  h_face_off [n_obj + 1]
+   is host memory. */
+size_t mp_surface_sample_scratch_bytes(int n_obj, const int32_t* h_face_off, int count, int block);
+/* For object o, with vertices vert_off[o] .. vert_off[o+1] - 1 of d_vertices and faces face_off[o] .. face_off[o+1] - 1 of d_faces
+   (indices local to the object), and for sample s with the uniforms (u0, u1, u2) = d_u[o][s]: d_face[o][s] = the lowest face f whose
+   inclusive prefix sum of quantised weights exceeds floor(total * k / 2^24), k = min((uint32)(u0 * 2^24), 2^24 - 1); d_points[o][s] =
+   a + e1 * r1 + e2 * r2 on that face (fmaf, fp32) with (r1, r2) = (u1, u2) clamped to [0, 1] and reflected when r1 + r2 > 1.  A weight is
+   twice the face's area in fp32, quantised to a 2^-40 grid under the object's largest weight, so all sums are exact integers and no
+   grid, block size or arrival order changes a bit.  An object with a non-finite coordinate of a referenced vertex, an index outside
+   its vertices (tested before the load), a non-finite weight or no area at all gives NaN points and face -1 and leaves the other
+   objects alone.  The d_ and h_ prefix arrays hold the same n_obj + 1 values, starting at 0.  block = the faces of one job: 0 the
+   library's choice (2048), else a multiple of 64 in 64 .. 2048 (for tests: a few hundred faces then make several blocks).  Five
+   launches on `stream`, no atomics, no workgroup waits for another; the prefix array of job counts is copied from pageable host memory.
+   Any bad argument returns non-zero before anything is launched. */
+int mp_surface_sample(const float* d_vertices /*[V_total,3]*/, const int32_t* d_faces /*[F_total,3]*/, const int32_t* d_vert_off /*[n_obj+1]*/,
+                      const int32_t* d_face_off /*[n_obj+1]*/, const int32_t* h_vert_off /*host*/, const int32_t* h_face_off /*host*/,
+                      int n_obj, const float* d_u /*[n_obj,count,3]*/, int count, int block, void* d_workspace,
+                      float* d_points /*[n_obj,count,3]*/, int32_t* d_face /*[n_obj,count]*/, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

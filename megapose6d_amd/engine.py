@@ -1065,6 +1065,49 @@ def model_info(points: torch.Tensor, n_points, tile: int = 0) -> Tuple[torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# points drawn uniformly over mesh surfaces (mesh database): csrc/surface_sample.hip
+SURFACE_BLOCK_STEP = 64              # a forced block is a multiple of this ...
+SURFACE_MAX_BLOCK = 2048             # ... and at most this; an object has at most this many blocks
+SURFACE_MAX_FACES = 1 << 22          # faces of one object
+
+
+def surface_sample(vertices: torch.Tensor, faces: torch.Tensor, vert_off, face_off, u: torch.Tensor, block: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Points drawn uniformly over the surface of triangle meshes (mp_surface_sample).  vertices [V_total,3] float32 and faces
+    [F_total,3] int32 (indices local to the object) on the device; vert_off, face_off [n_obj + 1] (host ints, an array or a tensor: the
+    launch needs them on both sides) the prefix arrays that cut them into objects, each object with 1 .. 2^22 faces; u
+    [n_obj,count,3] float32 uniforms in [0, 1) on the device (u0 picks the face in proportion to its area, u1 u2 the point in it:
+    the engine draws nothing); block = the faces of one job (0: the library's choice; a multiple of 64 up to 2048 forces it, for tests)
+    -> points [n_obj,count,3] float32, face [n_obj,count] int32.  No grid, block or arrival order changes a bit.  An object with a
+    non-finite coordinate of a referenced vertex, an index outside its vertices, or no area gives NaN points and face -1.  Nothing
+    synchronises (a tensor of offsets is read back before the launch)."""
+    vertices, faces, u = _dev_f32(vertices), _dev_i32(faces), _dev_f32(u)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise EngineError(f"vertices must be [V_total,3] and faces [F_total,3], got {tuple(vertices.shape)} and {tuple(faces.shape)}")
+    if u.dim() != 3 or u.shape[2] != 3 or u.shape[0] < 1 or u.shape[1] < 1:
+        raise EngineError(f"u must be [n_obj,count,3] with n_obj, count >= 1, got {tuple(u.shape)}")
+    n_obj, count = int(u.shape[0]), int(u.shape[1])
+    h_vo, h_fo = (np.ascontiguousarray(o.cpu().numpy() if isinstance(o, torch.Tensor) else o).astype(np.int64) for o in (vert_off, face_off))
+    if h_vo.shape != (n_obj + 1,) or h_fo.shape != (n_obj + 1,) or h_vo[0] != 0 or h_fo[0] != 0 or h_vo[-1] != vertices.shape[0] or h_fo[-1] != faces.shape[0]:
+        raise EngineError(f"vert_off and face_off must be [n_obj + 1 = {n_obj + 1}], start at 0 and end at {vertices.shape[0]} vertices and {faces.shape[0]} faces")
+    if (np.diff(h_vo) < 0).any() or (np.diff(h_fo) < 1).any() or (np.diff(h_fo) > SURFACE_MAX_FACES).any():
+        raise EngineError(f"vert_off must not descend, and every object must have 1 .. {SURFACE_MAX_FACES} faces")
+    h_vo, h_fo = h_vo.astype(np.int32), h_fo.astype(np.int32)
+    dev = vertices.device
+    lib = _lib.load()
+    n_bytes = lib.mp_surface_sample_scratch_bytes(n_obj, h_fo.ctypes.data, count, int(block))
+    if n_bytes == 0:
+        raise EngineError(f"surface_sample: block {block} is not 0 or a multiple of {SURFACE_BLOCK_STEP} up to {SURFACE_MAX_BLOCK}, or it cuts an object "
+                          f"into more than {SURFACE_MAX_BLOCK} blocks, or too many objects")
+    d_vo, d_fo = torch.from_numpy(h_vo).to(dev), torch.from_numpy(h_fo).to(dev)
+    ws = _workspace(n_bytes, dev)
+    points = torch.empty(n_obj, count, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(n_obj, count, dtype=torch.int32, device=dev)
+    check(lib.mp_surface_sample(vertices.data_ptr(), faces.data_ptr(), d_vo.data_ptr(), d_fo.data_ptr(), h_vo.ctypes.data, h_fo.ctypes.data, n_obj,
+                                u.data_ptr(), count, int(block), ws.data_ptr(), points.data_ptr(), face.data_ptr(), _stream()))
+    return points, face
+
+
+# --------------------------------------------------------------------------- #
 def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_images: torch.Tensor, K_rows: torch.Tensor,
                TCO: torch.Tensor, n_iterations: int = 100, n_levels: int = 4, tolerance: float = 0.05, n_min_points: int = 1000,
                user_masks: bool = False, association: str = "nn", return_iters: bool = False, masks: Optional[torch.Tensor] = None):

@@ -110,11 +110,68 @@ class MeshDataBase:
         if aabb or resample_n_points:
             raise NotImplementedError("only the hot-path configuration (all vertices) is supported")
         pts = [torch.from_numpy(self.engine_meshes[l]["points"]) for l in self.labels]
-        # symmetry sets, identity-padded to the longest one (rigid_mesh_database.py:117-129)
+        infos = {l: {"n_points": int(p.shape[0])} for l, p in zip(self.labels, pts)}
+        return BatchedMeshes(infos, self.labels, _pad_points(pts).float(), self._symmetries(n_sym, infos))
+
+    def _symmetries(self, n_sym: int, infos) -> torch.Tensor:
+        """the symmetry sets, identity-padded to the longest one (rigid_mesh_database.py:117-129); writes n_sym into infos"""
         syms = [torch.as_tensor(np.asarray(self.obj_dict[l].make_symmetry_poses(n_symmetries_continuous=n_sym))).float() for l in self.labels]
-        infos = {l: {"n_points": int(p.shape[0]), "n_sym": int(s.shape[0])} for l, p, s in zip(self.labels, pts, syms)}
         s_max = max(s.shape[0] for s in syms)
-        sym = torch.eye(4).repeat(len(pts), s_max, 1, 1)
-        for n, s in enumerate(syms):
+        sym = torch.eye(4).repeat(len(syms), s_max, 1, 1)
+        for n, (l, s) in enumerate(zip(self.labels, syms)):
             sym[n, : s.shape[0]] = s
-        return BatchedMeshes(infos, self.labels, _pad_points(pts).float(), sym)
+            infos[l]["n_sym"] = int(s.shape[0])
+        return sym
+
+    def batched_surface(self, n_points: int, n_sym: int = 64, seed: int = 0, device="cuda") -> BatchedMeshes:
+        """What the reference's batched(resample_n_points=n_points) gives (rigid_mesh_database.py:100-104): every object's vertices
+        replaced by n_points points drawn uniformly over its surface (trimesh.sample.sample_surface), here by one launch of
+        engine.surface_sample on `device` for all objects, on uniforms drawn by a CPU generator seeded with `seed`: the same points on
+        every machine.  An object without faces (a point cloud) keeps the deterministic subset of n_points of its vertices, the
+        reference's other branch (AssertionError if it has fewer).  An object the sampler fails (a non-finite coordinate, a face
+        index outside its vertices, no area) raises ValueError with its label.  CPU float32 tensors like batched(): the caller moves
+        them; nothing is padded, infos[label]["n_points"] == n_points for every object."""
+        n_points = int(n_points)
+        if n_points < 1:
+            raise ValueError(f"n_points must be at least 1, got {n_points}")
+        labels = self.labels
+        meshed = [l for l in labels if len(self.engine_meshes[l]["faces"]) > 0]
+        points = torch.empty(len(labels), n_points, 3, dtype=torch.float32)
+        for n, l in enumerate(labels):
+            if l not in meshed:
+                pts = self.engine_meshes[l]["points"]
+                points[n] = torch.from_numpy(pts[deterministic_point_ids(len(pts), n_points)])
+        if meshed:
+            from . import engine as eng
+
+            verts = [self.engine_meshes[l]["points"] for l in meshed]
+            faces = [self.engine_meshes[l]["faces"] for l in meshed]
+            vert_off = np.concatenate([[0], np.cumsum([len(v) for v in verts])])
+            face_off = np.concatenate([[0], np.cumsum([len(f) for f in faces])])
+            u = torch.rand(len(meshed), n_points, 3, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+            sampled, face = eng.surface_sample(torch.from_numpy(np.concatenate(verts).astype(np.float32)).to(device),
+                                               torch.from_numpy(np.concatenate(faces).astype(np.int32)).to(device), vert_off, face_off, u.to(device))
+            sampled, face = sampled.cpu(), face.cpu()
+            for k, l in enumerate(meshed):
+                if int(face[k, 0]) < 0:
+                    raise ValueError(f"object {l!r} cannot be sampled: a non-finite vertex, a face index outside its vertices, or no area")
+                points[labels.index(l)] = sampled[k]
+        infos = {l: {"n_points": n_points} for l in labels}
+        sym = self._symmetries(n_sym, infos)
+        return BatchedMeshes(infos, labels, points, sym)
+
+    def batched_aabb(self, n_sym: int = 64) -> BatchedMeshes:
+        """What the reference's batched(aabb=True) gives (rigid_mesh_database.py:96-99): every object's vertices replaced by the eight
+        corners of its axis-aligned box, in the order of lib3d/mesh_ops.py get_meshes_bounding_boxes: v0 = (xmin, ymax, zmax),
+        v1 = (xmax, ymax, zmax), v2 = (xmax, ymin, zmax), v3 = (xmin, ymin, zmax), v4 .. v7 the same at zmin.  The exact minimum
+        and maximum of the metre-scaled vertices, on the host."""
+        labels = self.labels
+        points = torch.empty(len(labels), 8, 3, dtype=torch.float32)
+        for n, l in enumerate(labels):
+            pts = self.engine_meshes[l]["points"]
+            (x0, y0, z0), (x1, y1, z1) = pts.min(0), pts.max(0)
+            points[n] = torch.as_tensor([[x0, y1, z1], [x1, y1, z1], [x1, y0, z1], [x0, y0, z1],
+                                         [x0, y1, z0], [x1, y1, z0], [x1, y0, z0], [x0, y0, z0]], dtype=torch.float32)
+        infos = {l: {"n_points": 8} for l in labels}
+        sym = self._symmetries(n_sym, infos)
+        return BatchedMeshes(infos, labels, points, sym)
