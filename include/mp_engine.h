@@ -718,6 +718,46 @@ int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const int32_t* d_i
                      void* d_ws, size_t ws_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Depth refiner (TEASER++): replaces inference/teaserpp_refiner.py:53-162                  */
+/* compute_teaserpp_refinement + :193-289 TeaserppRefiner.refine_poses (masks               */
+/* refiner_utils.py:30-56, points visualization/meshcat_utils.py:278-300).  pytorch3d's     */
+/* farthest point sampling and teaserpp_python's solver are third party (parity unpinned);  */
+/* the algorithm is the one stated in csrc/teaser_core.h (csrc/teaser.hip).                 */
+/* ------------------------------------------------------------------------------------ */
+/* Farthest point sampling of n_rows point sets d_points [n_rows,stride,3] fp32, of which the first d_counts[r] (clamped to 0 .. stride)
+   are valid: M = min(n_points, count) picks; pick 0 is point 0, every later pick the point with the largest running minimum of the
+   squared fp32 distance to the picks so far, a tie to the lowest index (pytorch3d.ops.sample_farthest_points without a random start).
+   use_fps == 0: index floor(k * count / M) instead.  d_idx [n_rows,n_points] int32 (-1 past M), d_m [n_rows] = M.  One launch, one
+   workgroup per row; d_workspace of mp_fps_workspace_bytes(n_rows, stride) bytes.  Any bad argument returns non-zero before the launch. */
+size_t mp_fps_workspace_bytes(int n_rows, int stride);
+int mp_fps(const float* d_points, const int32_t* d_counts, int n_rows, int stride, int n_points, int use_fps, int32_t* d_idx, int32_t* d_m,
+           void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* bytes of scratch of mp_teaser_refine for n_rows rows of H x W frames; with H = W = 0, of mp_teaser_solve (0 for sizes it refuses). */
+size_t mp_teaser_workspace_bytes(int n_rows, int H, int W);
+/* Robust registration of given correspondences d_src[r][k] -> d_dst[r][k], k < d_counts[r] <= stride <= 1024 ([n_rows,stride,3] fp32):
+   consistency graph (edge when the two pair distances differ by at most 2 noise_bound), inlier selection (0: the vertices of the largest
+   core number; 1: every vertex), GNC-TLS rotation over the TIMs of the selected vertices (tim_graph 0: consecutive pairs, 1: all pairs),
+   component-wise TLS translation, inlier count over all correspondences.  d_Rt [n_rows,12] float64 = [R t] row-major (the identity for
+   a row with fewer than 3 selected vertices), d_retval [n_rows] = 0 when num_inliers >= min_num_inliers, else -1.  Optional (NULL to
+   skip): d_degree, d_core, d_selected [n_rows,stride] int32 (-1 past a row's count), d_info [n_rows,5] int32 =
+   count, count, selected, GNC iterations, num_inliers.  Three launches; no atomics, every sum in a fixed order.  Any bad argument
+   returns non-zero before anything is launched. */
+int mp_teaser_solve(const float* d_src, const float* d_dst, const int32_t* d_counts, int n_rows, int stride, float noise_bound,
+                    int inlier_selection, int tim_graph, int min_num_inliers, double* d_Rt, int32_t* d_retval, int32_t* d_degree,
+                    int32_t* d_core, int32_t* d_selected, int32_t* d_info, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* The whole refiner from depth frames: d_depth_meas [n_images,H,W] metres, d_depth_rend [n_rows,H,W] rendered at d_TCO, d_K_rows
+   [n_rows,3,3].  Mask (mask_type 0 "simple": measured > 0 and rendered > 0; 1 "threshold": also |measured - rendered| <=
+   depth_delta_thresh), back-projection of both depths at the N mask pixels, M = min(n_points, N) samples of the source points (a row
+   with N < n_min_points keeps its pose), then mp_teaser_solve's chain; an accepted row's pose becomes [R t] * TCO.  n_points <= 1024.
+   Optional outputs as mp_teaser_solve with stride = n_points, d_sample_idx [n_rows,n_points] = indices into the row's mask pixels (-1 past
+   M), d_info = N, M, selected, GNC iterations, num_inliers.  Six launches on `stream`, no host round trip. */
+int mp_teaser_refine(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
+                     const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
+                     float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
+                     int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
+                     int32_t* d_info, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Detector network: replaces the torchvision Mask R-CNN    */
 /* behind `self.model([image_n ...])` in inference/detector.py:92                          */
 /* (models/mask_rcnn.py:23-46 = MaskRCNN(resnet_fpn_backbone("resnet50"), num_classes,     */

@@ -182,6 +182,12 @@ SIGNATURES = {
     "mp_model_info": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_surface_sample_scratch_bytes": (_sz, [_i, _vp, _i, _i]),
     "mp_surface_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "mp_fps_workspace_bytes": (_sz, [_i, _i]),
+    "mp_fps": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mp_teaser_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mp_teaser_solve": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mp_teaser_refine": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _sz, _vp]),
     "mp_icp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mp_icp_refine": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_icp_nn_max_points": (_i, []),

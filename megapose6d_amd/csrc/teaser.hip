@@ -1,0 +1,530 @@
+// teaser.hip -- the reference's second depth refiner (inference/teaserpp_refiner.py: TeaserppRefiner) on the device.
+//
+// Replaces a per-object CPU loop: numpy back-projection of the rendered and the measured depth (meshcat_utils.get_pointcloud), the masks
+// of refiner_utils.compute_masks, pytorch3d.ops.sample_farthest_points (n_points sequential argmax passes), teaserpp_python's
+// RobustRegistrationSolver (consistency graph, inlier selection, GNC-TLS rotation, component-wise TLS translation) and the inlier-count
+// acceptance rule (teaserpp_refiner.py:143-149, :276-284).  teaserpp_python and pytorch3d are third-party code absent from the
+// reference tree ("parity unpinned"); the algorithm is the one stated in teaser_core.h, which the host emulation and the float64
+// restatement of the tests share.  Inlier selection is the k-core rule (TEASER++'s KCORE_HEU idea), not the exact maximum clique.
+//
+// Structure: one train of launches on the caller's stream, no host round trip, no atomics, no workgroup waiting for another.
+//   teaser_compact  (row)        ordered compaction of the mask pixels: source points + pixel ids
+//   teaser_fps      (row)        farthest point sampling: a slice of the points and their running minima in registers, the rest streamed
+//                                from L2; one packed-key argmax per pick (wave butterfly, one LDS step across the waves)
+//   teaser_gather   (row, k)     the sampled correspondences
+//   teaser_graph    (tile, row)  the M x M consistency bit matrix, points in LDS, degrees by popcount
+//   teaser_kcore    (row)        k-core peel, one thread per vertex, its matrix row in registers; ordered list of the selected vertices
+//   teaser_solve    (row)        GNC-TLS rotation (float64 sums in a fixed tree, 4x4 Jacobi on one lane), TLS translation by voting,
+//                                inlier count, pose write
+// Roofline: latency-bound tail work (once per detection, after the CNN stages); the sampling kernel is the long pole, a chain of
+// n_points dependent argmax steps per row.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "teaser_core.h"
+
+namespace mp {
+
+using namespace teaser;
+
+// ---- compaction ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void teaser_compact(const float* __restrict__ depth_meas, const int32_t* __restrict__ im_ids,
+                                                           const float* __restrict__ depth_rend, const float* __restrict__ K_rows, int H, int W,
+                                                           int mask_type, float thresh, float* __restrict__ pts, int32_t* __restrict__ pix,
+                                                           int32_t* __restrict__ n_out) {
+  __shared__ int wave_sum[kWaves];
+  __shared__ int base_s;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int px = H * W;
+  const float* dm = depth_meas + (size_t)im_ids[row] * px;
+  const float* dr = depth_rend + (size_t)row * px;
+  const float* K = K_rows + (size_t)row * 9;
+  float* po = pts + (size_t)row * px * 3;
+  int32_t* xo = pix + (size_t)row * px;
+  if (tid == 0) base_s = 0;
+  __syncthreads();
+  for (int start = 0; start < px; start += kThreads) {
+    const int idx = start + tid;
+    float r = 0.0f;
+    bool in = false;
+    if (idx < px) {
+      r = dr[idx];
+      in = mask_pixel(dm[idx], r, mask_type, thresh);
+    }
+    const unsigned long long b = __ballot(in);
+    if (lane == 0) wave_sum[wave] = __popcll(b);
+    __syncthreads();
+    int off = base_s;
+    for (int w = 0; w < wave; ++w) off += wave_sum[w];
+    const int pos = off + __popcll(b & ((1ull << lane) - 1ull));
+    if (in) {   // pos < N <= px: inside the row's slice
+      float p[3];
+      backproject(idx % W, idx / W, r, K, p);
+      po[(size_t)pos * 3] = p[0]; po[(size_t)pos * 3 + 1] = p[1]; po[(size_t)pos * 3 + 2] = p[2];
+      xo[pos] = idx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int t = 0;
+      for (int w = 0; w < kWaves; ++w) t += wave_sum[w];
+      base_s += t;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) n_out[row] = base_s;
+}
+
+// ---- farthest point sampling -------------------------------------------------------------------------------------------------------------
+// points [row][stride][3]; counts[row] of them are valid (clamped to 0 .. stride).  idx_out [row][n_points] (-1 past M), m_out[row] = M.
+// mind [row][stride]: the running minima of the points past the register-resident ones (touched only when N > kFpsResident).
+__global__ __launch_bounds__(kThreads) void teaser_fps(const float* __restrict__ points, int stride, const int32_t* __restrict__ counts, int n_points,
+                                                       int n_min_points, int use_fps, float* __restrict__ mind, int32_t* __restrict__ idx_out,
+                                                       int32_t* __restrict__ m_out) {
+  __shared__ unsigned long long wave_best[2][kWaves];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int N = counts[row];
+  N = N < 0 ? 0 : (N > stride ? stride : N);
+  const int M = n_samples(N, n_points, n_min_points);
+  const float* P = points + (size_t)row * stride * 3;
+  int32_t* out = idx_out + (size_t)row * n_points;
+  if (tid == 0) m_out[row] = M;
+  for (int k = tid; k < n_points; k += kThreads) out[k] = (k < M && !use_fps) ? stride_pick(k, N, M) : (k == 0 && M > 0 ? 0 : -1);
+  if (M < 2 || !use_fps) return;
+  float rp[kFpsReg][3], rmin[kFpsReg];
+#pragma unroll
+  for (int k = 0; k < kFpsReg; ++k) {
+    const int i = tid + k * kThreads;
+    const bool ok = i < N;
+    rp[k][0] = ok ? P[(size_t)i * 3] : 0.0f;
+    rp[k][1] = ok ? P[(size_t)i * 3 + 1] : 0.0f;
+    rp[k][2] = ok ? P[(size_t)i * 3 + 2] : 0.0f;
+    rmin[k] = INFINITY;
+  }
+  float* md = mind + (size_t)row * stride;
+  for (int i = kFpsResident + tid; i < N; i += kThreads) md[i] = INFINITY;   // (a thread only ever reads the entries it wrote)
+  int last = 0;
+  for (int pick = 1; pick < M; ++pick) {
+    const float q[3] = {P[(size_t)last * 3], P[(size_t)last * 3 + 1], P[(size_t)last * 3 + 2]};
+    unsigned long long best = 0ull;
+#pragma unroll
+    for (int k = 0; k < kFpsReg; ++k) {
+      const int i = tid + k * kThreads;
+      if (i < N) {
+        const float d = dist2(rp[k], q);
+        if (d < rmin[k]) rmin[k] = d;
+        const unsigned long long key = fps_key(rmin[k], i);
+        best = key > best ? key : best;
+      }
+    }
+    for (int i = kFpsResident + tid; i < N; i += kThreads) {
+      const float p[3] = {P[(size_t)i * 3], P[(size_t)i * 3 + 1], P[(size_t)i * 3 + 2]};
+      const float d = dist2(p, q);
+      float mn = md[i];
+      if (d < mn) { mn = d; md[i] = d; }
+      const unsigned long long key = fps_key(mn, i);
+      best = key > best ? key : best;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long o = __shfl_xor(best, off);
+      best = o > best ? o : best;
+    }
+    // (two buffers by the parity of the pick: a wave can only overwrite a buffer after the barrier of the pick between, which every
+    //  wave passes after it has read)
+    if (lane == 0) wave_best[pick & 1][wave] = best;
+    __syncthreads();
+    best = 0ull;
+    for (int w = 0; w < kWaves; ++w) {
+      const unsigned long long o = wave_best[pick & 1][w];
+      best = o > best ? o : best;
+    }
+    last = fps_key_index(best);   // < N: the key of point 0 is always a candidate, and every candidate index is < N
+    if (tid == 0) out[pick] = last;
+  }
+}
+
+// the sampled correspondences: source = the compacted point, target = the measured depth back-projected at its pixel
+__global__ void teaser_gather(const float* __restrict__ pts, const int32_t* __restrict__ pix, const int32_t* __restrict__ idx, const int32_t* __restrict__ m_arr,
+                              const float* __restrict__ depth_meas, const int32_t* __restrict__ im_ids, const float* __restrict__ K_rows, int H, int W,
+                              int n_points, float* __restrict__ src_s, float* __restrict__ dst_s) {
+  const int row = blockIdx.y, k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_points || k >= m_arr[row]) return;
+  const size_t px = (size_t)H * W;
+  const int i = idx[(size_t)row * n_points + k];   // 0 <= i < N <= px
+  const int p = pix[row * px + i];                 // 0 <= p < px
+  const float* s = pts + (row * px + i) * 3;
+  float d[3];
+  backproject(p % W, p / W, depth_meas[(size_t)im_ids[row] * px + p], K_rows + (size_t)row * 9, d);
+  for (int c = 0; c < 3; ++c) {
+    src_s[((size_t)row * n_points + k) * 3 + c] = s[c];
+    dst_s[((size_t)row * n_points + k) * 3 + c] = d[c];
+  }
+}
+
+// ---- consistency graph ---------------------------------------------------------------------------------------------------------------------
+// adj [row][kMaxPoints][kWords]: vertex j sits at bit (j >> 5) of word (j & 31) of every row, so that the 32 lanes of a half-wave read 32
+// consecutive points from LDS (12-byte stride: conflict-free) at every step.  A workgroup = 32 vertices x 32 words.
+__global__ __launch_bounds__(kThreads) void teaser_graph(const float* __restrict__ src_s, const float* __restrict__ dst_s, int stride,
+                                                         const int32_t* __restrict__ m_arr, float noise_bound, uint32_t* __restrict__ adj,
+                                                         int32_t* __restrict__ deg) {
+  __shared__ float s[kMaxPoints * 3], d[kMaxPoints * 3];
+  const int row = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const int M = min(m_arr[row], min(stride, kMaxPoints));
+  if (tile * 32 >= M) return;
+  for (int k = tid; k < M * 3; k += kThreads) {
+    s[k] = src_s[(size_t)row * stride * 3 + k];
+    d[k] = dst_s[(size_t)row * stride * 3 + k];
+  }
+  __syncthreads();
+  const int w = tid & 31, i = tile * 32 + (tid >> 5);
+  uint32_t word = 0u;
+  if (i < M) {
+    for (int b = 0; b < 32; ++b) {
+      const int j = b * 32 + w;
+      if (j < M && j != i && edge(s + 3 * i, d + 3 * i, s + 3 * j, d + 3 * j, noise_bound)) word |= 1u << b;
+    }
+  }
+  adj[((size_t)row * kMaxPoints + i) * kWords + w] = word;   // i < kMaxPoints: tile < 32
+  int c = __popc(word);
+  for (int off = 16; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if (w == 0 && i < M) deg[(size_t)row * kMaxPoints + i] = c;
+}
+
+// ---- k-core peel + ordered list of the selected vertices -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void teaser_kcore(const uint32_t* __restrict__ adj, const int32_t* __restrict__ m_arr, int stride, int selection,
+                                                         int32_t* __restrict__ core_out, int32_t* __restrict__ sel_out, int32_t* __restrict__ sel_list,
+                                                         int32_t* __restrict__ msel) {
+  __shared__ unsigned char alive_b[kMaxPoints];
+  __shared__ uint32_t alive_w[kWords];
+  __shared__ int wave_v[kWaves];
+  const int row = blockIdx.x, v = threadIdx.x, lane = v & 63, wave = v >> 6;
+  const int M = min(m_arr[row], min(stride, kMaxPoints));
+  uint32_t nb[kWords];
+#pragma unroll
+  for (int w = 0; w < kWords; ++w) nb[w] = v < M ? adj[((size_t)row * kMaxPoints + v) * kWords + w] : 0u;
+  bool alive = v < M;
+  int core = 0, k = 0;
+  for (int round = 0; round <= kMaxPoints; ++round) {   // (every round with a vertex alive drops at least one)
+    alive_b[v] = alive ? 1 : 0;
+    __syncthreads();
+    if (v < kWords) {
+      uint32_t word = 0u;
+      for (int b = 0; b < 32; ++b) word |= (uint32_t)alive_b[b * 32 + v] << b;
+      alive_w[v] = word;
+    }
+    __syncthreads();
+    int dg = 0x7FFFFFFF;
+    if (alive) {
+      dg = 0;
+#pragma unroll
+      for (int w = 0; w < kWords; ++w) dg += __popc(nb[w] & alive_w[w]);
+    }
+    int mn = dg;
+    for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off));
+    if (lane == 0) wave_v[wave] = mn;
+    __syncthreads();
+    mn = 0x7FFFFFFF;
+    for (int w = 0; w < kWaves; ++w) mn = min(mn, wave_v[w]);
+    if (mn == 0x7FFFFFFF) break;   // (uniform: nobody alive)
+    k = max(k, mn);
+    if (alive && dg <= k) { core = k; alive = false; }
+  }
+  const bool sel = v < M && (selection == kSelectNone || core == k);
+  if (v < M) {
+    if (core_out) core_out[(size_t)row * kMaxPoints + v] = core;
+    if (sel_out) sel_out[(size_t)row * kMaxPoints + v] = sel ? 1 : 0;
+  }
+  __syncthreads();
+  const unsigned long long b = __ballot(sel);
+  if (lane == 0) wave_v[wave] = __popcll(b);
+  __syncthreads();
+  int off = 0, total = 0;
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) off += wave_v[w];
+    total += wave_v[w];
+  }
+  if (sel) sel_list[(size_t)row * kMaxPoints + off + __popcll(b & ((1ull << lane) - 1ull))] = v;
+  if (v == 0) msel[row] = total;
+}
+
+// ---- registration --------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum(double v, double* red) {   // fixed tree inside the wave, the waves in ascending order
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < kWaves; ++w) s += red[w];
+  return s;
+}
+
+__device__ __forceinline__ double block_max(double v, double* red) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  double s = red[0];
+  for (int w = 1; w < kWaves; ++w) s = fmax(s, red[w]);
+  return s;
+}
+
+__global__ __launch_bounds__(kThreads) void teaser_solve(const float* __restrict__ src_s, const float* __restrict__ dst_s, int stride,
+                                                         const int32_t* __restrict__ n_arr, const int32_t* __restrict__ m_arr,
+                                                         const int32_t* __restrict__ sel_list, const int32_t* __restrict__ msel, float noise_bound,
+                                                         int tim_graph, int min_num_inliers, const float* __restrict__ TCO, float* __restrict__ TCO_out,
+                                                         double* __restrict__ Rt_out, int32_t* __restrict__ retval, int32_t* __restrict__ info) {
+  __shared__ float ss[kMaxPoints * 3], ds[kMaxPoints * 3];
+  __shared__ double x[kMaxPoints], sorted[2 * kMaxPoints];
+  __shared__ double red[kWaves], sums[10], tr[3];
+  __shared__ unsigned long long wkey[kWaves];
+  __shared__ int wint[kWaves], e_win;
+  __shared__ GncState g;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int M = max(0, min(m_arr[row], min(stride, kMaxPoints)));
+  const int m = min(msel[row], M);
+  const float* S = src_s + (size_t)row * stride * 3;
+  const float* D = dst_s + (size_t)row * stride * 3;
+  if (M < 1 || m < 3) {   // the row keeps its pose
+    if (tid == 0) {
+      if (TCO_out) for (int k = 0; k < 16; ++k) TCO_out[(size_t)row * 16 + k] = TCO[(size_t)row * 16 + k];
+      if (Rt_out) for (int k = 0; k < 12; ++k) Rt_out[(size_t)row * 12 + k] = (k % 5 == 0) ? 1.0 : 0.0;
+      retval[row] = -1;
+      if (info) {
+        int32_t* f = info + (size_t)row * kInfo;
+        f[0] = n_arr[row]; f[1] = M; f[2] = m; f[3] = 0; f[4] = 0;
+      }
+    }
+    return;
+  }
+  for (int k = tid; k < m; k += kThreads) {
+    const int c = sel_list[(size_t)row * kMaxPoints + k];   // 0 <= c < M: written by teaser_kcore
+    for (int a = 0; a < 3; ++a) { ss[3 * k + a] = S[(size_t)c * 3 + a]; ds[3 * k + a] = D[(size_t)c * 3 + a]; }
+  }
+  __syncthreads();
+  const double beta = (double)noise_bound, beta2 = beta * beta;
+  PairAcc acc;
+  // ---- rotation ----
+  pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R, 0.0, true, g.R, 0.0, true, beta2, &acc);
+  for (int k = 0; k < 9; ++k) {
+    const double s = block_sum(acc.h[k], red);
+    if (tid == 0) sums[k] = s;
+  }
+  if (tid == 0) gnc_begin(&g, sums);
+  __syncthreads();
+  pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R, 0.0, true, g.R, 0.0, false, beta2, &acc);
+  {
+    const double mx = block_max(acc.max_r2, red);
+    if (tid == 0) gnc_set_mu(&g, mx, beta2);
+  }
+  __syncthreads();
+  while (!g.stop) {   // (uniform: g changes only between barriers)
+    pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R_prev, g.mu_prev, g.first_w != 0, g.R, g.mu, false, beta2, &acc);
+    for (int k = 0; k < 9; ++k) {
+      const double s = block_sum(acc.h[k], red);
+      if (tid == 0) sums[k] = s;
+    }
+    const double cost = block_sum(acc.cost, red);
+    __syncthreads();   // (every thread has read g before one lane rewrites it)
+    if (tid == 0) gnc_advance(&g, sums, cost);
+    __syncthreads();
+  }
+  // ---- translation ----
+  for (int axis = 0; axis < 3; ++axis) {
+    for (int k = tid; k < m; k += kThreads)
+      x[k] = (double)ds[3 * k + axis] - ((g.R[3 * axis] * (double)ss[3 * k] + g.R[3 * axis + 1] * (double)ss[3 * k + 1]) + g.R[3 * axis + 2] * (double)ss[3 * k + 2]);
+    __syncthreads();
+    for (int e = tid; e < 2 * m; e += kThreads) sorted[end_rank(x, m, e, beta)] = end_point(x, e, beta);   // a rank is a permutation of 0 .. 2m - 1
+    __syncthreads();
+    // the lowest (cost, e): costs are non-negative, so they order like their bits
+    double est0 = 0.0, est1 = 0.0;
+    unsigned long long kb = ~0ull;
+    int be = 0x7FFFFFFF;
+    if (tid < 2 * m - 1) {
+      kb = cost_bits(tls_candidate(x, m, 0.5 * (sorted[tid] + sorted[tid + 1]), beta, &est0));
+      be = tid;
+    }
+    if (tid + kThreads < 2 * m - 1) {
+      const int e = tid + kThreads;
+      const unsigned long long ob = cost_bits(tls_candidate(x, m, 0.5 * (sorted[e] + sorted[e + 1]), beta, &est1));
+      if (ob < kb) { kb = ob; be = e; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long ob = __shfl_xor(kb, off);
+      const int oe = __shfl_xor(be, off);
+      if (ob < kb || (ob == kb && oe < be)) { kb = ob; be = oe; }
+    }
+    if (lane == 0) { wkey[wave] = kb; wint[wave] = be; }
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long b = wkey[0];
+      int e = wint[0];
+      for (int w = 1; w < kWaves; ++w)
+        if (wkey[w] < b || (wkey[w] == b && wint[w] < e)) { b = wkey[w]; e = wint[w]; }
+      e_win = e;
+    }
+    __syncthreads();
+    if (e_win % kThreads == tid) tr[axis] = e_win < kThreads ? est0 : est1;   // e_win <= 2m - 2 < 2 kThreads
+    __syncthreads();
+  }
+  // ---- acceptance ----
+  int cnt = 0;
+  for (int k = tid; k < M; k += kThreads) cnt += is_inlier(g.R, tr, S + (size_t)k * 3, D + (size_t)k * 3, beta) ? 1 : 0;
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  if (lane == 0) wint[wave] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    int n_in = 0;
+    for (int w = 0; w < kWaves; ++w) n_in += wint[w];
+    const bool ok = n_in >= min_num_inliers;
+    if (TCO_out) {
+      if (ok) compose_pose(g.R, tr, TCO + (size_t)row * 16, TCO_out + (size_t)row * 16);
+      else for (int k = 0; k < 16; ++k) TCO_out[(size_t)row * 16 + k] = TCO[(size_t)row * 16 + k];
+    }
+    if (Rt_out)
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Rt_out[(size_t)row * 12 + 4 * r + c] = g.R[3 * r + c];
+        Rt_out[(size_t)row * 12 + 4 * r + 3] = tr[r];
+      }
+    retval[row] = ok ? 0 : -1;
+    if (info) {
+      int32_t* f = info + (size_t)row * kInfo;
+      f[0] = n_arr[row]; f[1] = M; f[2] = m; f[3] = g.iterations; f[4] = n_in;
+    }
+  }
+}
+
+}  // namespace mp
+
+using namespace mp;
+
+namespace {
+
+struct SolveWs {   // the scratch of graph + cores + solve for n rows
+  uint32_t* adj;
+  int32_t *deg, *core, *sel, *sel_list, *msel, *m_arr, *n_arr;
+};
+
+size_t solve_ws_bytes(int n) {
+  const size_t r = (size_t)n * kMaxPoints;
+  return align256(r * kWords * 4) + 4 * align256(r * 4) + 3 * align256((size_t)n * 4);
+}
+
+SolveWs take_solve_ws(unsigned char*& w, int n) {
+  const size_t r = (size_t)n * kMaxPoints;
+  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
+  SolveWs s;
+  s.adj = (uint32_t*)take(r * kWords * 4);
+  s.deg = (int32_t*)take(r * 4);
+  s.core = (int32_t*)take(r * 4);
+  s.sel = (int32_t*)take(r * 4);
+  s.sel_list = (int32_t*)take(r * 4);
+  s.msel = (int32_t*)take((size_t)n * 4);
+  s.m_arr = (int32_t*)take((size_t)n * 4);
+  s.n_arr = (int32_t*)take((size_t)n * 4);
+  return s;
+}
+
+bool solve_args_ok(float noise_bound, int selection, int tim_graph, int min_num_inliers) {
+  return std::isfinite(noise_bound) && noise_bound > 0.0f && (selection == kSelectKcore || selection == kSelectNone) &&
+         (tim_graph == kTimChain || tim_graph == kTimComplete) && min_num_inliers >= 0;
+}
+
+// graph -> cores -> solve on correspondences [n][stride][3] whose counts sit in ws.m_arr; optional [n][stride] copies of the telemetry
+int run_solve(const float* src, const float* dst, int n, int stride, const SolveWs& ws, float noise_bound, int selection, int tim_graph,
+              int min_num_inliers, const float* TCO, float* TCO_out, double* Rt, int32_t* retval, int32_t* deg, int32_t* core, int32_t* sel,
+              int32_t* info, hipStream_t s) {
+  MP_CHECK_HIP(hipMemsetAsync(ws.deg, 0xFF, 3 * align256((size_t)n * kMaxPoints * 4), s));   // deg, core, sel (adjacent): -1 past a row's M
+  hipLaunchKernelGGL(teaser_graph, dim3(kMaxPoints / 32, n), dim3(kThreads), 0, s, src, dst, stride, ws.m_arr, noise_bound, ws.adj, ws.deg);
+  hipLaunchKernelGGL(teaser_kcore, dim3(n), dim3(kThreads), 0, s, ws.adj, ws.m_arr, stride, selection, ws.core, ws.sel, ws.sel_list, ws.msel);
+  hipLaunchKernelGGL(teaser_solve, dim3(n), dim3(kThreads), 0, s, src, dst, stride, ws.n_arr, ws.m_arr, ws.sel_list, ws.msel, noise_bound, tim_graph,
+                     min_num_inliers, TCO, TCO_out, Rt, retval, info);
+  // telemetry [n][stride] from the [n][kMaxPoints] scratch (-1 past a row's M)
+  const int32_t* from[3] = {ws.deg, ws.core, ws.sel};
+  int32_t* to[3] = {deg, core, sel};
+  for (int k = 0; k < 3; ++k)
+    if (to[k])
+      MP_CHECK_HIP(hipMemcpy2DAsync(to[k], (size_t)stride * 4, from[k], (size_t)kMaxPoints * 4, (size_t)stride * 4, n, hipMemcpyDeviceToDevice, s));
+  MP_CHECK_HIP(hipGetLastError());
+  return MP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t mp_fps_workspace_bytes(int n_rows, int stride) {
+  if (n_rows < 0 || stride < 1) return 0;
+  return align256((size_t)n_rows * stride * 4) + 256;
+}
+
+extern "C" int mp_fps(const float* d_points, const int32_t* d_counts, int n_rows, int stride, int n_points, int use_fps, int32_t* d_idx, int32_t* d_m,
+                      void* d_ws, size_t ws_bytes, mp_stream stream) {
+  MP_REQUIRE(d_points && d_counts && d_idx && d_m && d_ws, "mp_fps: null pointer");
+  MP_REQUIRE(n_rows >= 0 && n_rows <= 65535 && stride >= 1 && (long long)stride * 3 < 2147483647LL && n_points >= 1, "mp_fps: bad size");
+  MP_REQUIRE(ws_bytes >= mp_fps_workspace_bytes(n_rows, stride), "mp_fps: workspace too small");
+  if (n_rows == 0) return MP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope prof("fps", 0.0, (double)n_rows * stride * 12.0, s);
+  hipLaunchKernelGGL(teaser_fps, dim3(n_rows), dim3(kThreads), 0, s, d_points, stride, d_counts, n_points, 1, use_fps ? 1 : 0, (float*)d_ws, d_idx, d_m);
+  MP_CHECK_HIP(hipGetLastError());
+  return MP_OK;
+}
+
+extern "C" size_t mp_teaser_workspace_bytes(int n_rows, int H, int W) {
+  if (n_rows < 0 || H < 0 || W < 0 || (long long)H * W * 3 >= 2147483647LL) return 0;
+  const size_t px = (size_t)H * W, n = (size_t)n_rows;
+  return solve_ws_bytes(n_rows) + 2 * align256(n * kMaxPoints * 12) + align256(n * kMaxPoints * 4) + align256(n * px * 12) + 2 * align256(n * px * 4) + 256;
+}
+
+extern "C" int mp_teaser_solve(const float* d_src, const float* d_dst, const int32_t* d_counts, int n_rows, int stride, float noise_bound,
+                               int inlier_selection, int tim_graph, int min_num_inliers, double* d_Rt, int32_t* d_retval, int32_t* d_degree,
+                               int32_t* d_core, int32_t* d_selected, int32_t* d_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
+  MP_REQUIRE(d_src && d_dst && d_counts && d_Rt && d_retval && d_ws, "mp_teaser_solve: null pointer");
+  MP_REQUIRE(n_rows >= 0 && n_rows <= 65535 && stride >= 1 && stride <= kMaxPoints, "mp_teaser_solve: 0 .. 65535 rows of 1 .. 1024 correspondences");
+  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers), "mp_teaser_solve: bad noise bound, selection, graph or inlier count");
+  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes(n_rows, 0, 0), "mp_teaser_solve: workspace too small");
+  if (n_rows == 0) return MP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* w = (unsigned char*)d_ws;
+  const SolveWs ws = take_solve_ws(w, n_rows);
+  ProfScope prof("teaser_solve", 0.0, (double)n_rows * stride * 24.0, s);
+  MP_CHECK_HIP(hipMemcpyAsync(ws.m_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));   // (the kernels clamp a count to 0 .. stride)
+  MP_CHECK_HIP(hipMemcpyAsync(ws.n_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));
+  return run_solve(d_src, d_dst, n_rows, stride, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, nullptr, nullptr, d_Rt, d_retval,
+                   d_degree, d_core, d_selected, d_info, s);
+}
+
+extern "C" int mp_teaser_refine(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
+                                const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
+                                float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
+                                int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
+                                int32_t* d_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
+  MP_REQUIRE(d_depth_meas && d_im_ids && d_depth_rend && d_K_rows && d_TCO && d_TCO_out && d_retval && d_ws, "mp_teaser_refine: null pointer");
+  MP_REQUIRE(n_images > 0 && n_rows >= 0 && n_rows <= 65535 && H >= 1 && W >= 1 && (long long)H * W * 3 < 2147483647LL, "mp_teaser_refine: bad size");
+  MP_REQUIRE(n_points >= 1 && n_points <= kMaxPoints, "mp_teaser_refine: n_points must be 1 .. 1024 (the consistency graph is a 1024 x 1024 bit matrix)");
+  MP_REQUIRE((mask_type == kMaskSimple || mask_type == kMaskThreshold) && n_min_points >= 0 && std::isfinite(depth_delta_thresh),
+             "mp_teaser_refine: bad mask type, threshold or n_min_points");
+  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers), "mp_teaser_refine: bad noise bound, selection, graph or inlier count");
+  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes(n_rows, H, W), "mp_teaser_refine: workspace too small");
+  if (n_rows == 0) return MP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t px = (size_t)H * W, n = (size_t)n_rows;
+  unsigned char* w = (unsigned char*)d_ws;
+  const SolveWs ws = take_solve_ws(w, n_rows);
+  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
+  float* src_s = (float*)take(n * kMaxPoints * 12);
+  float* dst_s = (float*)take(n * kMaxPoints * 12);
+  int32_t* idx = (int32_t*)take(n * kMaxPoints * 4);
+  float* pts = (float*)take(n * px * 12);
+  int32_t* pix = (int32_t*)take(n * px * 4);
+  float* mind = (float*)take(n * px * 4);
+  ProfScope prof("teaser_refine", 0.0, (double)n_rows * px * 8.0, s);
+  hipLaunchKernelGGL(teaser_compact, dim3(n_rows), dim3(kThreads), 0, s, d_depth_meas, d_im_ids, d_depth_rend, d_K_rows, H, W, mask_type, depth_delta_thresh,
+                     pts, pix, ws.n_arr);
+  hipLaunchKernelGGL(teaser_fps, dim3(n_rows), dim3(kThreads), 0, s, pts, (int)px, ws.n_arr, n_points, n_min_points, use_fps ? 1 : 0, mind, idx, ws.m_arr);
+  hipLaunchKernelGGL(teaser_gather, dim3(ceil_div(n_points, 256), n_rows), dim3(256), 0, s, pts, pix, idx, ws.m_arr, d_depth_meas, d_im_ids, d_K_rows, H, W,
+                     n_points, src_s, dst_s);
+  if (d_sample_idx) MP_CHECK_HIP(hipMemcpyAsync(d_sample_idx, idx, n * n_points * 4, hipMemcpyDeviceToDevice, s));
+  return run_solve(src_s, dst_s, n_rows, n_points, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, d_TCO, d_TCO_out, d_Rt, d_retval, d_degree,
+                   d_core, d_selected, d_info, s);
+}

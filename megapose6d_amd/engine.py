@@ -1150,6 +1150,100 @@ def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch
 
 
 # --------------------------------------------------------------------------- #
+TEASER_MAX_POINTS = 1024           # correspondences of one row, at most (the consistency graph is a 1024 x 1024 bit matrix)
+TEASER_MASK_TYPES = {"simple": 0, "threshold": 1}
+TEASER_SELECTIONS = {"kcore": 0, "none": 1}
+TEASER_TIM_GRAPHS = {"chain": 0, "complete": 1}
+TEASER_INFO = ("N", "M", "n_selected", "gnc_iterations", "num_inliers")
+
+
+def _teaser_mode(name: str, table: Dict[str, int], value: str) -> int:
+    if value not in table:
+        raise EngineError(f"{name} must be one of {sorted(table)}, got {value!r}")
+    return table[value]
+
+
+def farthest_point_sample(points: torch.Tensor, counts: torch.Tensor, n_points: int, use_fps: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Farthest point sampling of point sets (mp_fps).  points [n,stride,3] float32 and counts [n] int32 on the device (the first
+    counts[r] points of row r are valid) -> idx [n,n_points] int32 (-1 past M = min(n_points, count)), M [n] int32.  Pick 0 is point 0,
+    every later pick the point with the largest running minimum of the squared fp32 distance to the picks so far, a tie to the lowest
+    index; use_fps=False takes index floor(k * count / M)."""
+    points, counts = _dev_f32(points), _dev_i32(counts)
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[1] < 1 or counts.shape != (points.shape[0],) or int(n_points) < 1:
+        raise EngineError(f"points must be [n,stride >= 1,3], counts [n] and n_points >= 1, got {tuple(points.shape)}, {tuple(counts.shape)}, {n_points}")
+    n, stride = int(points.shape[0]), int(points.shape[1])
+    lib = _lib.load()
+    ws = _workspace(lib.mp_fps_workspace_bytes(n, stride), points.device)
+    idx = torch.empty(n, int(n_points), dtype=torch.int32, device=points.device)
+    m = torch.empty(n, dtype=torch.int32, device=points.device)
+    check(lib.mp_fps(points.data_ptr(), counts.data_ptr(), n, stride, int(n_points), int(bool(use_fps)), idx.data_ptr(), m.data_ptr(), ws.data_ptr(),
+                     ws.numel(), _stream()))
+    return idx, m
+
+
+def _teaser_telemetry(n: int, stride: int, device, want: bool):
+    if not want:
+        return None, None, None, None
+    return tuple(torch.full((n, stride), -1, dtype=torch.int32, device=device) for _ in range(3)) + (torch.zeros(n, len(TEASER_INFO), dtype=torch.int32, device=device),)
+
+
+def teaser_solve(src: torch.Tensor, dst: torch.Tensor, counts: torch.Tensor, noise_bound: float = 0.01, min_num_inliers: int = 0,
+                 inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False):
+    """Robust registration of given correspondences (mp_teaser_solve; the rules are in csrc/teaser_core.h).  src, dst [n,stride <= 1024,3]
+    float32, counts [n] int32 on the device -> Rt [n,3,4] float64 with dst ~ R src + t, retval [n] int32 (0 when num_inliers >=
+    min_num_inliers, else -1); with telemetry also a dict of degree, core, selected [n,stride] (-1 past a row's count) and info
+    [n,5] = TEASER_INFO."""
+    src, dst, counts = _dev_f32(src), _dev_f32(dst), _dev_i32(counts)
+    if src.dim() != 3 or src.shape[2] != 3 or dst.shape != src.shape or not 1 <= src.shape[1] <= TEASER_MAX_POINTS or counts.shape != (src.shape[0],):
+        raise EngineError(f"src and dst must be [n,1 .. {TEASER_MAX_POINTS},3] and counts [n], got {tuple(src.shape)}, {tuple(dst.shape)}, {tuple(counts.shape)}")
+    sel, graph = _teaser_mode("inlier_selection", TEASER_SELECTIONS, inlier_selection), _teaser_mode("rotation_tim_graph", TEASER_TIM_GRAPHS, rotation_tim_graph)
+    n, stride, dev = int(src.shape[0]), int(src.shape[1]), src.device
+    lib = _lib.load()
+    ws = _workspace(lib.mp_teaser_workspace_bytes(n, 0, 0), dev)
+    Rt = torch.empty(n, 3, 4, dtype=torch.float64, device=dev)
+    retval = torch.empty(n, dtype=torch.int32, device=dev)
+    degree, core, selected, info = _teaser_telemetry(n, stride, dev, telemetry)
+    check(lib.mp_teaser_solve(src.data_ptr(), dst.data_ptr(), counts.data_ptr(), n, stride, float(noise_bound), sel, graph, int(min_num_inliers),
+                              Rt.data_ptr(), retval.data_ptr(), _ptr(degree), _ptr(core), _ptr(selected), _ptr(info), ws.data_ptr(), ws.numel(), _stream()))
+    return (Rt, retval, dict(degree=degree, core=core, selected=selected, info=info)) if telemetry else (Rt, retval)
+
+
+def teaser_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_rows: torch.Tensor, TCO: torch.Tensor,
+                  mask_type: str = "simple", depth_delta_thresh: float = 0.1, n_min_points: int = 100, n_points: int = 1000,
+                  noise_bound: float = 0.01, min_num_inliers: int = 50, use_farthest_point_sampling: bool = True,
+                  inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False):
+    """The TEASER++ depth refiner from depth frames (mp_teaser_refine): depth_meas [B,H,W], im_ids [N], depth_rend [N,H,W] rendered at
+    TCO [N,4,4], K_rows [N,3,3] -> (TCO_refined [N,4,4], retval [N] int32 (0 refined / -1 input pose kept), info [N,5] int32 =
+    TEASER_INFO); with telemetry also a dict of Rt [N,3,4] float64, sample_idx [N,n_points] and degree, core, selected [N,n_points]."""
+    depth_meas, depth_rend, K_rows, TCO, im_ids = _dev_f32(depth_meas), _dev_f32(depth_rend), _dev_f32(K_rows), _dev_f32(TCO), _dev_i32(im_ids)
+    if depth_meas.dim() != 3 or TCO.dim() != 3 or TCO.shape[1:] != (4, 4):
+        raise EngineError(f"depth_meas must be [B,H,W] and TCO [N,4,4], got {tuple(depth_meas.shape)} and {tuple(TCO.shape)}")
+    n_im, H, W = (int(v) for v in depth_meas.shape)
+    N, dev = int(TCO.shape[0]), TCO.device
+    if depth_rend.shape != (N, H, W) or K_rows.shape != (N, 3, 3) or im_ids.shape != (N,):
+        raise EngineError(f"depth_rend must be [{N},{H},{W}], K_rows [{N},3,3], im_ids [{N}]")
+    if not 1 <= int(n_points) <= TEASER_MAX_POINTS:
+        raise EngineError(f"n_points must be 1 .. {TEASER_MAX_POINTS}, got {n_points}")
+    mask = _teaser_mode("mask_type", TEASER_MASK_TYPES, mask_type)
+    sel, graph = _teaser_mode("inlier_selection", TEASER_SELECTIONS, inlier_selection), _teaser_mode("rotation_tim_graph", TEASER_TIM_GRAPHS, rotation_tim_graph)
+    lib = _lib.load()
+    ws = _workspace(lib.mp_teaser_workspace_bytes(N, H, W), dev)
+    out = torch.empty_like(TCO)
+    retval = torch.empty(N, dtype=torch.int32, device=dev)
+    degree, core, selected, _ = _teaser_telemetry(N, int(n_points), dev, telemetry)
+    info = torch.zeros(N, len(TEASER_INFO), dtype=torch.int32, device=dev)
+    Rt = torch.empty(N, 3, 4, dtype=torch.float64, device=dev) if telemetry else None
+    sample_idx = torch.empty(N, int(n_points), dtype=torch.int32, device=dev) if telemetry else None
+    check(lib.mp_teaser_refine(depth_meas.data_ptr(), n_im, im_ids.data_ptr(), depth_rend.data_ptr(), K_rows.data_ptr(), TCO.data_ptr(), N, H, W, mask,
+                               float(depth_delta_thresh), int(n_min_points), int(n_points), float(noise_bound), int(min_num_inliers),
+                               int(bool(use_farthest_point_sampling)), sel, graph, out.data_ptr(), retval.data_ptr(), _ptr(Rt), _ptr(sample_idx), _ptr(degree),
+                               _ptr(core), _ptr(selected), info.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    if telemetry:
+        return out, retval, info, dict(Rt=Rt, sample_idx=sample_idx, degree=degree, core=core, selected=selected)
+    return out, retval, info
+
+
+# --------------------------------------------------------------------------- #
 class DetectorNet(_Handle):
     """mp_detector: the Mask R-CNN (ResNet-50 + FPN) detection graph resident on the device, one call per image batch
     (csrc/detector.hip).  `state_dict` uses torchvision's keys (= a checkpoint of the reference's DetectorMaskRCNN)."""

@@ -209,18 +209,29 @@ def load_pose_models(coarse_run_id: str, refiner_run_id: str, object_dataset, fo
     return load_model(coarse_run_id), load_model(refiner_run_id), mesh_db
 
 
-def load_named_model(model_name: str, object_dataset, n_workers: int = 4, bsz_images: int = 128) -> PoseEstimator:
+def make_depth_refiner(name: Optional[str], mesh_db, renderer):
+    """The depth refiner a configuration names: "ICP" / "icp" -> ICPRefiner, "teaserpp" -> TeaserppRefiner (the reference's
+    evaluation/evaluation.py:130-137), None -> none; any other name is an error, never a silent run without a refiner."""
+    if name is None:
+        return None
+    from .icp_refiner import ICPRefiner, TeaserppRefiner
+
+    if name in ("ICP", "icp"):
+        return ICPRefiner(mesh_db, renderer)
+    if name == "teaserpp":
+        return TeaserppRefiner(mesh_db, renderer)
+    raise ValueError(f"unknown depth refiner {name!r}: expected 'icp' or 'teaserpp'")
+
+
+def load_named_model(model_name: str, object_dataset, n_workers: int = 4, bsz_images: int = 128, depth_refiner: Optional[str] = None) -> PoseEstimator:
+    """depth_refiner (engine extension): replaces the depth refiner the named recipe lists ("icp" / "teaserpp")."""
     model = NAMED_MODELS[model_name]
     coarse_model, refiner_model, mesh_db = load_pose_models(
         coarse_run_id=model["coarse_run_id"], refiner_run_id=model["refiner_run_id"], object_dataset=object_dataset,
         force_panda3d_renderer=True, renderer_kwargs={"preload_cache": False, "split_objects": False, "n_workers": n_workers},
         models_root=LOCAL_DATA_DIR / "megapose-models")
-    depth_refiner = None
-    if model.get("depth_refiner", None) == "ICP":
-        from .icp_refiner import ICPRefiner
-
-        depth_refiner = ICPRefiner(mesh_db, refiner_model.renderer)
-    return PoseEstimator(refiner_model=refiner_model, coarse_model=coarse_model, detector_model=None, depth_refiner=depth_refiner,
+    refiner = make_depth_refiner(depth_refiner if depth_refiner is not None else model.get("depth_refiner", None), mesh_db, refiner_model.renderer)
+    return PoseEstimator(refiner_model=refiner_model, coarse_model=coarse_model, detector_model=None, depth_refiner=refiner,
                          bsz_objects=8, bsz_images=bsz_images)
 
 
