@@ -722,7 +722,8 @@ int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const int32_t* d_i
 /* compute_teaserpp_refinement + :193-289 TeaserppRefiner.refine_poses (masks               */
 /* refiner_utils.py:30-56, points visualization/meshcat_utils.py:278-300).  pytorch3d's     */
 /* farthest point sampling and teaserpp_python's solver are third party (parity unpinned);  */
-/* the algorithm is the one stated in csrc/teaser_core.h (csrc/teaser.hip).                 */
+/* the algorithm is the one stated in csrc/teaser_core.h and csrc/teaser_clique_core.h      */
+/* (csrc/teaser.hip, csrc/teaser_clique.hip).                                               */
 /* ------------------------------------------------------------------------------------ */
 /* Farthest point sampling of n_rows point sets d_points [n_rows,stride,3] fp32, of which the first d_counts[r] (clamped to 0 .. stride)
    are valid: M = min(n_points, count) picks; pick 0 is point 0, every later pick the point with the largest running minimum of the
@@ -736,7 +737,7 @@ int mp_fps(const float* d_points, const int32_t* d_counts, int n_rows, int strid
 size_t mp_teaser_workspace_bytes(int n_rows, int H, int W);
 /* Robust registration of given correspondences d_src[r][k] -> d_dst[r][k], k < d_counts[r] <= stride <= 1024 ([n_rows,stride,3] fp32):
    consistency graph (edge when the two pair distances differ by at most 2 noise_bound), inlier selection (0: the vertices of the largest
-   core number; 1: every vertex), GNC-TLS rotation over the TIMs of the selected vertices (tim_graph 0: consecutive pairs, 1: all pairs),
+   core number; 1: every vertex; 2: a maximum clique, see mp_teaser_solve_ex), GNC-TLS rotation over the TIMs of the selected vertices (tim_graph 0: consecutive pairs, 1: all pairs),
    component-wise TLS translation, inlier count over all correspondences.  d_Rt [n_rows,12] float64 = [R t] row-major (the identity for
    a row with fewer than 3 selected vertices), d_retval [n_rows] = 0 when num_inliers >= min_num_inliers, else -1.  Optional (NULL to
    skip): d_degree, d_core, d_selected [n_rows,stride] int32 (-1 past a row's count), d_info [n_rows,5] int32 =
@@ -756,6 +757,34 @@ int mp_teaser_refine(const float* d_depth_meas, int n_images, const int32_t* d_i
                      float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
                      int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
                      int32_t* d_info, void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* Exact maximum-clique inlier selection (inlier_selection 2: TEASER++'s default, PMC_EXACT): a bounded, deterministic branch and bound
+   on the consistency graph (the rule is stated in csrc/teaser_clique_core.h, the kernel is csrc/teaser_clique.hip).  The selected
+   vertices are the members of a maximum clique -- of the equal ones the first the rule meets -- or, when the search has coloured more
+   than max_clique_steps vertices, the best clique found until then (exact = 0).  mp_max_clique_default_steps() is the budget the
+   entries without the argument use; an argument may ask for 0 .. 16 times as much.
+   mp_max_clique: the search alone on n_rows adjacency matrices d_adjacency [n_rows,stride,stride] uint8, stride <= 1024, of which the
+   first d_counts[r] vertices (NULL: stride) are the graph; an edge exists when i != j and a[i][j] | a[j][i].  d_members [n_rows,stride]
+   int32 = the members in ascending order, -1 past the size; d_info [n_rows,4] int32 = size, upper bound (largest core number + 1),
+   exact, steps.  Three launches (pack, peel, search), one wave per row, no atomics. */
+int mp_max_clique_default_steps(void);
+size_t mp_max_clique_workspace_bytes(int n_rows, int stride);
+int mp_max_clique(const uint8_t* d_adjacency, const int32_t* d_counts, int n_rows, int stride, int max_steps, int32_t* d_members, int32_t* d_info,
+                  void* d_workspace, size_t workspace_bytes, mp_stream stream);
+/* mp_teaser_workspace_bytes, mp_teaser_solve and mp_teaser_refine with the step budget and the optional d_clique_info [n_rows,4] (as
+   d_info of mp_max_clique; written with inlier_selection 2 only).  The size also takes stride (= n_points of mp_teaser_refine) and the
+   selection: only selection 2 allocates search stacks.  The three entries above are these with the default budget and NULL; they
+   accept inlier_selection 2 when the workspace has the size given here.  With selections 0 and 1 nothing differs, bit for bit.
+   A negative max_clique_steps or one above 16 times the default returns non-zero before anything is launched. */
+size_t mp_teaser_workspace_bytes_ex(int n_rows, int H, int W, int stride, int inlier_selection);
+int mp_teaser_solve_ex(const float* d_src, const float* d_dst, const int32_t* d_counts, int n_rows, int stride, float noise_bound,
+                       int inlier_selection, int tim_graph, int min_num_inliers, double* d_Rt, int32_t* d_retval, int32_t* d_degree,
+                       int32_t* d_core, int32_t* d_selected, int32_t* d_info, int max_clique_steps, int32_t* d_clique_info, void* d_workspace,
+                       size_t workspace_bytes, mp_stream stream);
+int mp_teaser_refine_ex(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
+                        const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
+                        float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
+                        int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
+                        int32_t* d_info, int max_clique_steps, int32_t* d_clique_info, void* d_workspace, size_t workspace_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Detector network: replaces the torchvision Mask R-CNN    */

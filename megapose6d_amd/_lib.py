@@ -188,6 +188,13 @@ SIGNATURES = {
     "mp_teaser_solve": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_teaser_refine": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _sz, _vp]),
+    "mp_max_clique_default_steps": (_i, []),
+    "mp_max_clique_workspace_bytes": (_sz, [_i, _i]),
+    "mp_max_clique": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mp_teaser_workspace_bytes_ex": (_sz, [_i, _i, _i, _i, _i]),
+    "mp_teaser_solve_ex": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "mp_teaser_refine_ex": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _i, _vp, _vp, _sz, _vp]),
     "mp_icp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mp_icp_refine": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_icp_nn_max_points": (_i, []),

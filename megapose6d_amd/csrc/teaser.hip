@@ -5,7 +5,8 @@
 // RobustRegistrationSolver (consistency graph, inlier selection, GNC-TLS rotation, component-wise TLS translation) and the inlier-count
 // acceptance rule (teaserpp_refiner.py:143-149, :276-284).  teaserpp_python and pytorch3d are third-party code absent from the
 // reference tree ("parity unpinned"); the algorithm is the one stated in teaser_core.h, which the host emulation and the float64
-// restatement of the tests share.  Inlier selection is the k-core rule (TEASER++'s KCORE_HEU idea), not the exact maximum clique.
+// restatement of the tests share.  Inlier selection is the k-core rule (TEASER++'s KCORE_HEU idea) by default; the exact maximum clique
+// (TEASER++'s default) is selection 2, searched by teaser_clique.hip under a step budget.
 //
 // Structure: one train of launches on the caller's stream, no host round trip, no atomics, no workgroup waiting for another.
 //   teaser_compact  (row)        ordered compaction of the mask pixels: source points + pixel ids
@@ -14,6 +15,7 @@
 //   teaser_gather   (row, k)     the sampled correspondences
 //   teaser_graph    (tile, row)  the M x M consistency bit matrix, points in LDS, degrees by popcount
 //   teaser_kcore    (row)        k-core peel, one thread per vertex, its matrix row in registers; ordered list of the selected vertices
+//   clique_search   (rows)       selection 2 only (teaser_clique.hip): one wave per row replaces that list by the maximum clique's
 //   teaser_solve    (row)        GNC-TLS rotation (float64 sums in a fixed tree, 4x4 Jacobi on one lane), TLS translation by voting,
 //                                inlier count, pose write
 // Roofline: latency-bound tail work (once per detection, after the CNN stages); the sampling kernel is the long pole, a chain of
@@ -22,6 +24,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "teaser_clique_core.h"
 #include "teaser_core.h"
 
 namespace mp {
@@ -404,14 +407,15 @@ namespace {
 struct SolveWs {   // the scratch of graph + cores + solve for n rows
   uint32_t* adj;
   int32_t *deg, *core, *sel, *sel_list, *msel, *m_arr, *n_arr;
+  void* clique;   // the search stacks of selection 2 (null otherwise)
 };
 
-size_t solve_ws_bytes(int n) {
+size_t solve_ws_bytes(int n, int stride, int selection) {
   const size_t r = (size_t)n * kMaxPoints;
-  return align256(r * kWords * 4) + 4 * align256(r * 4) + 3 * align256((size_t)n * 4);
+  return align256(r * kWords * 4) + 4 * align256(r * 4) + 3 * align256((size_t)n * 4) + (selection == kSelectMaxClique ? clique_search_ws_bytes(n, stride) : 0);
 }
 
-SolveWs take_solve_ws(unsigned char*& w, int n) {
+SolveWs take_solve_ws(unsigned char*& w, int n, int stride, int selection) {
   const size_t r = (size_t)n * kMaxPoints;
   auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
   SolveWs s;
@@ -423,21 +427,26 @@ SolveWs take_solve_ws(unsigned char*& w, int n) {
   s.msel = (int32_t*)take((size_t)n * 4);
   s.m_arr = (int32_t*)take((size_t)n * 4);
   s.n_arr = (int32_t*)take((size_t)n * 4);
+  s.clique = selection == kSelectMaxClique ? take(clique_search_ws_bytes(n, stride)) : nullptr;
   return s;
 }
 
-bool solve_args_ok(float noise_bound, int selection, int tim_graph, int min_num_inliers) {
-  return std::isfinite(noise_bound) && noise_bound > 0.0f && (selection == kSelectKcore || selection == kSelectNone) &&
-         (tim_graph == kTimChain || tim_graph == kTimComplete) && min_num_inliers >= 0;
+bool solve_args_ok(float noise_bound, int selection, int tim_graph, int min_num_inliers, int max_steps) {
+  return std::isfinite(noise_bound) && noise_bound > 0.0f && (selection == kSelectKcore || selection == kSelectNone || selection == kSelectMaxClique) &&
+         (tim_graph == kTimChain || tim_graph == kTimComplete) && min_num_inliers >= 0 && clique_steps_ok(max_steps);
 }
 
-// graph -> cores -> solve on correspondences [n][stride][3] whose counts sit in ws.m_arr; optional [n][stride] copies of the telemetry
+// graph -> cores (-> maximum clique) -> solve on correspondences [n][stride][3] whose counts sit in ws.m_arr; optional [n][stride] copies of the telemetry
 int run_solve(const float* src, const float* dst, int n, int stride, const SolveWs& ws, float noise_bound, int selection, int tim_graph,
-              int min_num_inliers, const float* TCO, float* TCO_out, double* Rt, int32_t* retval, int32_t* deg, int32_t* core, int32_t* sel,
-              int32_t* info, hipStream_t s) {
+              int min_num_inliers, int max_steps, const float* TCO, float* TCO_out, double* Rt, int32_t* retval, int32_t* deg, int32_t* core,
+              int32_t* sel, int32_t* info, int32_t* clique_info, hipStream_t s) {
   MP_CHECK_HIP(hipMemsetAsync(ws.deg, 0xFF, 3 * align256((size_t)n * kMaxPoints * 4), s));   // deg, core, sel (adjacent): -1 past a row's M
   hipLaunchKernelGGL(teaser_graph, dim3(kMaxPoints / 32, n), dim3(kThreads), 0, s, src, dst, stride, ws.m_arr, noise_bound, ws.adj, ws.deg);
   hipLaunchKernelGGL(teaser_kcore, dim3(n), dim3(kThreads), 0, s, ws.adj, ws.m_arr, stride, selection, ws.core, ws.sel, ws.sel_list, ws.msel);
+  if (selection == kSelectMaxClique) {   // the clique's members replace the vertices of the largest core number in sel, sel_list and msel
+    const int rc = clique_search_launch(ws.adj, ws.core, ws.m_arr, n, stride, max_steps, ws.sel, ws.sel_list, ws.msel, clique_info, ws.clique, s);
+    if (rc != MP_OK) return rc;
+  }
   hipLaunchKernelGGL(teaser_solve, dim3(n), dim3(kThreads), 0, s, src, dst, stride, ws.n_arr, ws.m_arr, ws.sel_list, ws.msel, noise_bound, tim_graph,
                      min_num_inliers, TCO, TCO_out, Rt, retval, info);
   // telemetry [n][stride] from the [n][kMaxPoints] scratch (-1 past a row's M)
@@ -470,47 +479,89 @@ extern "C" int mp_fps(const float* d_points, const int32_t* d_counts, int n_rows
   return MP_OK;
 }
 
-extern "C" size_t mp_teaser_workspace_bytes(int n_rows, int H, int W) {
-  if (n_rows < 0 || H < 0 || W < 0 || (long long)H * W * 3 >= 2147483647LL) return 0;
+extern "C" size_t mp_teaser_workspace_bytes_ex(int n_rows, int H, int W, int stride, int inlier_selection) {
+  if (n_rows < 0 || H < 0 || W < 0 || (long long)H * W * 3 >= 2147483647LL || stride < 1 || stride > kMaxPoints) return 0;
+  if (!(inlier_selection == kSelectKcore || inlier_selection == kSelectNone || inlier_selection == kSelectMaxClique)) return 0;
   const size_t px = (size_t)H * W, n = (size_t)n_rows;
-  return solve_ws_bytes(n_rows) + 2 * align256(n * kMaxPoints * 12) + align256(n * kMaxPoints * 4) + align256(n * px * 12) + 2 * align256(n * px * 4) + 256;
+  return solve_ws_bytes(n_rows, stride, inlier_selection) + 2 * align256(n * kMaxPoints * 12) + align256(n * kMaxPoints * 4) + align256(n * px * 12) +
+         2 * align256(n * px * 4) + 256;
+}
+
+extern "C" size_t mp_teaser_workspace_bytes(int n_rows, int H, int W) { return mp_teaser_workspace_bytes_ex(n_rows, H, W, kMaxPoints, kSelectKcore); }
+
+extern "C" int mp_max_clique_default_steps(void) { return kCliqueDefaultSteps; }
+
+extern "C" size_t mp_max_clique_workspace_bytes(int n_rows, int stride) {
+  if (n_rows < 0 || stride < 1 || stride > kMaxPoints) return 0;
+  return solve_ws_bytes(n_rows, stride, kSelectMaxClique) + 256;
+}
+
+extern "C" int mp_max_clique(const uint8_t* d_adjacency, const int32_t* d_counts, int n_rows, int stride, int max_steps, int32_t* d_members, int32_t* d_info,
+                             void* d_ws, size_t ws_bytes, mp_stream stream) {
+  MP_REQUIRE(d_adjacency && d_members && d_info && d_ws, "mp_max_clique: null pointer");
+  MP_REQUIRE(n_rows >= 0 && n_rows <= 65535 && stride >= 1 && stride <= kMaxPoints, "mp_max_clique: 0 .. 65535 rows of 1 .. 1024 vertices");
+  MP_REQUIRE(clique_steps_ok(max_steps), "mp_max_clique: max_steps must be 0 .. 16 x the default budget");
+  MP_REQUIRE(ws_bytes >= mp_max_clique_workspace_bytes(n_rows, stride), "mp_max_clique: workspace too small");
+  if (n_rows == 0) return MP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* w = (unsigned char*)d_ws;
+  const SolveWs ws = take_solve_ws(w, n_rows, stride, kSelectMaxClique);
+  ProfScope prof("max_clique", 0.0, (double)n_rows * stride * stride, s);
+  int rc = clique_pack_launch(d_adjacency, d_counts, n_rows, stride, ws.adj, ws.deg, ws.m_arr, s);
+  if (rc != MP_OK) return rc;
+  hipLaunchKernelGGL(teaser_kcore, dim3(n_rows), dim3(kThreads), 0, s, ws.adj, ws.m_arr, stride, kSelectKcore, ws.core, ws.sel, ws.sel_list, ws.msel);
+  rc = clique_search_launch(ws.adj, ws.core, ws.m_arr, n_rows, stride, max_steps, ws.sel, ws.sel_list, ws.msel, d_info, ws.clique, s);
+  if (rc != MP_OK) return rc;
+  MP_CHECK_HIP(hipMemcpy2DAsync(d_members, (size_t)stride * 4, ws.sel_list, (size_t)kMaxPoints * 4, (size_t)stride * 4, n_rows, hipMemcpyDeviceToDevice, s));
+  MP_CHECK_HIP(hipGetLastError());
+  return MP_OK;
+}
+
+extern "C" int mp_teaser_solve_ex(const float* d_src, const float* d_dst, const int32_t* d_counts, int n_rows, int stride, float noise_bound,
+                                  int inlier_selection, int tim_graph, int min_num_inliers, double* d_Rt, int32_t* d_retval, int32_t* d_degree,
+                                  int32_t* d_core, int32_t* d_selected, int32_t* d_info, int max_clique_steps, int32_t* d_clique_info, void* d_ws,
+                                  size_t ws_bytes, mp_stream stream) {
+  MP_REQUIRE(d_src && d_dst && d_counts && d_Rt && d_retval && d_ws, "mp_teaser_solve: null pointer");
+  MP_REQUIRE(n_rows >= 0 && n_rows <= 65535 && stride >= 1 && stride <= kMaxPoints, "mp_teaser_solve: 0 .. 65535 rows of 1 .. 1024 correspondences");
+  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers, max_clique_steps),
+             "mp_teaser_solve: bad noise bound, selection, graph, inlier count or step budget");
+  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes_ex(n_rows, 0, 0, stride, inlier_selection), "mp_teaser_solve: workspace too small");
+  if (n_rows == 0) return MP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* w = (unsigned char*)d_ws;
+  const SolveWs ws = take_solve_ws(w, n_rows, stride, inlier_selection);
+  ProfScope prof("teaser_solve", 0.0, (double)n_rows * stride * 24.0, s);
+  MP_CHECK_HIP(hipMemcpyAsync(ws.m_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));   // (the kernels clamp a count to 0 .. stride)
+  MP_CHECK_HIP(hipMemcpyAsync(ws.n_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));
+  return run_solve(d_src, d_dst, n_rows, stride, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, max_clique_steps, nullptr, nullptr, d_Rt,
+                   d_retval, d_degree, d_core, d_selected, d_info, d_clique_info, s);
 }
 
 extern "C" int mp_teaser_solve(const float* d_src, const float* d_dst, const int32_t* d_counts, int n_rows, int stride, float noise_bound,
                                int inlier_selection, int tim_graph, int min_num_inliers, double* d_Rt, int32_t* d_retval, int32_t* d_degree,
                                int32_t* d_core, int32_t* d_selected, int32_t* d_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
-  MP_REQUIRE(d_src && d_dst && d_counts && d_Rt && d_retval && d_ws, "mp_teaser_solve: null pointer");
-  MP_REQUIRE(n_rows >= 0 && n_rows <= 65535 && stride >= 1 && stride <= kMaxPoints, "mp_teaser_solve: 0 .. 65535 rows of 1 .. 1024 correspondences");
-  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers), "mp_teaser_solve: bad noise bound, selection, graph or inlier count");
-  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes(n_rows, 0, 0), "mp_teaser_solve: workspace too small");
-  if (n_rows == 0) return MP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)d_ws;
-  const SolveWs ws = take_solve_ws(w, n_rows);
-  ProfScope prof("teaser_solve", 0.0, (double)n_rows * stride * 24.0, s);
-  MP_CHECK_HIP(hipMemcpyAsync(ws.m_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));   // (the kernels clamp a count to 0 .. stride)
-  MP_CHECK_HIP(hipMemcpyAsync(ws.n_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));
-  return run_solve(d_src, d_dst, n_rows, stride, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, nullptr, nullptr, d_Rt, d_retval,
-                   d_degree, d_core, d_selected, d_info, s);
+  return mp_teaser_solve_ex(d_src, d_dst, d_counts, n_rows, stride, noise_bound, inlier_selection, tim_graph, min_num_inliers, d_Rt, d_retval, d_degree, d_core,
+                            d_selected, d_info, kCliqueDefaultSteps, nullptr, d_ws, ws_bytes, stream);
 }
 
-extern "C" int mp_teaser_refine(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
-                                const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
-                                float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
-                                int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
-                                int32_t* d_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
+extern "C" int mp_teaser_refine_ex(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
+                                   const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
+                                   float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
+                                   int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
+                                   int32_t* d_info, int max_clique_steps, int32_t* d_clique_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
   MP_REQUIRE(d_depth_meas && d_im_ids && d_depth_rend && d_K_rows && d_TCO && d_TCO_out && d_retval && d_ws, "mp_teaser_refine: null pointer");
   MP_REQUIRE(n_images > 0 && n_rows >= 0 && n_rows <= 65535 && H >= 1 && W >= 1 && (long long)H * W * 3 < 2147483647LL, "mp_teaser_refine: bad size");
   MP_REQUIRE(n_points >= 1 && n_points <= kMaxPoints, "mp_teaser_refine: n_points must be 1 .. 1024 (the consistency graph is a 1024 x 1024 bit matrix)");
   MP_REQUIRE((mask_type == kMaskSimple || mask_type == kMaskThreshold) && n_min_points >= 0 && std::isfinite(depth_delta_thresh),
              "mp_teaser_refine: bad mask type, threshold or n_min_points");
-  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers), "mp_teaser_refine: bad noise bound, selection, graph or inlier count");
-  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes(n_rows, H, W), "mp_teaser_refine: workspace too small");
+  MP_REQUIRE(solve_args_ok(noise_bound, inlier_selection, tim_graph, min_num_inliers, max_clique_steps),
+             "mp_teaser_refine: bad noise bound, selection, graph, inlier count or step budget");
+  MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes_ex(n_rows, H, W, n_points, inlier_selection), "mp_teaser_refine: workspace too small");
   if (n_rows == 0) return MP_OK;
   hipStream_t s = (hipStream_t)stream;
   const size_t px = (size_t)H * W, n = (size_t)n_rows;
   unsigned char* w = (unsigned char*)d_ws;
-  const SolveWs ws = take_solve_ws(w, n_rows);
+  const SolveWs ws = take_solve_ws(w, n_rows, n_points, inlier_selection);
   auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
   float* src_s = (float*)take(n * kMaxPoints * 12);
   float* dst_s = (float*)take(n * kMaxPoints * 12);
@@ -525,6 +576,16 @@ extern "C" int mp_teaser_refine(const float* d_depth_meas, int n_images, const i
   hipLaunchKernelGGL(teaser_gather, dim3(ceil_div(n_points, 256), n_rows), dim3(256), 0, s, pts, pix, idx, ws.m_arr, d_depth_meas, d_im_ids, d_K_rows, H, W,
                      n_points, src_s, dst_s);
   if (d_sample_idx) MP_CHECK_HIP(hipMemcpyAsync(d_sample_idx, idx, n * n_points * 4, hipMemcpyDeviceToDevice, s));
-  return run_solve(src_s, dst_s, n_rows, n_points, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, d_TCO, d_TCO_out, d_Rt, d_retval, d_degree,
-                   d_core, d_selected, d_info, s);
+  return run_solve(src_s, dst_s, n_rows, n_points, ws, noise_bound, inlier_selection, tim_graph, min_num_inliers, max_clique_steps, d_TCO, d_TCO_out, d_Rt,
+                   d_retval, d_degree, d_core, d_selected, d_info, d_clique_info, s);
+}
+
+extern "C" int mp_teaser_refine(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend, const float* d_K_rows,
+                                const float* d_TCO, int n_rows, int H, int W, int mask_type, float depth_delta_thresh, int n_min_points, int n_points,
+                                float noise_bound, int min_num_inliers, int use_fps, int inlier_selection, int tim_graph, float* d_TCO_out,
+                                int32_t* d_retval, double* d_Rt, int32_t* d_sample_idx, int32_t* d_degree, int32_t* d_core, int32_t* d_selected,
+                                int32_t* d_info, void* d_ws, size_t ws_bytes, mp_stream stream) {
+  return mp_teaser_refine_ex(d_depth_meas, n_images, d_im_ids, d_depth_rend, d_K_rows, d_TCO, n_rows, H, W, mask_type, depth_delta_thresh, n_min_points,
+                             n_points, noise_bound, min_num_inliers, use_fps, inlier_selection, tim_graph, d_TCO_out, d_retval, d_Rt, d_sample_idx, d_degree,
+                             d_core, d_selected, d_info, kCliqueDefaultSteps, nullptr, d_ws, ws_bytes, stream);
 }

@@ -16,7 +16,8 @@
 //     in fp32, the norms sqrtf(dist2): symmetric bit for bit, because a difference and its negative square alike.
 //   * CORES.  k = 0; until no vertex is alive: d = the smallest alive degree, k = max(k, d), every alive vertex of degree <= k gets core
 //     number k and is dropped, degrees are recounted.  Core numbers are unique, so no order changes them.  Selected = the vertices whose
-//     core number is the largest (mode "none": every vertex), m of them, in ascending order c_0 .. c_{m-1}; m < 3 rejects the row.
+//     core number is the largest (mode "none": every vertex; mode "max_clique": the members of a maximum clique, by the rule of
+//     teaser_clique_core.h), m of them, in ascending order c_0 .. c_{m-1}; m < 3 rejects the row.
 //   * ROTATION (GNC-TLS) [PairAcc, pair_pass, rotation_of, gnc_weight].  Float64.  The TIMs are a = s_q - s_p, b = d_q - d_p over the pairs
 //     (p, q) = (c_k, c_{k+1}) (graph "chain") or all p < q (graph "complete").  beta = noise_bound; weights start at 1.  Iteration i:
 //     R_i = the rotation that maximises trace(R sum w a b^T) (the weighted Kabsch solution with the determinant fixed, here in Horn's

@@ -1152,9 +1152,10 @@ def icp_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch
 # --------------------------------------------------------------------------- #
 TEASER_MAX_POINTS = 1024           # correspondences of one row, at most (the consistency graph is a 1024 x 1024 bit matrix)
 TEASER_MASK_TYPES = {"simple": 0, "threshold": 1}
-TEASER_SELECTIONS = {"kcore": 0, "none": 1}
+TEASER_SELECTIONS = {"kcore": 0, "none": 1, "max_clique": 2}
 TEASER_TIM_GRAPHS = {"chain": 0, "complete": 1}
 TEASER_INFO = ("N", "M", "n_selected", "gnc_iterations", "num_inliers")
+TEASER_CLIQUE_INFO = ("size", "upper_bound", "exact", "steps")
 
 
 def _teaser_mode(name: str, table: Dict[str, int], value: str) -> int:
@@ -1181,40 +1182,92 @@ def farthest_point_sample(points: torch.Tensor, counts: torch.Tensor, n_points: 
     return idx, m
 
 
+def max_clique_step_limits() -> Tuple[int, int]:
+    """(the default step budget of the maximum-clique search, the largest budget an argument may ask for)"""
+    default = int(_lib.load().mp_max_clique_default_steps())
+    return default, 16 * default
+
+
+def _clique_steps(max_steps: Optional[int]) -> int:
+    default, ceiling = max_clique_step_limits()
+    if max_steps is None:
+        return default
+    if not 0 <= int(max_steps) <= ceiling:
+        raise EngineError(f"the step budget of the maximum-clique search must be 0 .. {ceiling}, got {max_steps}")
+    return int(max_steps)
+
+
+def max_clique(adjacency: torch.Tensor, counts: Optional[torch.Tensor] = None, max_steps: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exact maximum clique of graphs given as adjacency matrices (mp_max_clique; the rule is in csrc/teaser_clique_core.h).
+    adjacency [n,stride <= 1024,stride] (any dtype; non-zero = set; an edge exists when i != j and a[i][j] or a[j][i]), counts [n] int32
+    = the vertices of every row (None: stride) -> members [n,stride] int32 in ascending order (-1 past the size), info [n,4] int32 =
+    TEASER_CLIQUE_INFO: exact = 0 when the search coloured more than max_steps vertices (None: the default budget) and returns the best
+    clique found until then."""
+    if adjacency.dim() != 3 or adjacency.shape[1] != adjacency.shape[2] or not 1 <= adjacency.shape[1] <= TEASER_MAX_POINTS:
+        raise EngineError(f"adjacency must be [n,stride,stride] with stride 1 .. {TEASER_MAX_POINTS}, got {tuple(adjacency.shape)}")
+    steps = _clique_steps(max_steps)
+    adj = _dev(adjacency != 0, torch.uint8)
+    n, stride, dev = int(adj.shape[0]), int(adj.shape[1]), adj.device
+    if counts is not None:
+        counts = _dev_i32(counts)
+        if counts.shape != (n,):
+            raise EngineError(f"counts must be [{n}], got {tuple(counts.shape)}")
+    lib = _lib.load()
+    ws = _workspace(lib.mp_max_clique_workspace_bytes(n, stride), dev)
+    members = torch.empty(n, stride, dtype=torch.int32, device=dev)
+    info = torch.empty(n, len(TEASER_CLIQUE_INFO), dtype=torch.int32, device=dev)
+    check(lib.mp_max_clique(adj.data_ptr(), _ptr(counts), n, stride, steps, members.data_ptr(), info.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return members, info
+
+
 def _teaser_telemetry(n: int, stride: int, device, want: bool):
     if not want:
         return None, None, None, None
     return tuple(torch.full((n, stride), -1, dtype=torch.int32, device=device) for _ in range(3)) + (torch.zeros(n, len(TEASER_INFO), dtype=torch.int32, device=device),)
 
 
+def _clique_info(n: int, device, want: bool):
+    return torch.zeros(n, len(TEASER_CLIQUE_INFO), dtype=torch.int32, device=device) if want else None
+
+
 def teaser_solve(src: torch.Tensor, dst: torch.Tensor, counts: torch.Tensor, noise_bound: float = 0.01, min_num_inliers: int = 0,
-                 inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False):
-    """Robust registration of given correspondences (mp_teaser_solve; the rules are in csrc/teaser_core.h).  src, dst [n,stride <= 1024,3]
+                 inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False, max_clique_steps: Optional[int] = None):
+    """Robust registration of given correspondences (mp_teaser_solve_ex; the rules are in csrc/teaser_core.h).  src, dst [n,stride <= 1024,3]
     float32, counts [n] int32 on the device -> Rt [n,3,4] float64 with dst ~ R src + t, retval [n] int32 (0 when num_inliers >=
     min_num_inliers, else -1); with telemetry also a dict of degree, core, selected [n,stride] (-1 past a row's count) and info
-    [n,5] = TEASER_INFO."""
+    [n,5] = TEASER_INFO.  inlier_selection "max_clique" selects an exact maximum clique of the consistency graph under the step budget
+    max_clique_steps (None: the default; see max_clique); the telemetry dict then also holds clique [n,4] = TEASER_CLIQUE_INFO."""
     src, dst, counts = _dev_f32(src), _dev_f32(dst), _dev_i32(counts)
     if src.dim() != 3 or src.shape[2] != 3 or dst.shape != src.shape or not 1 <= src.shape[1] <= TEASER_MAX_POINTS or counts.shape != (src.shape[0],):
         raise EngineError(f"src and dst must be [n,1 .. {TEASER_MAX_POINTS},3] and counts [n], got {tuple(src.shape)}, {tuple(dst.shape)}, {tuple(counts.shape)}")
     sel, graph = _teaser_mode("inlier_selection", TEASER_SELECTIONS, inlier_selection), _teaser_mode("rotation_tim_graph", TEASER_TIM_GRAPHS, rotation_tim_graph)
     n, stride, dev = int(src.shape[0]), int(src.shape[1]), src.device
     lib = _lib.load()
-    ws = _workspace(lib.mp_teaser_workspace_bytes(n, 0, 0), dev)
+    steps = _clique_steps(max_clique_steps)
+    ws = _workspace(lib.mp_teaser_workspace_bytes_ex(n, 0, 0, stride, sel), dev)
     Rt = torch.empty(n, 3, 4, dtype=torch.float64, device=dev)
     retval = torch.empty(n, dtype=torch.int32, device=dev)
     degree, core, selected, info = _teaser_telemetry(n, stride, dev, telemetry)
-    check(lib.mp_teaser_solve(src.data_ptr(), dst.data_ptr(), counts.data_ptr(), n, stride, float(noise_bound), sel, graph, int(min_num_inliers),
-                              Rt.data_ptr(), retval.data_ptr(), _ptr(degree), _ptr(core), _ptr(selected), _ptr(info), ws.data_ptr(), ws.numel(), _stream()))
-    return (Rt, retval, dict(degree=degree, core=core, selected=selected, info=info)) if telemetry else (Rt, retval)
+    clique = _clique_info(n, dev, telemetry and inlier_selection == "max_clique")
+    check(lib.mp_teaser_solve_ex(src.data_ptr(), dst.data_ptr(), counts.data_ptr(), n, stride, float(noise_bound), sel, graph, int(min_num_inliers),
+                                 Rt.data_ptr(), retval.data_ptr(), _ptr(degree), _ptr(core), _ptr(selected), _ptr(info), steps, _ptr(clique), ws.data_ptr(),
+                                 ws.numel(), _stream()))
+    if not telemetry:
+        return Rt, retval
+    tel = dict(degree=degree, core=core, selected=selected, info=info)
+    if clique is not None:
+        tel["clique"] = clique
+    return Rt, retval, tel
 
 
 def teaser_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: torch.Tensor, K_rows: torch.Tensor, TCO: torch.Tensor,
                   mask_type: str = "simple", depth_delta_thresh: float = 0.1, n_min_points: int = 100, n_points: int = 1000,
                   noise_bound: float = 0.01, min_num_inliers: int = 50, use_farthest_point_sampling: bool = True,
-                  inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False):
-    """The TEASER++ depth refiner from depth frames (mp_teaser_refine): depth_meas [B,H,W], im_ids [N], depth_rend [N,H,W] rendered at
+                  inlier_selection: str = "kcore", rotation_tim_graph: str = "chain", telemetry: bool = False, max_clique_steps: Optional[int] = None):
+    """The TEASER++ depth refiner from depth frames (mp_teaser_refine_ex): depth_meas [B,H,W], im_ids [N], depth_rend [N,H,W] rendered at
     TCO [N,4,4], K_rows [N,3,3] -> (TCO_refined [N,4,4], retval [N] int32 (0 refined / -1 input pose kept), info [N,5] int32 =
-    TEASER_INFO); with telemetry also a dict of Rt [N,3,4] float64, sample_idx [N,n_points] and degree, core, selected [N,n_points]."""
+    TEASER_INFO); with telemetry also a dict of Rt [N,3,4] float64, sample_idx [N,n_points] and degree, core, selected [N,n_points],
+    and with inlier_selection "max_clique" (budget max_clique_steps, as teaser_solve) clique [N,4] = TEASER_CLIQUE_INFO."""
     depth_meas, depth_rend, K_rows, TCO, im_ids = _dev_f32(depth_meas), _dev_f32(depth_rend), _dev_f32(K_rows), _dev_f32(TCO), _dev_i32(im_ids)
     if depth_meas.dim() != 3 or TCO.dim() != 3 or TCO.shape[1:] != (4, 4):
         raise EngineError(f"depth_meas must be [B,H,W] and TCO [N,4,4], got {tuple(depth_meas.shape)} and {tuple(TCO.shape)}")
@@ -1227,20 +1280,25 @@ def teaser_refine(depth_meas: torch.Tensor, im_ids: torch.Tensor, depth_rend: to
     mask = _teaser_mode("mask_type", TEASER_MASK_TYPES, mask_type)
     sel, graph = _teaser_mode("inlier_selection", TEASER_SELECTIONS, inlier_selection), _teaser_mode("rotation_tim_graph", TEASER_TIM_GRAPHS, rotation_tim_graph)
     lib = _lib.load()
-    ws = _workspace(lib.mp_teaser_workspace_bytes(N, H, W), dev)
+    steps = _clique_steps(max_clique_steps)
+    ws = _workspace(lib.mp_teaser_workspace_bytes_ex(N, H, W, int(n_points), sel), dev)
     out = torch.empty_like(TCO)
     retval = torch.empty(N, dtype=torch.int32, device=dev)
     degree, core, selected, _ = _teaser_telemetry(N, int(n_points), dev, telemetry)
     info = torch.zeros(N, len(TEASER_INFO), dtype=torch.int32, device=dev)
     Rt = torch.empty(N, 3, 4, dtype=torch.float64, device=dev) if telemetry else None
     sample_idx = torch.empty(N, int(n_points), dtype=torch.int32, device=dev) if telemetry else None
-    check(lib.mp_teaser_refine(depth_meas.data_ptr(), n_im, im_ids.data_ptr(), depth_rend.data_ptr(), K_rows.data_ptr(), TCO.data_ptr(), N, H, W, mask,
-                               float(depth_delta_thresh), int(n_min_points), int(n_points), float(noise_bound), int(min_num_inliers),
-                               int(bool(use_farthest_point_sampling)), sel, graph, out.data_ptr(), retval.data_ptr(), _ptr(Rt), _ptr(sample_idx), _ptr(degree),
-                               _ptr(core), _ptr(selected), info.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-    if telemetry:
-        return out, retval, info, dict(Rt=Rt, sample_idx=sample_idx, degree=degree, core=core, selected=selected)
-    return out, retval, info
+    clique = _clique_info(N, dev, telemetry and inlier_selection == "max_clique")
+    check(lib.mp_teaser_refine_ex(depth_meas.data_ptr(), n_im, im_ids.data_ptr(), depth_rend.data_ptr(), K_rows.data_ptr(), TCO.data_ptr(), N, H, W, mask,
+                                  float(depth_delta_thresh), int(n_min_points), int(n_points), float(noise_bound), int(min_num_inliers),
+                                  int(bool(use_farthest_point_sampling)), sel, graph, out.data_ptr(), retval.data_ptr(), _ptr(Rt), _ptr(sample_idx),
+                                  _ptr(degree), _ptr(core), _ptr(selected), info.data_ptr(), steps, _ptr(clique), ws.data_ptr(), ws.numel(), _stream()))
+    if not telemetry:
+        return out, retval, info
+    tel = dict(Rt=Rt, sample_idx=sample_idx, degree=degree, core=core, selected=selected)
+    if clique is not None:
+        tel["clique"] = clique
+    return out, retval, info, tel
 
 
 # --------------------------------------------------------------------------- #

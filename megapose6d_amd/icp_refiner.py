@@ -9,7 +9,8 @@ oracle/icp_opencv.py, parity unpinned) -- or the cheaper projective-association 
 
 `TeaserppRefiner` is the reference's src/megapose/inference/teaserpp_refiner.py:165-289: the same rendered depth, correspondences
 pixel by pixel between the rendered and the measured depth, farthest point sampling and a truncated-least-squares registration, one
-batched device call (`mp_teaser_refine`, csrc/teaser.hip; the rules and the deviations are in csrc/teaser_core.h and DESIGN.md 3.14).
+batched device call (`mp_teaser_refine_ex`, csrc/teaser.hip; the rules and the deviations are in csrc/teaser_core.h,
+csrc/teaser_clique_core.h and DESIGN.md 3.14).
 """
 from __future__ import annotations
 
@@ -86,8 +87,10 @@ class TeaserppRefiner(DepthRefiner):
                  noise_bound: float = 0.01, min_num_inliers: int = 50, use_farthest_point_sampling: bool = True, *,
                  inlier_selection: str = "kcore", rotation_tim_graph: str = "chain"):
         # engine extensions (keyword-only): inlier_selection "kcore" = the vertices of the consistency graph's largest core number
-        # (TEASER++'s default is the exact maximum clique, which is not reproduced), "none" = every correspondence; rotation_tim_graph
-        # "chain" = consecutive pairs of the selected correspondences (TEASER++'s default), "complete" = all pairs
+        # (the default here), "max_clique" = an exact maximum clique of that graph (TEASER++'s default) searched under the step budget
+        # `max_clique_steps` (an attribute: None = the engine's default budget; a row that exhausts it selects the best clique found
+        # until then), "none" = every correspondence; rotation_tim_graph "chain" = consecutive pairs of the selected correspondences
+        # (TEASER++'s default), "complete" = all pairs
         if mask_type not in eng.TEASER_MASK_TYPES:
             raise ValueError(f"Unknown mask type {mask_type}")
         if inlier_selection not in eng.TEASER_SELECTIONS or rotation_tim_graph not in eng.TEASER_TIM_GRAPHS:
@@ -105,6 +108,7 @@ class TeaserppRefiner(DepthRefiner):
         self.use_farthest_point_sampling = use_farthest_point_sampling
         self.inlier_selection = inlier_selection
         self.rotation_tim_graph = rotation_tim_graph
+        self.max_clique_steps: Optional[int] = None
         self.light_datas = [Panda3dLightData("ambient")]
         self.debug: dict = {}
 
@@ -121,9 +125,11 @@ class TeaserppRefiner(DepthRefiner):
         TCO_ = predictions.poses.to(device=device, dtype=torch.float32)
         K_ = K[im_ids.long()].float()
         depth_rendered = self.renderer.render_depth(df.label.tolist(), TCO_, K_, tuple(depth.shape[-2:])).contiguous()
-        refined, retval, info = eng.teaser_refine(depth.float().contiguous(), im_ids, depth_rendered, K_, TCO_, self.mask_type, self.depth_delta_thresh,
-                                                  self.n_min_points, self.n_points, self.noise_bound, self.min_num_inliers,
-                                                  self.use_farthest_point_sampling, self.inlier_selection, self.rotation_tim_graph)
+        exact = self.inlier_selection == "max_clique"
+        refined, retval, info, *tel = eng.teaser_refine(depth.float().contiguous(), im_ids, depth_rendered, K_, TCO_, self.mask_type, self.depth_delta_thresh,
+                                                        self.n_min_points, self.n_points, self.noise_bound, self.min_num_inliers,
+                                                        self.use_farthest_point_sampling, self.inlier_selection, self.rotation_tim_graph, telemetry=exact,
+                                                        max_clique_steps=self.max_clique_steps)
         if "poses_input" in predictions_refined.tensors:
             predictions_refined.poses_input = predictions.poses.clone()
         else:
@@ -131,5 +137,7 @@ class TeaserppRefiner(DepthRefiner):
         predictions_refined.poses = refined
         extra = {"retval": retval, "n_mask_points": info[:, 0], "n_points": info[:, 1], "n_selected": info[:, 2], "gnc_iterations": info[:, 3],
                  "num_inliers": info[:, 4]}
+        if exact:
+            extra["clique_exact"], extra["clique_steps"] = tel[0]["clique"][:, 2], tel[0]["clique"][:, 3]
         self.debug = extra
         return predictions_refined, extra

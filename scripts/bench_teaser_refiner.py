@@ -43,23 +43,17 @@ from support import synthetic as syn  # noqa: E402
 from support import teaser as ts  # noqa: E402
 
 
-def main() -> int:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--frames", type=int, default=8)
-    ap.add_argument("--per-frame", type=int, default=8)
-    ap.add_argument("--cpu-rows", type=int, default=2)
-    args = ap.parse_args()
+def build_scenes(n_frames: int, per_frame: int):
+    """the workload of the docstring -> dict(renderer, labels, im_ids, gt, depth [frames,H,W], ids, K_im, K_rows, TCO (the input poses), rend)"""
     H, W, n_meshes = 480, 640, 16
-    n_cu, _, arch = eng.device_info()
     ds = syn.make_object_dataset(tempfile.mkdtemp(prefix="mp_bench_teaser_"), n_objects=n_meshes, seed=40, n_theta=48, n_z=50)
     renderer = Panda3dBatchRenderer(ds, n_workers=1)
     names = [o.label for o in ds.list_objects]
     rng = np.random.RandomState(9)
     K = torch.from_numpy(syn.K_EXAMPLE.astype(np.float32)).cuda()
     labels, im_ids, gt, frames = [], [], [], []
-    for f in range(args.frames):
-        labs = [names[(2 * f + j) % n_meshes] for j in range(args.per_frame)]
+    for f in range(n_frames):
+        labs = [names[(2 * f + j) % n_meshes] for j in range(per_frame)]
         poses = np.stack([syn.random_pose(rng, (0.5, 0.8), 0.3) for _ in labs]).astype(np.float32)
         d = renderer.render_depth(labs, torch.from_numpy(poses).cuda(), K[None].repeat(len(labs), 1, 1), (H, W))
         z = torch.where(d > 0, d, torch.full_like(d, float("inf"))).min(0).values
@@ -77,10 +71,25 @@ def main() -> int:
     depth = torch.stack(frames)
     n = len(labels)
     ids = torch.tensor(im_ids, dtype=torch.int32).cuda()
-    K_im = K[None].repeat(args.frames, 1, 1)
+    K_im = K[None].repeat(n_frames, 1, 1)
     K_rows = K_im[ids.long()]
     TCO = torch.from_numpy(init).cuda()
     rend = renderer.render_depth(labels, TCO, K_rows, (H, W)).contiguous()
+    return dict(renderer=renderer, labels=labels, im_ids=im_ids, gt=gt, depth=depth, ids=ids, K_im=K_im, K_rows=K_rows, TCO=TCO, rend=rend, H=H, W=W)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--per-frame", type=int, default=8)
+    ap.add_argument("--cpu-rows", type=int, default=2)
+    args = ap.parse_args()
+    n_cu, _, arch = eng.device_info()
+    sc = build_scenes(args.frames, args.per_frame)
+    renderer, labels, im_ids, gt, depth, ids, K_im, K_rows, TCO, rend, H, W = (sc[k] for k in ("renderer", "labels", "im_ids", "gt", "depth", "ids", "K_im", "K_rows", "TCO",
+                                                                                               "rend", "H", "W"))
+    n = len(labels)
     print(f"# {arch}, {n_cu} CUs; {n} detections over {args.frames} frames of {W} x {H}; best of {args.reps} after a warm-up")
 
     out = {}
