@@ -321,6 +321,30 @@ __device__ __forceinline__ NnPtrs row_ptrs(const NnScratch& sc, int row, int cap
   return p;
 }
 
+// OpenCV's loop is `while (!(1 - tol < fval_perc && fval_perc < 1 + tol) && i < max_it)` with fval_perc = 0 before the first pass: a level
+// whose iteration cap rounds to 0 (iterations < (level + 1) / 2), or whose band tolerance * (level + 1)^2 reaches past 1, runs NO
+// iteration -- its transform stays the identity and the pose carries through to the next level.
+__host__ __device__ inline int level_cap(int level, int iterations, float tolerance) {
+  const double tol_p = (double)tolerance * (level + 1) * (level + 1);
+  if (1.0 - tol_p < 0.0 && 0.0 < 1.0 + tol_p) return 0;
+  return (int)rint((double)iterations / (level + 1));
+}
+
+// the first level at or below `level` that iterates (-1: none)
+__device__ __forceinline__ int next_level(int level, int iterations, float tolerance) {
+  while (level >= 0 && level_cap(level, iterations, tolerance) == 0) --level;
+  return level;
+}
+
+// after the last level (thread 0; `pose` = the accumulated transform, normalised frame): undo the normalisation,
+// t = t / scale + mean_avg - R mean_avg, and retire the object
+__device__ __forceinline__ void retire(NnRow& R, const double* pose) {
+  const double* mean_avg = R.mean_avg;
+  for (int r = 0; r < 3; ++r)
+    R.pose[r * 4 + 3] = pose[r * 4 + 3] / R.scale + mean_avg[r] - (pose[r * 4] * mean_avg[0] + pose[r * 4 + 1] * mean_avg[1] + pose[r * 4 + 2] * mean_avg[2]);
+  R.active = 0;
+}
+
 // start of a pyramid level (whole workgroup; `pose` = the transform accumulated so far, in LDS): sub-sample the moved model and the scene
 // (samplePCUniform: every step-th point), reset the loop variables.  Thread 0 writes the scalars of the level into the row.
 __device__ void level_start(NnRow& R, const NnPtrs& P, const double* pose, int level, int iterations, float tolerance) {
@@ -340,7 +364,7 @@ __device__ void level_start(NnRow& R, const NnPtrs& P, const double* pose, int l
     for (int k = 0; k < 6; ++k) P.dst_s[(size_t)i * 6 + k] = P.dst[(size_t)i * step * 6 + k];
   if (tid == 0) {
     R.level = level; R.it = 0; R.nl = nl; R.ml = ml;
-    R.max_it = (int)rint((double)iterations / (level + 1));
+    R.max_it = level_cap(level, iterations, tolerance);
     R.tol_p = (double)tolerance * (level + 1) * (level + 1);
     R.fval_old = 9999999999.0; R.fval_perc = 0.0; R.fval_min = 9999999999.0;
     for (int k = 0; k < 16; ++k) R.pose_x[k] = (k % 5 == 0) ? 1.0 : 0.0;
@@ -428,7 +452,13 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_begin(NnScratch sc, int cap,
     R.active = 1;
   }
   __syncthreads();
-  level_start(R, P, pose_s, num_levels - 1, iterations, tolerance);
+  const int first = next_level(num_levels - 1, iterations, tolerance);
+  if (first >= 0) {
+    level_start(R, P, pose_s, first, iterations, tolerance);
+  } else if (tid == 0) {   // (tolerance > 1: not even the finest level iterates -- the identity, with the residual no level ever lowered)
+    R.residual = 9999999999.0;
+    retire(R, pose_s);
+  }
 }
 
 // exact nearest neighbour (float64 distances of the float32 clouds, like a kd-tree's exact answer) of the moved model points in the level's
@@ -650,17 +680,12 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_step(NnScratch sc, int cap, 
     R.residual = fval_min;
     for (int k = 0; k < 16; ++k) R.pose[k] = pose_s[k];
   }
-  if (level > 0) {
-    level_start(R, P, pose_s, level - 1, iterations, tolerance);
+  const int next = next_level(level - 1, iterations, tolerance);   // (the levels in between run no iteration: their `iters` entry stays 0)
+  if (next >= 0) {
+    level_start(R, P, pose_s, next, iterations, tolerance);
     return;
   }
-  // ---- undo the normalisation: t = t / scale + mean_avg - R mean_avg ------------------------------------------------------------------------
-  if (tid == 0) {
-    const double* mean_avg = R.mean_avg;
-    for (int r = 0; r < 3; ++r)
-      R.pose[r * 4 + 3] = pose_s[r * 4 + 3] / R.scale + mean_avg[r] - (pose_s[r * 4] * mean_avg[0] + pose_s[r * 4 + 1] * mean_avg[1] + pose_s[r * 4 + 2] * mean_avg[2]);
-    R.active = 0;
-  }
+  if (tid == 0) retire(R, pose_s);   // (level 0 here: a finest level that does not iterate means tolerance > 1, and then none does)
 }
 
 // TCO_refined = pose @ (TCO with the centroid shift added to its translation) when residual in [0, tolerance], else the input pose
@@ -780,7 +805,7 @@ extern "C" int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const i
   // object tracks its own level / iteration in its row and turns the launches it no longer needs into no-ops
   hipLaunchKernelGGL(icpnn_begin, dim3(n_rows), dim3(NN_THREADS), 0, s, sc, (int)cap, rows, n_iterations, tolerance, n_levels);
   int total_it = 0;
-  for (int level = 0; level < n_levels; ++level) total_it += (int)rint((double)n_iterations / (level + 1));
+  for (int level = 0; level < n_levels; ++level) total_it += level_cap(level, n_iterations, tolerance);   // (a level uses at most its cap: a `break` takes the place of an iteration)
   const dim3 sg(SEARCH_WGS, n_rows);
   for (int k = 0; k < total_it; ++k) {
     hipLaunchKernelGGL(icpnn_search, sg, dim3(SEARCH_THREADS), 0, s, sc, (int)cap, rows);

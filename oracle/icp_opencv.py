@@ -136,7 +136,9 @@ def _point_to_plane(src: np.ndarray, dst: np.ndarray):
 def opencv_icp(src_pc: np.ndarray, dst_pc: np.ndarray, iterations: int = 100, tolerance: float = 0.05, rejection_scale: float = 2.5,
                num_levels: int = 4, info: dict | None = None):
     """registerModelToScene(srcPC [n,6], dstPC [m,6]) -> (retval 0, residual, pose 4x4 mapping src onto dst).
-    `info` (optional dict) receives telemetry: 'iters' = iterations run per level (index = level)."""
+    `info` (optional dict) receives telemetry: 'iters' = iterations run per level (index = level), 'ends' = how each level ended
+    ('stop' = the relative-change rule, 'cap' = the iteration cap, 'few' = `break` with fewer than 6 matches, 'nonfinite' = `break` on a
+    non-finite solve) and 'caps' = each level's iteration cap."""
     n = src_pc.shape[0]
     src = src_pc.astype(np.float32).copy()
     dst = dst_pc.astype(np.float32).copy()
@@ -163,6 +165,7 @@ def opencv_icp(src_pc: np.ndarray, dst_pc: np.ndarray, iterations: int = 100, to
         moved = src_t.copy()
         pose_x = np.eye(4)
         i = 0
+        end = "cap"
         while (not (1 - tol_p < fval_perc < 1 + tol_p)) and i < max_it:
             d, ind = tree.query(moved[:, :3])
             d2 = (d * d).astype(np.float32)                               # FLANN's L2 functor returns SQUARED distances
@@ -177,10 +180,12 @@ def opencv_icp(src_pc: np.ndarray, dst_pc: np.ndarray, iterations: int = 100, to
             first[1:] = nj[1:] != nj[:-1]
             idx_model, idx_scene = ni[first], nj[first]
             if len(idx_model) < 6:
+                end = "few"
                 break
             s_m, d_m = src_t[idx_model].astype(np.float64), dst_s[idx_scene].astype(np.float64)
             rpy, t = _point_to_plane(s_m, d_m)
             if np.isnan(rpy).any() or np.isnan(t).any():
+                end = "nonfinite"
                 break
             pose_x = np.eye(4)
             pose_x[:3, :3] = _euler_to_dcm(rpy)
@@ -195,6 +200,8 @@ def opencv_icp(src_pc: np.ndarray, dst_pc: np.ndarray, iterations: int = 100, to
         residual = fval_min
         if info is not None:
             info.setdefault("iters", [0] * num_levels)[level] = i
+            info.setdefault("ends", [""] * num_levels)[level] = "stop" if end == "cap" and i < max_it else end
+            info.setdefault("caps", [0] * num_levels)[level] = max_it
     R, c = pose[:3, :3], pose[:3, 3]
     c = c / scale + mean_avg - R @ mean_avg
     out = np.eye(4)
@@ -210,8 +217,11 @@ def compute_masks_threshold(depth_rendered: np.ndarray, depth_measured: np.ndarr
     return mask_measured
 
 
-def icp_refinement(depth_measured, depth_rendered, object_mask_measured, cam_K, TCO_pred, n_min_points=1000, info=None):
-    """icp_refiner.py:128-175 -> (TCO_refined, retval, residual); retval -1 = rejected (the caller keeps the input pose)"""
+def icp_refinement(depth_measured, depth_rendered, object_mask_measured, cam_K, TCO_pred, n_min_points=1000, info=None, *,
+                   n_iterations=100, n_levels=4, tolerance=0.05):
+    """icp_refiner.py:128-175 -> (TCO_refined, retval, residual); retval -1 = rejected (the caller keeps the input pose).
+    n_iterations / n_levels / tolerance: the reference hard-codes (100, 4, 0.05); the engine's ICPRefiner takes them as arguments.
+    `info` also receives 'n_model' / 'n_scene', the point counts the >= n_min_points rule looks at."""
     # the reference hands numpy SCALARS of the float32 intrinsics to getXYZ / get_normal (:135-150), not python floats: `1 / fx` and every
     # product of the int16 offset table with it are then float32 operations (under numpy 1.x value-based casting and NEP 50 alike)
     cam_K = np.asarray(cam_K, dtype=np.float32)
@@ -227,6 +237,8 @@ def icp_refinement(depth_measured, depth_rendered, object_mask_measured, cam_K, 
     pts_src[:, :, :3] = get_xyz(depth_rendered, fx, fy, cx, cy)
     pts_src[:, :, 3:] = get_normal(depth_rendered, fx, fy, cx, cy, refine=True)
     pts_src = pts_src[np.logical_and(depth_valid, depth_rendered > 0)]
+    if info is not None:
+        info["n_model"], info["n_scene"] = len(pts_src), len(pts_tgt)
     if len(pts_tgt) < n_min_points or len(pts_src) < n_min_points:
         return TCO_pred.copy(), -1, -1.0
     T = np.asarray(TCO_pred, dtype=np.float32).copy()                  # (the reference's pose is a float32 array; += stays float32)
@@ -234,8 +246,7 @@ def icp_refinement(depth_measured, depth_rendered, object_mask_measured, cam_K, 
     shift = pts_tgt[:, :3].mean(0) - pts_src[:, :3].mean(0)
     T[:3, 3] += shift.reshape(-1)
     pts_src[:, :3] += shift[None]
-    tolerance = 0.05
-    retval, residual, pose = opencv_icp(pts_src.reshape(-1, 6), pts_tgt.reshape(-1, 6), 100, tolerance, 2.5, 4, info=info)
+    retval, residual, pose = opencv_icp(pts_src.reshape(-1, 6), pts_tgt.reshape(-1, 6), n_iterations, tolerance, 2.5, n_levels, info=info)
     T = pose @ T
     if residual > tolerance or residual < 0:
         retval = -1
