@@ -688,6 +688,44 @@ int mp_surface_sample(const float* d_vertices /*[V_total,3]*/, const int32_t* d_
                       float* d_points /*[n_obj,count,3]*/, int32_t* d_face /*[n_obj,count]*/, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Prediction overlays: the contour overlay of visualization/utils.py:56-85                 */
+/* make_contour_overlay (get_mask_from_rgb, cv2.Canny(mask, 30, 100), cv2.dilate 3x3, masked */
+/* paint), the mesh blend of visualization/bokeh_plotter.py:106-130 plot_overlay and the     */
+/* box frames of visualization/utils.py:129-146 draw_bounding_box, on uint8 images on the    */
+/* device (csrc/overlay.hip; contract in csrc/overlay_core.h).  OpenCV is third party: its   */
+/* Canny, dilate and rectangle are restated, parity unpinned.                                */
+/* ------------------------------------------------------------------------------------ */
+/* For each of n images of h x w: the label of a pixel is d_labels' (< 0 background, l >= 0 an instance) or, with d_labels == NULL, 0
+   where any channel of d_render is > 0 and -1 elsewhere.  A pixel is an EDGE of label l by OpenCV's Canny (L1 norm, aperture 3) on the
+   0 / 1 mask m = [label == l]: gx, gy the 3x3 Sobel responses of m with the border replicated, mag = |gx| + |gy| (zero outside the
+   image), and mag != 0 and non-maximum suppression with ax = |gx|, ay = |gy| << 15, t = ax * 13573: ay < t: mag > mag(x-1,y) and mag >=
+   mag(x+1,y); else ay > t + (ax << 16): mag > mag(x,y-1) and mag >= mag(x,y+1); else with s = -1 when (gx ^ gy) < 0, else +1: mag >
+   mag(x-s,y-1) and mag > mag(x+s,y+1).  (Every gradient of a 0 / 255 mask is a multiple of 255 and above both thresholds: hysteresis
+   changes nothing.)  e(q) = the largest label with an edge at q, or -1; out(p) = the largest e(q) over the q of the image within
+   Chebyshev distance k = dilate_iterations of p (k rounds of a 3x3 dilation per label, painted in ascending order).  d_contour = colour
+   (out mod n_colors) of d_colors where out >= 0, else the pixel of d_images; d_canny = 255 where out >= 0, else 0; d_mask = 255 where
+   label >= 0, else 0; d_mesh per channel = trunc((float)(render * 0.8 + 255 * 0.2)) where label >= 0, else trunc((float)(image * 0.6 +
+   255 * 0.4)), the sums in float64 (two 256-entry tables).  Integer arithmetic throughout, no atomics, every output byte written by one
+   thread: no grid or tile changes a bit.  Every output pointer is optional (NULL: not written).  h, w in 1 .. 8192, n * h * w * 3 <
+   2^31, k in 0 .. 8, n_colors >= 1.  One launch on `stream`, no scratch.  n == 0 is a successful no-op; any other bad argument (null
+   d_images or d_colors, neither d_render nor d_labels, d_mesh without d_render, a size, k or n_colors out of range) returns non-zero
+   before anything is launched. */
+int mp_overlay(const uint8_t* d_images /*[n,h,w,3]*/, const uint8_t* d_render /*[n,h,w,3] or NULL*/, const int32_t* d_labels /*[n,h,w] or NULL*/,
+               const uint8_t* d_colors /*[n_colors,3]*/, int n_colors, int n, int h, int w, int dilate_iterations,
+               uint8_t* d_contour /*[n,h,w,3] or NULL*/, uint8_t* d_canny /*[n,h,w] or NULL*/, uint8_t* d_mask /*[n,h,w] or NULL*/,
+               uint8_t* d_mesh /*[n,h,w,3] or NULL*/, mp_stream stream);
+/* Box frames on images: box j = d_boxes[j] (x1, y1, x2, y2, fp32, clamped to +-2^20 and truncated to integers; a box with a NaN
+   corner draws nothing) belongs to image d_image_ids[j] (one outside 0 .. n - 1 draws nothing).  Corners are not reordered.  A pixel (x, y) is on frame j when it lies inside
+   the box grown by t / 2 (x1 - t/2 <= x <= x2 + t/2, the same in y) and not inside the box shrunk by (t + 1) / 2 (x1 + (t+1)/2 <= x <=
+   x2 - (t+1)/2, the same in y), t = thickness in 1 .. 8.  d_out = colour (j mod n_colors) of the highest such j of the pixel's image,
+   else the pixel of d_images: a gather per pixel over the boxes, so no drawing order can race.  No text is drawn.  Sizes as mp_overlay;
+   n_boxes >= 0 (0 copies the images).  One launch, no scratch.  n == 0 is a successful no-op; any other bad argument returns non-zero
+   before anything is launched. */
+int mp_draw_boxes(const uint8_t* d_images /*[n,h,w,3]*/, const float* d_boxes /*[n_boxes,4]*/, const int32_t* d_image_ids /*[n_boxes]*/,
+                  int n_boxes, const uint8_t* d_colors /*[n_colors,3]*/, int n_colors, int n, int h, int w, int thickness,
+                  uint8_t* d_out /*[n,h,w,3]*/, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

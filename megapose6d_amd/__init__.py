@@ -5,7 +5,7 @@ of the reference's renderer / PosePredictor / PoseEstimator interfaces.  Importi
 first engine call loads `libmp_engine.so` and raises if it is missing (there is no CPU fallback).
 """
 from . import (detector, distances, distributed, engine, evaluation, icp_refiner, load_model, mask_rcnn, mesh_db, mesh_io, object_dataset, pose_estimator,  # noqa: F401
-               pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, types)
+               pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, types, visualization)
 from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner, TeaserppRefiner  # noqa: F401
 from .mask_rcnn import DetectorMaskRCNN  # noqa: F401

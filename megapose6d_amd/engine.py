@@ -1065,6 +1065,86 @@ def model_info(points: torch.Tensor, n_points, tile: int = 0) -> Tuple[torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# prediction overlays (visualisation): csrc/overlay.hip
+OVERLAY_OUTPUTS = ("contour", "mesh", "canny", "mask")
+OVERLAY_MAX_DILATE = 8               # dilate_iterations
+OVERLAY_MAX_THICKNESS = 8            # thickness of draw_boxes
+OVERLAY_MAX_SIDE = 8192              # h, w
+
+
+def _overlay_images(name: str, t: torch.Tensor, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+    t = _dev_bytes(name, t)
+    if t.dim() != 4 or t.shape[3] != 3 or (like is not None and t.shape != like.shape):
+        raise EngineError(f"{name} must be uint8 [n,h,w,3]" + ("" if like is None else f" like images {tuple(like.shape)}") + f", got {tuple(t.shape)}")
+    n, h, w = (int(v) for v in t.shape[:3])
+    if not (1 <= h <= OVERLAY_MAX_SIDE and 1 <= w <= OVERLAY_MAX_SIDE) or n * h * w * 3 >= 2 ** 31:
+        raise EngineError(f"{name}: h and w must be in 1 .. {OVERLAY_MAX_SIDE} and n * h * w * 3 below 2^31, got {tuple(t.shape)}")
+    return t
+
+
+def _overlay_colors(colors, device) -> torch.Tensor:
+    colors = torch.as_tensor(colors, dtype=torch.uint8).to(device).contiguous()
+    if colors.dim() != 2 or colors.shape[0] < 1 or colors.shape[1] != 3:
+        raise EngineError(f"colors must be uint8 [n_colors,3] with n_colors >= 1, got {tuple(colors.shape)}")
+    return colors
+
+
+def overlay(images: torch.Tensor, render: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, colors=((0, 255, 0),),
+            dilate_iterations: int = 1, outputs: Sequence[str] = ("contour", "mesh", "canny", "mask")) -> Dict[str, torch.Tensor]:
+    """Contour overlay, mesh blend, edge map and mask of a batch in one launch (mp_overlay).  images uint8 [n,h,w,3] on the device; render
+    the same or None; labels int32 [n,h,w] or None (< 0 background, l >= 0 an instance; without labels: 0 where any channel of the render
+    is > 0, else -1); colors uint8 [n_colors,3] (label l is drawn in colour l mod n_colors); dilate_iterations in 0 .. 8 -> a dict of
+    the requested outputs: "contour" [n,h,w,3] (each instance's occlusion-aware Canny contour, dilated, in its colour over the image),
+    "mesh" [n,h,w,3] (plot_overlay's blend; needs the render), "canny" [n,h,w] (255 on a contour), "mask" [n,h,w] (255 on an instance),
+    all uint8.  Nothing synchronises."""
+    images = _overlay_images("images", images)
+    dev = images.device
+    n, h, w = (int(v) for v in images.shape[:3])
+    outputs = tuple(outputs)
+    if any(o not in OVERLAY_OUTPUTS for o in outputs) or len(set(outputs)) != len(outputs):
+        raise EngineError(f"outputs must be distinct names of {OVERLAY_OUTPUTS}, got {outputs}")
+    if render is None and labels is None:
+        raise EngineError("overlay needs a render or a label map")
+    if render is None and "mesh" in outputs:
+        raise EngineError("the mesh blend needs a render")
+    if render is not None:
+        render = _overlay_images("render", render, images)
+    if labels is not None:
+        labels = _dev_i32(labels)
+        if labels.shape != images.shape[:3]:
+            raise EngineError(f"labels must be int32 [n,h,w] like images {tuple(images.shape)}, got {tuple(labels.shape)}")
+    colors = _overlay_colors(colors, dev)
+    k = int(dilate_iterations)
+    if not 0 <= k <= OVERLAY_MAX_DILATE:
+        raise EngineError(f"dilate_iterations must be in 0 .. {OVERLAY_MAX_DILATE}, got {dilate_iterations}")
+    out = {o: torch.empty((n, h, w, 3) if o in ("contour", "mesh") else (n, h, w), dtype=torch.uint8, device=dev) for o in outputs}
+    check(_lib.load().mp_overlay(images.data_ptr(), _ptr(render), _ptr(labels), colors.data_ptr(), colors.shape[0], n, h, w, k,
+                                 _ptr(out.get("contour")), _ptr(out.get("canny")), _ptr(out.get("mask")), _ptr(out.get("mesh")), _stream()))
+    return out
+
+
+def draw_boxes(images: torch.Tensor, boxes: torch.Tensor, image_ids: torch.Tensor, colors=((255, 0, 0),), thickness: int = 2) -> torch.Tensor:
+    """Box frames on images (mp_draw_boxes).  images uint8 [n,h,w,3] on the device; boxes [n_boxes,4] float32 (x1, y1, x2, y2, truncated
+    to integers); image_ids [n_boxes] int32 (an id outside 0 .. n - 1 draws nothing); colors uint8 [n_colors,3] (box j is drawn in colour
+    j mod n_colors; of overlapping frames the highest j shows); thickness in 1 .. 8 -> uint8 [n,h,w,3].  No text is drawn.  Nothing
+    synchronises."""
+    images = _overlay_images("images", images)
+    dev = images.device
+    n, h, w = (int(v) for v in images.shape[:3])
+    boxes, image_ids = _dev_f32(boxes), _dev_i32(image_ids)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or image_ids.shape != boxes.shape[:1]:
+        raise EngineError(f"boxes must be [n_boxes,4] and image_ids [n_boxes], got {tuple(boxes.shape)}, {tuple(image_ids.shape)}")
+    colors = _overlay_colors(colors, dev)
+    t = int(thickness)
+    if not 1 <= t <= OVERLAY_MAX_THICKNESS:
+        raise EngineError(f"thickness must be in 1 .. {OVERLAY_MAX_THICKNESS}, got {thickness}")
+    out = torch.empty_like(images)
+    check(_lib.load().mp_draw_boxes(images.data_ptr(), boxes.data_ptr(), image_ids.data_ptr(), boxes.shape[0], colors.data_ptr(), colors.shape[0],
+                                    n, h, w, t, out.data_ptr(), _stream()))
+    return out
+
+
+# --------------------------------------------------------------------------- #
 # points drawn uniformly over mesh surfaces (mesh database): csrc/surface_sample.hip
 SURFACE_BLOCK_STEP = 64              # a forced block is a multiple of this ...
 SURFACE_MAX_BLOCK = 2048             # ... and at most this; an object has at most this many blocks
