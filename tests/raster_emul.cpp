@@ -56,10 +56,13 @@ bool tile_touched(const TileTest& t, int tx, int ty) {
   return true;
 }
 
-Lists bin_view(const MeshRef& m, const float* T, const float* Kv, int h, int w, int ns, int cap_list) {
+// cap_large < 0: the device's rule for this mesh as the largest of its database, 4 F + 4096 entries of (large piece, touched tile)
+Lists bin_view(const MeshRef& m, const float* T, const float* Kv, int h, int w, int ns, int cap_list, int cap_large = -1) {
   const int tiles_x = (w + TILE - 1) / TILE, tiles_y = (h + TILE - 1) / TILE, n_tiles = tiles_x * tiles_y;
   Lists L;
   std::vector<int> counts(n_tiles, 0);
+  long long total_large = 0;   // what raster_bin's large list would hold: one entry per (large piece, tile it can own a sample in)
+  if (cap_large < 0) cap_large = 4 * m.n_faces + 4096;
   const int F = view_finite(T, Kv) ? m.n_faces : 0;
   for (int t = 0; t < F; ++t) {
     int n_pieces = 1;
@@ -70,18 +73,20 @@ Lists bin_view(const MeshRef& m, const float* T, const float* Kv, int h, int w, 
       int tx0, ty0, tx1, ty1;
       tile_range(p, ns, w, h, tx0, ty0, tx1, ty1);
       if (tx0 > tx1 || ty0 > ty1) continue;
-      if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > LARGE_TILES || piece_extent(p) > SMALL_EXTENT) L.large.push_back(p.id);
-      else {
-        const TileTest tt = tile_test_setup(p, ns);
-        for (int ty = ty0; ty <= ty1; ++ty)
-          for (int tx = tx0; tx <= tx1; ++tx)
-            if (tile_touched(tt, tx, ty)) ++counts[ty * tiles_x + tx];
-      }
+      const bool is_large = (tx1 - tx0 + 1) * (ty1 - ty0 + 1) > LARGE_TILES || piece_extent(p) > SMALL_EXTENT;
+      if (is_large) L.large.push_back(p.id);
+      const TileTest tt = tile_test_setup(p, ns);
+      for (int ty = ty0; ty <= ty1; ++ty)
+        for (int tx = tx0; tx <= tx1; ++tx)
+          if (tile_touched(tt, tx, ty)) {
+            if (is_large) ++total_large;
+            else ++counts[ty * tiles_x + tx];
+          }
     }
   }
   L.tile_off.assign(n_tiles + 1, 0);
   for (int i = 0; i < n_tiles; ++i) L.tile_off[i + 1] = L.tile_off[i] + counts[i];
-  L.overflow = L.tile_off[n_tiles] > cap_list;
+  L.overflow = L.tile_off[n_tiles] > cap_list || total_large > cap_large;   // (raster_bin: total > cap_list || total_l > cap_large)
   if (L.overflow) return L;
   L.list.assign(L.tile_off[n_tiles], TileRec{});
   std::vector<int> cursor(L.tile_off.begin(), L.tile_off.end() - 1);
@@ -252,11 +257,70 @@ extern "C" void raster_emul_render(const float* verts, const float* normals, con
     off += std::max(1, tex_w >> l) * std::max(1, tex_h >> l);
   }
   std::vector<int32_t> ids(n_views, 0);
-  if (cap_list <= 0) cap_list = 4 * n_faces + 2048;
+  if (cap_list <= 0) cap_list = 3 * n_faces + 2048;   // the device's rule (raster_db.hip: raster_bin_layout)
   if (flags & 16u)
     render_views<4>(&m, &tx, ids.data(), TCO, K, n_views, h, w, flags, *lights, out, stride_v, views_per_item, stride_view, stride_y, stride_x,
                     c_rgb, c_normals, c_depth, cap_list, reverse_lists);
   else
     render_views<1>(&m, &tx, ids.data(), TCO, K, n_views, h, w, flags, *lights, out, stride_v, views_per_item, stride_view, stride_y, stride_x,
                     c_rgb, c_normals, c_depth, cap_list, reverse_lists);
+}
+
+// What raster_bin counts for every view, with this file's own make_piece / tile_range / tile_touched: per tile the binned records
+// (`binned`, [n_views][n_tiles]) and the large-list entries (`large`: the same tile test applied to the large pieces, as raster_bin
+// does), and per view `stats` [n_views][4] = {pieces that exist (id >= 0), pieces with a snapped coordinate beyond 2^21 sub-pixel
+// units, unclipped triangles dropped because a projected vertex lies beyond GUARD, clipped pieces}.  The host reference of the
+// per-view header and the tile offsets the device writes (tests/test_gpu_raster_limits.py).
+extern "C" void raster_emul_bin_counts(const float* verts, const int32_t* faces, int n_verts, int n_faces, const float* TCO, const float* K,
+                                       int n_views, int h, int w, int ns, int32_t* binned, int32_t* large, int32_t* stats) {
+  MeshRef m;
+  memset(&m, 0, sizeof(m));
+  m.verts = verts; m.faces = faces; m.n_verts = n_verts; m.n_faces = n_faces;
+  const int tiles_x = (w + TILE - 1) / TILE, tiles_y = (h + TILE - 1) / TILE, n_tiles = tiles_x * tiles_y;
+  for (int view = 0; view < n_views; ++view) {
+    const float* T = TCO + (size_t)view * 16;
+    const float* Kv = K + (size_t)view * 9;
+    int32_t* cb = binned + (size_t)view * n_tiles;
+    int32_t* cl = large + (size_t)view * n_tiles;
+    int32_t* st = stats + (size_t)view * 4;
+    std::fill(cb, cb + n_tiles, 0);
+    std::fill(cl, cl + n_tiles, 0);
+    st[0] = st[1] = st[2] = st[3] = 0;
+    const int F = view_finite(T, Kv) ? n_faces : 0;
+    for (int t = 0; t < F; ++t) {
+      int n_pieces = 1;
+      for (int which = 0; which < n_pieces; ++which) {
+        Piece p;
+        n_pieces = make_piece<false>(m, T, Kv, t, which, p);
+        if (p.id < 0) {
+          if (which == 0 && n_pieces == 1) {   // an unclipped triangle: was it the guard band that dropped it?
+            bool unclipped = true, beyond = false;
+            for (int k = 0; k < 3; ++k) {
+              const float* q = verts + 3 * (size_t)faces[3 * t + k];
+              const float x = dot3p(T[0], T[1], T[2], q[0], q[1], q[2], T[3]), y = dot3p(T[4], T[5], T[6], q[0], q[1], q[2], T[7]);
+              const float z = dot3p(T[8], T[9], T[10], q[0], q[1], q[2], T[11]);
+              unclipped = unclipped && z >= Z_NEAR;
+              const float iz = 1.0f / z;
+              beyond = beyond || !(fabsf(fmaf(Kv[0], x * iz, Kv[2])) < GUARD) || !(fabsf(fmaf(Kv[4], y * iz, Kv[5])) < GUARD);
+            }
+            if (unclipped && beyond) ++st[2];
+          }
+          continue;
+        }
+        ++st[0];
+        if (p.flags & 2) ++st[3];
+        int amax = 0;
+        for (int k = 0; k < 3; ++k) amax = imax(amax, imax(p.X[k] < 0 ? -p.X[k] : p.X[k], p.Y[k] < 0 ? -p.Y[k] : p.Y[k]));
+        if (amax > (1 << 21)) ++st[1];
+        int tx0, ty0, tx1, ty1;
+        tile_range(p, ns, w, h, tx0, ty0, tx1, ty1);
+        if (tx0 > tx1 || ty0 > ty1) continue;
+        int32_t* cnt = ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > LARGE_TILES || piece_extent(p) > SMALL_EXTENT) ? cl : cb;
+        const TileTest tt = tile_test_setup(p, ns);
+        for (int ty = ty0; ty <= ty1; ++ty)
+          for (int tx = tx0; tx <= tx1; ++tx)
+            if (tile_touched(tt, tx, ty)) ++cnt[ty * tiles_x + tx];
+      }
+    }
+  }
 }
