@@ -867,6 +867,9 @@ int mp_detector_forward(mp_detector* det, const float* d_images, int n_images, i
                         mp_stream stream);
 /* Parity taps (tests): after a forward, the device address + logical shape of an intermediate inside `d_workspace`:
  * "P2".."P6" padded-NHWC pyramid levels {n, h, w, 256} with border 1; "x0" the preprocessed batch {n, Hp, Wp, 4} with border 3;
+ * "pool" the stem + max-pool output {n, Hp/4, Wp/4, 64} and "C2".."C5" the ResNet stage outputs the FPN read {n, h, w, 256 << (k-2)}, border 1;
+ * "L2".."L5" the FPN's top-down maps (lateral 1x1 + upsampled upper level; P_k is the 3x3 convolution of L_k) {n, h, w, 256}, border 1;
+ * "roi7" the box head's RoIAlign rows {n*post, 7*7*256} ((y, x, channel) order); "roi14" the mask head's {n*D, 14, 14, 256} with border 1;
  * "keys" the RPN objectness logits {n, anchors} in (level, y, x, anchor) order; "proposals" {n, post_nms_top_n, 4} + "proposal_counts" {n} (int32);
  * "class_logits" {n*post, padded 5*n_classes row: n_classes logits then 4*n_classes deltas}; "mask_logits" {n*D*14*14*4, padded n_classes}.
  * Returns MP_ERR_INVALID for an unknown name or before the first forward. */

@@ -549,6 +549,7 @@ struct DetPlan {
   int n_seg_rpn;
   size_t total = 0;
   std::map<std::string, size_t> off;    // float offsets
+  std::string stage_buf[4];             // which of s{st}.xa / s{st}.xb holds the stage's output C2..C5 (set by the forward: what the FPN read)
   size_t take(const std::string& name, size_t floats) {
     const size_t o = total;
     off[name] = o;
@@ -904,11 +905,13 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
       if (rc) return rc;
       idn = F(S + ".d");
     }
-    float* y = (x == F(S + ".xa")) ? F(S + ".xb") : F(S + ".xa");
+    const std::string yk = S + ((x == F(S + ".xa")) ? ".xb" : ".xa");
+    float* y = F(yk);
     rc = run_conv_layer(b.c3, F(S + ".t2"), n, oh, ow, 1, y, 1, idn, 1, s, SK, DET_SPLITK_FLOATS);
     if (rc) return rc;
     x = y; xh = oh; xw = ow;
     stage_out[st] = y;
+    p.stage_buf[st] = yk;
   }
   // FPN (ops/feature_pyramid_network.py): last_inner = inner[3](C5); P5 = layer[3](last_inner); going down: lateral + nearest upsample
   rc = run_conv_layer(d->fpn_inner[3], stage_out[3], n, p.fh[3], p.fw[3], 1, F("L3"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
@@ -1053,14 +1056,31 @@ extern "C" int mp_detector_debug_tensor(const mp_detector* d, const char* what, 
   MP_REQUIRE(d->ran, "mp_detector_debug_tensor: no forward has run yet");
   const DetPlan& p = d->last;
   const std::string w = what;
-  auto it = p.off.find(w);
+  const bool is_stage = w.size() == 2 && w[0] == 'C' && w[1] >= '2' && w[1] <= '5';   // C2..C5: the buffer the stage's last block wrote
+  const bool is_inner = w.size() == 2 && w[0] == 'L' && w[1] >= '2' && w[1] <= '5';   // L2..L5: the FPN's top-down maps (plan buffers L0..L3)
+  auto it = p.off.find(is_stage ? p.stage_buf[w[1] - '2'] : is_inner ? "L" + std::to_string(w[1] - '2') : w);
   MP_REQUIRE(it != p.off.end(), "mp_detector_debug_tensor: unknown tensor '%s'", what);
   *d_ptr = (const float*)d->last_ws + it->second;
   *border = 0;
   const int R = d->cfg.rpn_post_nms_top_n, D = d->cfg.box_detections_per_img;
-  if (w.size() == 2 && w[0] == 'P' && w[1] >= '2' && w[1] <= '6') {
+  if (w.size() == 2 && (is_inner || (w[0] == 'P' && w[1] >= '2' && w[1] <= '6'))) {
     const int l = w[1] - '2';
     shape4[0] = p.n; shape4[1] = p.fh[l]; shape4[2] = p.fw[l]; shape4[3] = DET_FPN_C;
+    *border = 1;
+    *row_stride = DET_FPN_C;
+  } else if (is_stage) {
+    const int st = w[1] - '2';
+    shape4[0] = p.n; shape4[1] = p.fh[st]; shape4[2] = p.fw[st]; shape4[3] = 256 << st;
+    *border = 1;
+    *row_stride = shape4[3];
+  } else if (w == "pool") {   // stem + max-pool output, the input of the first body stage
+    shape4[0] = p.n; shape4[1] = p.Hp / 4; shape4[2] = p.Wp / 4; shape4[3] = 64;
+    *border = 1;
+    *row_stride = 64;
+  } else if (w == "roi7") {   // box head RoIAlign rows [7][7][256]
+    shape4[0] = (int64_t)p.n * R; shape4[1] = 7 * 7 * DET_FPN_C; shape4[2] = 1; shape4[3] = 1; *row_stride = 7 * 7 * DET_FPN_C;
+  } else if (w == "roi14") {  // mask head RoIAlign maps
+    shape4[0] = (int64_t)p.n * D; shape4[1] = 14; shape4[2] = 14; shape4[3] = DET_FPN_C;
     *border = 1;
     *row_stride = DET_FPN_C;
   } else if (w == "proposals") {

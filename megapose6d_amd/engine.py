@@ -1446,7 +1446,9 @@ class DetectorNet(_Handle):
         return boxes, scores, labels, counts, masks
 
     def debug_tensor(self, what: str) -> torch.Tensor:
-        """a COPY of an intermediate of the last forward (parity tests): padded maps come back as their [n,h,w,c] interior"""
+        """a COPY of an intermediate of the last forward (parity tests): padded maps come back as their [n,h,w,c] interior.
+        Taps: "x0", "pool", "C2".."C5", "L2".."L5", "P2".."P6", "keys", "proposals", "proposal_scores", "proposal_counts", "roi7", "class_logits",
+        "f_cnt", "det_resized", "roi14", "mask_logits" (shapes: mp_detector_debug_tensor in include/mp_engine.h)"""
         lib = _lib.load()
         ptr, shp, border, rs, n_el = C.c_void_p(), (C.c_int64 * 4)(), C.c_int32(0), C.c_int64(0), C.c_int64(0)
         check(lib.mp_detector_debug_tensor(self.handle, what.encode(), C.byref(ptr), shp, C.byref(border), C.byref(rs), C.byref(n_el)))

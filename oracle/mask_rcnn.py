@@ -159,33 +159,61 @@ def _bn(sd, p, x):  # FrozenBatchNorm2d (ops/misc.py): scale = w * rsqrt(var + e
     return x * scale.reshape(1, -1, 1, 1) + shift.reshape(1, -1, 1, 1)
 
 
-def resnet50_fpn(sd: Dict[str, torch.Tensor], x: torch.Tensor) -> List[torch.Tensor]:
-    """-> [P2, P3, P4, P5, pool] (FPN outputs "0".."3","pool"), 256 channels each"""
+def resnet_stem(sd: Dict[str, torch.Tensor], x: torch.Tensor) -> torch.Tensor:
+    """conv1 + bn1 + relu + maxpool: [n, 3, H, W] -> [n, 64, H / 4, W / 4]"""
     B = "backbone.body."
     x = F.relu(_bn(sd, B + "bn1", F.conv2d(x, sd[B + "conv1.weight"], stride=2, padding=3)))
-    x = F.max_pool2d(x, 3, 2, 1)
-    feats = []
-    for li, n in enumerate(RESNET50_BLOCKS):
-        for bi in range(n):
-            P = f"{B}layer{li + 1}.{bi}."
-            stride = 2 if (bi == 0 and li > 0) else 1
-            idn = x
-            o = F.relu(_bn(sd, P + "bn1", F.conv2d(x, sd[P + "conv1.weight"])))
-            o = F.relu(_bn(sd, P + "bn2", F.conv2d(o, sd[P + "conv2.weight"], stride=stride, padding=1)))
-            o = _bn(sd, P + "bn3", F.conv2d(o, sd[P + "conv3.weight"]))
-            if bi == 0:
-                idn = _bn(sd, P + "downsample.1", F.conv2d(x, sd[P + "downsample.0.weight"], stride=stride))
-            x = F.relu(o + idn)
-        feats.append(x)
+    return F.max_pool2d(x, 3, 2, 1)
+
+
+def resnet_stage(sd: Dict[str, torch.Tensor], x: torch.Tensor, li: int) -> torch.Tensor:
+    """body stage `layer{li + 1}` (li = 0..3): the stage's input -> C{li + 2}"""
+    B = "backbone.body."
+    for bi in range(RESNET50_BLOCKS[li]):
+        P = f"{B}layer{li + 1}.{bi}."
+        stride = 2 if (bi == 0 and li > 0) else 1
+        idn = x
+        o = F.relu(_bn(sd, P + "bn1", F.conv2d(x, sd[P + "conv1.weight"])))
+        o = F.relu(_bn(sd, P + "bn2", F.conv2d(o, sd[P + "conv2.weight"], stride=stride, padding=1)))
+        o = _bn(sd, P + "bn3", F.conv2d(o, sd[P + "conv3.weight"]))
+        if bi == 0:
+            idn = _bn(sd, P + "downsample.1", F.conv2d(x, sd[P + "downsample.0.weight"], stride=stride))
+        x = F.relu(o + idn)
+    return x
+
+
+def fpn_inner(sd: Dict[str, torch.Tensor], c: torch.Tensor, i: int, top: torch.Tensor = None) -> torch.Tensor:
+    """the top-down map of level i (0..3): lateral 1x1 conv of C{i + 2}, plus the nearest-upsampled top-down map of level i + 1"""
     F_ = "backbone.fpn."
-    last = F.conv2d(feats[3], sd[F_ + "inner_blocks.3.weight"], sd[F_ + "inner_blocks.3.bias"])
-    outs = [F.conv2d(last, sd[F_ + "layer_blocks.3.weight"], sd[F_ + "layer_blocks.3.bias"], padding=1)]
+    lat = F.conv2d(c, sd[F_ + f"inner_blocks.{i}.weight"], sd[F_ + f"inner_blocks.{i}.bias"])
+    return lat if top is None else lat + F.interpolate(top, size=lat.shape[-2:], mode="nearest")
+
+
+def fpn_layer(sd: Dict[str, torch.Tensor], inner: torch.Tensor, i: int) -> torch.Tensor:
+    """P{i + 2}: the 3x3 output conv of level i on its top-down map"""
+    F_ = "backbone.fpn."
+    return F.conv2d(inner, sd[F_ + f"layer_blocks.{i}.weight"], sd[F_ + f"layer_blocks.{i}.bias"], padding=1)
+
+
+def fpn(sd: Dict[str, torch.Tensor], feats: Sequence[torch.Tensor]) -> List[torch.Tensor]:
+    """[C2, C3, C4, C5] -> [P2, P3, P4, P5, pool]"""
+    last = fpn_inner(sd, feats[3], 3)
+    outs = [fpn_layer(sd, last, 3)]
     for i in (2, 1, 0):
-        lat = F.conv2d(feats[i], sd[F_ + f"inner_blocks.{i}.weight"], sd[F_ + f"inner_blocks.{i}.bias"])
-        last = lat + F.interpolate(last, size=lat.shape[-2:], mode="nearest")
-        outs.insert(0, F.conv2d(last, sd[F_ + f"layer_blocks.{i}.weight"], sd[F_ + f"layer_blocks.{i}.bias"], padding=1))
+        last = fpn_inner(sd, feats[i], i, last)
+        outs.insert(0, fpn_layer(sd, last, i))
     outs.append(F.max_pool2d(outs[-1], 1, 2, 0))
     return outs
+
+
+def resnet50_fpn(sd: Dict[str, torch.Tensor], x: torch.Tensor) -> List[torch.Tensor]:
+    """-> [P2, P3, P4, P5, pool] (FPN outputs "0".."3","pool"), 256 channels each"""
+    x = resnet_stem(sd, x)
+    feats = []
+    for li in range(len(RESNET50_BLOCKS)):
+        x = resnet_stage(sd, x, li)
+        feats.append(x)
+    return fpn(sd, feats)
 
 
 def transform_images(images: Sequence[torch.Tensor], min_size: int, max_size: int):
@@ -386,16 +414,22 @@ def postprocess_detections(logits, reg, proposals, image_sizes):
     return res
 
 
+def mask_head_logits(sd, x: torch.Tensor) -> torch.Tensor:
+    """mask head + predictor on RoIAlign features [K, 256, 14, 14] -> the logits of every class [K, n_classes, 28, 28] (before
+    maskrcnn_inference's sigmoid and class selection)"""
+    for i in range(1, 5):
+        x = F.relu(F.conv2d(x, sd[f"roi_heads.mask_head.mask_fcn{i}.weight"], sd[f"roi_heads.mask_head.mask_fcn{i}.bias"], padding=1))
+    x = F.relu(F.conv_transpose2d(x, sd["roi_heads.mask_predictor.conv5_mask.weight"], sd["roi_heads.mask_predictor.conv5_mask.bias"], stride=2))
+    return F.conv2d(x, sd["roi_heads.mask_predictor.mask_fcn_logits.weight"], sd["roi_heads.mask_predictor.mask_fcn_logits.bias"])
+
+
 def mask_branch(sd, feats4, dets, image_sizes) -> List[torch.Tensor]:
     boxes = [d["boxes"] for d in dets]
     if sum(len(b) for b in boxes) == 0:
         return [torch.zeros(0, 1, 28, 28) for _ in dets]
-    x = multiscale_roi_align(feats4, boxes, image_sizes, 14)
-    for i in range(1, 5):
-        x = F.relu(F.conv2d(x, sd[f"roi_heads.mask_head.mask_fcn{i}.weight"], sd[f"roi_heads.mask_head.mask_fcn{i}.bias"], padding=1))
-    x = F.relu(F.conv_transpose2d(x, sd["roi_heads.mask_predictor.conv5_mask.weight"], sd["roi_heads.mask_predictor.conv5_mask.bias"], stride=2))
-    x = F.conv2d(x, sd["roi_heads.mask_predictor.mask_fcn_logits.weight"], sd["roi_heads.mask_predictor.mask_fcn_logits.bias"])
-    prob = x.sigmoid()
+    # (RoIAlign samples in float32, as in box_branch; the layers after it run in the dtype of the weights)
+    x = multiscale_roi_align(feats4, boxes, image_sizes, 14).to(sd["roi_heads.mask_head.mask_fcn1.weight"].dtype)
+    prob = mask_head_logits(sd, x).sigmoid()
     labels = torch.cat([d["labels"] for d in dets])
     prob = prob[torch.arange(len(labels)), labels][:, None]
     return list(prob.split([len(b) for b in boxes], dim=0))

@@ -1,6 +1,6 @@
 """Shared pieces of the detector stage tests (tests/test_gpu_zz_detector_stages.py): reading the engine's debug taps (padded NHWC maps,
-row matrices whose rows are padded past their logical width), the layout conversions the oracle (oracle/mask_rcnn.py) needs, and a
-rank-for-rank matcher of selection results that tolerates only counted, near-tied exceptions."""
+row matrices whose rows are padded past their logical width), the layout conversions the oracle (oracle/mask_rcnn.py) needs, a float64
+MultiScaleRoIAlign reference that takes its decisions in float32 as the kernel does, and a rank-for-rank matcher of selection results that tolerates only counted, near-tied exceptions."""
 from __future__ import annotations
 
 import ctypes as C
@@ -46,6 +46,93 @@ def mask_logits_28(rows: torch.Tensor, n_det: int) -> torch.Tensor:
     cs = rows.shape[1]
     t = rows.reshape(n_det, 14, 14, 2, 2, cs).permute(0, 5, 1, 3, 2, 4)   # det, c, y, a, x, b
     return t.reshape(n_det, cs, 28, 28)
+
+
+def debug_map(net, what: str) -> torch.Tensor:
+    """a padded-NHWC tap as its [n, h, w, c] interior, after asserting that the border ring around it is zero"""
+    flat, shp, b, _ = raw_debug(net, what)
+    n, h, w, c = shp
+    assert b > 0, (what, b)
+    full = flat.view(n, h + 2 * b, w + 2 * b, c)
+    inner = full[:, b : b + h, b : b + w].clone()
+    full[:, b : b + h, b : b + w] = 0
+    assert (full == 0).all(), f"{what}: non-zero border"
+    return inner
+
+
+def roi_levels(boxes: torch.Tensor, k_min: int = 2, k_max: int = 5) -> torch.Tensor:
+    """LevelMapper of MultiScaleRoIAlign (ops/poolers.py) in float32: k = floor(4 + log2(sqrt(area) / 224) + 1e-6) clamped to
+    [k_min, k_max]; boxes [K, 4] float32"""
+    boxes = boxes.float()
+    area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+    return torch.floor(4 + torch.log2(torch.sqrt(area) / 224) + torch.tensor(1e-6)).clamp(k_min, k_max).long()
+
+
+def multiscale_roi_align_f64(maps: Sequence[torch.Tensor], boxes: Sequence[torch.Tensor], image_sizes, P: int, chunk_bytes: int = 1 << 28):
+    """float64 reference of MultiScaleRoIAlign(["0".."3"], P, sampling_ratio = 2) (oracle.mask_rcnn.multiscale_roi_align).
+    maps: P2..P5 as [n, h, w, c] (NHWC interiors of the engine's taps, any float dtype); boxes: one [k, 4] float32 tensor per image.
+    -> (out [K, P, P, c] float64, levels [K] in 2..5), K = the boxes of all images in order.
+
+    What DECIDES something runs in float32, operation for operation as oracle.thirdparty.roi_align and det_roi_align_kernel do: the
+    level, the scaled box, max(size, 1), the bin size, the sample coordinates, the skip test (< -1 or > size), the clamps at 0 and at
+    the last row / column, the integer corner.  The fractional part c - floor(c) is exact in float32; from it on everything is float64:
+    1 - l, the four corner weights, the interpolation and the mean of the 2 x 2 samples."""
+    f32 = torch.float32
+    rois = torch.cat([b.to(f32).reshape(-1, 4) for b in boxes])
+    bidx = torch.cat([torch.full((len(b),), i, dtype=torch.long) for i, b in enumerate(boxes)])
+    K, C = len(rois), int(maps[0].shape[-1])
+    oh, ow = max(s[0] for s in image_sizes), max(s[1] for s in image_sizes)
+    scales = []
+    for f in maps:   # poolers.py infer_scale, from the sizes of the (unpadded) images
+        s1 = 2.0 ** float(torch.tensor(float(f.shape[1]) / float(oh)).log2().round())
+        s2 = 2.0 ** float(torch.tensor(float(f.shape[2]) / float(ow)).log2().round())
+        assert s1 == s2, (s1, s2)
+        scales.append(s1)
+    k_min, k_max = int(-np.log2(scales[0])), int(-np.log2(scales[-1]))
+    levels = roi_levels(rois, k_min, k_max)
+    out = torch.zeros(K, P, P, C, dtype=torch.float64)
+    g = 2
+    per_roi = (P * g) ** 2 * C * 8 * 3   # gathered corner values, their weighted copy and the accumulator
+    step = max(1, chunk_bytes // per_roi)
+
+    def prep(c, size):
+        invalid = (c < -1.0) | (c > size)
+        c = torch.where(c <= 0, torch.zeros_like(c), c)
+        lo = c.floor().long()
+        at_edge = lo >= size - 1
+        lo = torch.where(at_edge, torch.full_like(lo, size - 1), lo)
+        hi = torch.where(at_edge, lo, lo + 1)
+        c = torch.where(at_edge, lo.to(f32), c)
+        l = (c - lo.to(f32)).double()   # exact in float32
+        return invalid, lo, hi, l, 1.0 - l
+
+    for li, (f, sc) in enumerate(zip(maps, scales)):
+        n, H, W, _ = f.shape
+        flat = f.reshape(n * H * W, C).double()
+        sel_all = torch.where(levels == li + k_min)[0]
+        for s0 in range(0, len(sel_all), step):
+            sel = sel_all[s0 : s0 + step]
+            b = rois[sel]
+            x1, y1, x2, y2 = b[:, 0] * sc, b[:, 1] * sc, b[:, 2] * sc, b[:, 3] * sc
+            rw, rh = torch.clamp(x2 - x1, min=1.0), torch.clamp(y2 - y1, min=1.0)
+            bin_h, bin_w = rh / P, rw / P
+            i_ = torch.arange(g, dtype=f32)
+            p_ = torch.arange(P, dtype=f32)
+            ys = y1[:, None, None] + p_[None, :, None] * bin_h[:, None, None] + ((i_[None, None, :] + 0.5) * bin_h[:, None, None] / g)
+            xs = x1[:, None, None] + p_[None, :, None] * bin_w[:, None, None] + ((i_[None, None, :] + 0.5) * bin_w[:, None, None] / g)
+            assert ys.dtype == f32 and xs.dtype == f32
+            inv_y, ylo, yhi, ly, hy = prep(ys, H)   # [k, P, g]
+            inv_x, xlo, xhi, lx, hx = prep(xs, W)
+            live = (~(inv_y[:, :, :, None, None] | inv_x[:, None, None, :, :])).double()   # [k, P, g, P, g]
+            base = (bidx[sel] * (H * W))[:, None, None, None, None]
+            acc = torch.zeros(len(sel), P, g, P, g, C, dtype=torch.float64)
+            for yi, wy in ((ylo, hy), (yhi, ly)):
+                for xi, wx in ((xlo, hx), (xhi, lx)):
+                    idx = base + yi[:, :, :, None, None] * W + xi[:, None, None, :, :]
+                    wgt = wy[:, :, :, None, None] * wx[:, None, None, :, :] * live
+                    acc += flat[idx.reshape(-1)].view(*idx.shape, C) * wgt[..., None]
+            out[sel] = acc.sum(dim=(2, 4)) / float(g * g)
+    return out, levels
 
 
 def iou_f32(a: np.ndarray, b: np.ndarray) -> np.ndarray:

@@ -100,6 +100,142 @@ def test_oracle_is_pinned_to_its_golden_outputs():
     assert np.abs(out[0]["masks28"][:4, 0].numpy() - g["masks28_first4"][0]).max() < 1e-5
 
 
+def _old_resnet50_fpn(sd, x):
+    """the trunk as ONE function, as oracle.mask_rcnn.resnet50_fpn was written before it was split into stem / stages / fpn"""
+    import torch.nn.functional as F
+
+    from oracle import mask_rcnn as om
+
+    B = "backbone.body."
+    x = F.relu(om._bn(sd, B + "bn1", F.conv2d(x, sd[B + "conv1.weight"], stride=2, padding=3)))
+    x = F.max_pool2d(x, 3, 2, 1)
+    feats = []
+    for li, n in enumerate(om.RESNET50_BLOCKS):
+        for bi in range(n):
+            P = f"{B}layer{li + 1}.{bi}."
+            stride = 2 if (bi == 0 and li > 0) else 1
+            idn = x
+            o = F.relu(om._bn(sd, P + "bn1", F.conv2d(x, sd[P + "conv1.weight"])))
+            o = F.relu(om._bn(sd, P + "bn2", F.conv2d(o, sd[P + "conv2.weight"], stride=stride, padding=1)))
+            o = om._bn(sd, P + "bn3", F.conv2d(o, sd[P + "conv3.weight"]))
+            if bi == 0:
+                idn = om._bn(sd, P + "downsample.1", F.conv2d(x, sd[P + "downsample.0.weight"], stride=stride))
+            x = F.relu(o + idn)
+        feats.append(x)
+    F_ = "backbone.fpn."
+    last = F.conv2d(feats[3], sd[F_ + "inner_blocks.3.weight"], sd[F_ + "inner_blocks.3.bias"])
+    outs = [F.conv2d(last, sd[F_ + "layer_blocks.3.weight"], sd[F_ + "layer_blocks.3.bias"], padding=1)]
+    for i in (2, 1, 0):
+        lat = F.conv2d(feats[i], sd[F_ + f"inner_blocks.{i}.weight"], sd[F_ + f"inner_blocks.{i}.bias"])
+        last = lat + F.interpolate(last, size=lat.shape[-2:], mode="nearest")
+        outs.insert(0, F.conv2d(last, sd[F_ + f"layer_blocks.{i}.weight"], sd[F_ + f"layer_blocks.{i}.bias"], padding=1))
+    outs.append(F.max_pool2d(outs[-1], 1, 2, 0))
+    return outs, feats
+
+
+def test_split_trunk_equals_the_one_piece_composition_bit_for_bit():
+    """resnet_stem, resnet_stage and fpn, called one by one (as the stage tests do), and resnet50_fpn that composes them give the
+    bits of the unsplit trunk in float32; 1 x 64 x 96 is the smallest frame of the stage tests (P5 2 x 3, P6 1 x 2)"""
+    from oracle import mask_rcnn as om
+
+    sd = om.synthetic_state_dict(2)
+    for n, h, w in ((1, 64, 96), (2, 96, 128)):
+        batch, _, _ = om.transform_images(list(om.synthetic_images(n, h, w)), h, w)
+        with torch.no_grad():
+            ref, ref_c = _old_resnet50_fpn(sd, batch)
+            got = om.resnet50_fpn(sd, batch)
+            x = om.resnet_stem(sd, batch)
+            cs = []
+            for li in range(4):
+                x = om.resnet_stage(sd, x, li)
+                cs.append(x)
+            parts = om.fpn(sd, cs)
+        Hp, Wp = batch.shape[2:]
+        assert [tuple(t.shape) for t in got] == [(n, 256, Hp >> k, Wp >> k) for k in (2, 3, 4, 5)] + [(n, 256, ((Hp >> 5) + 1) // 2, ((Wp >> 5) + 1) // 2)]
+        assert all(torch.equal(a, b) for a, b in zip(cs, ref_c))
+        assert all(torch.equal(a, b) for a, b in zip(got, ref)) and all(torch.equal(a, b) for a, b in zip(parts, ref))
+
+
+def test_mask_branch_runs_in_float64_and_agrees_with_float32_to_round_off():
+    """mask_branch casts the (float32) RoIAlign output to the weights' dtype, as box_branch does: with float64 weights it runs, and
+    the float32 branch differs from it by round-off.  mask_head_logits is the same chain before the sigmoid and the class selection.
+    Bound: the logits come from six layers of <= 2304-term float32 dot products of O(1) terms: 1e-5 of the scale is ~100 ulp, an order
+    above what sequential-sum round-off gives there and four orders below a wrong weight or pixel (the probabilities' slope is <= 1/4)."""
+    from oracle import mask_rcnn as om
+
+    C = 3
+    sd = om.synthetic_state_dict(C)
+    sd64 = {k: v.double() for k, v in sd.items()}
+    g = torch.Generator().manual_seed(3)
+    feats = [torch.randn(2, 256, 64 >> k, 96 >> k, generator=g) for k in range(4)]
+    sizes = [(250, 380), (256, 384)]
+    boxes = [torch.tensor([[10.0, 20.0, 200.0, 240.0], [300.0, 5.0, 330.0, 40.0], [0.0, 0.0, 384.0, 256.0]]), torch.tensor([[50.0, 60.0, 50.0, 90.0]])]
+    dets = [dict(boxes=b, labels=torch.tensor([1, 2, 1][: len(b)])) for b in boxes]
+    with torch.no_grad():
+        m32 = om.mask_branch(sd, feats, dets, sizes)
+        m64 = om.mask_branch(sd64, [f.double() for f in feats], dets, sizes)
+        roi = om.multiscale_roi_align(feats, boxes, sizes, 14)
+        l32, l64 = om.mask_head_logits(sd, roi), om.mask_head_logits(sd64, roi.double())
+    assert [tuple(m.shape) for m in m64] == [(3, 1, 28, 28), (1, 1, 28, 28)] and m64[0].dtype == torch.float64 and m32[0].dtype == torch.float32
+    assert l64.shape == (4, C, 28, 28) and l64.dtype == torch.float64
+    lab = torch.tensor([1, 2, 1, 1])
+    assert torch.equal(torch.cat(m32), l32.sigmoid()[torch.arange(4), lab][:, None])   # mask_branch = sigmoid + selection of these logits
+    assert torch.equal(torch.cat(m64), l64.sigmoid()[torch.arange(4), lab][:, None])
+    scale = max(1.0, l64.abs().max().item())
+    err_l = (l32.double() - l64).abs().max().item() / scale
+    err_p = (torch.cat(m32).double() - torch.cat(m64)).abs().max().item()
+    print(f"[mask_branch] float32 vs float64: logits {err_l:.3e} of scale {scale:.2f}, probabilities {err_p:.3e}")
+    assert err_l < 1e-5 and err_p < 2.5e-6, (err_l, err_p)
+    assert l64.abs().max() > 0.1   # (not a comparison of zeros)
+
+
+def test_float64_roi_align_reference_equals_the_oracles_to_round_off():
+    """tests/support/detector.py multiscale_roi_align_f64 against oracle.mask_rcnn.multiscale_roi_align (float32, torchvision's
+    operation order) on random maps: same level for every box, values within float32 round-off.  Bound: an output is the mean of 4
+    samples of 4 products each, accumulated in float32: <= 16 products, 16 additions and a division, each rounded to half an ulp of at
+    most max|map| -> 33 * 2^-24 * max|map|."""
+    from oracle import mask_rcnn as om
+    from oracle import thirdparty as tp
+    from tests.support import detector as sup
+
+    g = torch.Generator().manual_seed(11)
+    n, Hp, Wp = 2, 128, 160
+    feats = [torch.randn(n, 16, Hp >> k, Wp >> k, generator=g) for k in (2, 3, 4, 5)]
+    sizes = [(120, 150), (128, 160)]
+    special = torch.tensor([
+        [40.0, 30.0, 40.0, 90.0],        # zero width: max(roi_w, 1)
+        [20.0, 70.0, 100.0, 70.0],       # zero height
+        [-300.0, -200.0, -100.0, -90.0],  # wholly outside: every sample is skipped
+        [100.0, 90.0, 420.0, 380.0],     # runs past the right / bottom edge
+        [-50.0, -40.0, 60.0, 50.0],      # starts before the frame
+        [0.0, 0.0, 112.0, 112.0], [10.0, 0.0, 66.0, 224.0],      # sqrt(area) = 112 exactly -> level 3
+        [0.0, 0.0, 224.0, 224.0], [0.0, 8.0, 112.0, 456.0],      # 224 -> 4
+        [0.0, 0.0, 448.0, 448.0], [-100.0, 0.0, 796.0, 224.0],   # 448 -> 5
+        [0.0, 0.0, 111.99, 112.0], [0.0, 0.0, 223.99, 224.0], [0.0, 0.0, 447.99, 448.0],   # just below each threshold
+    ])
+    xy = torch.rand(40, 2, generator=g) * torch.tensor([150.0, 120.0])
+    wh = torch.exp(torch.rand(40, 2, generator=g) * 5.5)   # 1 .. 245 px
+    boxes = [torch.cat([special, torch.cat([xy[:20], xy[:20] + wh[:20]], 1)]), torch.cat([special.flip(0), torch.cat([xy[20:], xy[20:] + wh[20:]], 1)])]
+    all_boxes = torch.cat(boxes)
+    bidx = torch.cat([torch.full((len(b),), float(i)) for i, b in enumerate(boxes)])
+    for P in (7, 14):
+        ref = om.multiscale_roi_align(feats, boxes, sizes, P)                                     # [K, c, P, P] float32
+        got, lv = sup.multiscale_roi_align_f64([f.permute(0, 2, 3, 1) for f in feats], boxes, sizes, P, chunk_bytes=1 << 20)   # (several chunks)
+        assert got.dtype == torch.float64 and got.shape == (len(all_boxes), P, P, 16)
+        assert lv[: len(special)].tolist() == [2, 2, 3, 4, 2, 3, 3, 4, 4, 5, 5, 2, 3, 4] and set(lv.tolist()) == {2, 3, 4, 5}
+        # the oracle's row of every box is RoIAlign on the level chosen here, bit for bit: the same level
+        for k in range(len(all_boxes)):
+            l = int(lv[k]) - 2
+            one = tp.roi_align(feats[l], torch.cat([bidx[k : k + 1, None], all_boxes[k : k + 1]], 1), (P, P), spatial_scale=1.0 / (4 << l), sampling_ratio=2)
+            assert torch.equal(one[0], ref[k]), k
+        err = (got.permute(0, 3, 1, 2) - ref.double()).abs().max().item()
+        bound = 33 * 2.0 ** -24 * max(f.abs().max().item() for f in feats)
+        print(f"[roi_align_f64] P {P}: err {err:.3e} (bound {bound:.3e})")
+        assert err <= bound, (P, err, bound)
+        assert (got[2] == 0).all() and (ref[2] == 0).all()   # the box outside the frame
+        assert got[0].abs().max() > 0 and got[1].abs().max() > 0
+
+
 def test_native_checker_generates_the_oracles_synthetic_network(tmp_path):
     """scripts/microbench/native_detector_check.cpp (the torch-free parity runner used on the GPU box) regenerates weights and images
     from the same hash as oracle.mask_rcnn.synthetic_*: its --checksums mode (host only) must agree tensor by tensor, bit for bit"""

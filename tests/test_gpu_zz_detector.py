@@ -2,7 +2,10 @@
 (oracle/mask_rcnn.py, a restatement of torchvision 0.12's Mask R-CNN inference -- third party, parity unpinned).
 Weights and images are hash-generated on both sides (oracle.mask_rcnn.synthetic_*); the oracle's results come from the committed
 compact goldens (tests/golden/detector_*.npz) and, for one small case, from a fresh oracle run on the host CPU.
-Tolerances: feature maps 1e-3 relative to their scale (fp32 MFMA vs MKL-DNN summation order over ~60 layers; measured ~1e-6),
+Tolerances: feature maps 8.2e-6 relative to the scale of the golden's subsample (every 4th row and column, every 16th channel) =
+2 x (1.6e-6 + 2.5e-6): the float32 oracle that wrote the goldens is off the float64 oracle by at most 1.6e-6 of that scale, and the engine's
+whole trunk from x0 is off the float64 oracle by 8.4e-7 of the FULL map's scale (tests/test_gpu_zz_detector_stages.py, "un-forced"), which
+is up to 2.98 x the subsample's (measured against the goldens themselves: the "[golden]" lines of the test output, 1.8e-6);
 boxes 5e-2 px, scores 2e-4, labels exact; a couple of detections may swap or drop where two scores tie within round-off.
 (The same comparison runs torch-free in scripts/microbench/native_detector_check.cpp; its MI355X log is profiles/r02_detector_native_check.txt.)"""
 from pathlib import Path
@@ -13,6 +16,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
+PYRAMID_TOL = 8.2e-6
 
 
 def _model(C, mn, mx):
@@ -46,7 +50,9 @@ def test_detector_matches_the_oracle_goldens(case):
     for l in range(2, 7):   # pyramid
         f = net.debug_tensor(f"P{l}").cpu().numpy()
         ref = g[f"P{l}_sub"]
-        assert np.abs(f[:, ::4, ::4, ::16] - ref).max() < 1e-3 * max(1.0, np.abs(ref).max()), l
+        err = float(np.abs(f[:, ::4, ::4, ::16] - ref).max() / max(1.0, np.abs(ref).max()))
+        print(f"[golden] {case}: P{l} err {err:.3e}")
+        assert err < PYRAMID_TOL, (l, err)
         assert abs(np.abs(f).mean() - float(g[f"P{l}_absmean"][0])) < 1e-4
     props, pcnt = net.debug_tensor("proposals").cpu().numpy(), net.debug_tensor("proposal_counts").cpu().numpy().ravel()
     assert (pcnt == g["proposal_counts"]).all()   # (measured on the MI355X: every proposal identical; tolerances are what is achieved)

@@ -4,6 +4,11 @@ ENGINE's own input to that stage (DetectorNet.debug_tensor), so that a differenc
 Stages: preprocess (x0 vs om.transform_images), RPN (om.rpn_proposals on the engine's P2..P6, ranked on the engine's own fp32
 objectness logits "keys"), box head (om.box_branch on the engine's P2..P5 and proposals), post-processing (om.postprocess_detections on
 the engine's class_logits and proposals) and masks (sigmoid, class select and om.paste_masks on the engine's mask_logits and boxes).
+Between those: the trunk (x0 -> pool -> C2 -> C3 -> C4 -> C5 -> L5..L2 -> P2..P5, each step from the engine's own tap; P6 is P5[:, ::2, ::2]
+bit for bit), RoIAlign (the roi7 / roi14 taps against a float64 RoIAlign of the engine's P2..P5 on its own proposals / detections), the
+mask head (roi14 -> the 28 x 28 logits of every class, before the sigmoid and the class selection) and the RPN objectness logits (the
+"keys" tap against om.rpn_proposals without the override, every anchor).  Every element of every live row is compared; borders, pad
+columns and the rows past a count must be zero (the mask logits past the count: finite).
 
 Arithmetic: continuous operations (resize weights, convolutions / FC of the heads, softmax, sigmoid, box decoding, bilinear paste) run
 in float64 from the engine's fp32 inputs; selection decisions are taken on the fp32 values the kernels ranked (the RPN keys, the mask-box
@@ -22,6 +27,27 @@ Tolerances (worst errors of the MI355X run in the test output, "[stage]" lines):
   class logits   6e-6 x max(1, |ref|)  the box head's 12544-term fp32 MFMA dot products vs float64 (measured 3.6e-6)
   masks          2e-6 abs   fp32 bilinear source coordinate (30 / w) * (x + 0.5) - 0.5 (<= 30, ulp 1.9e-6) vs float64, times the
                             step between neighbouring 28 x 28 probabilities (measured 1.2e-6 on the "clip" boxes, 660 px wide)
+Bounds of the trunk / RoIAlign / mask head / RPN logit stages: max |got - ref| / max(1, max |ref|) of the compared tensor, = 2 x the worst
+error of the MI355X run over all specs (the factor covers split-K partitions that depend on the CU count; the inputs are fixed).  "f32"
+is the float32 oracle against the float64 one on the same input (CPU, worst spec): beyond 4 x f32 an error counts as a finding.
+  pool           1.4e-6   stem 7 x 7 + max pool from x0 (measured 6.8e-7; f32 6.7e-7)
+  C2 C3 C4 C5    9.2e-7 9.6e-7 8.6e-7 7.6e-7   one body stage (3, 4, 6, 3 bottlenecks) from the previous tap (measured 4.6e-7 4.8e-7
+                            4.3e-7 3.8e-7; f32 4.7e-7 6.7e-7 8.9e-7 5.0e-7)
+  L2..L5         8.8e-7   lateral 1 x 1 of C_k + the upsampled L_(k+1) tap (measured 4.4e-7)
+  P_k from L_k   1.3e-6   the 3 x 3 output convolution alone (measured 6.4e-7); "clip": 5.5e-6 (measured 2.71e-6), see below
+  P2..P5         1.4e-6   the FPN as one stage from C2..C5 (measured 6.9e-7; f32 5.6e-7); "clip": 5.7e-6 (measured 2.82e-6; f32 5.4e-7)
+                            FINDING, localised with the L taps: at 480 x 640 the P2 convolution (K = 2304) has 300 tiles and runs its K loop
+                            un-split, one fp32 accumulation of 2304 terms; the smaller frames split K.  A plain sequential fp32 sum in the
+                            kernel's K order (kh, kw, c) on the same L2 tap is off float64 by 2.84e-6 of the scale AT THE SAME ELEMENT
+                            (c 2, y 109, x 16), with the same median (6.0e-7 abs) and 99.9th percentile (6.8e-6 abs) as the engine's error,
+                            and differs from the engine by 8.5e-7: summation-order round-off (the oracle's blocked sums: 3.6e-7), no
+                            wrong index.  Spec.fpn_tol carries the bound of that path; the other specs keep the tight one.
+  un-forced      (reported) x0 -> P2..P6 in one go: 8.4e-7 on the golden cases, 2.82e-6 on "clip"; tests/test_gpu_zz_detector.py's bound
+                            is derived from it
+  roi7 roi14     3.5e-7   fp32 bilinear weights and 16-term sum vs float64, coordinates in fp32 on both sides (measured 1.73e-7; f32 1.53e-7)
+  mask logits    2.6e-6   four 3 x 3 convolutions, the transposed convolution and the logits from the roi14 tap (measured 1.27e-6 at
+                            scale 0.42; f32 4.4e-7)
+  RPN logits     2.1e-6   3 x 3 + 1 x 1 head from P2..P6 (measured 1.02e-6 on "clip", 4.7e-7 elsewhere; f32 4.7e-7); "tied": exactly 0.25
 Selections are compared rank for rank (tests/support/detector.py match_ranked); a neighbour swap or an entry at the cut is admitted only
 where the oracle keys differ by less than KEY_EPS (fp32 round-off of the keys), and at most MAX_EXC of them per list.  A mask may differ
 beyond 2e-6 only if one of its box edges lies within 1e-4 px of an integer in float64 (the truncation point), counted the same way.
@@ -45,12 +71,16 @@ SCORE_TOL = 3e-7
 LOGIT_TOL = 6e-6
 MASK_TOL = 2e-6
 KEY_EPS = 1e-6
+TRUNK_TOL = {"pool": 1.4e-6, "C2": 9.2e-7, "C3": 9.6e-7, "C4": 8.6e-7, "C5": 7.6e-7, "L": 8.8e-7, "PL": 1.3e-6, "P": 1.4e-6}
+ROI_TOL = 3.5e-7
+MASK_LOGIT_TOL = 2.6e-6
+RPN_KEY_TOL = 2.1e-6
 MAX_EXC = 2
 T_IOU = float(np.float32(896) / (np.float32(1024) + np.float32(1024) - np.float32(896)))   # fp32 IoU of two 32 px anchors 4 px apart
 
 # engine option -> the oracle's module constant
 OM_CONST = {"rpn_pre_nms_top_n": "RPN_PRE_NMS_TOP_N", "rpn_post_nms_top_n": "RPN_POST_NMS_TOP_N", "rpn_nms_thresh": "RPN_NMS_THRESH",
-            "box_score_thresh": "BOX_SCORE_THRESH", "box_nms_thresh": "BOX_NMS_THRESH", "box_detections_per_img": "BOX_DETECTIONS_PER_IMG"}
+            "rpn_min_size": "RPN_MIN_SIZE", "box_min_size": "BOX_MIN_SIZE", "box_score_thresh": "BOX_SCORE_THRESH", "box_nms_thresh": "BOX_NMS_THRESH", "box_detections_per_img": "BOX_DETECTIONS_PER_IMG"}
 
 
 @dataclass
@@ -66,6 +96,7 @@ class Spec:
     exact: bool = False                                          # constant keys: oracle in float32, eps = 0, exact boxes
     box_tol: float = 2e-4                                        # RPN proposals, px
     post_box_tol: float = 4e-5                                   # detections (decoded from the engine's own deltas), px
+    fpn_tol: Dict[str, float] = field(default_factory=dict)      # TRUNK_TOL entries of a spec whose FPN convolutions run an un-split K loop
 
 
 def _tied(**ov):
@@ -94,12 +125,25 @@ SPECS = {
     # head does the same once more (10 * 31.5, 5 * 6 with its weights 10, 10, 5, 5)
     "clip": Spec(1, 480, 640, 480, 640, 3, {"rpn.head.bbox_pred.weight": 0.0, "rpn.head.bbox_pred.bias": [31.5, 31.5, 6.0, 6.0] * 3,
                                             "roi_heads.box_predictor.bbox_pred.weight": 0.0,
-                                            "roi_heads.box_predictor.bbox_pred.bias": [315.0, 315.0, 30.0, 30.0] * 3}, box_tol=3e-3, post_box_tol=3e-3),
+                                            "roi_heads.box_predictor.bbox_pred.bias": [315.0, 315.0, 30.0, 30.0] * 3}, box_tol=3e-3, post_box_tol=3e-3,
+                 fpn_tol={"PL": 5.5e-6, "P": 5.7e-6}),
     # NMS segments at their capacity (DET_MAX_SEG = 1024) and at one entry
     "seg1024": Spec(1, 192, 256, 192, 256, 5, overrides={"rpn_pre_nms_top_n": 1024, "rpn_post_nms_top_n": 1024}),
     "seg1": Spec(1, 192, 256, 192, 256, 5, overrides={"rpn_pre_nms_top_n": 1, "rpn_post_nms_top_n": 1}),
 }
 STAGE_SPECS = list(SPECS)
+# the trunk's own cases: "tied", "cut*" and "seg*" share weights and sizes with "native"; "small" (P2 16 x 24, P5 2 x 3, P6 1 x 2) has
+# maps smaller than the convolution's tile and narrower than the reach of the 3 x 3 window
+TRUNK_SPECS = ["native", "resized", "batch2", "batch3", "odd", "clip", "small"]
+SPECS["small"] = Spec(1, 64, 96, 64, 96, 3)
+# RoIAlign's own case: "clip"'s RPN deltas, identity box deltas and no small-box filter, so that the detections ARE the clipped proposals
+# [ctr + w / 4, ctr + h / 4, W, H]: frame-sized ones down to boxes of zero width or height at the right / bottom border (the filters of
+# "clip" drop those, and its detections, a quarter of their proposals' size, stop at level 3).  On the CPU oracle: 643 proposals on the
+# levels {2: 503, 3: 93, 4: 46, 5: 1}, 318 of zero size; 100 detections on {2: 85, 3: 8, 4: 6, 5: 1}, 44 of zero size.
+ROI_SPECS = ["clipdet"]
+SPECS["clipdet"] = Spec(1, 480, 640, 480, 640, 3, {"rpn.head.bbox_pred.weight": 0.0, "rpn.head.bbox_pred.bias": [31.5, 31.5, 6.0, 6.0] * 3,
+                                                   "roi_heads.box_predictor.bbox_pred.weight": 0.0, "roi_heads.box_predictor.bbox_pred.bias": 0.0},
+                        {"rpn_min_size": 0.0, "box_min_size": 0.0})
 
 _SD: Dict[int, Dict[str, torch.Tensor]] = {}
 _RUNS: Dict[str, "Run"] = {}
@@ -165,6 +209,22 @@ class Run:
         self.fcnt = [min(k, self.D) for k in self.survivors]
         self.props = [self.tap["proposals"][i, : self.pcnt[i]].to(self.dt) for i in range(spec.n)]
         self._cache = {}
+        self._maps = {}
+
+    @property
+    def sd64(self):
+        """the float64 weights (the continuous stages run in float64 on the exact specs too)"""
+        if self.dt == torch.float64:
+            return self.sd_d
+        if "sd64" not in self._cache:
+            self._cache["sd64"] = {k: v.double() for k, v in self.sd.items()}
+        return self._cache["sd64"]
+
+    def map(self, what: str) -> torch.Tensor:
+        """a padded-NHWC tap's interior [n, h, w, c] (fp32), its border ring asserted to be zero"""
+        if what not in self._maps:
+            self._maps[what] = sup.debug_map(self.net, what)
+        return self._maps[what]
 
     def oracle(self, stage: str):
         if stage not in self._cache:
@@ -172,6 +232,10 @@ class Run:
                 if stage == "rpn":
                     hw = (int(self.tap["x0"].shape[1]), int(self.tap["x0"].shape[2]))   # the padded batch
                     self._cache[stage] = om.rpn_proposals(self.sd_d, self.feats, self.sizes, hw, objectness_override=self.tap["keys"])
+                elif stage == "rpn_free":   # the head's own objectness logits: no override, float64 on every spec
+                    hw = (int(self.tap["x0"].shape[1]), int(self.tap["x0"].shape[2]))
+                    feats = self.feats if self.dt == torch.float64 else [f.double() for f in self.feats]
+                    self._cache[stage] = om.rpn_proposals(self.sd64, feats, self.sizes, hw)[1]["objectness"]
                 elif stage == "box":   # one image at a time (the RoIAlign reference holds [rois, 256, 7, 2, 7, 2] sample arrays)
                     lg, rg = [], []
                     for i in range(self.spec.n):
@@ -204,11 +268,12 @@ def _report(stage, name, **errs):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # stages, parametrised spec-major so that each spec's forward serves its five stages
 # ---------------------------------------------------------------------------------------------------------------------------------
-STAGES = ["preprocess", "rpn", "box_head", "postprocess", "masks"]
+STAGES = ["preprocess", "rpn", "box_head", "postprocess", "masks", "trunk", "roi7", "mask_head", "rpn_logits"]
+CASES = [(name, stage) for name in SPECS for stage in STAGES
+         if (stage == "trunk" and name in TRUNK_SPECS) or (stage != "trunk" and name in STAGE_SPECS) or (stage in ("roi7", "mask_head") and name in ROI_SPECS)]
 
 
-@pytest.mark.parametrize("stage", STAGES)
-@pytest.mark.parametrize("name", STAGE_SPECS)
+@pytest.mark.parametrize("name,stage", CASES, ids=[f"{n}-{s}" for n, s in CASES])
 def test_detector_stage_matches_the_oracle(name, stage):
     run = _run(name)
     globals()[f"_check_{stage}"](run, name)
@@ -355,6 +420,127 @@ def _check_masks(run: Run, name: str):
         n_cmp += k
     _report("masks", name, err=worst, masks=n_cmp, exceptions=n_exc)
     assert torch.isfinite(masks).all() and n_exc <= MAX_EXC
+
+
+def _rel_err(got: torch.Tensor, ref: torch.Tensor):
+    """-> (max |got - ref| / max(1, max |ref|), max |ref|): every element, the reference in float64"""
+    assert tuple(got.shape) == tuple(ref.shape), (got.shape, ref.shape)
+    assert ref.dtype == torch.float64 and torch.isfinite(got).all()
+    if ref.numel() == 0:
+        return 0.0, 0.0
+    top = ref.abs().max().item()
+    return (got.double() - ref).abs().max().item() / max(1.0, top), top
+
+
+def _check_trunk(run: Run, name: str):
+    """x0 -> pool -> C2 -> C3 -> C4 -> C5 -> P2..P5 -> P6, every step fed the engine's own tap in float64; then the whole trunk
+    un-forced from x0 (reported: the figure the bound of tests/test_gpu_zz_detector.py is derived from)"""
+    from oracle import mask_rcnn as om
+
+    sd = run.sd64
+    x0 = run.tap["x0"]                       # [n, Hp, Wp, 4]: the resized images AND the engine's zero padding up to the multiple of 32
+    n, Hp, Wp, _ = x0.shape
+    assert (x0[..., 3] == 0).all()
+    x = sup.nhwc_to_nchw(x0[..., :3])
+    maps = {w: run.map(w) for w in ("pool", "C2", "C3", "C4", "C5", "L2", "L3", "L4", "L5", "P2", "P3", "P4", "P5", "P6")}
+    errs, scales = {}, {}
+    with torch.no_grad():
+        errs["pool"], scales["pool"] = _rel_err(sup.nhwc_to_nchw(maps["pool"], torch.float32), om.resnet_stem(sd, x))
+        prev = "pool"
+        for li in range(4):
+            w = f"C{li + 2}"
+            errs[w], scales[w] = _rel_err(sup.nhwc_to_nchw(maps[w], torch.float32), om.resnet_stage(sd, sup.nhwc_to_nchw(maps[prev]), li))
+            prev = w
+        cs = [sup.nhwc_to_nchw(maps[f"C{k}"]) for k in range(2, 6)]
+        ref = om.fpn(sd, cs)
+        for k in range(2, 6):   # the FPN as one stage, from C2..C5
+            errs[f"P{k}"], scales[f"P{k}"] = _rel_err(sup.nhwc_to_nchw(maps[f"P{k}"], torch.float32), ref[k - 2])
+        for k in range(5, 1, -1):   # and layer by layer: the top-down map from C{k} and the engine's L{k + 1}, P{k} from the engine's L{k}
+            top = sup.nhwc_to_nchw(maps[f"L{k + 1}"]) if k < 5 else None
+            errs[f"L{k}"], scales[f"L{k}"] = _rel_err(sup.nhwc_to_nchw(maps[f"L{k}"], torch.float32), om.fpn_inner(sd, cs[k - 2], k - 2, top))
+            e = (sup.nhwc_to_nchw(maps[f"P{k}"]) - om.fpn_layer(sd, sup.nhwc_to_nchw(maps[f"L{k}"]), k - 2)).abs() / max(1.0, scales[f"P{k}"])
+            errs[f"P{k}|L{k}"] = e.max().item()
+            if k == 2:   # the distribution of the largest map's error: round-off has a smooth tail, a wrong index has outliers
+                errs["P2|L2 median"], errs["P2|L2 p99.9"] = e.median().item(), e.flatten().kthvalue(int(0.999 * e.numel())).values.item()
+        free = om.resnet50_fpn(sd, x)
+    assert tuple(maps["P2"].shape) == (n, Hp // 4, Wp // 4, 256) and tuple(maps["P5"].shape) == (n, Hp // 32, Wp // 32, 256)
+    assert tuple(maps["P6"].shape) == (n, ref[4].shape[2], ref[4].shape[3], 256)
+    assert torch.equal(maps["P6"], maps["P5"][:, ::2, ::2])   # LastLevelMaxPool = a stride-2 subsample: bit for bit
+    unforced = {f"P{k}": _rel_err(sup.nhwc_to_nchw(maps[f"P{k}"], torch.float32), free[k - 2])[0] for k in range(2, 7)}
+    _report("trunk", name, **errs, unforced=max(unforced.values()), P2_hw=tuple(maps["P2"].shape[1:3]), P6_hw=tuple(maps["P6"].shape[1:3]),
+            scale_C5=scales["C5"], scale_P2=scales["P2"])
+    for w, e in errs.items():
+        key = "PL" if "|" in w else w[0] if w[0] in "PL" else w
+        assert e <= run.spec.fpn_tol.get(key, TRUNK_TOL[key]), (w, e)
+
+
+def _check_roi(run: Run, name: str, what: str):
+    """the RoIAlign output tap ("roi7": the proposals, "roi14": the detections) against the float64 RoIAlign of the engine's P2..P5"""
+    n = run.spec.n
+    if what == "roi7":
+        P, per, cnt, boxes = 7, run.R, run.pcnt, run.tap["proposals"]
+        rows = sup.debug_rows(run.net, "roi7")
+        assert rows.shape == (n * per, 49 * 256)
+        got = rows.view(n * per, 7, 7, 256)
+    else:
+        P, per, cnt, boxes = 14, run.D, run.fcnt, run.tap["det_resized"]
+        got = run.map("roi14")               # (border ring asserted zero)
+        assert tuple(got.shape) == (n * per, 14, 14, 256)
+    live_boxes = [boxes[i, : cnt[i]] for i in range(n)]
+    live = torch.cat([torch.arange(i * per, i * per + cnt[i]) for i in range(n)])
+    dead = torch.ones(n * per, dtype=torch.bool)
+    dead[live] = False
+    assert (got[dead] == 0).all()            # rows past the count
+    ref, lv = sup.multiscale_roi_align_f64([run.tap[f"P{l}"] for l in range(2, 6)], live_boxes, run.sizes, P)
+    err, top = _rel_err(got[live], ref)
+    b = torch.cat(live_boxes)
+    sc = 0.5 ** lv.float()
+    narrow = int((((b[:, 2] - b[:, 0]) * sc < 1) | ((b[:, 3] - b[:, 1]) * sc < 1)).sum()) if len(b) else 0   # max(roi_w, 1) / max(roi_h, 1) clamps
+    zero = int(((b[:, 2] == b[:, 0]) | (b[:, 3] == b[:, 1])).sum()) if len(b) else 0
+    _report("roi", name, what=what, rel_err=err, scale=top, rows=len(live), levels=sorted(set(lv.tolist())), clamped=narrow, zero_size=zero)
+    assert err <= ROI_TOL, err
+    return got, live, lv, narrow, zero
+
+
+def _assert_roi_coverage(name: str, what: str, lv, narrow: int, zero: int):
+    """what the RoIAlign cases are there for: every pyramid level, and boxes under one cell of their level (max(roi_w, 1), max(roi_h, 1))"""
+    if name == "clipdet":
+        assert set(lv.tolist()) == {2, 3, 4, 5} and zero > 0, (what, sorted(set(lv.tolist())), zero)
+    if name == "clip":   # (its small-box filters leave no box of zero size, and its detections stop at level 3: see "clipdet")
+        assert narrow > 0 and (what == "roi14" or set(lv.tolist()) == {2, 3, 4, 5}), (what, sorted(set(lv.tolist())), narrow)
+
+
+def _check_roi7(run: Run, name: str):
+    _, _, lv, narrow, zero = _check_roi(run, name, "roi7")
+    _assert_roi_coverage(name, "roi7", lv, narrow, zero)
+
+
+def _check_mask_head(run: Run, name: str):
+    from oracle import mask_rcnn as om
+
+    spec, D = run.spec, run.D
+    roi, live, lv, narrow, zero = _check_roi(run, name, "roi14")
+    rows = sup.debug_rows(run.net, "mask_logits")
+    C = spec.C
+    assert rows.shape[0] == spec.n * D * 196 * 4 and (rows[:, C:] == 0).all()   # the pad columns past C
+    assert torch.isfinite(rows).all()                                           # rows past the count included
+    m28 = sup.mask_logits_28(rows, spec.n * D)
+    with torch.no_grad():
+        ref = om.mask_head_logits(run.sd64, sup.nhwc_to_nchw(roi[live])) if len(live) else torch.zeros(0, C, 28, 28, dtype=torch.float64)
+    err, top = _rel_err(m28[live][:, :C], ref)
+    _report("mask_head", name, rel_err=err, scale=top, masks=len(live), classes=C)
+    assert err <= MASK_LOGIT_TOL, err
+    _assert_roi_coverage(name, "roi14", lv, narrow, zero)
+
+
+def _check_rpn_logits(run: Run, name: str):
+    ref = run.oracle("rpn_free")
+    keys = run.tap["keys"]
+    err, top = _rel_err(keys, ref)
+    _report("rpn_logits", name, rel_err=err, scale=top, anchors=int(keys.shape[1]))
+    if name == "tied":   # zeroed weights, bias 0.25: exact
+        assert (keys == np.float32(0.25)).all() and (ref == 0.25).all()
+    assert err <= RPN_KEY_TOL, err
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
