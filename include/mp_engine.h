@@ -343,6 +343,23 @@ int mp_conv_stem_pack_weights_sparse(const float* h_w_oihw, int Cout, int Cin, i
 int mp_conv_stem_xrec_sparse(const mp_conv_desc* desc, const void* d_packed, const void* d_packed_sparse, int n_f32,
                              const unsigned char* d_tile_flags, float* d_ypool, int pool_border, mp_stream stream);
 
+/* Tail plane (round 8).  A walk whose last real record element sits alone in its 16-byte chunk (real elements mod 8 = 1) multiplies
+ * seven zeros per tap for it.  Its tail-plane form walks only the chunks in front of that element and takes the element from a plane
+ * the kernel builds in LDS: one K slice per kernel row holds the element's KS taps of that row.  mp_conv_stem_tail_forms: bit 0 = the
+ * dense walk has the form (the RGB refiner's 33 real elements: 7x7 62 -> 52 steps), bit 1 = the background walk has it (3 n_f32 mod
+ * 8 = 1, leading fp32-kind channels, integer channels behind them: the RGB crop's 9 pieces, 7x7 26 -> 14 steps; this also gives the
+ * coarse net's 16-element record a background walk, which mp_conv_stem_sparse_chunks has none for); 0 = the record has no lone tail
+ * element or the widened patch does not fit (7x7, 48 elements).  mp_conv_stem_pack_weights_tail packs the blob of one form (background
+ * = 0 / 1) in the layout of mp_conv_stem_pack_weights_mask; mp_conv_stem_xrec_tail = mp_conv_stem_xrec_sparse where bit 0 / bit 1 of
+ * tail_forms says that d_packed / d_packed_sparse is the tail blob (d_packed_sparse and d_tile_flags may be NULL: dense walk only).
+ * Evaluated products are the same exact piece products; skipped ones are exact zeros; the order of the fp32 additions differs. */
+int mp_conv_stem_tail_forms(int KS, int n_f32, int n_u8);
+size_t mp_conv_stem_tail_packed_bytes(int KS, int n_f32, int n_u8, int Cout, int background);
+int mp_conv_stem_pack_weights_tail(const float* h_w_oihw, int Cout, int Cin, int KS, uint32_t f32_mask, int background, const float* h_scale,
+                                   void* h_packed);
+int mp_conv_stem_xrec_tail(const mp_conv_desc* desc, const void* d_packed, const void* d_packed_sparse, int n_f32,
+                           const unsigned char* d_tile_flags, float* d_ypool, int pool_border, int tail_forms, mp_stream stream);
+
 /* 3x3 stride-2 pad-1 max pool on padded NHWC (input must be >= 0, i.e. post-ReLU).        */
 int mp_maxpool3x3s2(const float* d_x, int N, int H, int W, int C, int in_border, float* d_y,
                     int out_border, float* d_y_act, const float* d_act_scale, const float* d_act_shift,

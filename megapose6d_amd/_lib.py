@@ -140,6 +140,10 @@ SIGNATURES = {
     "mp_conv_stem_sparse_packed_bytes": (_sz, [_i, _i, _i, _i]),
     "mp_conv_stem_pack_weights_sparse": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mp_conv_stem_xrec_sparse": (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "mp_conv_stem_tail_forms": (_i, [_i, _i, _i]),
+    "mp_conv_stem_tail_packed_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mp_conv_stem_pack_weights_tail": (_i, [_vp, _i, _i, _i, _u32, _i, _vp, _vp]),
+    "mp_conv_stem_xrec_tail": (_i, [C.POINTER(ConvDesc), _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "mp_conv_stem_bg_stats": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i]),
     "mp_conv_stem_xrec": (_i, [C.POINTER(ConvDesc), _vp, _i, _vp]),
     "mp_conv_stem_xrec_pool": (_i, [C.POINTER(ConvDesc), _vp, _i, _vp, _i, _vp]),

@@ -38,6 +38,7 @@ struct mp_backbone {
   int stageC[4] = {64, 128, 256, 512};
   bool wide;
   bool direct_bf16 = true;   // MP_CONV_DIRECT_BF16 when the backbone was created: 0 = the non-Winograd layers stay on the fp32-MFMA kernel
+  bool stem_tail = true;     // MP_STEM_TAIL when the backbone was created: 0 = the stem keeps the walks without the tail plane (conv_stem.hip)
   ConvLayer stem;
   std::vector<Block> blocks;
   std::vector<int> stage_of_block;  // 0..3
@@ -49,6 +50,7 @@ struct mp_backbone {
   std::mutex blob_mu;                     // guards the two maps below: prepare (one thread) vs forwards looking blobs up on other threads / streams
   std::map<uint32_t, void*> stem_blobs;   // f32-kind channel mask -> device blob (mp_backbone_xrec_prepare); never freed before destroy
   std::map<uint32_t, void*> stem_blobs_sparse;   // ... -> blob of the background-tile walk (leading-channel masks with something to skip)
+  std::map<uint32_t, int> stem_tail_forms;       // ... -> which of the two blobs is packed for a tail-plane walk (mp_conv_stem_tail_forms bits)
   // workspace bookkeeping: borders are zeroed once per (pointer, batch, h, w); several workspaces may be live at once
   // (one per HIP stream when half-batches are interleaved on two streams)
   struct WsKey { void* ptr; int batch, h, w; };
@@ -127,6 +129,7 @@ extern "C" int mp_backbone_create_wide(int kind, int width, int c_in, int head_k
   bb->kind = kind;
   bb->wide = kind != MP_BACKBONE_VANILLA_RESNET34;
   bb->direct_bf16 = !(getenv("MP_CONV_DIRECT_BF16") && atoi(getenv("MP_CONV_DIRECT_BF16")) == 0);   // read per backbone: one process can build both forms
+  bb->stem_tail = !(getenv("MP_STEM_TAIL") && atoi(getenv("MP_STEM_TAIL")) == 0);                   // (the same: A/B in one build)
   bb->c_in = c_in;
   bb->c_in_p = (c_in + 3) / 4 * 4;
   bb->head_kind = head_kind;
@@ -228,9 +231,14 @@ extern "C" int mp_backbone_xrec_prepare(mp_backbone* bb, uint32_t f32_mask) {
   if (!mp_conv_stem_supported(bb->stem.K, n_f32, n_u8) || bb->stem.Cout % 64 != 0) return 0;
   std::lock_guard<std::mutex> blob_lock(bb->blob_mu);
   if (!bb->stem_blobs.count(f32_mask)) {
-    std::vector<unsigned char> blob(mp_conv_stem_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout));
-    if (mp_conv_stem_pack_weights_mask(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, f32_mask,
-                                       bb->stem_scale_host.empty() ? nullptr : bb->stem_scale_host.data(), blob.data()) != MP_OK)
+    const bool leading = f32_mask == (n_f32 >= 32 ? 0xFFFFFFFFu : (1u << n_f32) - 1u);
+    // tail-plane walks where the record has them (the background one for leading-channel masks only, like the background walk itself)
+    int forms = bb->stem_tail ? mp_conv_stem_tail_forms(bb->stem.K, n_f32, n_u8) & (leading ? 3 : 1) : 0;
+    const float* h_scale = bb->stem_scale_host.empty() ? nullptr : bb->stem_scale_host.data();
+    std::vector<unsigned char> blob((forms & 1) ? mp_conv_stem_tail_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout, 0)
+                                                : mp_conv_stem_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout));
+    if (((forms & 1) ? mp_conv_stem_pack_weights_tail(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, f32_mask, 0, h_scale, blob.data())
+                     : mp_conv_stem_pack_weights_mask(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, f32_mask, h_scale, blob.data())) != MP_OK)
       return 0;
     void* d = nullptr;
     if (hipMalloc(&d, blob.size()) != hipSuccess) return 0;
@@ -238,20 +246,26 @@ extern "C" int mp_backbone_xrec_prepare(mp_backbone* bb, uint32_t f32_mask) {
     bb->allocs.push_back(d);
     bb->stem_blobs[f32_mask] = d;
     // the background-tile walk: only for leading-channel masks (no depth channels) with fewer fp32-kind chunks than the record has
-    if (f32_mask == (n_f32 >= 32 ? 0xFFFFFFFFu : (1u << n_f32) - 1u) && mp_conv_stem_sparse_chunks(bb->stem.K, n_f32, n_u8) > 0) {
-      std::vector<unsigned char> sb(mp_conv_stem_sparse_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout));
+    // (in its tail-plane form the coarse net's 16-element record has one too)
+    bool have_sparse = false;
+    if (leading && ((forms & 2) || mp_conv_stem_sparse_chunks(bb->stem.K, n_f32, n_u8) > 0)) {
+      std::vector<unsigned char> sb((forms & 2) ? mp_conv_stem_tail_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout, 1)
+                                                : mp_conv_stem_sparse_packed_bytes(bb->stem.K, n_f32, n_u8, bb->stem.Cout));
       void* ds = nullptr;
-      if (mp_conv_stem_pack_weights_sparse(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, n_f32,
-                                           bb->stem_scale_host.empty() ? nullptr : bb->stem_scale_host.data(), sb.data()) == MP_OK &&
+      if (((forms & 2) ? mp_conv_stem_pack_weights_tail(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, f32_mask, 1, h_scale, sb.data())
+                       : mp_conv_stem_pack_weights_sparse(bb->stem_w_host.data(), bb->stem.Cout, bb->c_in, bb->stem.K, n_f32, h_scale, sb.data())) == MP_OK &&
           hipMalloc(&ds, sb.size()) == hipSuccess) {
         if (hipMemcpy(ds, sb.data(), sb.size(), hipMemcpyHostToDevice) == hipSuccess) {
           bb->allocs.push_back(ds);
           bb->stem_blobs_sparse[f32_mask] = ds;
+          have_sparse = true;
         } else {
           (void)hipFree(ds);
         }
       }
     }
+    if (!have_sparse) forms &= 1;
+    bb->stem_tail_forms[f32_mask] = forms;
   }
   return mp_xrec_elements(n_f32, n_u8);
 }
@@ -293,12 +307,15 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
   if (x_mode == 2) {
     const void* d_stem_pieces = nullptr;
     const void* d_sparse_blob = nullptr;
+    int tail_forms = 0;
     {
       std::lock_guard<std::mutex> blob_lock(bb->blob_mu);
       const auto blob_it = bb->stem_blobs.find(f32_mask);
       if (blob_it != bb->stem_blobs.end()) d_stem_pieces = blob_it->second;
       const auto sp_it = bb->stem_blobs_sparse.find(f32_mask);
       if (sp_it != bb->stem_blobs_sparse.end()) d_sparse_blob = sp_it->second;
+      const auto tf_it = bb->stem_tail_forms.find(f32_mask);
+      if (tf_it != bb->stem_tail_forms.end()) tail_forms = tf_it->second;
     }
     MP_REQUIRE(d_stem_pieces != nullptr, "mp_backbone_forward_xrec: no piece blob for the fp32-kind channel mask 0x%x of this %d-channel stem: "
                "call mp_backbone_xrec_prepare first (it returns 0 if the stem has no exact-piece form)", f32_mask, bb->c_in);
@@ -313,15 +330,17 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
     const void* d_sparse = d_tile_flags ? d_sparse_blob : nullptr;   // background-tile walk where it applies
     if (fuse_pool) {
       d.d_y = nullptr;
-      rc = d_sparse ? mp_conv_stem_xrec_sparse(&d, d_stem_pieces, d_sparse, n_f32, d_tile_flags, A[0], 1, s)
-                    : mp_conv_stem_xrec_pool(&d, d_stem_pieces, n_f32, A[0], 1, s);
+      rc = tail_forms ? mp_conv_stem_xrec_tail(&d, d_stem_pieces, d_sparse, n_f32, d_sparse ? d_tile_flags : nullptr, A[0], 1, tail_forms, s)
+           : d_sparse ? mp_conv_stem_xrec_sparse(&d, d_stem_pieces, d_sparse, n_f32, d_tile_flags, A[0], 1, s)
+                      : mp_conv_stem_xrec_pool(&d, d_stem_pieces, n_f32, A[0], 1, s);
       // pre-activation WideResNets (round 6): relu(bn1(pooled)) by a small elementwise pass over the pooled map (the fused pool completes
       // straddling windows with atomics, so the stem itself cannot emit it) instead of the separate pool kernel's pass over the 4x larger stem map
       if (!rc && bb->wide) rc = mp_bn_relu_nhwc(A[0], batch, g.hs[0], g.ws[0], bb->stageC[0], 1, Aact[0], bb->blocks[0].pre.d_scale, bb->blocks[0].pre.d_shift, s);
       stem_pooled = true;
     } else {
-      rc = d_sparse ? mp_conv_stem_xrec_sparse(&d, d_stem_pieces, d_sparse, n_f32, d_tile_flags, nullptr, 0, s)
-                    : mp_conv_stem_xrec(&d, d_stem_pieces, n_f32, s);
+      rc = tail_forms ? mp_conv_stem_xrec_tail(&d, d_stem_pieces, d_sparse, n_f32, d_sparse ? d_tile_flags : nullptr, nullptr, 0, tail_forms, s)
+           : d_sparse ? mp_conv_stem_xrec_sparse(&d, d_stem_pieces, d_sparse, n_f32, d_tile_flags, nullptr, 0, s)
+                      : mp_conv_stem_xrec(&d, d_stem_pieces, n_f32, s);
     }
   } else {
     rc = run_conv_layer(bb->stem, d_x, batch, h, w, bb->in_border, S, 1, nullptr, 1, s, SK, SPLITK_WS_FLOATS, nullptr, nullptr, nullptr, x_f16);

@@ -72,6 +72,9 @@ struct Params {
   const unsigned char* __restrict__ tile_flags;   // [N][fl_ty][fl_tx]
   const unsigned char* __restrict__ w_sparse;
   int fl_tx, fl_ty, q_use, n_steps_sparse;
+  // tail plane (TAIL instances): chunks per pixel of the dense walk's main slices (Q, or Q - 1 with a tail), and whether the dense / the
+  // background walk ends in KS tail slices; q_use then counts the background walk's main chunks only
+  int q_dense, tail_dense, tail_sparse;
   int H, W, pad;         // input size in pixels, convolution padding (to place the patch in the flag grid)
   int count_bg;          // != 0: one atomic per background workgroup into g_stem_bg (mp_conv_stem_bg_stats; only while the event profiler runs)
 };
@@ -80,17 +83,32 @@ __device__ unsigned long long g_stem_bg[2];   // workgroups that took the backgr
 
 constexpr size_t LDS_PER_WG = 80 * 1024;   // two workgroups per CU share the 160 KB
 
-template <int KS, int Q>
+// TAIL (round 8): the TAIL PLANE.  A record whose last real element sits alone in its 16-byte chunk (real elements mod 8 = 1: the 33 of
+// the RGB refiner's 40-element record, the 9 crop pieces every background walk needs) makes the walk multiply seven zeros per tap for
+// it.  Such a walk visits only the chunks in front of that element ("main" slices) and takes the tail element from a plane built in LDS
+// behind every patch row: entry (patch row r, output column i) = [e(r, 2i), e(r, 2i+1), .., e(r, 2i+KS-1), 0..] = the tail channel's KS
+// taps of one kernel row for output pixel i, i.e. ONE K slice.  KS tail slices (one per kernel row) follow the KS * KS * (Q - 1) main
+// slices; the weights are packed to match (mp_conv_stem_pack_weights_tail).  The plane has no pitch of its own: every patch row is
+// widened by TW chunks, entry (r, i) at r * PITCH + (ROW16 + i) * 16, so that the M-tile offsets j * 2 * PITCH stay the same immediates for
+// lanes on main and on tail slices, and every A fragment stays one aligned ds_read_b128 (consecutive i = consecutive chunks: no conflict).
+constexpr size_t patch_bytes(int KS, int Q, bool tail) {   // Geo<KS, Q, tail>::PATCH, for the host (which instances exist)
+  const int PH = 2 * (TH - 1) + KS, PW = 2 * (TW - 1) + KS, plane = tail ? TW : 0;
+  const bool padded = Q % 2 == 0 && (size_t)(PH + 1) * ((PW * (Q + 1) + plane) | 1) * 16 <= LDS_PER_WG;
+  return (size_t)(PH + 1) * ((PW * (padded ? Q + 1 : Q) + plane) | 1) * 16;
+}
+
+template <int KS, int Q, bool TAIL = false>
 struct Geo {
   static constexpr int PH = 2 * (TH - 1) + KS, PW = 2 * (TW - 1) + KS;   // patch size in pixels
+  static constexpr int PLANE16 = TAIL ? TW : 0;                           // tail-plane entries behind every patch row
   // LDS pixel pitch in 16-byte chunks.  The 8 lanes a ds_read_b128 serves per clock are 8 consecutive output pixels = input pixels two apart:
   // their chunk addresses are 2 i QP (+ a common offset) and fall into 8 different 16-byte bank groups iff QP is ODD.  An even record
   // (Q = 2: the coarse net, Q = 4, Q = 6: RGBD) is therefore staged with one chunk of padding per pixel wherever the patch still fits two
   // workgroups per CU (round 4's Q = 2 instance ran with 2-way conflicts: SQ_LDS_BANK_CONFLICT 1.9e9 per launch); the 7x7 / Q = 6 patch
   // does not fit padded and keeps its 2-way conflict.
-  static constexpr int QP = (Q % 2 == 0 && (size_t)(PH + 1) * ((PW * (Q + 1)) | 1) * 16 <= LDS_PER_WG) ? Q + 1 : Q;
+  static constexpr int QP = (Q % 2 == 0 && (size_t)(PH + 1) * ((PW * (Q + 1) + PLANE16) | 1) * 16 <= LDS_PER_WG) ? Q + 1 : Q;
   static constexpr int ROW16 = PW * QP;                                   // 16-byte chunks per patch row (incl. the per-pixel padding)
-  static constexpr int PITCH16 = ROW16 | 1;                               // odd pitch (in chunks): row wraps keep the odd slice distance
+  static constexpr int PITCH16 = (ROW16 + PLANE16) | 1;                   // odd pitch (in chunks): row wraps keep the odd slice distance
   static constexpr int PITCH = PITCH16 * 16;
   static constexpr int KWQ = KS * Q;                                      // slices per kernel row
   static constexpr int S = KS * KWQ;                                      // slices in all
@@ -114,9 +132,10 @@ struct Geo {
 // packed for that walk: 26 instead of 62 steps, and it stages only those chunks.  Every product that is evaluated is exact and every
 // skipped one is an exact zero; the grouping of the remaining products into MFMAs differs from the dense walk, i.e. the order of the fp32
 // additions (the error class of every other launch-shape difference, bounded by the record tests at 1e-5 of the feature scale).
-template <int KS, int Q, bool POOL, bool SP = false>
+template <int KS, int Q, bool POOL, bool SP = false, bool TAIL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_stem_bf16x3(Params p) {
-  using G = Geo<KS, Q>;
+  using G = Geo<KS, Q, TAIL>;
+  constexpr bool RT = SP || TAIL;   // the chunks walked per pixel are a run-time number
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -140,7 +159,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       if (blockIdx.x == 0) atomicAdd(&g_stem_bg[1], (unsigned long long)gridDim.x);
     }
   }
-  const int QU = SP && sparse ? p.q_use : Q;                       // record chunks walked per pixel
+  const bool tail = TAIL && (SP && sparse ? p.tail_sparse : p.tail_dense) != 0;   // this walk ends in KS tail slices (workgroup-uniform)
+  const int QU = SP && sparse ? p.q_use : (TAIL ? p.q_dense : Q);   // record chunks walked per pixel (main slices)
+  const int QS = QU + (tail ? 1 : 0);                               // ... staged: the tail element is the first of chunk QU
   const int n_steps = SP && sparse ? p.n_steps_sparse : p.n_steps;
 
   // ---- patch: PH rows of ROW16 16-byte chunks, global -> registers -> LDS (rows beyond the image: range-checked to zero) ------------
@@ -159,7 +180,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int k = 0; k < HALF; ++k) {
         const int c = tid + 256 * (h * HALF + k);
         const int row = c / SRC16, col = c - row * SRC16;
-        const bool want = c < N_CH && (!SP || col % Q < QU);   // (background tile: only the chunks that are walked)
+        const bool want = c < N_CH && (!RT || col % Q < QS);   // (background tile: only the chunks that are walked)
         v[k] = want ? __builtin_amdgcn_raw_buffer_load_b128(r_x, org + row * row_bytes + col * 16, 0, 0) : u32x4{0, 0, 0, 0};
       }
 #pragma unroll
@@ -167,10 +188,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const int c = tid + 256 * (h * HALF + k);
         const int row = c / SRC16, col = c - row * SRC16;
         const int lcol = G::QP == Q ? col : col + (col / Q) * (G::QP - Q);   // pixel * QP + q
-        if (c < N_CH && (!SP || col % Q < QU)) *reinterpret_cast<u32x4*>(lds + row * G::PITCH + lcol * 16) = v[k];
+        if (c < N_CH && (!RT || col % Q < QS)) *reinterpret_cast<u32x4*>(lds + row * G::PITCH + lcol * 16) = v[k];
       }
     }
-    // (the padding chunk of every pixel is never read: a slice's chunk index is q < Q)
+    // (the padding chunk of every pixel is never read: a slice's chunk index is q < Q; the zero row spans the tail-plane columns too)
     for (int c = tid; c < G::PITCH16; c += 256) *reinterpret_cast<u32x4*>(lds + G::PH * G::PITCH + c * 16) = u32x4{0, 0, 0, 0};
   }
 
@@ -191,27 +212,55 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   int a_row = (2 * i) * (16 * G::QP);            // pixel (kernel row 0, column i); + PITCH per kernel row
   // slice s_r of a kernel row = (kw, q) = (s_r / Q, s_r % Q) sits at chunk kw * QP + q = s_r + kw * (QP - Q) of the row run
   // (SP: QU chunks per pixel are walked: kw = sr / QU by a multiply-shift that is exact for sr < 64, QU <= 6)
-  const int kwq = SP ? KS * QU : G::KWQ;
+  const int kwq = RT ? KS * QU : G::KWQ;
   const int qu_m = 1024 / QU + 1;
   auto slice_off = [&](int sr) {
-    if constexpr (SP) {
+    if constexpr (RT) {
       const int kw = (sr * qu_m) >> 10;
       return (kw * G::QP + (sr - kw * QU)) * 16;
     } else {
       return G::QP == Q ? sr * 16 : (sr + (sr / Q) * (G::QP - Q)) * 16;
     }
   };
-  int a_off = a_row + slice_off(s_r);
+  // tail walk: slice KS * kwq + ky is the plane entry (patch row ky + 2 j, column i); the padding slices behind the last kernel row stay
+  // on row KS (+ 2 j <= PH: plane entries of real rows, finite, and the zero row), their weights are zero
+  int s_t = g - KS * kwq;                        // s - (number of main slices)
+  const int t_base = (G::ROW16 + i) * 16;
+  auto slice_addr = [&]() {
+    int off = a_row + slice_off(s_r);
+    if constexpr (TAIL) {
+      if (tail && s_t >= 0) off = t_base + min(s_t, KS) * G::PITCH;
+    }
+    return off;
+  };
+  int a_off = slice_addr();
   auto advance = [&]() {                         // s += 4
     s_r += 4;
+    s_t += 4;
     if (s_r >= kwq) { s_r -= kwq; a_row += G::PITCH; }
-    a_off = a_row + slice_off(s_r);
+    a_off = slice_addr();
   };
   f32x4 acc[TH];
 #pragma unroll
   for (int j = 0; j < TH; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   u32x4 a0[TH], a1[TH];
 
+  if constexpr (TAIL) {
+    if (tail) {   // the tail plane, from the staged patch: entry (r, i) = element 0 of chunk QU of the pixels (r, 2i .. 2i + KS - 1)
+      __syncthreads();
+      for (int e = tid; e < G::PH * TW; e += 256) {
+        const int r = e / TW, pi = e - r * TW;
+        const unsigned char* src = lds + r * G::PITCH + (2 * pi * G::QP + QU) * 16;
+        unsigned short el[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) el[k] = k < KS ? *reinterpret_cast<const unsigned short*>(src + k * (G::QP * 16)) : (unsigned short)0;
+        u32x4 v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (unsigned)el[2 * k] | ((unsigned)el[2 * k + 1] << 16);
+        *reinterpret_cast<u32x4*>(lds + r * G::PITCH + (G::ROW16 + pi) * 16) = v;
+      }
+    }
+  }
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < TH; ++j) a0[j] = *reinterpret_cast<const u32x4*>(lds + a_off + j * 2 * G::PITCH);
@@ -338,17 +387,17 @@ __global__ __launch_bounds__(256) void pool_zero_kernel(float* __restrict__ y, i
       make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-template <int KS, int Q, bool POOL = false, bool SP = false>
+template <int KS, int Q, bool POOL = false, bool SP = false, bool TAIL = false>
 int launch(const Params& p, hipStream_t s, double flops, double bytes, const char* name) {
   // executed on the bf16 pipe: every 16x16x32 MFMA of every step, three weight pieces (this counts the record padding, the step padding
   // and the nine products of the fp32-kind channels as what they cost)
   const double executed = 2.0 * (double)p.N * p.tiles_y * p.tiles_x * (TH * TW) * p.Cout * (double)p.n_steps * 32.0 * 3.0;
-  using G = Geo<KS, Q>;
+  using G = Geo<KS, Q, TAIL>;
   static int attr_dev = -1;
   int dev = 0;
   MP_CHECK_HIP(hipGetDevice(&dev));
   if (attr_dev != dev) {
-    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_stem_bf16x3<KS, Q, POOL, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
+    MP_CHECK_HIP(hipFuncSetAttribute((const void*)conv_stem_bf16x3<KS, Q, POOL, SP, TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS));
     attr_dev = dev;
   }
   if (POOL) {
@@ -357,12 +406,14 @@ int launch(const Params& p, hipStream_t s, double flops, double bytes, const cha
     hipLaunchKernelGGL(pool_zero_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p.ypool, p.N, p.Hq, p.Wq, p.Cout, p.pool_border);
   }
   ProfScope prof(name, flops, bytes, s, executed, 2500.0);
-  hipLaunchKernelGGL((conv_stem_bf16x3<KS, Q, POOL, SP>), dim3((unsigned)((long)p.N * p.tiles_y * p.tiles_x * p.n_cb)), dim3(256), G::LDS, s, p);
+  hipLaunchKernelGGL((conv_stem_bf16x3<KS, Q, POOL, SP, TAIL>), dim3((unsigned)((long)p.N * p.tiles_y * p.tiles_x * p.n_cb)), dim3(256), G::LDS, s, p);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
 
-inline int n_steps(int KS, int Q) { return ((KS * KS * Q + 3) / 4 + 1) / 2 * 2; }
+inline int steps_of_slices(int S) { return ((S + 3) / 4 + 1) / 2 * 2; }   // steps of 4 slices, even
+inline int n_steps(int KS, int Q) { return steps_of_slices(KS * KS * Q); }
+inline int n_steps_tail(int KS, int q_main) { return steps_of_slices(KS * KS * q_main + KS); }   // main slices + one tail slice per kernel row
 
 }  // namespace stem
 }  // namespace mp
@@ -391,8 +442,10 @@ extern "C" size_t mp_conv_stem_packed_bytes(int KS, int n_f32, int n_u8, int Cou
 // (observation depth + one rendered depth per view) -- and sits, in channel order, in front of the integer channels:
 //   [x1,x2,x3 of every fp32-kind channel | k of every integer channel | zero padding]
 // q_walk = record chunks per pixel the kernel's slice walk visits: Q for the dense walk; the chunks that hold fp32-kind pieces for the
-// background-tile walk (mp_conv_stem_sparse_*)
-static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, const float* scale, void* packed, int q_walk);
+// background-tile walk (mp_conv_stem_sparse_*).  tail: q_walk counts the main chunks only, and KS tail slices follow them -- tail slice
+// ky, element e < KS = the weight (ky, kx = e) of record slot 8 q_walk (mp_conv_stem_pack_weights_tail)
+static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, const float* scale, void* packed, int q_walk,
+                             bool tail = false);
 
 extern "C" int mp_conv_stem_pack_weights_mask(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, const float* scale, void* packed) {
   return pack_weights_walk(w, Cout, Cin, KS, f32_mask, scale, packed, 0);
@@ -421,7 +474,38 @@ extern "C" int mp_conv_stem_pack_weights_sparse(const float* w, int Cout, int Ci
   return pack_weights_walk(w, Cout, Cin, KS, n_f32 >= 32 ? 0xFFFFFFFFu : (1u << n_f32) - 1u, scale, packed, q_use);
 }
 
-static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, const float* scale, void* packed, int q_walk) {
+// Tail-plane forms (round 8).  bit 0: the DENSE walk has one -- the record's last real element sits alone in its chunk (real elements
+// mod 8 = 1), so the walk takes chunks 0 .. Q - 2 per tap and the last element from the tail plane: KS * KS * (Q - 1) + KS slices.
+// bit 1: the BACKGROUND walk has one -- the last fp32-kind piece sits alone in its chunk (3 n_f32 mod 8 = 1: the RGB crop's 9 pieces) and
+// integer channels follow it; this is defined, like mp_conv_stem_sparse_chunks, for leading fp32-kind channels only, and also for records
+// that mp_conv_stem_sparse_chunks has no form for (the coarse net's 16 elements: 26 -> 14 steps).  0 where the widened patch does not fit
+// two workgroups per CU (7x7 / Q = 6) or the record has no lone tail element: those keep the present walks.
+extern "C" int mp_conv_stem_tail_forms(int KS, int n_f32, int n_u8) {
+  if (!mp_conv_stem_supported(KS, n_f32, n_u8)) return 0;
+  const int real = 3 * n_f32 + n_u8, Q = (real + 7) / 8, bg = 3 * n_f32;
+  if (stem::patch_bytes(KS, Q, true) > stem::LDS_PER_WG) return 0;
+  int forms = 0;
+  if (real % 8 == 1) forms |= 1;
+  if (bg % 8 == 1 && bg > 8 && n_u8 > 0) forms |= 2;
+  return forms;
+}
+static int tail_main_chunks(int n_f32, int n_u8, int background) { return background ? 3 * n_f32 / 8 : (3 * n_f32 + n_u8) / 8; }
+extern "C" size_t mp_conv_stem_tail_packed_bytes(int KS, int n_f32, int n_u8, int Cout, int background) {
+  if (!(mp_conv_stem_tail_forms(KS, n_f32, n_u8) & (background ? 2 : 1))) return 0;
+  return (size_t)(Cout / stem::NCO) * 4 * stem::n_steps_tail(KS, tail_main_chunks(n_f32, n_u8, background)) * 3072;
+}
+// the piece blob of a tail walk, layout as mp_conv_stem_pack_weights_mask: background = 0 the dense walk (any channel mask),
+// != 0 the background walk (f32_mask must name the leading channels)
+extern "C" int mp_conv_stem_pack_weights_tail(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, int background, const float* scale,
+                                              void* packed) {
+  const int n_f32 = __builtin_popcount(f32_mask), n_u8 = Cin - n_f32;
+  MP_REQUIRE(n_u8 >= 0 && (mp_conv_stem_tail_forms(KS, n_f32, n_u8) & (background ? 2 : 1)), "mp_conv_stem_pack_weights_tail: this record has no such tail-plane form");
+  MP_REQUIRE(!background || f32_mask == (n_f32 >= 32 ? 0xFFFFFFFFu : (1u << n_f32) - 1u),
+             "mp_conv_stem_pack_weights_tail: the background walk is defined for leading fp32-kind channels only");
+  return pack_weights_walk(w, Cout, Cin, KS, f32_mask, scale, packed, tail_main_chunks(n_f32, n_u8, background), true);
+}
+
+static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t f32_mask, const float* scale, void* packed, int q_walk, bool tail) {
   MP_REQUIRE(Cin >= 1 && Cin <= 32 && (Cin == 32 || (f32_mask >> Cin) == 0u), "mp_conv_stem_pack_weights_mask: mask names channels >= Cin (<= 32 input channels)");
   const int n_f32 = __builtin_popcount(f32_mask), n_u8 = Cin - n_f32;
   MP_REQUIRE(w && packed && n_u8 >= 0 && Cout % stem::NCO == 0 && mp_conv_stem_supported(KS, n_f32, n_u8),
@@ -431,7 +515,9 @@ static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t
     if ((f32_mask >> c) & 1u) ch_of_f32[a++] = c; else ch_of_u8[b++] = c;
   }
   const int Q = q_walk > 0 ? q_walk : mp_xrec_elements(n_f32, n_u8) / 8;   // chunks walked per pixel (slot 8 q + e names the same channel either way)
-  const int T = stem::n_steps(KS, Q), S = KS * KS * Q;
+  MP_REQUIRE(!tail || q_walk > 0, "mp_conv_stem_pack_weights: a tail walk names its main chunks");
+  const int S_main = KS * KS * Q, S = S_main + (tail ? KS : 0);
+  const int T = stem::steps_of_slices(S);
   unsigned short* out = (unsigned short*)packed;
   memset(out, 0, (size_t)(Cout / stem::NCO) * 4 * T * 3072);
   for (int co = 0; co < Cout; ++co) {
@@ -439,9 +525,12 @@ static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t
     const double sc = scale ? (double)scale[co] : 1.0;
     for (int s = 0; s < S; ++s) {
       const int t = s / 4, g = s % 4;
-      const int kh = s / (KS * Q), rr = s % (KS * Q), kw = rr / Q, q = rr % Q;
-      for (int e = 0; e < 8; ++e) {
-        const int slot = 8 * q + e;
+      const bool ts = s >= S_main;   // tail slice: kernel row s - S_main, element e = kernel column, record slot 8 Q
+      const int rr = s % (KS * Q);
+      const int kh = ts ? s - S_main : s / (KS * Q), q = ts ? Q : rr % Q;
+      for (int e = 0; e < (ts ? KS : 8); ++e) {
+        const int kw = ts ? e : rr / Q;
+        const int slot = ts ? 8 * q : 8 * q + e;
         int ch;
         double f;
         if (slot < 3 * n_f32) { ch = ch_of_f32[slot / 3]; f = sc; }
@@ -460,8 +549,9 @@ static int pack_weights_walk(const float* w, int Cout, int Cin, int KS, uint32_t
 
 // d_x = xrec tensor (bf16 records, padded NHWC with border in_border); the other fields as mp_conv2d_nhwc; KH = KW in {5, 7},
 // stride 2, Cout % 64 == 0, no residual / second output
+// tail_forms: bit 0 = d_packed is the dense tail blob, bit 1 = d_packed_sparse is the background tail blob (mp_conv_stem_pack_weights_tail)
 static int stem_xrec_impl(const mp_conv_desc* d, const void* d_packed, int n_f32, float* d_ypool, int pool_border, mp_stream stream,
-                          const void* d_packed_sparse = nullptr, const unsigned char* d_tile_flags = nullptr) {
+                          const void* d_packed_sparse = nullptr, const unsigned char* d_tile_flags = nullptr, int tail_forms = 0) {
   MP_REQUIRE(d && d->d_x && d_packed && (d->d_y || d_ypool), "mp_conv_stem_xrec: null pointer");
   MP_REQUIRE(!d_ypool || (d->relu && pool_border >= 0), "mp_conv_stem_xrec_pool: the fused max pool needs the ReLU (its atomicMax orders non-negative floats)");
   const int n_u8 = d->c_real - n_f32;
@@ -476,7 +566,10 @@ static int stem_xrec_impl(const mp_conv_desc* d, const void* d_packed, int n_f32
   p.Hp = d->H + 2 * d->in_border; p.Wp = d->W + 2 * d->in_border; p.in_off = d->in_border - d->pad;
   p.Cout = d->Cout; p.Hop = p.Ho + 2 * d->out_border; p.Wop = p.Wo + 2 * d->out_border; p.out_border = d->out_border;
   p.tiles_x = ceil_div(p.Wo, stem::TW); p.tiles_y = ceil_div(p.Ho, stem::TH); p.n_cb = d->Cout / stem::NCO;
-  p.n_steps = stem::n_steps(d->KH, Q);
+  MP_REQUIRE((tail_forms & ~mp_conv_stem_tail_forms(d->KH, n_f32, n_u8)) == 0, "mp_conv_stem_xrec_tail: this record has no such tail-plane form (mp_conv_stem_tail_forms)");
+  p.tail_dense = tail_forms & 1; p.tail_sparse = 0;
+  p.q_dense = p.tail_dense ? Q - 1 : Q;
+  p.n_steps = p.tail_dense ? stem::n_steps_tail(d->KH, Q - 1) : stem::n_steps(d->KH, Q);
   p.relu = d->relu;
   const long img = (long)p.Hp * p.Wp * 16 * Q, outb = (long)p.Hop * p.Wop * d->Cout * 4;   // per image: the batch index is applied in 64 bits
   MP_REQUIRE(img < (1L << 31) && outb < (1L << 31) && (long)d->N * p.tiles_y * p.tiles_x * p.n_cb < (1L << 31), "mp_conv_stem_xrec: image too large for 32-bit offsets");
@@ -485,19 +578,33 @@ static int stem_xrec_impl(const mp_conv_desc* d, const void* d_packed, int n_f32
   p.Hq = (p.Ho + 2 - 3) / 2 + 1; p.Wq = (p.Wo + 2 - 3) / 2 + 1;
   p.H = d->H; p.W = d->W; p.pad = d->pad;
   p.tile_flags = nullptr; p.w_sparse = nullptr; p.fl_tx = p.fl_ty = 0; p.q_use = Q; p.n_steps_sparse = p.n_steps;
-  const int q_use = mp_conv_stem_sparse_chunks(d->KH, n_f32, n_u8);
+  const bool bg_tail = (tail_forms & 2) != 0;
+  const int q_use = bg_tail ? 3 * n_f32 / 8 : mp_conv_stem_sparse_chunks(d->KH, n_f32, n_u8);   // (tail form: its main chunks)
   const bool sp = d_packed_sparse && d_tile_flags && q_use > 0;
   p.count_bg = 0;
   if (sp) {   // the rasteriser's job flags of the launch that wrote these records: one byte per (image, 8x8-pixel tile)
-    p.count_bg = mp_profile_active();
+    p.count_bg = Q > 2 ? mp_profile_active() : 0;   // (mp_conv_stem_bg_stats describes the refiner stem: records of more than two chunks)
     p.tile_flags = d_tile_flags; p.w_sparse = (const unsigned char*)d_packed_sparse;
-    p.fl_tx = ceil_div(d->W, 8); p.fl_ty = ceil_div(d->H, 8); p.q_use = q_use; p.n_steps_sparse = stem::n_steps(d->KH, q_use);
+    p.fl_tx = ceil_div(d->W, 8); p.fl_ty = ceil_div(d->H, 8); p.q_use = q_use; p.tail_sparse = bg_tail ? 1 : 0;
+    p.n_steps_sparse = bg_tail ? stem::n_steps_tail(d->KH, q_use) : stem::n_steps(d->KH, q_use);
   }
   const double M = (double)d->N * p.Ho * p.Wo;
   const double flops = 2.0 * M * d->Cout * d->KH * d->KW * d->c_real;
   const double bytes = (double)d->N * img + (d->d_y ? 4.0 * M * d->Cout : 0.0) + (d_ypool ? 4.0 * (double)d->N * p.Hq * p.Wq * d->Cout : 0.0) +
-                       (double)mp_conv_stem_packed_bytes(d->KH, n_f32, n_u8, d->Cout);
+                       (double)p.n_cb * 4 * p.n_steps * 3072;
   hipStream_t s = (hipStream_t)stream;
+  // the tail-plane instances (widened patch rows) exist where that patch fits: mp_conv_stem_tail_forms is 0 elsewhere
+#define MP_STEM_GO_TAIL(KSV, QV)                                                                                                     \
+  if (tail_forms && d->KH == KSV && Q == QV) {                                                                                     \
+    if (sp)                                                                                                                        \
+      return d_ypool ? stem::launch<KSV, QV, true, true, true>(p, s, flops, bytes, "conv_stem_bf16x3+maxpool<" #KSV "x" #KSV ",Q" #QV ">")   \
+                     : stem::launch<KSV, QV, false, true, true>(p, s, flops, bytes, "conv_stem_bf16x3<" #KSV "x" #KSV ",Q" #QV ">");       \
+    return d_ypool ? stem::launch<KSV, QV, true, false, true>(p, s, flops, bytes, "conv_stem_bf16x3+maxpool<" #KSV "x" #KSV ",Q" #QV ">")    \
+                   : stem::launch<KSV, QV, false, false, true>(p, s, flops, bytes, "conv_stem_bf16x3<" #KSV "x" #KSV ",Q" #QV ">");        \
+  }
+  MP_STEM_GO_TAIL(7, 2) MP_STEM_GO_TAIL(7, 3) MP_STEM_GO_TAIL(7, 4) MP_STEM_GO_TAIL(7, 5)   // (7x7 / Q = 6 does not fit)
+  MP_STEM_GO_TAIL(5, 2) MP_STEM_GO_TAIL(5, 3) MP_STEM_GO_TAIL(5, 4) MP_STEM_GO_TAIL(5, 5) MP_STEM_GO_TAIL(5, 6)
+#undef MP_STEM_GO_TAIL
 #define MP_STEM_GO(KSV, QV)                                                                                                          \
   if (d->KH == KSV && Q == QV) {                                                                                                   \
     if (sp)                                                                                                                        \
@@ -532,6 +639,16 @@ extern "C" int mp_conv_stem_xrec_sparse(const mp_conv_desc* d, const void* d_pac
                                         const unsigned char* d_tile_flags, float* d_ypool, int pool_border, mp_stream stream) {
   MP_REQUIRE(d && (d->d_y || d_ypool), "mp_conv_stem_xrec_sparse: null output");
   return stem_xrec_impl(d, d_packed, n_f32, d_ypool, pool_border, stream, d_packed_sparse, d_tile_flags);
+}
+
+// the tail-plane walks (mp_conv_stem_tail_forms): bit 0 of tail_forms = d_packed is the dense walk's tail blob, bit 1 = d_packed_sparse is
+// the background walk's tail blob (mp_conv_stem_pack_weights_tail); a clear bit = the blob of the present walk (mp_conv_stem_pack_weights_mask
+// / _sparse).  d_packed_sparse and d_tile_flags may both be NULL (every workgroup takes the dense walk), d_ypool may be NULL.
+extern "C" int mp_conv_stem_xrec_tail(const mp_conv_desc* d, const void* d_packed, const void* d_packed_sparse, int n_f32,
+                                      const unsigned char* d_tile_flags, float* d_ypool, int pool_border, int tail_forms, mp_stream stream) {
+  MP_REQUIRE(d && (d->d_y || d_ypool), "mp_conv_stem_xrec_tail: null output");
+  MP_REQUIRE(tail_forms >= 0 && tail_forms <= 3, "mp_conv_stem_xrec_tail: tail_forms is a mask of bits 0 and 1");
+  return stem_xrec_impl(d, d_packed, n_f32, d_ypool, pool_border, stream, d_packed_sparse, d_tile_flags, tail_forms);
 }
 
 // background-tile statistics of the SP launches issued while the event profiler was active: workgroups that took the short walk, all

@@ -499,6 +499,25 @@ def conv_stem_pack_weights_sparse(w_oihw: np.ndarray, n_f32: int, scale: Optiona
     return _pack_weights(lib.mp_conv_stem_pack_weights_sparse, w_oihw, scale, n, np.uint8, Cout, Cin, KH, n_f32)
 
 
+def conv_stem_tail_forms(K: int, n_f32: int, n_u8: int) -> int:
+    """which walks of this record have a tail-plane form (mp_conv_stem_tail_forms): bit 0 the dense walk, bit 1 the background walk"""
+    return int(_lib.load().mp_conv_stem_tail_forms(K, n_f32, n_u8))
+
+
+def conv_stem_pack_weights_tail(w_oihw: np.ndarray, n_f32: int, scale: Optional[np.ndarray] = None, background: bool = False,
+                                f32_mask: Optional[int] = None) -> Optional[np.ndarray]:
+    """the piece blob of the stem's tail-plane walk (mp_conv_stem_pack_weights_tail): the dense walk's, or with `background` the
+    background-tile walk's; None if this record has no such form"""
+    lib = _lib.load()
+    Cout, Cin, KH, KW = np.shape(w_oihw)
+    mask = leading_mask(n_f32) if f32_mask is None else int(f32_mask)
+    nf = bin(mask).count("1")
+    n = lib.mp_conv_stem_tail_packed_bytes(KH, nf, Cin - nf, Cout, int(background))
+    if n == 0:
+        return None
+    return _pack_weights(lib.mp_conv_stem_pack_weights_tail, w_oihw, scale, n, np.uint8, Cout, Cin, KH, mask, int(background))
+
+
 def conv_stem_bg_stats(reset: bool = True) -> Tuple[float, float]:
     """(workgroups that took the background-tile walk, all workgroups of such launches) counted while the event profiler was active"""
     a, b = C.c_double(), C.c_double()
@@ -509,13 +528,20 @@ def conv_stem_bg_stats(reset: bool = True) -> Tuple[float, float]:
 def conv_stem_xrec(xrec: torch.Tensor, N: int, H: int, W: int, c_real: int, n_f32: int, in_border: int, w_pieces: torch.Tensor,
                    bias: Optional[torch.Tensor], Cout: int, K: int, pad: int, y: Optional[torch.Tensor], out_border: int, relu: bool = False,
                    y_pool: Optional[torch.Tensor] = None, pool_border: int = 1, w_sparse: Optional[torch.Tensor] = None,
-                   tile_flags: Optional[torch.Tensor] = None) -> None:
+                   tile_flags: Optional[torch.Tensor] = None, tail_forms: int = 0) -> None:
     """stride-2 stem convolution of a bfloat16 record tensor (mp_conv_stem_xrec); with `y_pool` the 3x3 / stride-2 / pad-1 max pool of its
     output is written too (mp_conv_stem_xrec_pool; `y` may then be None); with `w_sparse` + `tile_flags` (uint8 [N, ceil(H/8), ceil(W/8)],
-    0 = the tile's integer channels are all 0) workgroups over background take the short walk (mp_conv_stem_xrec_sparse)"""
+    0 = the tile's integer channels are all 0) workgroups over background take the short walk (mp_conv_stem_xrec_sparse); with
+    `tail_forms` bit 0 / bit 1 says that `w_pieces` / `w_sparse` is the blob of a tail-plane walk (mp_conv_stem_xrec_tail)"""
     assert xrec.dtype == torch.bfloat16 and w_pieces.dtype == torch.uint8
     d = _conv_desc(xrec.data_ptr(), N, H, W, (c_real + 3) // 4 * 4, in_border, Cout, K, 2, pad, _ptr(y), out_border, bias, relu=relu)
     d.c_real = c_real
+    if tail_forms:
+        sp = w_sparse is not None and tile_flags is not None
+        assert not sp or (tile_flags.dtype == torch.uint8 and tile_flags.is_cuda and w_sparse.dtype == torch.uint8)
+        check(_lib.load().mp_conv_stem_xrec_tail(C.byref(d), w_pieces.data_ptr(), w_sparse.data_ptr() if sp else None, n_f32,
+                                                 tile_flags.data_ptr() if sp else None, _ptr(y_pool), pool_border, int(tail_forms), _stream()))
+        return
     if w_sparse is not None and tile_flags is not None:
         assert tile_flags.dtype == torch.uint8 and tile_flags.is_cuda and w_sparse.dtype == torch.uint8
         check(_lib.load().mp_conv_stem_xrec_sparse(C.byref(d), w_pieces.data_ptr(), w_sparse.data_ptr(), n_f32, tile_flags.data_ptr(),
