@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "block_primitives.h"
 #include "mp_engine.h"
 #include "mp_engine_debug.h"
 
@@ -48,16 +49,6 @@ int device_lds_bytes();
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// wave-wide butterflies: every lane ends with the same bits
-__device__ __forceinline__ float wave_sum_all(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ float wave_max_all(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
 
 // XCD-aware bijective remap of a linear workgroup id (8 XCDs, round-robin dispatch):
 // physical id p runs on XCD p % 8; give each XCD a contiguous chunk of logical ids so that

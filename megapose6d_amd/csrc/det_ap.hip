@@ -25,11 +25,6 @@ namespace mp {
 constexpr int kDetLanesPerGroup = dap::kMaxThetas;            // 16
 constexpr int kDetGroupsPerBlock = 256 / kDetLanesPerGroup;   // 16
 
-__device__ __forceinline__ int32_t wave_sum_all_i32(int32_t v) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-
 // units [blockIdx.y * per_block, + per_block) of the n_units of candidate blockIdx.x; a unit is 16 bytes (VEC) or one
 template <bool VEC>
 __global__ __launch_bounds__(256) void mask_pair_counts_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt,
@@ -69,9 +64,9 @@ __global__ __launch_bounds__(256) void mask_pair_counts_kernel(const uint8_t* __
       area_b += b;
     }
   }
-  inter = wave_sum_all_i32(inter);
-  area_a = wave_sum_all_i32(area_a);
-  area_b = wave_sum_all_i32(area_b);
+  inter = wave_sum_all(inter);
+  area_a = wave_sum_all(area_a);
+  area_b = wave_sum_all(area_b);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
     red[wave][0] = inter;

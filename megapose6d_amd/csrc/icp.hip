@@ -10,8 +10,8 @@
 //     differences of the back-projected measured points),
 //   * data association is PROJECTIVE (transform the source point, project it with K, take the target pixel it lands on)
 //     instead of OpenCV's kd-tree search -- fully parallel, no host involvement,
-//   * each iteration accumulates the 6x6 point-to-plane normal equations per object with block reductions into per-block partial
-//     slots that the one-thread Cholesky solve adds up in a fixed order (no float atomics: results are bit-reproducible); levels subsample the mask pixels (stride 8,4,2,1) and tighten the
+//   * each iteration accumulates the 6x6 point-to-plane normal equations per object with block reductions (block_primitives.h) into
+//     per-block partial slots that the one-thread Cholesky solve adds up in a fixed order (no float atomics: results are bit-reproducible); levels subsample the mask pixels (stride 8,4,2,1) and tighten the
 //     rejection distance (0.20, 0.15, 0.10, 0.05 m).
 // The CPU oracle of THIS algorithm is oracle/icp.py.  Roofline: latency-bound (200 tiny launches), negligible next to the CNN.
 #include "common.h"
@@ -62,22 +62,13 @@ __global__ void icp_target_normals(const float* __restrict__ depth, const float*
   o[0] = n[0]; o[1] = n[1]; o[2] = n[2];
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum_all(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-  return s;
-}
+constexpr int ICP_WAVES = 256 / 64;   // icp_stats and icp_accumulate run 256 threads (their __launch_bounds__)
 
 // mask size + centroids of target / source points (icp_refiner.py:157-162)
 __global__ __launch_bounds__(256) void icp_stats(const float* __restrict__ depth_meas, const int32_t* __restrict__ im_ids,
                                                  const float* __restrict__ depth_rend, const float* __restrict__ K, int H, int W,
                                                  float delta_thresh, IcpRow* __restrict__ rows) {
-  __shared__ float red[4];
+  __shared__ float red[ICP_WAVES];
   const int n = blockIdx.y;
   const float* dm = depth_meas + (size_t)im_ids[n] * H * W;
   const float* dr = depth_rend + (size_t)n * H * W;
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(256) void icp_stats(const float* __restrict__ depth
     v[4] += u * zs * ifx; v[5] += w_ * zs * ify; v[6] += zs;
   }
   for (int k = 0; k < 7; ++k) {
-    const float s = block_sum(v[k], red);
+    const float s = block_sum_all<ICP_WAVES>(v[k], red);
     if (threadIdx.x == 0) rows[n].stat_part[blockIdx.x][k == 0 ? 0 : k + 1] = s;
   }
 }
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(256) void icp_accumulate(const float* __restrict__ 
                                                       const int32_t* __restrict__ im_ids, const float* __restrict__ depth_rend,
                                                       const float* __restrict__ K, int H, int W, int stride, float d_max,
                                                       float delta_thresh, IcpRow* __restrict__ rows) {
-  __shared__ float red[4];
+  __shared__ float red[ICP_WAVES];
   const int n = blockIdx.y;
   if (rows[n].status == 0) return;
   const float* dm = depth_meas + (size_t)im_ids[n] * H * W;
@@ -165,7 +156,7 @@ __global__ __launch_bounds__(256) void icp_accumulate(const float* __restrict__ 
     a[28] += 1.f;
   }
   for (int k = 0; k < 29; ++k) {
-    const float s = block_sum(a[k], red);
+    const float s = block_sum_all<ICP_WAVES>(a[k], red);
     if (threadIdx.x == 0) rows[n].acc_part[blockIdx.x][k] = s;
   }
 }
@@ -265,7 +256,7 @@ extern "C" int mp_icp_refine(const float* d_depth_meas, int n_images, const int3
   MP_REQUIRE(n_rows <= 65535 && n_images <= 65535, "mp_icp_refine: at most 65535 rows / images");
   hipStream_t s = (hipStream_t)stream;
   float* normals = (float*)d_ws;
-  IcpRow* rows = (IcpRow*)(((uintptr_t)(normals + (size_t)n_images * H * W * 3) + 255) & ~(uintptr_t)255);
+  IcpRow* rows = (IcpRow*)align256((uintptr_t)(normals + (size_t)n_images * H * W * 3));
   MP_CHECK_HIP(hipMemsetAsync(rows, 0, (size_t)n_rows * sizeof(IcpRow), s));
   ProfScope prof("icp_refine", 0.0, (double)n_rows * H * W * 8.0 * n_iterations, s);
   hipLaunchKernelGGL(icp_target_normals, dim3(ceil_div((long)H * W, 256), n_images), dim3(256), 0, s, d_depth_meas, d_K_images, H, W, normals);

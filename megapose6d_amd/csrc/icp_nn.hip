@@ -18,7 +18,7 @@
 // iteration count is enqueued up front and every object keeps its own level / iteration / stop state in device memory, so the
 // data-dependent loop never touches the host and a finished object just turns its remaining launches into no-ops.  search: exact
 // brute-force nearest neighbours in float64 over the whole chip (scene tiled through LDS); step (one workgroup per object): radix-select
-// medians, 64-bit atomicMin one-to-one filter, float64 normal equations reduced in a fixed order (deterministic), Cholesky solve.
+// medians, 64-bit atomicMin one-to-one filter, float64 normal equations reduced in the one order of block_primitives.h, Cholesky solve.
 // Arithmetic follows the restatement (float32 where numpy / OpenCV hold float32, float64 where they compute in double).
 // Roofline: latency / VALU-bound tail work of config 5 (once per detection after the CNN stages), negligible next to them.
 #include <algorithm>
@@ -28,7 +28,7 @@
 
 namespace mp {
 
-constexpr int NN_THREADS = 1024;
+constexpr int NN_THREADS = 1024, NN_WAVES = NN_THREADS / 64;
 constexpr int FILL_RINGS = 10;
 constexpr int IDX_BITS = 18;           // scene index bits of the nearest-neighbour merge key -> at most 2^18 points per object
 constexpr int GAUSS_RADIUS = 8;        // scipy.ndimage.gaussian_filter(sigma=2): truncate 4.0 -> radius int(4 * 2 + 0.5) = 8
@@ -189,10 +189,8 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_compact(const float* __restr
                                                             const float* __restrict__ pts_rend, int H, int W, const unsigned char* __restrict__ masks, int cap,
                                                             int n_min_points, float* __restrict__ src, float* __restrict__ dst,
                                                             NnRow* __restrict__ rows) {
-  __shared__ int wave_sum[2][NN_THREADS / 64];
-  __shared__ int base_s[2];
-  const int n = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int wave_count[2][NN_WAVES];
+  const int n = blockIdx.x, tid = threadIdx.x;
   const float* dm = depth_meas + (size_t)im_ids[n] * H * W;
   const float* dr = depth_rend + (size_t)n * H * W;
   const unsigned char* mk = masks ? masks + (size_t)im_ids[n] * H * W : nullptr;
@@ -200,8 +198,7 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_compact(const float* __restr
   const float* pr = pts_rend + (size_t)n * H * W * 6;
   float* so = src + (size_t)n * cap * 6;
   float* dq = dst + (size_t)n * cap * 6;
-  if (tid < 2) base_s[tid] = 0;
-  __syncthreads();
+  int base_t = 0, base_s = 0;   // scene / model points kept so far (the same in every thread)
   for (int start = 0; start < H * W; start += NN_THREADS) {
     const int idx = start + tid;
     bool in_t = false, in_s = false;
@@ -211,29 +208,20 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_compact(const float* __restr
       in_t = mask && m > 0.2f && m < 5.0f;
       in_s = in_t && r > 0.f;
     }
-    const unsigned long long bt = __ballot(in_t), bs = __ballot(in_s);
-    const unsigned long long lower = (1ull << lane) - 1ull;
-    if (lane == 0) { wave_sum[0][wave] = __popcll(bt); wave_sum[1][wave] = __popcll(bs); }
-    __syncthreads();
-    int off_t = base_s[0], off_s = base_s[1];
-    for (int w = 0; w < wave; ++w) { off_t += wave_sum[0][w]; off_s += wave_sum[1][w]; }
-    const int pos_t = off_t + __popcll(bt & lower), pos_s = off_s + __popcll(bs & lower);
-    if (in_t && pos_t < cap)
+    int kept_t, kept_s;
+    const int pos_t = base_t + block_compact<NN_WAVES>(in_t, wave_count[0], &kept_t);
+    const int pos_s = base_s + block_compact<NN_WAVES>(in_s, wave_count[1], &kept_s);
+    if (in_t && pos_t < cap)   // (a point past the capacity is dropped but still counted: the row is then rejected below)
       for (int k = 0; k < 6; ++k) dq[(size_t)pos_t * 6 + k] = pm[(size_t)idx * 6 + k];
     if (in_s && pos_s < cap)
       for (int k = 0; k < 6; ++k) so[(size_t)pos_s * 6 + k] = pr[(size_t)idx * 6 + k];
-    __syncthreads();
-    if (tid < 2) {
-      int t = 0;
-      for (int w = 0; w < NN_THREADS / 64; ++w) t += wave_sum[tid][w];
-      base_s[tid] += t;
-    }
-    __syncthreads();
+    base_t += kept_t;
+    base_s += kept_s;
   }
   if (tid == 0) {
     NnRow& r = rows[n];
-    r.m = base_s[0];
-    r.n = base_s[1];
+    r.m = base_t;
+    r.n = base_s;
     r.status = (r.n >= n_min_points && r.m >= n_min_points && r.n <= cap && r.m <= cap) ? 1 : 0;   // icp_refiner.py:152-155
     r.residual = -1.0;
     r.active = 0;
@@ -254,18 +242,6 @@ struct NnScratch {   // per object, global memory (cap points each)
   unsigned long long* nnkey;   // [cap] nearest-neighbour merge across scene segments: (distance bits | scene index) per model point
   unsigned long long* key;   // [cap] picky filter: (d2 bits << 32 | model index) per scene point
 };
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {   // deterministic: fixed tree inside the wave, fixed wave order
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < NN_THREADS / 64; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
 
 // lower median (element (n-1)/2 of the sorted array) of n non-negative float32 values: 4-pass radix select on the bit patterns
 __device__ float block_median(const float* __restrict__ a, int n, unsigned* hist, unsigned* sh) {
@@ -374,7 +350,7 @@ __device__ void level_start(NnRow& R, const NnPtrs& P, const double* pose, int l
 // centroid pre-shift, OpenCV's mean / scale normalisation, start of the coarsest level.  One workgroup per object.
 __global__ __launch_bounds__(NN_THREADS) void icpnn_begin(NnScratch sc, int cap, NnRow* __restrict__ rows, int iterations, float tolerance,
                                                           int num_levels) {
-  __shared__ double red[NN_THREADS / 64];
+  __shared__ double red[NN_WAVES];
   __shared__ double pose_s[16];
   __shared__ float stage[6 * NN_THREADS];
   __shared__ float msum[6];
@@ -418,7 +394,7 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_begin(NnScratch sc, int cap,
     double a = 0.0, b = 0.0;
     for (int i = tid; i < n; i += NN_THREADS) a += (double)src[(size_t)i * 6 + k];
     for (int i = tid; i < m; i += NN_THREADS) b += (double)dst[(size_t)i * 6 + k];
-    const double sa = block_sum_d(a, red), sb = block_sum_d(b, red);
+    const double sa = block_sum_all<NN_WAVES>(a, red), sb = block_sum_all<NN_WAVES>(b, red);
     mean_avg[k] = 0.5 * (sa / n + sb / m);
   }
   for (int i = tid; i < n; i += NN_THREADS)
@@ -435,8 +411,8 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_begin(NnScratch sc, int cap,
     const double b0 = dst[(size_t)i * 6], b1 = dst[(size_t)i * 6 + 1], b2 = dst[(size_t)i * 6 + 2];
     dd += sqrt(b0 * b0 + b1 * b1 + b2 * b2);
   }
-  ds = block_sum_d(ds, red);
-  dd = block_sum_d(dd, red);
+  ds = block_sum_all<NN_WAVES>(ds, red);
+  dd = block_sum_all<NN_WAVES>(dd, red);
   const double scale = (double)n / ((ds + dd) * 0.5);
   const float scale_f = (float)scale;
   for (int i = tid; i < n; i += NN_THREADS)
@@ -523,7 +499,7 @@ __global__ __launch_bounds__(SEARCH_THREADS) void icpnn_search(NnScratch sc, int
 // the next level -- or, after the finest one, undo the normalisation and retire the object.
 __global__ __launch_bounds__(NN_THREADS) void icpnn_step(NnScratch sc, int cap, NnRow* __restrict__ rows, int iterations, float tolerance,
                                                          float rejection_scale) {
-  __shared__ double red[NN_THREADS / 64];
+  __shared__ double red[NN_WAVES];
   __shared__ unsigned hist[256];
   __shared__ unsigned sh_u[2];
   __shared__ double sh_d[40];
@@ -592,12 +568,12 @@ __global__ __launch_bounds__(NN_THREADS) void icpnn_step(NnScratch sc, int cap, 
     ++cnt;
   }
   for (int k = 0; k < 27; ++k) {
-    const double s = block_sum_d(a[k], red);
+    const double s = block_sum_all<NN_WAVES>(a[k], red);
     if (tid == 0) sh_d[k] = s;
   }
   {
-    const double s = block_sum_d(fsq, red);
-    const double c = block_sum_d((double)cnt, red);
+    const double s = block_sum_all<NN_WAVES>(fsq, red);
+    const double c = block_sum_all<NN_WAVES>((double)cnt, red);
     if (tid == 0) { sh_d[27] = s; sh_d[28] = c; }
   }
   __syncthreads();
@@ -719,8 +695,6 @@ __global__ void icpnn_finalize(const NnRow* __restrict__ rows, const float* __re
 
 using namespace mp;
 
-static size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 extern "C" int mp_icp_nn_max_points(void) { return 1 << IDX_BITS; }   // (the search packs a scene index into IDX_BITS bits)
 
 // points per object the buffers of a call are sized for: every pixel of the frame, up to the key's limit
@@ -730,11 +704,11 @@ extern "C" size_t mp_icp_nn_workspace_bytes(int n_images, int n_rows, int H, int
   const size_t px = (size_t)H * W, cap = nn_cap(H, W);
   const size_t imgs = (size_t)n_images + n_rows;
   size_t b = 0;
-  b += 3 * a256(imgs * px * 4);            // fill ping / pong, gaussian temp
-  b += 2 * a256(imgs * px);                // valid ping / pong
-  b += a256(imgs * px * 6 * 4);            // points + normals of every image
-  b += 5 * a256((size_t)n_rows * cap * 6 * 4) + 2 * a256((size_t)n_rows * cap * 4) + a256((size_t)n_rows * cap * 4) + 2 * a256((size_t)n_rows * cap * 8);
-  b += a256((size_t)n_rows * sizeof(NnRow)) + a256(imgs * 4) + 4096;
+  b += 3 * align256(imgs * px * 4);            // fill ping / pong, gaussian temp
+  b += 2 * align256(imgs * px);                // valid ping / pong
+  b += align256(imgs * px * 6 * 4);            // points + normals of every image
+  b += 5 * align256((size_t)n_rows * cap * 6 * 4) + 2 * align256((size_t)n_rows * cap * 4) + align256((size_t)n_rows * cap * 4) + 2 * align256((size_t)n_rows * cap * 8);
+  b += align256((size_t)n_rows * sizeof(NnRow)) + align256(imgs * 4) + 4096;
   return b;
 }
 
@@ -754,7 +728,7 @@ extern "C" int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const i
   const size_t px = (size_t)H * W, cap = nn_cap(H, W);
   const int imgs = n_images + n_rows;   // image batch: the measured frames first, then the rendered depth of every object
   unsigned char* w = (unsigned char*)d_ws;
-  auto take = [&](size_t bytes) { unsigned char* p = w; w += a256(bytes); return p; };
+  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
   float* fa = (float*)take(imgs * px * 4);
   float* fb = (float*)take(imgs * px * 4);
   float* raw = (float*)take(imgs * px * 4);

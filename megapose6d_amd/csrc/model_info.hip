@@ -12,8 +12,8 @@
 //                             read that the LDS broadcasts (identical addresses never conflict), and 16 KiB at the largest tile leave
 //                             the workgroups per CU to the registers.  Stages that lie wholly after the block need no per-lane test;
 //                             the stages that overlap it look at j >= i only.  Lanes with i >= n_points and stage entries with
-//                             j >= n_points are masked out, never clamped: a padding row is not read.  Lane best -> wave butterfly ->
-//                             LDS -> one 16-byte vector store to partials[job].
+//                             j >= n_points are masked out, never clamped: a padding row is not read.  Lane best -> workgroup best
+//                             [block_primitives.h] -> one 16-byte vector store to partials[job].
 //   model_info_reduce_kernel  one workgroup per object: folds the object's partials under the same order, takes min and max per axis and
 //                             the finiteness of rows 0 .. n_points - 1, and stores d2, the pair and the bounds (NaN, -1 -1, NaN for an
 //                             object with a non-finite coordinate).
@@ -26,45 +26,19 @@ namespace mp {
 
 using minfo::Cand;
 
-__device__ __forceinline__ Cand wave_best_all(Cand v) {
-  for (int off = 32; off > 0; off >>= 1) {
-    Cand o;
-    o.d2 = __shfl_xor(v.d2, off);
-    o.i = __shfl_xor(v.i, off);
-    o.j = __shfl_xor(v.j, off);
-    if (minfo::better(o, v)) v = o;
-  }
-  return v;
-}
+constexpr int kWaves = minfo::kBlock / 64;
 
-// every lane returns the workgroup's best
-__device__ __forceinline__ Cand block_best(Cand v, Cand* red) {
-  v = wave_best_all(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  Cand best = red[0];
-  for (int w = 1; w < minfo::kBlock / 64; ++w)
-    if (minfo::better(red[w], best)) best = red[w];
-  return best;
-}
-
-// the object of a job: the largest o with job_off[o] <= job
-__device__ __forceinline__ int object_of(const int32_t* __restrict__ job_off, int n_obj, int job) {
-  int lo = 0, hi = n_obj;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (job_off[mid] <= job) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+struct BestOp {   // the better of two candidates under minfo::better's total order
+  static constexpr bool kFromZero = false;
+  __device__ __forceinline__ Cand operator()(Cand a, Cand b) const { return minfo::better(b, a) ? b : a; }
+};
 
 __global__ __launch_bounds__(256) void model_info_pairs_kernel(const float* __restrict__ points, int stride,
                                                                const int32_t* __restrict__ n_points,
                                                                const int32_t* __restrict__ job_off, int n_obj, int tile, int chunk,
                                                                int4* __restrict__ partials) {
   __shared__ float4 stage[minfo::kMaxTile];
-  __shared__ Cand red[minfo::kBlock / 64];
+  __shared__ Cand red[kWaves];
   const int job = blockIdx.x, tid = threadIdx.x;
   const int obj = object_of(job_off, n_obj, job);
   int n = n_points[obj];
@@ -107,7 +81,7 @@ __global__ __launch_bounds__(256) void model_info_pairs_kernel(const float* __re
     }
   }
   const Cand mine = best_j == minfo::kNone ? minfo::none() : Cand{best_d2, i, best_j};
-  const Cand best = block_best(mine, red);
+  const Cand best = block_reduce_all<kWaves>(mine, red, BestOp());
   if (tid == 0) partials[job] = make_int4(__float_as_int(best.d2), best.i, best.j, 0);
 }
 
@@ -116,9 +90,9 @@ __global__ __launch_bounds__(256) void model_info_reduce_kernel(const float* __r
                                                                 const int32_t* __restrict__ job_off, const int4* __restrict__ partials,
                                                                 float* __restrict__ d2_out, int32_t* __restrict__ pair_out,
                                                                 float* __restrict__ bounds_out) {
-  __shared__ Cand red[minfo::kBlock / 64];
-  __shared__ float lo_s[minfo::kBlock / 64][3], hi_s[minfo::kBlock / 64][3];
-  __shared__ int bad_s[minfo::kBlock / 64];
+  __shared__ Cand red[kWaves];
+  __shared__ float red_f[kWaves];
+  __shared__ int red_bad[kWaves];
   const int obj = blockIdx.x, tid = threadIdx.x;
   int n = n_points[obj];
   n = n < stride ? n : stride;
@@ -128,7 +102,7 @@ __global__ __launch_bounds__(256) void model_info_reduce_kernel(const float* __r
     const Cand o{__int_as_float(v.x), v.y, v.z};
     if (minfo::better(o, mine)) mine = o;
   }
-  const Cand best = block_best(mine, red);
+  const Cand best = block_reduce_all<kWaves>(mine, red, BestOp());
   const float* P = points + (size_t)obj * stride * 3;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   int bad = 0;
@@ -138,37 +112,19 @@ __global__ __launch_bounds__(256) void model_info_reduce_kernel(const float* __r
     lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
     hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    bad |= __shfl_xor(bad, off);
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], off));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off));
-    }
+  bad = block_reduce_all<kWaves>(bad, red_bad, OrOp());
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = block_min_all<kWaves>(lo[a], red_f);
+    hi[a] = block_max_all<kWaves>(hi[a], red_f);
   }
-  const int lane = tid & 63, wave = tid >> 6;
-  if (lane == 0) {
-    bad_s[wave] = bad;
-    for (int a = 0; a < 3; ++a) {
-      lo_s[wave][a] = lo[a];
-      hi_s[wave][a] = hi[a];
-    }
-  }
-  __syncthreads();
   if (tid != 0) return;
-  for (int w = 1; w < minfo::kBlock / 64; ++w) {
-    bad_s[0] |= bad_s[w];
-    for (int a = 0; a < 3; ++a) {
-      lo_s[0][a] = fminf(lo_s[0][a], lo_s[w][a]);
-      hi_s[0][a] = fmaxf(hi_s[0][a], hi_s[w][a]);
-    }
-  }
-  const bool ok = !bad_s[0] && best.j != minfo::kNone;
+  const bool ok = !bad && best.j != minfo::kNone;
   d2_out[obj] = ok ? best.d2 : NAN;
   pair_out[2 * obj] = ok ? best.i : -1;
   pair_out[2 * obj + 1] = ok ? best.j : -1;
   for (int a = 0; a < 3; ++a) {
-    bounds_out[6 * obj + a] = ok ? lo_s[0][a] : NAN;
-    bounds_out[6 * obj + 3 + a] = ok ? hi_s[0][a] - lo_s[0][a] : NAN;
+    bounds_out[6 * obj + a] = ok ? lo[a] : NAN;
+    bounds_out[6 * obj + 3 + a] = ok ? hi[a] - lo[a] : NAN;
   }
 }
 

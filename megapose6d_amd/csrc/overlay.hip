@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a) {
 }
 
 // Boxes are taken 256 at a time: lane l looks at box j0 + l and keeps it when it belongs to the tile's image, has no NaN corner and its
-// grown rectangle meets the tile; the kept boxes are compacted in ascending j into LDS (wave ballot + the waves' counts: no atomics, a
+// grown rectangle meets the tile; the kept boxes are compacted in ascending j into LDS (block_compact: no atomics, a
 // fixed order), and every pixel walks that list from the last to the first under on_frame.  A later chunk holds higher j and overrides.
 __global__ __launch_bounds__(256) void draw_boxes_kernel(const uint8_t* __restrict__ images, const float* __restrict__ boxes,
                                                          const int32_t* __restrict__ image_ids, int n_boxes,
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void draw_boxes_kernel(const uint8_t* __restri
   __shared__ int4 corners[ovl::kBlock];
   __shared__ int32_t index[ovl::kBlock];
   __shared__ int32_t wave_count[ovl::kBlock / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int per_image = tiles_x * tiles_y;
   const int img = blockIdx.x / per_image, rest = blockIdx.x - img * per_image;
   const int ty = rest / tiles_x, tx = rest - ty * tiles_x;
@@ -207,16 +207,9 @@ __global__ __launch_bounds__(256) void draw_boxes_kernel(const uint8_t* __restri
       c.z = ovl::box_corner(boxes[4 * j + 2], &keep); c.w = ovl::box_corner(boxes[4 * j + 3], &keep);
       keep = keep && c.x - grow < x0 + ovl::kTileW && c.z + grow >= x0 && c.y - grow < y0 + ovl::kTileH && c.w + grow >= y0;
     }
-    const unsigned long long votes = __ballot(keep);
-    if (lane == 0) wave_count[wave] = __popcll(votes);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int v = 0; v < ovl::kBlock / 64; ++v) {
-      before += v < wave ? wave_count[v] : 0;
-      total += wave_count[v];
-    }
+    int total;
+    const int slot = block_compact<ovl::kBlock / 64>(keep, wave_count, &total);   // (its first barrier: the walk of the chunk before is over)
     if (keep) {
-      const int slot = before + __popcll(votes & ((1ull << lane) - 1ull));
       corners[slot] = c;
       index[slot] = j;
     }
@@ -231,7 +224,6 @@ __global__ __launch_bounds__(256) void draw_boxes_kernel(const uint8_t* __restri
             break;
           }
         }
-    __syncthreads();
   }
   if (!live) return;
   const bool wide = wide_i != 0;

@@ -51,12 +51,6 @@ __global__ void normalize_T_kernel(const float* __restrict__ T, int b, float* __
   for (int k = 0; k < 16; ++k) O[(size_t)i * 16 + k] = o[k];
 }
 
-// block reduce of (min, max) pairs -------------------------------------------------------------
-__device__ __forceinline__ float wave_min(float v) {
-  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-  return v;
-}
-
 // extents of R*p over a mesh's (padded) point set: one block per (mesh, rotation)
 __global__ __launch_bounds__(256) void init_extents_kernel(const float* __restrict__ pts, int n_pts, const float* __restrict__ R,
                                                            int n_rot, float* __restrict__ ext) {
@@ -72,7 +66,7 @@ __global__ __launch_bounds__(256) void init_extents_kernel(const float* __restri
     xmin = fminf(xmin, x); xmax = fmaxf(xmax, x);
     ymin = fminf(ymin, y); ymax = fmaxf(ymax, y);
   }
-  xmin = wave_min(xmin); xmax = wave_max_all(xmax); ymin = wave_min(ymin); ymax = wave_max_all(ymax);
+  xmin = wave_min_all(xmin); xmax = wave_max_all(xmax); ymin = wave_min_all(ymin); ymax = wave_max_all(ymax);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red[wave][0] = xmin; red[wave][1] = xmax; red[wave][2] = ymin; red[wave][3] = ymax; }
   __syncthreads();
@@ -218,7 +212,7 @@ __global__ __launch_bounds__(256) void pose_prepare_kernel(
     umin = fminf(umin, u); umax = fmaxf(umax, u);
     vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
   }
-  umin = wave_min(umin); umax = wave_max_all(umax); vmin = wave_min(vmin); vmax = wave_max_all(vmax);
+  umin = wave_min_all(umin); umax = wave_max_all(umax); vmin = wave_min_all(vmin); vmax = wave_max_all(vmax);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red[wave][0] = umin; red[wave][1] = umax; red[wave][2] = vmin; red[wave][3] = vmax; }
   __syncthreads();

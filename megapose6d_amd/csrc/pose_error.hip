@@ -130,7 +130,6 @@ __global__ __launch_bounds__(256) void sym_finalize_kernel(const float* __restri
                                                            float* __restrict__ T_gt_sym, float* __restrict__ errs,
                                                            float* __restrict__ diffs) {
   __shared__ float Tw[16];
-  __shared__ int best_s;
   const int row = blockIdx.x, mesh = mesh_ids[row];
   const int ns = syms ? (n_sym ? min(n_sym[mesh], S_max) : S_max) : S_max;
   const int nv = n_points ? min(n_points[mesh], n_pts) : n_pts;
@@ -174,7 +173,6 @@ __global__ __launch_bounds__(256) void sym_finalize_kernel(const float* __restri
         Tw[k] = O[k];
         if (T_gt_sym) T_gt_sym[(size_t)row * 16 + k] = O[k];
       }
-      best_s = bi;
     }
   }
   if (!diffs) return;

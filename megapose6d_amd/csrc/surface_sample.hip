@@ -29,70 +29,19 @@ namespace mp {
 
 namespace {
 
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v, int d) {
-  const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d) {
-  const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
+constexpr int kWaves = ssamp::kThreads / 64;
 
 // inclusive scan of one value per lane over the workgroup's 256 lanes; red holds one entry per wave
 __device__ __forceinline__ uint64_t block_scan_inclusive(uint64_t v, uint64_t* red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = shfl_up_u64(v, d);
+    const uint64_t o = shfl_up_any(v, d);
     if (lane >= d) v += o;
   }
   if (lane == 63) red[wave] = v;
   __syncthreads();
   for (int w = 0; w < wave; ++w) v += red[w];
   return v;
-}
-
-// every lane returns the workgroup's sum
-__device__ __forceinline__ uint64_t block_sum_all(uint64_t v, uint64_t* red) {
-  for (int off = 32; off > 0; off >>= 1) v += shfl_xor_u64(v, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t s = 0;
-  for (int w = 0; w < ssamp::kThreads / 64; ++w) s += red[w];
-  return s;
-}
-
-// every lane returns the workgroup's largest weight and the OR of the flags
-__device__ __forceinline__ void block_max_or(float* mx, int* bad, float* red_mx, int* red_bad) {
-  float m = *mx;
-  int b = *bad;
-  for (int off = 32; off > 0; off >>= 1) {
-    m = fmaxf(m, __shfl_xor(m, off));
-    b |= __shfl_xor(b, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red_mx[threadIdx.x >> 6] = m;
-    red_bad[threadIdx.x >> 6] = b;
-  }
-  __syncthreads();
-  m = red_mx[0];
-  b = red_bad[0];
-  for (int w = 1; w < ssamp::kThreads / 64; ++w) {
-    m = fmaxf(m, red_mx[w]);
-    b |= red_bad[w];
-  }
-  *mx = m;
-  *bad = b;
-}
-
-// the object of a job: the largest o with job_off[o] <= job (at most 31 halvings of n_obj)
-__device__ __forceinline__ int object_of(const int32_t* __restrict__ job_off, int n_obj, int job) {
-  int lo = 0, hi = n_obj;
-  for (int s = 0; s < 31 && hi - lo > 1; ++s) {
-    const int mid = (lo + hi) >> 1;
-    if (job_off[mid] <= job) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 struct Job {
@@ -132,8 +81,8 @@ __global__ __launch_bounds__(256) void surface_weights_kernel(const float* __res
                                                               const int32_t* __restrict__ job_off, int n_obj, int block,
                                                               int v_total, int f_total, float* __restrict__ w_out, float* __restrict__ job_max,
                                                               int32_t* __restrict__ job_bad) {
-  __shared__ float red_mx[ssamp::kThreads / 64];
-  __shared__ int red_bad[ssamp::kThreads / 64];
+  __shared__ float red_mx[kWaves];
+  __shared__ int red_bad[kWaves];
   const Job j = job_of(job_off, face_off, n_obj, block, f_total);
   const int32_t n_vert = vertices_of(vert_off, j.obj, v_total);
   const float* V = vertices + 3 * (size_t)vert_off[j.obj];
@@ -162,7 +111,8 @@ __global__ __launch_bounds__(256) void surface_weights_kernel(const float* __res
     w_out[f] = w;
     mx = fmaxf(mx, w);
   }
-  block_max_or(&mx, &bad, red_mx, red_bad);
+  mx = block_max_all<kWaves>(mx, red_mx);
+  bad = block_reduce_all<kWaves>(bad, red_bad, OrOp());
   if (threadIdx.x == 0) {
     job_max[blockIdx.x] = mx;
     job_bad[blockIdx.x] = bad;
@@ -173,9 +123,9 @@ __global__ __launch_bounds__(256) void surface_block_sum_kernel(const int32_t* _
                                                                 int n_obj, int block, int f_total, const float* __restrict__ w,
                                                                 const float* __restrict__ job_max, const int32_t* __restrict__ job_bad,
                                                                 uint64_t* __restrict__ block_sum, int32_t* __restrict__ obj_e) {
-  __shared__ float red_mx[ssamp::kThreads / 64];
-  __shared__ int red_bad[ssamp::kThreads / 64];
-  __shared__ uint64_t red[ssamp::kThreads / 64];
+  __shared__ float red_mx[kWaves];
+  __shared__ int red_bad[kWaves];
+  __shared__ uint64_t red[kWaves];
   const Job j = job_of(job_off, face_off, n_obj, block, f_total);
   float wmax = 0.0f;
   int bad = 0;
@@ -183,13 +133,14 @@ __global__ __launch_bounds__(256) void surface_block_sum_kernel(const int32_t* _
     wmax = fmaxf(wmax, job_max[p]);
     bad |= job_bad[p];
   }
-  block_max_or(&wmax, &bad, red_mx, red_bad);
+  wmax = block_max_all<kWaves>(wmax, red_mx);
+  bad = block_reduce_all<kWaves>(bad, red_bad, OrOp());
   const bool failed = bad || !(wmax > 0.0f);
   const int e = failed ? ssamp::kFailed : ssamp::exponent_of(wmax);
   uint64_t s = 0;
   if (!failed)
     for (int i = threadIdx.x; i < j.n; i += ssamp::kThreads) s += ssamp::quantise(w[j.f0 + i], e);
-  s = block_sum_all(s, red);
+  s = block_sum_all<kWaves>(s, red);
   if (threadIdx.x == 0) {
     block_sum[blockIdx.x] = s;
     if (j.b == 0) obj_e[j.obj] = e;
@@ -197,7 +148,7 @@ __global__ __launch_bounds__(256) void surface_block_sum_kernel(const int32_t* _
 }
 
 __global__ __launch_bounds__(256) void surface_block_prefix_kernel(const int32_t* __restrict__ job_off, uint64_t* __restrict__ block_sum) {
-  __shared__ uint64_t red[ssamp::kThreads / 64];
+  __shared__ uint64_t red[kWaves];
   constexpr int kPer = ssamp::kMaxBlocks / ssamp::kThreads;
   const int first = job_off[blockIdx.x];
   int n = job_off[blockIdx.x + 1] - first;
@@ -222,7 +173,7 @@ __global__ __launch_bounds__(256) void surface_scan_kernel(const int32_t* __rest
                                                            int block, int f_total, const float* __restrict__ w,
                                                            const uint64_t* __restrict__ block_prefix,
                                                            const int32_t* __restrict__ obj_e, uint64_t* __restrict__ C) {
-  __shared__ uint64_t red[ssamp::kThreads / 64];
+  __shared__ uint64_t red[kWaves];
   constexpr int kPer = ssamp::kMaxBlock / ssamp::kThreads;
   const Job j = job_of(job_off, face_off, n_obj, block, f_total);
   const int e = obj_e[j.obj];

@@ -12,11 +12,12 @@
 //   teaser_compact  (row)        ordered compaction of the mask pixels: source points + pixel ids
 //   teaser_fps      (row)        farthest point sampling: a slice of the points and their running minima in registers, the rest streamed
 //                                from L2; one packed-key argmax per pick (wave butterfly, one LDS step across the waves)
+// The reductions and ordered compactions are those of block_primitives.h, which states their order and their barriers once.
 //   teaser_gather   (row, k)     the sampled correspondences
 //   teaser_graph    (tile, row)  the M x M consistency bit matrix, points in LDS, degrees by popcount
 //   teaser_kcore    (row)        k-core peel, one thread per vertex, its matrix row in registers; ordered list of the selected vertices
 //   clique_search   (rows)       selection 2 only (teaser_clique.hip): one wave per row replaces that list by the maximum clique's
-//   teaser_solve    (row)        GNC-TLS rotation (float64 sums in a fixed tree, 4x4 Jacobi on one lane), TLS translation by voting,
+//   teaser_solve    (row)        GNC-TLS rotation (float64 workgroup sums, 4x4 Jacobi on one lane), TLS translation by voting,
 //                                inlier count, pose write
 // Roofline: latency-bound tail work (once per detection, after the CNN stages); the sampling kernel is the long pole, a chain of
 // n_points dependent argmax steps per row.
@@ -36,17 +37,15 @@ __global__ __launch_bounds__(kThreads) void teaser_compact(const float* __restri
                                                            const float* __restrict__ depth_rend, const float* __restrict__ K_rows, int H, int W,
                                                            int mask_type, float thresh, float* __restrict__ pts, int32_t* __restrict__ pix,
                                                            int32_t* __restrict__ n_out) {
-  __shared__ int wave_sum[kWaves];
-  __shared__ int base_s;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  __shared__ int wave_count[kWaves];
+  const int row = blockIdx.x, tid = threadIdx.x;
   const int px = H * W;
   const float* dm = depth_meas + (size_t)im_ids[row] * px;
   const float* dr = depth_rend + (size_t)row * px;
   const float* K = K_rows + (size_t)row * 9;
   float* po = pts + (size_t)row * px * 3;
   int32_t* xo = pix + (size_t)row * px;
-  if (tid == 0) base_s = 0;
-  __syncthreads();
+  int base = 0;   // points kept so far (the same in every thread)
   for (int start = 0; start < px; start += kThreads) {
     const int idx = start + tid;
     float r = 0.0f;
@@ -55,27 +54,17 @@ __global__ __launch_bounds__(kThreads) void teaser_compact(const float* __restri
       r = dr[idx];
       in = mask_pixel(dm[idx], r, mask_type, thresh);
     }
-    const unsigned long long b = __ballot(in);
-    if (lane == 0) wave_sum[wave] = __popcll(b);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wave; ++w) off += wave_sum[w];
-    const int pos = off + __popcll(b & ((1ull << lane) - 1ull));
+    int kept;
+    const int pos = base + block_compact<kWaves>(in, wave_count, &kept);
     if (in) {   // pos < N <= px: inside the row's slice
       float p[3];
       backproject(idx % W, idx / W, r, K, p);
       po[(size_t)pos * 3] = p[0]; po[(size_t)pos * 3 + 1] = p[1]; po[(size_t)pos * 3 + 2] = p[2];
       xo[pos] = idx;
     }
-    __syncthreads();
-    if (tid == 0) {
-      int t = 0;
-      for (int w = 0; w < kWaves; ++w) t += wave_sum[w];
-      base_s += t;
-    }
-    __syncthreads();
+    base += kept;
   }
-  if (tid == 0) n_out[row] = base_s;
+  if (tid == 0) n_out[row] = base;
 }
 
 // ---- farthest point sampling -------------------------------------------------------------------------------------------------------------
@@ -128,12 +117,14 @@ __global__ __launch_bounds__(kThreads) void teaser_fps(const float* __restrict__
       const unsigned long long key = fps_key(mn, i);
       best = key > best ? key : best;
     }
+    // (this argmax stays written out: the sampling chain is the refiner's long pole, and through wave_max_all -- the same instructions
+    //  in the reduction -- the kernel came out scheduled 9 % slower)
     for (int off = 32; off > 0; off >>= 1) {
       const unsigned long long o = __shfl_xor(best, off);
       best = o > best ? o : best;
     }
-    // (two buffers by the parity of the pick: a wave can only overwrite a buffer after the barrier of the pick between, which every
-    //  wave passes after it has read)
+    // (one barrier per pick where block_max_all has two: two buffers by the parity of the pick, and a wave can only overwrite a buffer
+    //  after the barrier of the pick between, which every wave passes after it has read)
     if (lane == 0) wave_best[pick & 1][wave] = best;
     __syncthreads();
     best = 0ull;
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(kThreads) void teaser_kcore(const uint32_t* __restr
   __shared__ unsigned char alive_b[kMaxPoints];
   __shared__ uint32_t alive_w[kWords];
   __shared__ int wave_v[kWaves];
-  const int row = blockIdx.x, v = threadIdx.x, lane = v & 63, wave = v >> 6;
+  const int row = blockIdx.x, v = threadIdx.x;
   const int M = min(m_arr[row], min(stride, kMaxPoints));
   uint32_t nb[kWords];
 #pragma unroll
@@ -222,12 +213,7 @@ __global__ __launch_bounds__(kThreads) void teaser_kcore(const uint32_t* __restr
 #pragma unroll
       for (int w = 0; w < kWords; ++w) dg += __popc(nb[w] & alive_w[w]);
     }
-    int mn = dg;
-    for (int off = 32; off > 0; off >>= 1) mn = min(mn, __shfl_xor(mn, off));
-    if (lane == 0) wave_v[wave] = mn;
-    __syncthreads();
-    mn = 0x7FFFFFFF;
-    for (int w = 0; w < kWaves; ++w) mn = min(mn, wave_v[w]);
+    const int mn = block_min_all<kWaves>(dg, wave_v);
     if (mn == 0x7FFFFFFF) break;   // (uniform: nobody alive)
     k = max(k, mn);
     if (alive && dg <= k) { core = k; alive = false; }
@@ -237,41 +223,18 @@ __global__ __launch_bounds__(kThreads) void teaser_kcore(const uint32_t* __restr
     if (core_out) core_out[(size_t)row * kMaxPoints + v] = core;
     if (sel_out) sel_out[(size_t)row * kMaxPoints + v] = sel ? 1 : 0;
   }
-  __syncthreads();
-  const unsigned long long b = __ballot(sel);
-  if (lane == 0) wave_v[wave] = __popcll(b);
-  __syncthreads();
-  int off = 0, total = 0;
-  for (int w = 0; w < kWaves; ++w) {
-    if (w < wave) off += wave_v[w];
-    total += wave_v[w];
-  }
-  if (sel) sel_list[(size_t)row * kMaxPoints + off + __popcll(b & ((1ull << lane) - 1ull))] = v;
+  int total;
+  const int pos = block_compact<kWaves>(sel, wave_v, &total);
+  if (sel) sel_list[(size_t)row * kMaxPoints + pos] = v;
   if (v == 0) msel[row] = total;
 }
 
 // ---- registration --------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double* red) {   // fixed tree inside the wave, the waves in ascending order
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < kWaves; ++w) s += red[w];
-  return s;
-}
-
-__device__ __forceinline__ double block_max(double v, double* red) {
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = red[0];
-  for (int w = 1; w < kWaves; ++w) s = fmax(s, red[w]);
-  return s;
-}
+struct CostAt { unsigned long long bits; int e; };   // a translation candidate: the bits of its cost, its interval
+struct LowerCostOp {                                  // the lower (cost, e): a total order, no two candidates share an e
+  static constexpr bool kFromZero = false;
+  __device__ __forceinline__ CostAt operator()(CostAt a, CostAt b) const { return (b.bits < a.bits || (b.bits == a.bits && b.e < a.e)) ? b : a; }
+};
 
 __global__ __launch_bounds__(kThreads) void teaser_solve(const float* __restrict__ src_s, const float* __restrict__ dst_s, int stride,
                                                          const int32_t* __restrict__ n_arr, const int32_t* __restrict__ m_arr,
@@ -281,10 +244,10 @@ __global__ __launch_bounds__(kThreads) void teaser_solve(const float* __restrict
   __shared__ float ss[kMaxPoints * 3], ds[kMaxPoints * 3];
   __shared__ double x[kMaxPoints], sorted[2 * kMaxPoints];
   __shared__ double red[kWaves], sums[10], tr[3];
-  __shared__ unsigned long long wkey[kWaves];
-  __shared__ int wint[kWaves], e_win;
+  __shared__ CostAt wbest[kWaves];
+  __shared__ int wint[kWaves];
   __shared__ GncState g;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row = blockIdx.x, tid = threadIdx.x;
   const int M = max(0, min(m_arr[row], min(stride, kMaxPoints)));
   const int m = min(msel[row], M);
   const float* S = src_s + (size_t)row * stride * 3;
@@ -311,24 +274,24 @@ __global__ __launch_bounds__(kThreads) void teaser_solve(const float* __restrict
   // ---- rotation ----
   pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R, 0.0, true, g.R, 0.0, true, beta2, &acc);
   for (int k = 0; k < 9; ++k) {
-    const double s = block_sum(acc.h[k], red);
+    const double s = block_sum_all<kWaves>(acc.h[k], red);
     if (tid == 0) sums[k] = s;
   }
   if (tid == 0) gnc_begin(&g, sums);
   __syncthreads();
   pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R, 0.0, true, g.R, 0.0, false, beta2, &acc);
   {
-    const double mx = block_max(acc.max_r2, red);
+    const double mx = block_max_all<kWaves>(acc.max_r2, red);
     if (tid == 0) gnc_set_mu(&g, mx, beta2);
   }
   __syncthreads();
   while (!g.stop) {   // (uniform: g changes only between barriers)
     pair_pass(ss, ds, m, tim_graph, tid, kThreads, g.R_prev, g.mu_prev, g.first_w != 0, g.R, g.mu, false, beta2, &acc);
     for (int k = 0; k < 9; ++k) {
-      const double s = block_sum(acc.h[k], red);
+      const double s = block_sum_all<kWaves>(acc.h[k], red);
       if (tid == 0) sums[k] = s;
     }
-    const double cost = block_sum(acc.cost, red);
+    const double cost = block_sum_all<kWaves>(acc.cost, red);
     __syncthreads();   // (every thread has read g before one lane rewrites it)
     if (tid == 0) gnc_advance(&g, sums, cost);
     __syncthreads();
@@ -353,33 +316,15 @@ __global__ __launch_bounds__(kThreads) void teaser_solve(const float* __restrict
       const unsigned long long ob = cost_bits(tls_candidate(x, m, 0.5 * (sorted[e] + sorted[e + 1]), beta, &est1));
       if (ob < kb) { kb = ob; be = e; }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long ob = __shfl_xor(kb, off);
-      const int oe = __shfl_xor(be, off);
-      if (ob < kb || (ob == kb && oe < be)) { kb = ob; be = oe; }
-    }
-    if (lane == 0) { wkey[wave] = kb; wint[wave] = be; }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned long long b = wkey[0];
-      int e = wint[0];
-      for (int w = 1; w < kWaves; ++w)
-        if (wkey[w] < b || (wkey[w] == b && wint[w] < e)) { b = wkey[w]; e = wint[w]; }
-      e_win = e;
-    }
-    __syncthreads();
+    const int e_win = block_reduce_all<kWaves>(CostAt{kb, be}, wbest, LowerCostOp()).e;
     if (e_win % kThreads == tid) tr[axis] = e_win < kThreads ? est0 : est1;   // e_win <= 2m - 2 < 2 kThreads
     __syncthreads();
   }
   // ---- acceptance ----
   int cnt = 0;
   for (int k = tid; k < M; k += kThreads) cnt += is_inlier(g.R, tr, S + (size_t)k * 3, D + (size_t)k * 3, beta) ? 1 : 0;
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  if (lane == 0) wint[wave] = cnt;
-  __syncthreads();
+  const int n_in = block_sum_all<kWaves>(cnt, wint);
   if (tid == 0) {
-    int n_in = 0;
-    for (int w = 0; w < kWaves; ++w) n_in += wint[w];
     const bool ok = n_in >= min_num_inliers;
     if (TCO_out) {
       if (ok) compose_pose(g.R, tr, TCO + (size_t)row * 16, TCO_out + (size_t)row * 16);

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kCliqueLanes) void clique_search(const uint32_t* __
       coreL[v] = (uint16_t)c;
       kmax = max(kmax, c);
     }
-    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o));
+    kmax = wave_max_all(kmax);
     for (int k = lane; k < kCliqueOrderCache; k += kCliqueLanes) ocache[k] = 0xFFFFFFFFu;   // (no offset has this tag)
     if (lane < kCliqueSetCache) ptag[lane] = -1;
     __syncthreads();
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(kCliqueLanes) void clique_search(const uint32_t* __
         const int v = lane * 32 + __ffs((int)t) - 1;
         key = max(key, greedy_key(coreL[v], v));
       }
-      for (int o = 32; o > 0; o >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, o));
+      key = wave_max_all(key);
       if (key == 0u) break;
       const int v = greedy_key_vertex(key);   // in P: v < M
       if (lane == (v >> 5)) bestw |= 1u << (v & 31);

@@ -190,6 +190,26 @@ def _residual_reject_row(H, W, k, depth, K, T, params):
     raise AssertionError("no candidate is rejected by its residual")
 
 
+def compact_cases() -> list:
+    """the ordered compaction of the mask pixels at its edges, on a frame of 7 x 37 = 259 pixels (no multiple of the wave or of the
+    workgroup), surface over the whole frame: the caller's mask keeps 65 scattered pixels of which the rendered depth covers 61 (scene
+    and model counts differ, neither a multiple of 64; one pyramid level, so that all of them enter the solve), every pixel (two levels),
+    and none.  The first two are accepted: their poses depend on every point and on the order of the compacted lists."""
+    H, W = 7, 37
+    order = _scattered_pixels(H, W, 65)
+    mask = np.zeros(H * W, bool)
+    mask[order] = True
+    rend = bowl(H, W, dx=0.4, dy=-0.3, dz=0.004, radius=None).ravel().copy()
+    rend[order[61:]] = 0
+    some = _single("compact_7x37_keep65", H, W, radius=None, masks=mask.reshape(H, W), rend=rend.reshape(H, W), n_levels=1)
+    some.m, some.n = [65], [61]
+    every = _single("compact_7x37_keep_all", H, W, radius=None, masks=np.ones((H, W), bool), n_levels=2)
+    every.m = every.n = [H * W]
+    none = _single("compact_7x37_keep_none", H, W, radius=None, masks=np.zeros((H, W), bool))
+    none.m = none.n = [0]
+    return [some, every, none]
+
+
 @functools.lru_cache(maxsize=None)
 def batch_case() -> IcpCase:
     """3 frames of 96 x 128, each its own surface and K; 6 rows in the order [2, 0, 2, 1, 0, 2] (frame 2 is used three times); row 1 has
@@ -227,7 +247,7 @@ def capacity_case() -> IcpCase:
 
 @functools.lru_cache(maxsize=None)
 def nn_cases() -> tuple:
-    return tuple(frame_cases() + count_cases() + content_cases() + param_cases() + [batch_case(), capacity_case()])
+    return tuple(frame_cases() + count_cases() + content_cases() + param_cases() + [batch_case(), capacity_case()] + compact_cases())
 
 
 def nn_case(name: str) -> IcpCase:
@@ -236,7 +256,8 @@ def nn_case(name: str) -> IcpCase:
 
 NN_CASE_NAMES = ([f"frame_{H}x{W}" for H, W in ((7, 200), (17, 23), (37, 53), (64, 64), (96, 128))] + [f"count_m{m}_n{n}" for m, n in COUNTS]
                  + ["content_hole26", "content_corner_hole", "content_nonfinite", "content_range_ends", "content_tenth_exact"]
-                 + [f"param_it{ni}_lv{nl}" for ni, nl in PARAMS] + ["param_tol0.01", "param_tol0.2", "param_tol1.5", "batch", "capacity"])
+                 + [f"param_it{ni}_lv{nl}" for ni, nl in PARAMS] + ["param_tol0.01", "param_tol0.2", "param_tol1.5", "batch", "capacity"]
+                 + ["compact_7x37_keep65", "compact_7x37_keep_all", "compact_7x37_keep_none"])
 
 
 # ---- the restatement's answers ------------------------------------------------------------------------------------------------------

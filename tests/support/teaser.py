@@ -353,9 +353,11 @@ FPS_RESIDENT = 16384   # points of a row the sampling kernel keeps in registers 
 # The launches from depth frames both test files run: name -> (frame_case arguments, keywords of the refiner).  Frames of 32 x 24 to
 # 160 x 120, 3 to 5 rows over 2 images, mask counts around the wave (63, 64, 65) and the workgroup (1023, 1025), one more than the
 # register-resident points of the sampling kernel and every pixel of a frame, an empty mask, rows under n_min_points, a row of
-# outliers only ("noise") and one whose threshold mask drops half the pixels ("far"); n_points 64, 65, 100 and 1000.
+# outliers only ("noise") and one whose threshold mask drops half the pixels ("far"); n_points 64, 65, 100 and 1000.  "odd": a frame of
+# 7 x 37 = 259 pixels, no multiple of the wave or the workgroup, whose masks keep 65 pixels, every pixel and none (the compaction's edges).
 FRAME_CASES = {
     "tiny": ((24, 32, (1, 63, 64, 65, 0), ("",) * 5, 3), dict(n_min_points=1, n_points=64, min_num_inliers=20)),
+    "odd": ((7, 37, (65, 7 * 37, 0), ("",) * 3, 11), dict(n_min_points=1, n_points=64, min_num_inliers=20)),
     "small": ((24, 32, (700, 64, 0, 300, 500), ("", "", "", "far", "noise"), 5), dict(n_min_points=100, n_points=100, min_num_inliers=50)),
     "mid": ((48, 64, (1023, 1025, 3000, 2000), ("", "", "noise", "far"), 7), dict(n_min_points=100, n_points=65, min_num_inliers=30)),
     "big": ((120, 160, (FPS_RESIDENT + 1, 120 * 160, 5000), ("", "", ""), 9), dict(n_min_points=100, n_points=1000, min_num_inliers=50)),

@@ -1,6 +1,7 @@
 """-m gpu: the two on-device depth refiners (csrc/icp_nn.hip, csrc/icp.hip) on the analytic cases of tests/support/icp_cases.py -- small
 and odd frames, per-frame intrinsics, rows out of frame order, point counts on their boundaries, holes / non-finite / boundary pixels,
-n_iterations / n_levels / tolerance other than (100, 4, 0.05), an over-capacity mask, an uninitialised workspace -- through the engine
+n_iterations / n_levels / tolerance other than (100, 4, 0.05), an over-capacity mask, masks of 65 of 259 pixels, all and none (the
+ordered compaction's edges), an uninitialised workspace -- through the engine
 entry, against the CPU restatements.  tests/test_icp_cases_cpu.py shows on the restatements alone that every case reaches the edge it
 is named after and that the reference's choice of solver (SVD against the device's Cholesky) moves no pose by more than 1e-7.
 

@@ -190,6 +190,30 @@ def test_draw_boxes_equals_the_emulation(t):
     assert np.array_equal(none.cpu().numpy(), images)
 
 
+def test_draw_boxes_lists_the_kept_boxes_in_order_across_waves_and_chunks():
+    """259 boxes on two images of 20 x 24 (one chunk of 256 and one of 3; tiles of 16 rows): the kept boxes of a tile are listed in
+    ascending order from all four waves.  `some`: 65 scattered boxes belong to image 0 and lie in rows 1 .. 13 (65 kept in its upper tile,
+    none in its lower one), the other 194 to image 1 and far outside it (none kept).  `every`: all 259 belong to image 0 and cross row 16
+    (every box kept in both of its tiles).  Every byte against the emulation."""
+    from megapose6d_amd import engine as eng
+
+    images, _, _ = ov.box_case()
+    n, rng = 259, np.random.RandomState(7)
+    x1, y1 = rng.uniform(-2, 14, n), rng.uniform(1, 8, n)
+    some = np.stack([x1, y1, x1 + rng.uniform(2, 12, n), y1 + rng.uniform(1, 5, n)], 1).astype(np.float32)
+    ids = np.ones(n, np.int32)
+    ids[rng.permutation(n)[:65]] = 0
+    some[ids == 1] += np.float32(200.0)
+    assert some[ids == 0, 3].max() < 14 and (ids == 0).sum() == 65
+    every = np.stack([x1, y1, x1 + rng.uniform(2, 12, n), rng.uniform(16, 19, n)], 1).astype(np.float32)
+    for boxes, box_ids in ((some, ids), (every, np.zeros(n, np.int32))):
+        for t in (1, 2):
+            got = eng.draw_boxes(_dev(images), _dev(boxes), _dev(box_ids), colors=ov.COLORS, thickness=t)
+            want = ov.emul_boxes(images, boxes, box_ids, t=t)
+            assert np.array_equal(got.cpu().numpy(), want) and not np.array_equal(want[0], images[0])
+            assert np.array_equal(want[1], images[1])
+
+
 @pytest.fixture(scope="module")
 def rendered_scene(object_dataset):
     """two overlapping objects of the test meshes at 96 x 128 under the white ambient light of the reference's script"""
