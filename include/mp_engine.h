@@ -705,6 +705,37 @@ int mp_surface_sample(const float* d_vertices /*[V_total,3]*/, const int32_t* d_
                       float* d_points /*[n_obj,count,3]*/, int32_t* d_face /*[n_obj,count]*/, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Object symmetries: does a candidate rotation about the object's centre map its surface    */
+/* into itself within a tolerance?  The `symmetries_discrete` / `symmetries_continuous` of   */
+/* a BOP models_info.json are built from the answers (evaluation.find_symmetries)            */
+/* (csrc/symmetry.hip; contract in csrc/symmetry_core.h).                                    */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_symmetry_check needs (0 for n_obj < 1): the prefix arrays and tolerances of the call. */
+size_t mp_symmetry_check_scratch_bytes(int n_obj);
+/* For candidate k of object o (rows cand_off[o] .. cand_off[o+1] - 1 of d_cand_R, each a row-major 3x3 rotation R) with g(p) = R (p - c)
+   + c, c = d_centers[o]: d_dev2[k] = the maximum over the object's test points p (rows test_off[o] .. test_off[o+1] - 1 of d_tests) of
+   the minimum over its triangles (faces face_off[o] .. face_off[o+1] - 1 of d_faces, indices local to its vertices vert_off[o] ..
+   vert_off[o+1] - 1 of d_vertices) of the squared point-to-triangle distance of g(p) (closest-point case analysis in fp32; a zero-area
+   triangle acts as a segment or a point); d_worst[k] = the test point that reaches it, the lowest on equal distances; d_accept[k] =
+   d_dev2[k] <= tol[o]^2.  mode 0: a screen with early outs sets d_accept (a lane stops at its first triangle within tol, a candidate at
+   its first block of 256 test points with an unsatisfied lane), then only the accepted candidates are measured: a rejected one gets
+   d_dev2 = NaN and d_worst = -1.  mode 1: every candidate is measured, no early out.  The flags of the two modes are equal; the result
+   is the maximum of a total order, so no tile, grid or arrival order changes a bit.  A non-finite coordinate makes the distances it
+   enters NaN, which never win: the candidate gets dev2 = +inf and is rejected.  The prefix arrays (n_obj + 1 entries, starting at 0),
+   h_tol [n_obj] and h_faces (a copy of d_faces) are host memory; rows beyond the last prefix entry are padding and are never read.
+   tile = the triangles of one LDS stage: 0 the library's choice (256), else a multiple of 64 in 64 .. 512.  At most 2^20 candidates in
+   one call; none at all is a successful no-op.  One or two launches on `stream`, no atomics; the prefix arrays are copied from pageable
+   host memory.  Any bad argument (n_obj < 1, an object without vertices, triangles or test points, a face index outside the object's
+   vertices, a tol that is not finite or is negative, too many candidates, a bad tile or mode, a null pointer) returns non-zero before
+   anything is launched. */
+int mp_symmetry_check(const float* d_vertices /*[V_total,3]*/, const int32_t* d_faces /*[F_total,3]*/, const int32_t* h_faces /*host copy*/,
+                      const float* d_tests /*[T_total,3]*/, const float* d_cand_R /*[C_total,9]*/, const float* d_centers /*[n_obj,3]*/,
+                      const int32_t* h_vert_off /*host*/, const int32_t* h_face_off /*host*/, const int32_t* h_test_off /*host*/,
+                      const int32_t* h_cand_off /*host*/, const float* h_tol /*[n_obj], host*/, int n_obj, int tile, int mode,
+                      void* d_scratch, uint8_t* d_accept /*[C_total]*/, float* d_dev2 /*[C_total]*/, int32_t* d_worst /*[C_total]*/,
+                      mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Prediction overlays: the contour overlay of visualization/utils.py:56-85                 */
 /* make_contour_overlay (get_mask_from_rgb, cv2.Canny(mask, 30, 100), cv2.dilate 3x3, masked */
 /* paint), the mesh blend of visualization/bokeh_plotter.py:106-130 plot_overlay and the     */

@@ -184,6 +184,8 @@ SIGNATURES = {
     "mp_det_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mp_model_info_scratch_bytes": (_sz, [_i, _vp, _i]),
     "mp_model_info": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mp_symmetry_check_scratch_bytes": (_sz, [_i]),
+    "mp_symmetry_check": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_overlay": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_draw_boxes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mp_surface_sample_scratch_bytes": (_sz, [_i, _vp, _i, _i]),

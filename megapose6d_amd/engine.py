@@ -1091,6 +1091,60 @@ def model_info(points: torch.Tensor, n_points, tile: int = 0) -> Tuple[torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# object symmetries (evaluation): csrc/symmetry.hip
+SYMMETRY_TILE_STEP = 64              # a forced tile is a multiple of this ...
+SYMMETRY_MAX_TILE = 512              # ... and at most this
+SYMMETRY_MAX_CANDIDATES = 1 << 20    # candidates of one call
+
+
+def symmetry_check(vertices: torch.Tensor, faces, tests: torch.Tensor, cand_R: torch.Tensor, centers: torch.Tensor, vert_off, face_off,
+                   test_off, cand_off, tol, mode: int = 0, tile: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Which candidate rotations map an object's surface into itself (mp_symmetry_check).  vertices [V,3] float32, tests [T,3] float32
+    (the test points), cand_R [C,3,3] float32 (the candidates, row-major rotations about the object's centre) and centers [n_obj,3]
+    float32 on the device; faces [F,3] int32 (indices local to the object; an array or a tensor: the launch checks a host copy of them and
+    reads a device copy); vert_off, face_off, test_off, cand_off [n_obj + 1] host ints, the prefix arrays that cut the four into
+    objects (rows beyond their last entry are padding and are never read); tol [n_obj] host floats, finite and not negative; mode 0 =
+    screen with early outs, then measure the accepted candidates; mode 1 = measure every candidate; tile = the triangles of one LDS
+    stage (0: the library's choice; a multiple of 64 up to 512 forces it, for tests) -> accept [C] uint8, dev2 [C] float32 (the largest
+    squared distance of a transformed test point to the surface; NaN for a candidate that mode 0 rejected), worst [C] int32 (the test
+    point that reaches it, -1 likewise).  No tile, grid or arrival order changes a bit.  Nothing synchronises (tensors of offsets or
+    faces on the device are read back before the launch)."""
+    vertices, tests, cand_R, centers = _dev_f32(vertices), _dev_f32(tests), _dev_f32(cand_R), _dev_f32(centers)
+    dev = vertices.device
+    h_faces = np.ascontiguousarray(faces.cpu().numpy() if isinstance(faces, torch.Tensor) else faces)
+    if h_faces.ndim != 2 or h_faces.shape[1] != 3 or h_faces.dtype.kind not in "iu":
+        raise EngineError(f"faces must be integers [F,3], got {h_faces.dtype} {tuple(h_faces.shape)}")
+    h_faces = h_faces.astype(np.int32)
+    d_faces = faces.to(dev).contiguous() if isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 else torch.from_numpy(h_faces).to(dev)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or tests.dim() != 2 or tests.shape[1] != 3:
+        raise EngineError(f"vertices must be [V,3] and tests [T,3], got {tuple(vertices.shape)} and {tuple(tests.shape)}")
+    if cand_R.dim() != 3 or tuple(cand_R.shape[1:]) != (3, 3) or centers.dim() != 2 or centers.shape[1] != 3:
+        raise EngineError(f"cand_R must be [C,3,3] and centers [n_obj,3], got {tuple(cand_R.shape)} and {tuple(centers.shape)}")
+    n_obj = int(centers.shape[0])
+    offs = [np.ascontiguousarray(o.cpu().numpy() if isinstance(o, torch.Tensor) else o).astype(np.int64) for o in (vert_off, face_off, test_off, cand_off)]
+    rows = (vertices.shape[0], h_faces.shape[0], tests.shape[0], cand_R.shape[0])
+    if n_obj < 1 or any(o.shape != (n_obj + 1,) or o[0] != 0 or (np.diff(o) < 0).any() or o[-1] > r for o, r in zip(offs, rows)):
+        raise EngineError(f"vert_off, face_off, test_off and cand_off must be [n_obj + 1 = {n_obj + 1}], start at 0, not descend and end within "
+                          f"{rows} rows")
+    if offs[3][-1] > SYMMETRY_MAX_CANDIDATES:
+        raise EngineError(f"symmetry_check: {offs[3][-1]} candidates, more than {SYMMETRY_MAX_CANDIDATES} in one call")
+    offs = [o.astype(np.int32) for o in offs]
+    h_tol = np.ascontiguousarray(tol, np.float32).reshape(-1)
+    if h_tol.shape != (n_obj,):
+        raise EngineError(f"tol must be [n_obj = {n_obj}], got {h_tol.shape}")
+    lib = _lib.load()
+    ws = _workspace(lib.mp_symmetry_check_scratch_bytes(n_obj), dev)
+    n_cand = int(cand_R.shape[0])
+    accept = torch.zeros(n_cand, dtype=torch.uint8, device=dev)
+    dev2 = torch.full((n_cand,), float("nan"), dtype=torch.float32, device=dev)
+    worst = torch.full((n_cand,), -1, dtype=torch.int32, device=dev)
+    check(lib.mp_symmetry_check(vertices.data_ptr(), d_faces.data_ptr(), h_faces.ctypes.data, tests.data_ptr(), cand_R.data_ptr(), centers.data_ptr(),
+                                offs[0].ctypes.data, offs[1].ctypes.data, offs[2].ctypes.data, offs[3].ctypes.data, h_tol.ctypes.data, n_obj,
+                                int(tile), int(mode), ws.data_ptr(), accept.data_ptr(), dev2.data_ptr(), worst.data_ptr(), _stream()))
+    return accept, dev2, worst
+
+
+# --------------------------------------------------------------------------- #
 # prediction overlays (visualisation): csrc/overlay.hip
 OVERLAY_OUTPUTS = ("contour", "mesh", "canny", "mask")
 OVERLAY_MAX_DILATE = 8               # dilate_iterations

@@ -14,6 +14,8 @@ modal boxes and visible masks (csrc/det_ap.hip: the pixel counts of mask pairs, 
 -- and BOP's model info (csrc/model_info.hip: the exact diameter, the largest distance between two model points, and the bounds;
 bop_toolkit's calc_model_info): `model_info`, `bop_models_info`, `save_models_info`, `load_models_info`, and the `diameters=` keyword
 that scales every threshold by it instead of the default box diagonal.
+-- and the symmetries all of the above minimise over, found from the mesh alone (csrc/symmetry.hip decides which candidate rotations map
+the surface into itself): `find_symmetries`, `symmetry_poses`, and the `symmetries=` keyword of `bop_models_info` / `save_models_info`.
 Dataset readers, BOP result-file formats, the xarray meters and plots are NOT here.
 
 Where this departs from the reference, on purpose:
@@ -31,6 +33,8 @@ Where this departs from the reference, on purpose:
     caller's (stock `pycocotools` overwrites it with `iscrowd`), and a NaN IoU never matches.
   * the default diameter is the diagonal of the bounding box (the reference's ModelNet meter), which is never smaller than BOP's;
     `diameters="exact"` or a models_info.json gives BOP's.  `model_info` is unpinned against `bop_toolkit` (absent).
+  * `find_symmetries` has no counterpart in the reference (BOP's symmetries are annotated by hand): rotations only, candidates from
+    vertex anchors, so a scanned mesh with only approximate symmetry can be missed; unpinned against BOP's own annotations.
 """
 from __future__ import annotations
 
@@ -935,25 +939,40 @@ def _bop_obj_key(label):
     return int(m.group(1)) if m else label
 
 
-def bop_models_info(info: pd.DataFrame, scale: float = 1000.0) -> Dict[object, Dict[str, float]]:
+def bop_models_info(info: pd.DataFrame, scale: float = 1000.0, symmetries: Optional[pd.DataFrame] = None) -> Dict[object, Dict[str, object]]:
     """The table of `model_info` -> the dict bop_toolkit saves as models_info.json: {obj_id: {diameter, min_x, min_y, min_z, size_x,
     size_y, size_z}}, every length times `scale` (BOP's files are in millimetres), keyed by the integer id where the label has one
-    ("obj_000005" -> 5), else by the label.  No symmetry fields: generating them is not built."""
+    ("obj_000005" -> 5), else by the label.  With `symmetries` = the table of `find_symmetries`, an object it lists also gets BOP's
+    `symmetries_discrete` (each a row-major 4x4 matrix as 16 numbers, the translation times `scale`) and `symmetries_continuous`
+    ({"axis", "offset"}, the offset times `scale`), each only where the object has one, as in BOP's files."""
     out = {}
     for label, row in info.iterrows():
         key = _bop_obj_key(label)
         if key in out:
             raise ValueError(f"two labels give the object key {key!r}")
         out[key] = {name: float(row[name]) * float(scale) for name in MODEL_INFO_COLUMNS[:7]}
+        if symmetries is not None and label in symmetries.index:
+            sym = symmetries.loc[label]
+            discrete = []
+            for T in sym["symmetries_discrete"]:
+                T = np.array(T, np.float64).reshape(4, 4)
+                T[:3, 3] *= float(scale)
+                discrete.append([float(v) for v in T.flatten()])
+            continuous = [{"axis": [float(v) for v in s["axis"]], "offset": [float(v) * float(scale) for v in s["offset"]]}
+                          for s in sym["symmetries_continuous"]]
+            if discrete:
+                out[key]["symmetries_discrete"] = discrete
+            if continuous:
+                out[key]["symmetries_continuous"] = continuous
     return out
 
 
-def save_models_info(path, info, scale: float = 1000.0) -> None:
-    """Write models_info.json: `info` the table of `model_info` (scaled by `scale` through `bop_models_info`) or a dict that is
-    already BOP's (written as it is)."""
+def save_models_info(path, info, scale: float = 1000.0, symmetries: Optional[pd.DataFrame] = None) -> None:
+    """Write models_info.json: `info` the table of `model_info` (scaled by `scale` through `bop_models_info`, with the symmetry fields
+    of `symmetries`, the table of `find_symmetries`, if given) or a dict that is already BOP's (written as it is)."""
     import json
 
-    data = bop_models_info(info, scale) if isinstance(info, pd.DataFrame) else info
+    data = bop_models_info(info, scale, symmetries) if isinstance(info, pd.DataFrame) else info
     with open(path, "w") as f:
         json.dump({str(k): v for k, v in data.items()}, f, indent=2, sort_keys=True)
 
@@ -973,3 +992,266 @@ def load_models_info(path, scale: float = 0.001, label_format: str = "obj_{:06d}
         diameters[label] = float(fields["diameter"]) * float(scale)
         infos[label] = fields
     return (diameters, infos) if return_info else diameters
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# Object symmetries from the mesh alone: the two symmetry fields of models_info.json (csrc/symmetry.hip decides the candidates)
+# --------------------------------------------------------------------------------------------------------------------------------
+SYMMETRY_MAX_CANDIDATES = 4096        # candidates of one object by default: 64 anchors' worth of 64; a finely tessellated sphere has more
+SYMMETRY_DUPLICATE_ANGLE = 1e-3       # radians: two rotations (and two axes) closer than this are one; a point at the object's radius
+#                                       moves by a tenth of the default tolerance (0.01 x diameter) under such a rotation
+SYMMETRY_COLUMNS = ("status", "n_candidates", "n_symmetries", "center", "rotations", "deviation", "symmetries_discrete", "symmetries_continuous")
+
+
+def _unit(v: np.ndarray) -> np.ndarray:
+    return v / np.linalg.norm(v)
+
+
+def _anchor_frame(c: np.ndarray, p1: np.ndarray, p2: np.ndarray) -> np.ndarray:
+    """the right-handed orthonormal frame of two anchors about c, as columns: e1 along p1 - c, e2 the part of p2 - c normal to it"""
+    e1 = _unit(p1 - c)
+    q = p2 - c
+    e2 = _unit(q - (q @ e1) * e1)
+    return np.stack([e1, e2, np.cross(e1, e2)], axis=1)
+
+
+def surface_centroid(vertices: np.ndarray, faces: np.ndarray) -> np.ndarray:
+    """The area-weighted centroid of a triangle surface, in float64: every symmetry of the surface fixes it."""
+    v = np.asarray(vertices, np.float64)
+    f = np.asarray(faces, np.int64)
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+    total = area.sum()
+    if not total > 0.0:
+        return v.mean(0)
+    return ((a + b + c) / 3.0 * area[:, None]).sum(0) / total
+
+
+def symmetry_candidates(vertices: np.ndarray, faces: np.ndarray, tol: float, max_candidates: int = SYMMETRY_MAX_CANDIDATES):
+    """The candidate rotations of one object, on the host in float64, O(V) per anchor -> (status, center [3], rotations [n,3,3],
+    n_candidates).  The centre c is the surface centroid.  The anchor a1 is the vertex farthest from c, a2 the vertex farthest from
+    the line (c, a1) (ties: the lowest index); both are maxima of convex functions over the surface, so they are attained at vertices
+    and a symmetry maps them to vertices with the same invariants.  For every vertex b1 with | |b1 - c| - |a1 - c| | <= tol, every
+    vertex b2 that matches a2's distance to the line, |a2 - c| and |a2 - a1| (each within tol) gives the candidate
+    frame(c, b1, b2) frame(c, a1, a2)^T, a proper rotation; candidates are ordered by (b1, b2).  status "degenerate": no vertex is
+    farther than tol from the line (no second anchor); "too_many_candidates": more than max_candidates (the count is returned, no
+    rotation is); else "ok"."""
+    v = np.asarray(vertices, np.float64)
+    c = surface_centroid(v, faces)
+    none = np.zeros((0, 3, 3))
+    q = v - c
+    r = np.linalg.norm(q, axis=1)
+    i1 = int(np.argmax(r))
+    if not r[i1] > tol:
+        return "degenerate", c, none, 0
+
+    def line_distance(u):
+        return np.linalg.norm(q - (q @ u)[:, None] * u, axis=1)
+
+    l1 = line_distance(q[i1] / r[i1])
+    i2 = int(np.argmax(l1))
+    if not l1[i2] > tol:
+        return "degenerate", c, none, 0
+    d12 = np.linalg.norm(v[i2] - v[i1])
+    pairs = []
+    for b1 in np.flatnonzero(np.abs(r - r[i1]) <= tol):
+        lb = line_distance(q[b1] / r[b1])
+        ok = (np.abs(lb - l1[i2]) <= tol) & (np.abs(r - r[i2]) <= tol) & (np.abs(np.linalg.norm(v - v[b1], axis=1) - d12) <= tol)
+        pairs += [(int(b1), int(b2)) for b2 in np.flatnonzero(ok)]
+        if len(pairs) > max_candidates:    # the count so far already refuses the object
+            return "too_many_candidates", c, none, len(pairs)
+    Fa = _anchor_frame(c, v[i1], v[i2])
+    rotations = np.stack([_anchor_frame(c, v[b1], v[b2]) @ Fa.T for b1, b2 in pairs]) if pairs else none
+    return "ok", c, rotations, len(pairs)
+
+
+def _relative_angles(R: np.ndarray, Rs: np.ndarray) -> np.ndarray:
+    """the rotation angles of R Rs[k]^T"""
+    tr = np.einsum("ij,kij->k", R, Rs)
+    return np.arccos(np.clip((tr - 1.0) / 2.0, -1.0, 1.0))
+
+
+def _axis_angle(R: np.ndarray) -> Tuple[np.ndarray, float]:
+    """axis (unit, its largest component positive) and angle in (0, pi] of a rotation that is not the identity"""
+    angle = float(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    if np.linalg.norm(w) > 1e-6:
+        axis = _unit(w)
+    else:                                  # a half turn: R + I = 2 a a^T
+        S = (R + np.eye(3)) / 2.0
+        axis = _unit(S[:, int(np.argmax(np.diag(S)))])
+    k = int(np.argmax(np.abs(axis)))
+    return (axis if axis[k] > 0 else -axis), angle
+
+
+def symmetry_group(center: np.ndarray, rotations: np.ndarray, continuous_min_order: int = 16):
+    """The accepted rotations of one object (in candidate order) -> (status, unique rotations [n,3,3] with the identity first,
+    symmetries_discrete [list of 4x4], symmetries_continuous [list of {"axis", "offset"}]), float64.  Rotations within
+    SYMMETRY_DUPLICATE_ANGLE of an earlier one are dropped.  The others are clustered by axis; an axis whose cyclic order (its elements
+    and the identity) is at least continuous_min_order is BOP's continuous symmetry {"axis": its largest component positive, "offset":
+    center}; the discrete symmetries are then one representative, the first in candidate order, of every coset of that axis' rotations
+    but their own, else every element but the identity, each as T = [R | c - R c].  More than one such axis (a sphere): everything stays
+    discrete, status "many_continuous_axes"."""
+    c = np.asarray(center, np.float64)
+    unique = [np.eye(3)]
+    for R in np.asarray(rotations, np.float64).reshape(-1, 3, 3):
+        if _relative_angles(R, np.stack(unique)).min() >= SYMMETRY_DUPLICATE_ANGLE:
+            unique.append(R)
+    axes, members = [], []                 # the clusters: axis, and the indices into unique
+    for k in range(1, len(unique)):
+        axis, _ = _axis_angle(unique[k])
+        for n, a in enumerate(axes):
+            if np.arccos(min(1.0, abs(float(a @ axis)))) < SYMMETRY_DUPLICATE_ANGLE:
+                members[n].append(k)
+                break
+        else:
+            axes.append(axis)
+            members.append([k])
+    continuous_axes = [n for n in range(len(axes)) if len(members[n]) + 1 >= continuous_min_order]
+
+    def pose(R):
+        T = np.eye(4)
+        T[:3, :3] = R
+        T[:3, 3] = c - R @ c
+        return T
+
+    status, continuous = "ok", []
+    discrete_ids = list(range(1, len(unique)))
+    if len(continuous_axes) > 1:
+        status = "many_continuous_axes"
+    elif len(continuous_axes) == 1:
+        a = axes[continuous_axes[0]]
+        continuous = [{"axis": a.copy(), "offset": c.copy()}]
+        reps = [0]                         # the identity stands for the axis' own rotations
+        for k in range(1, len(unique)):
+            # unique[k] and unique[j] are in one coset when unique[j]^T unique[k] turns about a: it fixes a
+            if not any(np.linalg.norm(unique[j].T @ unique[k] @ a - a) < 2.0 * SYMMETRY_DUPLICATE_ANGLE for j in reps):
+                reps.append(k)
+        discrete_ids = reps[1:]
+    return status, np.stack(unique), [pose(unique[k]) for k in discrete_ids], continuous
+
+
+def symmetry_table(labels, problems, accept, dev2, continuous_min_order: int = 16) -> pd.DataFrame:
+    """The host side of `find_symmetries`: problems = per object (status, center, rotations, n_candidates) of `symmetry_candidates`,
+    accept and dev2 [C_total] what `engine.symmetry_check` gave for the candidates of all objects, one after the other -> the
+    DataFrame of `find_symmetries`."""
+    accept, dev2 = np.asarray(accept).astype(bool), np.asarray(dev2, np.float64)
+    rows, at = [], 0
+    for status, center, rotations, n_cand in problems:
+        n = len(rotations)
+        acc, d2 = accept[at:at + n], dev2[at:at + n]
+        at += n
+        group_status, unique, discrete, continuous = symmetry_group(center, rotations[acc], continuous_min_order)
+        deviation = float(np.sqrt(d2[acc].max())) if acc.any() else 0.0
+        rows.append(dict(status=status if status != "ok" else group_status, n_candidates=int(n_cand), n_symmetries=len(unique), center=center,
+                         rotations=unique, deviation=deviation, symmetries_discrete=discrete, symmetries_continuous=continuous))
+    return pd.DataFrame(rows, columns=list(SYMMETRY_COLUMNS), index=pd.Index(list(labels), name="label"))
+
+
+def find_symmetries(mesh_db, rel_tol: float = 0.01, n_samples: int = 512, seed: int = 0, continuous_min_order: int = 16,
+                    max_candidates: int = SYMMETRY_MAX_CANDIDATES, diameters=None, device="cuda", measure_all: bool = False, tile: int = 0,
+                    backend=None) -> pd.DataFrame:
+    """The rotational symmetries of every object of `mesh_db` (a MeshDataBase of objects with faces), found from the mesh alone: what
+    a BOP dataset declares by hand in models_info.json.  A rotation R about the centre c is a symmetry when g(p) = R (p - c) + c takes
+    every test point (the vertices, then n_samples points drawn over the surface by `engine.surface_sample` on the uniforms of a CPU
+    generator seeded with `seed`, as `MeshDataBase.batched_surface` draws them) to within tol = rel_tol x diameter of the surface.  The
+    candidates come from `symmetry_candidates` on the host; one `engine.symmetry_check` call on `device` decides those of all objects;
+    `symmetry_group` turns the accepted ones into BOP's fields.  diameters: None = the exact diameter of `model_info` (one more launch
+    on `device`), or a mapping label -> metres.  measure_all: measure every candidate (the check's mode 1) instead of screening first;
+    tile as `engine.symmetry_check` takes it.  backend: what supplies surface_sample and symmetry_check (default: the engine).
+    -> a DataFrame indexed by label:
+      status                 "ok"; "degenerate" (no vertex farther than tol from the line through the centre and the farthest vertex);
+                             "too_many_candidates" (more than max_candidates; a finely tessellated sphere); "many_continuous_axes"
+                             (more than one axis of order >= continuous_min_order: everything is kept discrete).  A refused object is
+                             reported as asymmetric.
+      n_candidates           rotations tested
+      n_symmetries           the order of the group found, the identity included
+      center                 [3] float64, metres
+      rotations              [n_symmetries,3,3] float64, the identity first, then in candidate order
+      deviation              the largest distance, in metres, by which an accepted rotation takes a test point off the surface
+      symmetries_discrete    list of [4,4] float64 in metres, T = [R | c - R c]; never the identity
+      symmetries_continuous  list of {"axis": [3], "offset": [3]}: an axis whose cyclic order is at least continuous_min_order (a
+                             parameter of the contract, not a measurement)
+    LIMITS.  Reflections are not symmetries here (BOP's are rigid).  Candidates come from vertex anchors: a scanned mesh whose symmetry
+    is only approximate, with no vertex near the image of the anchors, can be missed; CAD meshes are covered.  Unpinned against
+    bop_toolkit's annotations (absent).  One synchronising copy."""
+    backend = eng if backend is None else backend
+    labels = list(mesh_db.labels)
+    verts = [np.asarray(mesh_db.engine_meshes[l]["points"], np.float32) for l in labels]
+    faces = [np.asarray(mesh_db.engine_meshes[l]["faces"], np.int32).reshape(-1, 3) for l in labels]
+    for l, f in zip(labels, faces):
+        if len(f) == 0:
+            raise ValueError(f"object {l!r} has no faces: a symmetry is one of a surface")
+    n_samples = int(n_samples)
+    if n_samples < 0 or not (np.isfinite(rel_tol) and rel_tol > 0.0):
+        raise ValueError(f"n_samples must not be negative and rel_tol must be positive and finite, got {n_samples} and {rel_tol}")
+    if int(max_candidates) < 1 or int(continuous_min_order) < 2:
+        raise ValueError(f"max_candidates must be at least 1 and continuous_min_order at least 2, got {max_candidates} and {continuous_min_order}")
+    if diameters is None:
+        diameters = model_info(mesh_db.batched().to(device))["diameter"].to_dict()
+    tol = []
+    for l in labels:
+        d = float(diameters[l])
+        if not (np.isfinite(d) and d > 0.0):
+            raise ValueError(f"the diameter of {l!r} is {d}: it must be positive and finite")
+        tol.append(float(rel_tol) * d)
+    problems = [symmetry_candidates(v, f, t, int(max_candidates)) for v, f, t in zip(verts, faces, tol)]
+    vert_off = np.concatenate([[0], np.cumsum([len(v) for v in verts])])
+    face_off = np.concatenate([[0], np.cumsum([len(f) for f in faces])])
+    test_off = np.concatenate([[0], np.cumsum([len(v) + n_samples for v in verts])])
+    cand_off = np.concatenate([[0], np.cumsum([len(p[2]) for p in problems])])
+    d_verts = torch.from_numpy(np.concatenate(verts)).to(device)
+    h_faces = np.concatenate(faces)
+    d_faces = torch.from_numpy(h_faces).to(device)
+    failed = None
+    if n_samples > 0:
+        u = torch.rand(len(labels), n_samples, 3, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float32)
+        sampled, face = backend.surface_sample(d_verts, d_faces, vert_off, face_off, u.to(device))
+        failed = face[:, 0] < 0
+        tests = torch.cat([t for n in range(len(labels)) for t in (d_verts[vert_off[n]:vert_off[n + 1]], sampled[n])])
+    else:
+        tests = d_verts
+    cand_R = torch.from_numpy(np.concatenate([p[2] for p in problems]).astype(np.float32).reshape(-1, 3, 3)).to(device)
+    centers = torch.from_numpy(np.stack([p[1] for p in problems]).astype(np.float32)).to(device)
+    accept, dev2, _ = backend.symmetry_check(d_verts, h_faces, tests, cand_R, centers, vert_off, face_off, test_off, cand_off,
+                                             np.asarray(tol, np.float32), mode=1 if measure_all else 0, tile=tile)
+    flags = failed.float() if failed is not None else torch.zeros(len(labels), device=accept.device)
+    table = torch.cat([accept.float(), dev2, flags.to(accept.device)]).cpu().numpy()   # the one synchronising copy
+    n_cand = int(cand_off[-1])
+    for l, bad, problem in zip(labels, table[2 * n_cand:], problems):
+        if bad and problem[0] == "ok":       # an object already refused (a needle has no area) needs no test points
+            raise ValueError(f"object {l!r} cannot be sampled: a non-finite vertex, a face index outside its vertices, or no area")
+    return symmetry_table(labels, problems, table[:n_cand] > 0, table[n_cand:2 * n_cand], continuous_min_order)
+
+
+def symmetry_poses(fields, n_symmetries_continuous: int = 64, scale: float = 1.0) -> np.ndarray:
+    """The symmetry set of one object -> [n,4,4] float64.  fields: a row of `find_symmetries`' table or an object's dict of a
+    models_info.json (`load_models_info(return_info=True)`): "symmetries_discrete" (4x4 matrices, or their 16 numbers) and
+    "symmetries_continuous" ({"axis", "offset"}), either may be missing; translations and offsets are multiplied by `scale` (0.001
+    for a BOP file in millimetres).  A continuous symmetry about ANY axis and offset is discretised into n_symmetries_continuous
+    rotations by Rodrigues' formula, R = I + sin(t) K + (1 - cos(t)) K^2 about the unit axis, t = o - R o.  The order is
+    `symmetries.make_symmetries_poses`': the identity first among the discrete symmetries, and with continuous ones the product
+    continuous x discrete, the continuous index running inside."""
+    def get(name):
+        v = fields[name] if name in fields else None
+        return [] if v is None else list(v)
+
+    discrete = [np.eye(4)]
+    for T in get("symmetries_discrete"):
+        T = np.array(T, np.float64).reshape(4, 4)
+        T[:3, 3] *= float(scale)
+        discrete.append(T)
+    continuous = []
+    for s in get("symmetries_continuous"):
+        axis = _unit(np.asarray(s["axis"], np.float64))
+        offset = np.asarray(s["offset"], np.float64) * float(scale)
+        K = np.array([[0.0, -axis[2], axis[1]], [axis[2], 0.0, -axis[0]], [-axis[1], axis[0], 0.0]])
+        for n in range(int(n_symmetries_continuous)):
+            t = 2.0 * np.pi * n / int(n_symmetries_continuous)
+            M = np.eye(4)
+            M[:3, :3] = np.eye(3) + np.sin(t) * K + (1.0 - np.cos(t)) * (K @ K)
+            M[:3, 3] = offset - M[:3, :3] @ offset
+            continuous.append(M)
+    if not continuous:
+        return np.stack(discrete)
+    return np.stack([c @ d for d in discrete for c in continuous])

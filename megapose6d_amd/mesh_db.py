@@ -87,6 +87,29 @@ class BatchedMeshes(TensorCollection):
         return self
 
 
+def with_symmetries(meshes: BatchedMeshes, poses: Dict[str, object]) -> BatchedMeshes:
+    """`meshes` with the symmetry sets of the objects named in `poses` replaced: {label: [n,4,4] poses, the identity first} (e.g.
+    evaluation.symmetry_poses of a row of evaluation.find_symmetries).  The other objects keep theirs; the table is identity-padded
+    to the longest set and n_sym is rewritten, as MeshDataBase builds them.  The points are shared, not copied; `meshes` is left
+    alone.  An unknown label raises KeyError."""
+    labels = list(meshes.labels)
+    sets = {l: meshes.symmetries[n, : meshes.infos[l]["n_sym"]].detach().cpu().double() for n, l in enumerate(labels)}
+    for l, p in poses.items():
+        if l not in sets:
+            raise KeyError(l)
+        p = torch.as_tensor(np.asarray(p, np.float64)).reshape(-1, 4, 4)
+        if p.shape[0] < 1:
+            raise ValueError(f"object {l!r}: a symmetry set holds at least the identity")
+        sets[l] = p
+    s_max = max(s.shape[0] for s in sets.values())
+    sym = torch.eye(4).repeat(len(labels), s_max, 1, 1)
+    infos = {l: dict(meshes.infos[l]) for l in labels}
+    for n, l in enumerate(labels):
+        sym[n, : sets[l].shape[0]] = sets[l].float()
+        infos[l]["n_sym"] = int(sets[l].shape[0])
+    return BatchedMeshes(infos, labels, meshes.points, sym.to(meshes.points.device))
+
+
 class MeshDataBase:
     def __init__(self, obj_list):
         self.obj_list = list(obj_list)
