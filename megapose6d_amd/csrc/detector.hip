@@ -454,153 +454,229 @@ __global__ __launch_bounds__(256) void det_mask_paste_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// host side: weights
+// host side: the network, stated once
 // ---------------------------------------------------------------------------------------------------------------------------------
-struct Bottleneck {
-  ConvLayer c1, c2, c3, down;
-  bool has_down = false;
-};
-
-struct SpecEntry {
-  std::string name;
-  int64_t shape[4];
-  int n_dims;
-};
-
-static std::vector<SpecEntry> det_spec(int C) {
-  std::vector<SpecEntry> v;
-  auto add = [&](const std::string& n, std::initializer_list<int64_t> s) {
-    SpecEntry e;
-    e.name = n;
-    e.n_dims = (int)s.size();
-    int k = 0;
-    for (int64_t d : s) e.shape[k++] = d;
-    for (; k < 4; ++k) e.shape[k] = 1;
-    v.push_back(e);
-  };
-  auto bn = [&](const std::string& p, int64_t c) {
-    for (const char* s : {"weight", "bias", "running_mean", "running_var"}) add(p + "." + s, {c});
-  };
-  const std::string B = "backbone.body.";
-  add(B + "conv1.weight", {64, 3, 7, 7});
-  bn(B + "bn1", 64);
-  static const int nb[4] = {3, 4, 6, 3}, pl[4] = {64, 128, 256, 512};
-  int64_t inplanes = 64;
-  for (int li = 0; li < 4; ++li)
-    for (int bi = 0; bi < nb[li]; ++bi) {
-      const std::string P = B + "layer" + std::to_string(li + 1) + "." + std::to_string(bi) + ".";
-      const int64_t p = pl[li];
-      add(P + "conv1.weight", {p, inplanes, 1, 1});
-      bn(P + "bn1", p);
-      add(P + "conv2.weight", {p, p, 3, 3});
-      bn(P + "bn2", p);
-      add(P + "conv3.weight", {4 * p, p, 1, 1});
-      bn(P + "bn3", 4 * p);
-      if (bi == 0) {
-        add(P + "downsample.0.weight", {4 * p, inplanes, 1, 1});
-        bn(P + "downsample.1", 4 * p);
-      }
-      inplanes = 4 * p;
-    }
-  static const int64_t fc[4] = {256, 512, 1024, 2048};
-  for (int i = 0; i < 4; ++i) {
-    const std::string s = std::to_string(i);
-    add("backbone.fpn.inner_blocks." + s + ".weight", {256, fc[i], 1, 1});
-    add("backbone.fpn.inner_blocks." + s + ".bias", {256});
-    add("backbone.fpn.layer_blocks." + s + ".weight", {256, 256, 3, 3});
-    add("backbone.fpn.layer_blocks." + s + ".bias", {256});
-  }
-  add("rpn.head.conv.weight", {256, 256, 3, 3});
-  add("rpn.head.conv.bias", {256});
-  add("rpn.head.cls_logits.weight", {DET_A, 256, 1, 1});
-  add("rpn.head.cls_logits.bias", {DET_A});
-  add("rpn.head.bbox_pred.weight", {4 * DET_A, 256, 1, 1});
-  add("rpn.head.bbox_pred.bias", {4 * DET_A});
-  add("roi_heads.box_head.fc6.weight", {1024, 256 * 7 * 7});
-  add("roi_heads.box_head.fc6.bias", {1024});
-  add("roi_heads.box_head.fc7.weight", {1024, 1024});
-  add("roi_heads.box_head.fc7.bias", {1024});
-  add("roi_heads.box_predictor.cls_score.weight", {C, 1024});
-  add("roi_heads.box_predictor.cls_score.bias", {C});
-  add("roi_heads.box_predictor.bbox_pred.weight", {4 * (int64_t)C, 1024});
-  add("roi_heads.box_predictor.bbox_pred.bias", {4 * (int64_t)C});
-  for (int i = 1; i <= 4; ++i) {
-    add("roi_heads.mask_head.mask_fcn" + std::to_string(i) + ".weight", {256, 256, 3, 3});
-    add("roi_heads.mask_head.mask_fcn" + std::to_string(i) + ".bias", {256});
-  }
-  add("roi_heads.mask_predictor.conv5_mask.weight", {256, 256, 2, 2});
-  add("roi_heads.mask_predictor.conv5_mask.bias", {256});
-  add("roi_heads.mask_predictor.mask_fcn_logits.weight", {C, 256, 1, 1});
-  add("roi_heads.mask_predictor.mask_fcn_logits.bias", {C});
-  return v;
-}
-
 }  // namespace mp
 
 using namespace mp;
 
-// workspace plan: every buffer of a forward at (n, H, W), bump-allocated in floats (64-float aligned, + slack the conv's last K chunk
-// may read past a tensor's end)
-struct DetPlan {
-  int n, H, W, hr, wr, Hp, Wp;          // input, resized, padded (multiple of 32)
-  float ratio_h, ratio_w, sy, sx;
-  int fh[DET_LEVELS], fw[DET_LEVELS];   // P2..P6
-  int a_total;                          // anchors per image
-  int n_seg_rpn;
-  size_t total = 0;
-  std::map<std::string, size_t> off;    // float offsets
-  std::string stage_buf[4];             // which of s{st}.xa / s{st}.xb holds the stage's output C2..C5 (set by the forward: what the FPN read)
-  size_t take(const std::string& name, size_t floats) {
-    const size_t o = total;
-    off[name] = o;
-    total += (floats + 63) / 64 * 64;
-    return o;
-  }
-};
-
-struct mp_detector {
-  mp_detector_config cfg;
-  int C, Cpred_s, Cmask_s;   // classes; padded row strides of the predictor / mask-logit outputs
-  ConvLayer stem;
-  std::vector<Bottleneck> blocks;
-  std::vector<int> stage_of_block;
-  ConvLayer fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred, mask_fcn[4], mask_deconv, mask_logits;
-  float base_anchors[DET_LEVELS][DET_A][4];
-  std::vector<void*> allocs;
-  // last forward (debug taps)
-  bool ran = false;
-  DetPlan last;
-  void* last_ws = nullptr;
-};
-
 namespace {
 
+constexpr int RES_BLOCKS[4] = {3, 4, 6, 3};          // ResNet-50: bottlenecks per stage ...
+constexpr int RES_PLANES[4] = {64, 128, 256, 512};   // ... and their inner width; a stage writes 4 x planes channels (C2..C5, the FPN's inputs)
+constexpr int RES_MAX_BLOCKS = 6;
 constexpr size_t DET_SPLITK_FLOATS = 16u << 20;
-
-inline size_t tensor_floats(int N, int H, int W, int C, int b) { return (size_t)N * (H + 2 * b) * (W + 2 * b) * C + (size_t)(W + 2 * b) * C + 64; }
-
 const char* const WHO = "mp_detector_create";
 
-// OIHW weights (+ optional FrozenBatchNorm `bn`, + optional bias) -> the layer in its fp32 form; cout_pad > Cout appends zero output channels
-int det_make_conv(mp_detector* d, const StateMap& sm, const float* w_oihw, int Cout, int Cin, int K, int stride, int pad, const std::string& bn,
-                  const float* bias, int cout_pad, ConvLayer* L) {
-  return make_conv_layer(d->allocs, sm, WHO, w_oihw, bn, bias, cout_pad, Cin, (Cin + 3) / 4 * 4, Cout, K, stride, pad, 0u, L);
-}
+inline int pad4(int c) { return (c + 3) / 4 * 4; }   // row strides of the predictor (5 C) / mask-logit (C) outputs, input channels of a layer
 
-int det_conv_from_key(mp_detector* d, const StateMap& sm, const std::string& wkey, int Cout, int Cin, int K, int stride, int pad,
-                      const std::string& bn, const std::string& bias_key, ConvLayer* L) {
-  const float* w = find(sm, wkey, (int64_t)Cout * Cin * K * K, WHO);
-  if (!w) return MP_ERR_INVALID;
-  const float* b = nullptr;
-  if (!bias_key.empty()) {
-    b = find(sm, bias_key, Cout, WHO);
-    if (!b) return MP_ERR_INVALID;
+struct Bottleneck {
+  ConvLayer c1, c2, c3, down;   // `down` only in a stage's first block
+};
+
+struct DetLayers {
+  ConvLayer stem;
+  Bottleneck block[4][RES_MAX_BLOCKS];
+  ConvLayer fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred, mask_fcn[4], mask_deconv, mask_logits;
+};
+
+struct Dims {
+  int n;
+  int64_t d[4];
+  int64_t numel() const {
+    int64_t m = 1;
+    for (int k = 0; k < n; ++k) m *= d[k];
+    return m;
   }
-  return det_make_conv(d, sm, w, Cout, Cin, K, stride, pad, bn, b, 0, L);
+};
+
+// The checkpoint's tensors (torchvision's state_dict keys) and the layers built from them, in checkpoint order.  A Sink has
+//   bool tensor(name, dims, &p)   one checkpoint tensor; p = its host data where the sink `builds`
+//   bool layer(L, w, bn, bias, cout_pad, Cout, Cin, K, stride, pad)   OIHW weights (+ bn prefix or "", + bias or null) -> *L
+// and `rc`, what a false return of those leaves behind: the walk stops there and returns it.
+template <class Sink>
+int det_walk(int C, DetLayers& net, Sink& k) {
+#define DET_STEP(e) do { if (!(e)) return k.rc; } while (0)
+  // a layer that takes its weight as the checkpoint holds it, [Cout, Cin, K, K] (`linear`: [Cout, Cin]), under FrozenBatchNorm `bn` or,
+  // with bn = "", with a bias of its own
+  auto plain = [&](ConvLayer* L, const std::string& name, const std::string& bn, int Cout, int Cin, int K, int stride, int pad, bool linear = false,
+                   int cout_pad = 0) {
+    const float *w = nullptr, *b = nullptr, *folded = nullptr;   // (make_conv_layer reads the four vectors of `bn` itself and folds them)
+    if (!k.tensor(name + ".weight", linear ? Dims{2, {Cout, Cin}} : Dims{4, {Cout, Cin, K, K}}, &w)) return false;
+    if (bn.empty() && !k.tensor(name + ".bias", Dims{1, {Cout}}, &b)) return false;
+    for (const char* s : {"weight", "bias", "running_mean", "running_var"})
+      if (!bn.empty() && !k.tensor(bn + "." + s, Dims{1, {Cout}}, &folded)) return false;
+    return k.layer(L, w, bn, b, cout_pad, Cout, Cin, K, stride, pad);
+  };
+  // two heads over one input as ONE 1x1 layer: the rows of `a`, then those of `b`, then zero rows up to cout_p
+  auto stacked = [&](ConvLayer* L, const std::string& a, const std::string& b, int Ca, int Cb, int Cin, int cout_p, bool linear) {
+    const float *wa = nullptr, *ba = nullptr, *wb = nullptr, *bb = nullptr;
+    auto wd = [&](int c) { return linear ? Dims{2, {c, Cin}} : Dims{4, {c, Cin, 1, 1}}; };
+    if (!k.tensor(a + ".weight", wd(Ca), &wa) || !k.tensor(a + ".bias", Dims{1, {Ca}}, &ba) || !k.tensor(b + ".weight", wd(Cb), &wb) ||
+        !k.tensor(b + ".bias", Dims{1, {Cb}}, &bb))
+      return false;
+    std::vector<float> w, bias;
+    if (Sink::builds) {
+      w.assign((size_t)cout_p * Cin, 0.f);
+      bias.assign(cout_p, 0.f);
+      memcpy(w.data(), wa, sizeof(float) * Ca * Cin);
+      memcpy(w.data() + (size_t)Ca * Cin, wb, sizeof(float) * Cb * Cin);
+      memcpy(bias.data(), ba, sizeof(float) * Ca);
+      memcpy(bias.data() + Ca, bb, sizeof(float) * Cb);
+    }
+    return k.layer(L, w.data(), "", bias.data(), cout_p, cout_p, Cin, 1, 1, 0);
+  };
+
+  const std::string B = "backbone.body.";
+  DET_STEP(plain(&net.stem, B + "conv1", B + "bn1", 64, 3, 7, 2, 3));
+  int inplanes = 64;
+  for (int st = 0; st < 4; ++st)
+    for (int bi = 0; bi < RES_BLOCKS[st]; ++bi) {
+      const std::string P = B + "layer" + std::to_string(st + 1) + "." + std::to_string(bi) + ".";
+      const int p = RES_PLANES[st], stride = (bi == 0 && st > 0) ? 2 : 1;
+      Bottleneck& blk = net.block[st][bi];
+      DET_STEP(plain(&blk.c1, P + "conv1", P + "bn1", p, inplanes, 1, 1, 0));
+      DET_STEP(plain(&blk.c2, P + "conv2", P + "bn2", p, p, 3, stride, 1));   // (torchvision: stride on the 3x3)
+      DET_STEP(plain(&blk.c3, P + "conv3", P + "bn3", 4 * p, p, 1, 1, 0));
+      if (bi == 0) DET_STEP(plain(&blk.down, P + "downsample.0", P + "downsample.1", 4 * p, inplanes, 1, stride, 0));
+      inplanes = 4 * p;
+    }
+  for (int i = 0; i < 4; ++i) {
+    const std::string s = std::to_string(i);
+    DET_STEP(plain(&net.fpn_inner[i], "backbone.fpn.inner_blocks." + s, "", DET_FPN_C, 4 * RES_PLANES[i], 1, 1, 0));
+    DET_STEP(plain(&net.fpn_layer[i], "backbone.fpn.layer_blocks." + s, "", DET_FPN_C, DET_FPN_C, 3, 1, 1));
+  }
+  DET_STEP(plain(&net.rpn_conv, "rpn.head.conv", "", DET_FPN_C, DET_FPN_C, 3, 1, 1));
+  DET_STEP(stacked(&net.rpn_head, "rpn.head.cls_logits", "rpn.head.bbox_pred", DET_A, 4 * DET_A, DET_FPN_C, 16, false));
+  {  // fc6: torchvision flattens [R, 256, 7, 7] channel-major; the RoIAlign output here is [R, 7, 7, 256]
+    const float *w6 = nullptr, *b6 = nullptr;
+    DET_STEP(k.tensor("roi_heads.box_head.fc6.weight", Dims{2, {1024, 256 * 7 * 7}}, &w6));
+    DET_STEP(k.tensor("roi_heads.box_head.fc6.bias", Dims{1, {1024}}, &b6));
+    std::vector<float> w;
+    if (Sink::builds) {
+      w.resize((size_t)1024 * 12544);
+      for (int o = 0; o < 1024; ++o)
+        for (int c = 0; c < 256; ++c)
+          for (int q = 0; q < 49; ++q) w[(size_t)o * 12544 + (size_t)q * 256 + c] = w6[(size_t)o * 12544 + (size_t)c * 49 + q];
+    }
+    DET_STEP(k.layer(&net.fc6, w.data(), "", b6, 0, 1024, 12544, 1, 1, 0));
+  }
+  DET_STEP(plain(&net.fc7, "roi_heads.box_head.fc7", "", 1024, 1024, 1, 1, 0, true));
+  DET_STEP(stacked(&net.pred, "roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred", C, 4 * C, 1024, pad4(5 * C), true));
+  for (int i = 0; i < 4; ++i)
+    DET_STEP(plain(&net.mask_fcn[i], "roi_heads.mask_head.mask_fcn" + std::to_string(i + 1), "", DET_FPN_C, DET_FPN_C, 3, 1, 1));
+  {  // ConvTranspose2d(256, 256, 2, 2): out[o, 2y+a, 2x+b] = sum_i in[i, y, x] W[i, o, a, b] + bias[o]  ->  1x1 conv onto (a, b, o)
+    const float *wt = nullptr, *bt = nullptr;
+    DET_STEP(k.tensor("roi_heads.mask_predictor.conv5_mask.weight", Dims{4, {256, 256, 2, 2}}, &wt));
+    DET_STEP(k.tensor("roi_heads.mask_predictor.conv5_mask.bias", Dims{1, {256}}, &bt));
+    std::vector<float> w, b;
+    if (Sink::builds) {
+      w.resize((size_t)1024 * 256);
+      b.resize(1024);
+      for (int ab = 0; ab < 4; ++ab)
+        for (int o = 0; o < 256; ++o) {
+          b[ab * 256 + o] = bt[o];
+          for (int i = 0; i < 256; ++i) w[((size_t)ab * 256 + o) * 256 + i] = wt[((size_t)i * 256 + o) * 4 + ab];
+        }
+    }
+    DET_STEP(k.layer(&net.mask_deconv, w.data(), "", b.data(), 0, 1024, 256, 1, 1, 0));
+  }
+  // (zero output channels up to the padded row; the bias is read for the C real ones only)
+  DET_STEP(plain(&net.mask_logits, "roi_heads.mask_predictor.mask_fcn_logits", "", C, DET_FPN_C, 1, 1, 0, false, pad4(C)));
+#undef DET_STEP
+  return MP_OK;
 }
 
-int det_make_plan(const mp_detector* d, int n, int H, int W, DetPlan* p) {
-  const mp_detector_config& c = d->cfg;
+struct SpecEntry {
+  std::string name;
+  Dims dims;
+};
+
+struct SpecSink {   // mp_detector_state_spec: the list of (name, shape)
+  static constexpr bool builds = false;
+  int rc = MP_OK;
+  std::vector<SpecEntry> v;
+  bool tensor(const std::string& name, const Dims& d, const float** p) {
+    *p = nullptr;
+    v.push_back({name, d});
+    return true;
+  }
+  bool layer(ConvLayer*, const float*, const std::string&, const float*, int, int, int, int, int, int) { return true; }
+};
+
+struct CreateSink {   // mp_detector_create: look the tensor up, build the layer in its fp32 form
+  static constexpr bool builds = true;
+  std::vector<void*>& allocs;
+  const StateMap& sm;
+  int rc = MP_OK;
+  bool tensor(const std::string& name, const Dims& d, const float** p) {
+    *p = find(sm, name, d.numel(), WHO);
+    if (!*p) rc = MP_ERR_INVALID;
+    return *p != nullptr;
+  }
+  bool layer(ConvLayer* L, const float* w, const std::string& bn, const float* bias, int cout_pad, int Cout, int Cin, int K, int stride, int pad) {
+    rc = make_conv_layer(allocs, sm, WHO, w, bn, bias, cout_pad, Cin, pad4(Cin), Cout, K, stride, pad, 0u, L);
+    return rc == MP_OK;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host side: workspace plan
+// ---------------------------------------------------------------------------------------------------------------------------------
+inline size_t tensor_floats(int N, int H, int W, int C, int b) { return (size_t)N * (H + 2 * b) * (W + 2 * b) * C + (size_t)(W + 2 * b) * C + 64; }
+
+// one workspace buffer: where it lies and what it was sized from (what mp_detector_debug_tensor publishes of it)
+struct DetBuf {
+  size_t off = 0;                    // from the workspace's start, in 4-byte elements
+  int64_t shape[4] = {0, 0, 0, 0};   // logical extent
+  int border = 0;                    // zero ring around a padded NHWC map
+  int64_t row_stride = 0;
+  int64_t n_elements = 0;            // 4-byte elements the layout spans, border and row padding included (the slack behind it is not)
+  bool is_int = false;               // int32, else float
+};
+
+struct DetStage {
+  DetBuf x[2], t1, t1in, t2, d;   // the blocks' outputs alternate between x[0] and x[1]
+};
+
+// every buffer of a forward at (n, H, W), bump-allocated in floats (64-float aligned, + the slack the conv's last K chunk may read past a
+// tensor's end)
+struct DetPlan {
+  int n, H, W, hr, wr, Hp, Wp;          // input, resized, padded (multiple of 32)
+  float ratio_h, ratio_w;               // input / resized
+  int fh[DET_LEVELS], fw[DET_LEVELS];   // P2..P6
+  int a_total;                          // anchors per image
+  size_t total = 0;
+  DetBuf x0, stem, pool;
+  DetStage stage[4];
+  int stage_buf[4] = {0, 0, 0, 0};      // which x[] of a stage holds its output C2..C5 (set by the forward: what the FPN read)
+  DetBuf L[4], U[4], P[DET_LEVELS], rpn_t[DET_LEVELS], rpn_h[DET_LEVELS];
+  DetBuf keys, seg_off, seg_off2, seg_off3, idx1, cnt1, cand_box, cand_score, cand_keep, keys2, idx2, proposals, proposal_scores, proposal_counts;
+  DetBuf roi7, fc6, fc7, class_logits, c2_box, c2_key, c2_idx, c2_cnt, c2_sbox, c2_skey, c2_keep, c2_inv, c2_fkey, f_idx, f_cnt, det_resized;
+  DetBuf roi14, m_a, m_b, m_up, mask_logits, splitk, end;
+
+  void take(DetBuf& b, size_t floats, DetBuf what) {
+    b = what;
+    b.off = total;
+    total += (floats + 63) / 64 * 64;
+  }
+  // padded NHWC map {N, h, w, c} inside a zero ring of b pixels
+  void map(DetBuf& B, int N, int h, int w, int c, int b) {
+    take(B, tensor_floats(N, h, w, c, b), DetBuf{0, {N, h, w, c}, b, c, (int64_t)N * (h + 2 * b) * (w + 2 * b) * c, false});
+  }
+  // row matrix {rows, width}, the rows `stride` >= width apart
+  void rows(DetBuf& B, int rows, int width, int stride) {
+    take(B, tensor_floats(rows, 1, 1, stride, 0), DetBuf{0, {rows, width, 1, 1}, 0, stride, (int64_t)rows * stride, false});
+  }
+  // flat list {N, per, width} (+ slack elements behind it)
+  void list(DetBuf& B, size_t N, size_t per, int width, bool is_int = false, size_t slack = 0) {
+    const int64_t n_el = (int64_t)(N * per * width);
+    take(B, (size_t)n_el + slack, DetBuf{0, {(int64_t)N, (int64_t)per, width, 1}, 0, width, n_el, is_int});
+  }
+};
+
+int det_make_plan(const mp_detector_config& c, int n, int H, int W, DetPlan* p) {
+  *p = DetPlan();
   p->n = n; p->H = H; p->W = W;
   // transform.py _resize_image_and_masks: scale = min(min_size / min(h, w), max_size / max(h, w)) in float32; out = floor(in * scale)
   const float scale = std::min((float)c.min_size / (float)std::min(H, W), (float)c.max_size / (float)std::max(H, W));
@@ -609,8 +685,6 @@ int det_make_plan(const mp_detector* d, int n, int H, int W, DetPlan* p) {
   MP_REQUIRE(p->hr >= 32 && p->wr >= 32, "mp_detector: resized image %dx%d too small", p->hr, p->wr);
   p->Hp = (p->hr + 31) / 32 * 32;
   p->Wp = (p->wr + 31) / 32 * 32;
-  p->sy = (float)H / (float)p->hr;
-  p->sx = (float)W / (float)p->wr;
   p->ratio_h = (float)H / (float)p->hr;
   p->ratio_w = (float)W / (float)p->wr;
   for (int l = 0; l < 4; ++l) { p->fh[l] = p->Hp >> (l + 2); p->fw[l] = p->Wp >> (l + 2); }
@@ -618,75 +692,123 @@ int det_make_plan(const mp_detector* d, int n, int H, int W, DetPlan* p) {
   p->fw[4] = (p->fw[3] - 1) / 2 + 1;
   p->a_total = 0;
   for (int l = 0; l < DET_LEVELS; ++l) p->a_total += p->fh[l] * p->fw[l] * DET_A;
-  p->n_seg_rpn = n * DET_LEVELS;
-  p->total = 0;
-  p->off.clear();
-  const int C = d->C, R = c.rpn_post_nms_top_n, Kp = c.rpn_pre_nms_top_n, D = c.box_detections_per_img;
-  p->take("x0", tensor_floats(n, p->Hp, p->Wp, 4, 3));
-  p->take("stem", tensor_floats(n, p->Hp / 2, p->Wp / 2, 64, 1));
-  p->take("pool", tensor_floats(n, p->Hp / 4, p->Wp / 4, 64, 1));
-  static const int pl[4] = {64, 128, 256, 512};
+  const int C = c.n_classes, R = c.rpn_post_nms_top_n, Kp = c.rpn_pre_nms_top_n, D = c.box_detections_per_img;
+  const bool i32 = true;
+  p->map(p->x0, n, p->Hp, p->Wp, 4, 3);
+  p->map(p->stem, n, p->Hp / 2, p->Wp / 2, 64, 1);
+  p->map(p->pool, n, p->Hp / 4, p->Wp / 4, 64, 1);
   for (int s = 0; s < 4; ++s) {
-    const int h = p->fh[s], w = p->fw[s];
-    const std::string S = "s" + std::to_string(s);
-    p->take(S + ".xa", tensor_floats(n, h, w, 4 * pl[s], 1));
-    p->take(S + ".xb", tensor_floats(n, h, w, 4 * pl[s], 1));
-    p->take(S + ".t1", tensor_floats(n, h, w, pl[s], 1));
+    const int h = p->fh[s], w = p->fw[s], pl = RES_PLANES[s];
+    DetStage& S = p->stage[s];
+    p->map(S.x[0], n, h, w, 4 * pl, 1);
+    p->map(S.x[1], n, h, w, 4 * pl, 1);
+    p->map(S.t1, n, h, w, pl, 1);
     // block 0 runs its first 1x1 at the INPUT resolution of the stage: its own buffer (a buffer must keep ONE geometry, its zero
     // border is only established once per forward)
-    p->take(S + ".t1in", tensor_floats(n, s == 0 ? h : 2 * h, s == 0 ? w : 2 * w, pl[s], 1));
-    p->take(S + ".t2", tensor_floats(n, h, w, pl[s], 1));
-    p->take(S + ".d", tensor_floats(n, h, w, 4 * pl[s], 1));
-    p->take("L" + std::to_string(s), tensor_floats(n, h, w, DET_FPN_C, 1));
-    p->take("U" + std::to_string(s), tensor_floats(n, h, w, DET_FPN_C, 1));
+    p->map(S.t1in, n, s == 0 ? h : 2 * h, s == 0 ? w : 2 * w, pl, 1);
+    p->map(S.t2, n, h, w, pl, 1);
+    p->map(S.d, n, h, w, 4 * pl, 1);
+    p->map(p->L[s], n, h, w, DET_FPN_C, 1);
+    p->map(p->U[s], n, h, w, DET_FPN_C, 1);
   }
   for (int l = 0; l < DET_LEVELS; ++l) {
-    p->take("P" + std::to_string(l + 2), tensor_floats(n, p->fh[l], p->fw[l], DET_FPN_C, 1));
-    p->take("rpn_t" + std::to_string(l), tensor_floats(n, p->fh[l], p->fw[l], DET_FPN_C, 0));
-    p->take("rpn_h" + std::to_string(l), tensor_floats(n, p->fh[l], p->fw[l], 16, 0));
+    p->map(p->P[l], n, p->fh[l], p->fw[l], DET_FPN_C, 1);
+    p->map(p->rpn_t[l], n, p->fh[l], p->fw[l], DET_FPN_C, 0);
+    p->map(p->rpn_h[l], n, p->fh[l], p->fw[l], 16, 0);
   }
-  p->take("keys", (size_t)n * p->a_total);
-  p->take("seg_off", 64 + (size_t)n * std::max(DET_LEVELS, C) + 2);   // int32 segment tables of the sorts
-  p->take("seg_off2", 64 + (size_t)n + 2);
-  p->take("seg_off3", 64 + (size_t)n + 2);
-  p->take("idx1", (size_t)n * DET_LEVELS * Kp);
-  p->take("cnt1", (size_t)n * DET_LEVELS + 64);
-  p->take("cand_box", (size_t)n * DET_LEVELS * Kp * 4);
-  p->take("cand_score", (size_t)n * DET_LEVELS * Kp);
-  p->take("cand_keep", (size_t)n * DET_LEVELS * Kp);
-  p->take("keys2", (size_t)n * DET_LEVELS * Kp);
-  p->take("idx2", (size_t)n * R);
-  p->take("proposals", (size_t)n * R * 4);
-  p->take("proposal_scores", (size_t)n * R);
-  p->take("proposal_counts", (size_t)n + 64);
-  p->take("roi7", tensor_floats(n * R, 1, 1, 7 * 7 * DET_FPN_C, 0));
-  p->take("fc6", tensor_floats(n * R, 1, 1, 1024, 0));
-  p->take("fc7", tensor_floats(n * R, 1, 1, 1024, 0));
-  p->take("class_logits", tensor_floats(n * R, 1, 1, d->Cpred_s, 0));
-  const size_t n_c2 = (size_t)n * (C - 1) * R;
-  p->take("c2_box", n_c2 * 4);
-  p->take("c2_key", n_c2);
-  p->take("c2_idx", n_c2);
-  p->take("c2_cnt", (size_t)n * (C - 1) + 64);
-  p->take("c2_sbox", n_c2 * 4);
-  p->take("c2_skey", n_c2);
-  p->take("c2_keep", n_c2);
-  p->take("c2_inv", n_c2);
-  p->take("c2_fkey", n_c2);
-  p->take("f_idx", (size_t)n * D);
-  p->take("f_cnt", (size_t)n + 64);
-  p->take("det_resized", (size_t)n * D * 4);
-  p->take("roi14", tensor_floats(n * D, 14, 14, DET_FPN_C, 1));
-  p->take("m_a", tensor_floats(n * D, 14, 14, DET_FPN_C, 1));
-  p->take("m_b", tensor_floats(n * D, 14, 14, DET_FPN_C, 1));
-  p->take("m_up", tensor_floats(n * D, 14, 14, 4 * DET_FPN_C, 0));
-  p->take("mask_logits", tensor_floats(n * D * 14 * 14 * 4, 1, 1, d->Cmask_s, 0));
-  p->take("splitk", DET_SPLITK_FLOATS);
-  p->take("end", 4096);
+  const size_t N = n, n_lv = N * DET_LEVELS, n_cls = N * (C - 1);   // segments of the sorts: images, (image, level), (image, class)
+  p->list(p->keys, N, p->a_total, 1);
+  p->list(p->seg_off, N, std::max(DET_LEVELS, C), 1, i32, 64 + 2);   // segment tables of the sorts
+  p->list(p->seg_off2, N, 1, 1, i32, 64 + 2);
+  p->list(p->seg_off3, N, 1, 1, i32, 64 + 2);
+  p->list(p->idx1, n_lv, Kp, 1, i32);
+  p->list(p->cnt1, n_lv, 1, 1, i32, 64);
+  p->list(p->cand_box, n_lv, Kp, 4);
+  p->list(p->cand_score, n_lv, Kp, 1);
+  p->list(p->cand_keep, n_lv, Kp, 1, i32);
+  p->list(p->keys2, n_lv, Kp, 1);
+  p->list(p->idx2, N, R, 1, i32);
+  p->list(p->proposals, N, R, 4);
+  p->list(p->proposal_scores, N, R, 1);
+  p->list(p->proposal_counts, N, 1, 1, i32, 64);
+  p->rows(p->roi7, n * R, 7 * 7 * DET_FPN_C, 7 * 7 * DET_FPN_C);   // (y, x, channel)
+  p->rows(p->fc6, n * R, 1024, 1024);
+  p->rows(p->fc7, n * R, 1024, 1024);
+  p->rows(p->class_logits, n * R, 5 * C, pad4(5 * C));
+  p->list(p->c2_box, n_cls, R, 4);
+  p->list(p->c2_key, n_cls, R, 1);
+  p->list(p->c2_idx, n_cls, R, 1, i32);
+  p->list(p->c2_cnt, n_cls, 1, 1, i32, 64);
+  p->list(p->c2_sbox, n_cls, R, 4);
+  p->list(p->c2_skey, n_cls, R, 1);
+  p->list(p->c2_keep, n_cls, R, 1, i32);
+  p->list(p->c2_inv, n_cls, R, 1, i32);
+  p->list(p->c2_fkey, n_cls, R, 1);
+  p->list(p->f_idx, N, D, 1, i32);
+  p->list(p->f_cnt, N, 1, 1, i32, 64);
+  p->list(p->det_resized, N, D, 4);
+  p->map(p->roi14, n * D, 14, 14, DET_FPN_C, 1);
+  p->map(p->m_a, n * D, 14, 14, DET_FPN_C, 1);
+  p->map(p->m_b, n * D, 14, 14, DET_FPN_C, 1);
+  p->map(p->m_up, n * D, 14, 14, 4 * DET_FPN_C, 0);
+  p->rows(p->mask_logits, n * D * 14 * 14 * 4, C, pad4(C));
+  p->list(p->splitk, 1, DET_SPLITK_FLOATS, 1);
+  p->list(p->end, 1, 4096, 1);
   return MP_OK;
 }
 
+// the taps mp_detector_debug_tensor publishes; every other buffer is internal
+struct DetTap {
+  const char* name;
+  DetBuf DetPlan::*buf;
+};
+const DetTap DET_TAPS[] = {{"x0", &DetPlan::x0}, {"pool", &DetPlan::pool}, {"keys", &DetPlan::keys}, {"proposals", &DetPlan::proposals},
+                           {"proposal_scores", &DetPlan::proposal_scores}, {"proposal_counts", &DetPlan::proposal_counts},
+                           {"roi7", &DetPlan::roi7}, {"class_logits", &DetPlan::class_logits}, {"f_cnt", &DetPlan::f_cnt},
+                           {"det_resized", &DetPlan::det_resized}, {"roi14", &DetPlan::roi14}, {"mask_logits", &DetPlan::mask_logits}};
+
+const DetBuf* det_find_tap(const DetPlan& p, const char* what) {
+  if (what[0] && what[1] && !what[2]) {   // C2..C5: the buffer the stage's last block wrote; L2..L5: the FPN's top-down maps; P2..P6
+    const int k = what[1] - '2';
+    if (what[0] == 'C' && k >= 0 && k < 4) return &p.stage[k].x[p.stage_buf[k]];
+    if (what[0] == 'L' && k >= 0 && k < 4) return &p.L[k];
+    if (what[0] == 'P' && k >= 0 && k < DET_LEVELS) return &p.P[k];
+  }
+  for (const DetTap& t : DET_TAPS)
+    if (!strcmp(t.name, what)) return &(p.*t.buf);
+  return nullptr;
+}
+
+// what the steps of one forward share; the first error sticks and turns the steps after it into no-ops
+struct DetRun {
+  hipStream_t s;
+  float* splitk;
+  int n;   // images
+  int rc = MP_OK;
+  void conv(const ConvLayer& L, const float* x, int N, int H, int W, int in_border, float* y, int out_border, const float* res, int relu) {
+    if (!rc) rc = run_conv_layer(L, x, N, H, W, in_border, y, out_border, res, relu, s, splitk, DET_SPLITK_FLOATS);
+  }
+  // stable rank sort of `per_image` x n segments of `len` keys each: the indices of every segment's `top` largest keys + how many it has
+  void rank_topk(const float* keys, int per_image, int len, int top, int* seg_off, int* idx, int* cnt) {
+    if (rc) return;
+    const int n_seg = n * per_image;
+    hipLaunchKernelGGL(det_seg_offsets_kernel, dim3(ceil_div((long)n_seg + 1, 256)), dim3(256), 0, s, n_seg, len, seg_off);
+    hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div(len, 256), n_seg), dim3(256), 0, s, keys, seg_off, top, idx, cnt);
+  }
+};
+
 }  // namespace
+
+struct mp_detector {
+  mp_detector_config cfg;
+  DetLayers net;
+  float base_anchors[DET_LEVELS][DET_A][4];
+  std::vector<void*> allocs;
+  // last forward (debug taps)
+  bool ran = false;
+  DetPlan last;
+  void* last_ws = nullptr;
+};
 
 extern "C" int mp_detector_default_config(mp_detector_config* cfg, int n_classes, int min_size, int max_size) {
   MP_REQUIRE(cfg && n_classes >= 2 && min_size > 0 && max_size >= min_size, "mp_detector_default_config: bad arguments");
@@ -710,11 +832,14 @@ extern "C" int mp_detector_default_config(mp_detector_config* cfg, int n_classes
 
 extern "C" int mp_detector_state_spec(int n_classes, int idx, char* name, int name_len, int64_t* shape4, int32_t* n_dims) {
   MP_REQUIRE(n_classes >= 2 && idx >= 0 && name && name_len > 0 && shape4 && n_dims, "mp_detector_state_spec: bad arguments");
-  const std::vector<SpecEntry> v = det_spec(n_classes);
-  if (idx >= (int)v.size()) return 1;
-  snprintf(name, name_len, "%s", v[idx].name.c_str());
-  for (int k = 0; k < 4; ++k) shape4[k] = v[idx].shape[k];
-  *n_dims = v[idx].n_dims;
+  SpecSink k;
+  DetLayers unbuilt;
+  det_walk(n_classes, unbuilt, k);
+  if (idx >= (int)k.v.size()) return 1;
+  const SpecEntry& e = k.v[idx];
+  snprintf(name, name_len, "%s", e.name.c_str());
+  for (int i = 0; i < 4; ++i) shape4[i] = i < e.dims.n ? e.dims.d[i] : 1;
+  *n_dims = e.dims.n;
   return MP_OK;
 }
 
@@ -736,98 +861,12 @@ extern "C" int mp_detector_create(const mp_detector_config* cfg, const mp_named_
   for (int i = 0; i < n_tensors; ++i) sm[st[i].name] = std::make_pair(st[i].h_data, st[i].numel);
   mp_detector* d = new mp_detector();
   d->cfg = *cfg;
-  const int C = d->C = cfg->n_classes;
-  d->Cpred_s = (5 * C + 3) / 4 * 4;
-  d->Cmask_s = (C + 3) / 4 * 4;
-  int rc;
-#define DET_TRY(e) do { rc = (e); if (rc) { mp_detector_destroy(d); return rc; } } while (0)
-  const std::string B = "backbone.body.";
-  DET_TRY(det_conv_from_key(d, sm, B + "conv1.weight", 64, 3, 7, 2, 3, B + "bn1", "", &d->stem));
-  static const int nb[4] = {3, 4, 6, 3}, pl[4] = {64, 128, 256, 512};
-  int inplanes = 64;
-  for (int li = 0; li < 4; ++li)
-    for (int bi = 0; bi < nb[li]; ++bi) {
-      const std::string P = B + "layer" + std::to_string(li + 1) + "." + std::to_string(bi) + ".";
-      const int p = pl[li], stride = (bi == 0 && li > 0) ? 2 : 1;
-      Bottleneck blk;
-      DET_TRY(det_conv_from_key(d, sm, P + "conv1.weight", p, inplanes, 1, 1, 0, P + "bn1", "", &blk.c1));
-      DET_TRY(det_conv_from_key(d, sm, P + "conv2.weight", p, p, 3, stride, 1, P + "bn2", "", &blk.c2));     // (torchvision: stride on the 3x3)
-      DET_TRY(det_conv_from_key(d, sm, P + "conv3.weight", 4 * p, p, 1, 1, 0, P + "bn3", "", &blk.c3));
-      blk.has_down = bi == 0;
-      if (blk.has_down) DET_TRY(det_conv_from_key(d, sm, P + "downsample.0.weight", 4 * p, inplanes, 1, stride, 0, P + "downsample.1", "", &blk.down));
-      d->blocks.push_back(blk);
-      d->stage_of_block.push_back(li);
-      inplanes = 4 * p;
-    }
-  static const int fc[4] = {256, 512, 1024, 2048};
-  for (int i = 0; i < 4; ++i) {
-    const std::string s = std::to_string(i);
-    DET_TRY(det_conv_from_key(d, sm, "backbone.fpn.inner_blocks." + s + ".weight", 256, fc[i], 1, 1, 0, "", "backbone.fpn.inner_blocks." + s + ".bias", &d->fpn_inner[i]));
-    DET_TRY(det_conv_from_key(d, sm, "backbone.fpn.layer_blocks." + s + ".weight", 256, 256, 3, 1, 1, "", "backbone.fpn.layer_blocks." + s + ".bias", &d->fpn_layer[i]));
+  CreateSink k{d->allocs, sm};
+  const int rc = det_walk(cfg->n_classes, d->net, k);
+  if (rc) {   // a missing or mis-sized tensor (find has set the message), or a layer that could not be built
+    mp_detector_destroy(d);
+    return rc;
   }
-  DET_TRY(det_conv_from_key(d, sm, "rpn.head.conv.weight", 256, 256, 3, 1, 1, "", "rpn.head.conv.bias", &d->rpn_conv));
-  {  // cls_logits (A) + bbox_pred (4A) as ONE 1x1 convolution with 16 output channels
-    const float* wc = find(sm, "rpn.head.cls_logits.weight", DET_A * 256, WHO);
-    const float* bc = find(sm, "rpn.head.cls_logits.bias", DET_A, WHO);
-    const float* wb = find(sm, "rpn.head.bbox_pred.weight", 4 * DET_A * 256, WHO);
-    const float* bb = find(sm, "rpn.head.bbox_pred.bias", 4 * DET_A, WHO);
-    if (!wc || !bc || !wb || !bb) { mp_detector_destroy(d); return MP_ERR_INVALID; }
-    std::vector<float> w(16 * 256, 0.f), b(16, 0.f);
-    memcpy(w.data(), wc, sizeof(float) * DET_A * 256);
-    memcpy(w.data() + DET_A * 256, wb, sizeof(float) * 4 * DET_A * 256);
-    memcpy(b.data(), bc, sizeof(float) * DET_A);
-    memcpy(b.data() + DET_A, bb, sizeof(float) * 4 * DET_A);
-    DET_TRY(det_make_conv(d, sm, w.data(), 16, 256, 1, 1, 0, "", b.data(), 16, &d->rpn_head));
-  }
-  {  // fc6: torchvision flattens [R, 256, 7, 7] channel-major; the RoIAlign output here is [R, 7, 7, 256]
-    const float* w6 = find(sm, "roi_heads.box_head.fc6.weight", (int64_t)1024 * 12544, WHO);
-    const float* b6 = find(sm, "roi_heads.box_head.fc6.bias", 1024, WHO);
-    if (!w6 || !b6) { mp_detector_destroy(d); return MP_ERR_INVALID; }
-    std::vector<float> w((size_t)1024 * 12544);
-    for (int o = 0; o < 1024; ++o)
-      for (int c = 0; c < 256; ++c)
-        for (int q = 0; q < 49; ++q) w[(size_t)o * 12544 + (size_t)q * 256 + c] = w6[(size_t)o * 12544 + (size_t)c * 49 + q];
-    DET_TRY(det_make_conv(d, sm, w.data(), 1024, 12544, 1, 1, 0, "", b6, 0, &d->fc6));
-  }
-  DET_TRY(det_conv_from_key(d, sm, "roi_heads.box_head.fc7.weight", 1024, 1024, 1, 1, 0, "", "roi_heads.box_head.fc7.bias", &d->fc7));
-  {  // cls_score (C) + bbox_pred (4C) as one layer
-    const float* wc = find(sm, "roi_heads.box_predictor.cls_score.weight", (int64_t)C * 1024, WHO);
-    const float* bc = find(sm, "roi_heads.box_predictor.cls_score.bias", C, WHO);
-    const float* wb = find(sm, "roi_heads.box_predictor.bbox_pred.weight", (int64_t)4 * C * 1024, WHO);
-    const float* bb = find(sm, "roi_heads.box_predictor.bbox_pred.bias", 4 * C, WHO);
-    if (!wc || !bc || !wb || !bb) { mp_detector_destroy(d); return MP_ERR_INVALID; }
-    std::vector<float> w((size_t)d->Cpred_s * 1024, 0.f), b(d->Cpred_s, 0.f);
-    memcpy(w.data(), wc, sizeof(float) * C * 1024);
-    memcpy(w.data() + (size_t)C * 1024, wb, sizeof(float) * 4 * C * 1024);
-    memcpy(b.data(), bc, sizeof(float) * C);
-    memcpy(b.data() + C, bb, sizeof(float) * 4 * C);
-    DET_TRY(det_make_conv(d, sm, w.data(), d->Cpred_s, 1024, 1, 1, 0, "", b.data(), d->Cpred_s, &d->pred));
-  }
-  for (int i = 0; i < 4; ++i) {
-    const std::string k = "roi_heads.mask_head.mask_fcn" + std::to_string(i + 1);
-    DET_TRY(det_conv_from_key(d, sm, k + ".weight", 256, 256, 3, 1, 1, "", k + ".bias", &d->mask_fcn[i]));
-  }
-  {  // ConvTranspose2d(256, 256, 2, 2): out[o, 2y+a, 2x+b] = sum_i in[i, y, x] W[i, o, a, b] + bias[o]  ->  1x1 conv onto (a, b, o)
-    const float* wt = find(sm, "roi_heads.mask_predictor.conv5_mask.weight", 256 * 256 * 4, WHO);
-    const float* bt = find(sm, "roi_heads.mask_predictor.conv5_mask.bias", 256, WHO);
-    if (!wt || !bt) { mp_detector_destroy(d); return MP_ERR_INVALID; }
-    std::vector<float> w((size_t)1024 * 256), b(1024);
-    for (int ab = 0; ab < 4; ++ab)
-      for (int o = 0; o < 256; ++o) {
-        b[ab * 256 + o] = bt[o];
-        for (int i = 0; i < 256; ++i) w[((size_t)ab * 256 + o) * 256 + i] = wt[((size_t)i * 256 + o) * 4 + ab];
-      }
-    DET_TRY(det_make_conv(d, sm, w.data(), 1024, 256, 1, 1, 0, "", b.data(), 0, &d->mask_deconv));
-  }
-  {
-    const float* wl = find(sm, "roi_heads.mask_predictor.mask_fcn_logits.weight", (int64_t)C * 256, WHO);
-    const float* bl = find(sm, "roi_heads.mask_predictor.mask_fcn_logits.bias", C, WHO);
-    if (!wl || !bl) { mp_detector_destroy(d); return MP_ERR_INVALID; }
-    std::vector<float> b(d->Cmask_s, 0.f);
-    memcpy(b.data(), bl, sizeof(float) * C);
-    DET_TRY(det_make_conv(d, sm, wl, C, 256, 1, 1, 0, "", b.data(), d->Cmask_s, &d->mask_logits));
-  }
-#undef DET_TRY
   // anchor_utils.py generate_anchors: h_ratios = sqrt(ar), w_ratios = 1 / h_ratios, base = round([-w, -h, w, h] / 2) (float32, half to even)
   for (int l = 0; l < DET_LEVELS; ++l)
     for (int a = 0; a < DET_A; ++a) {
@@ -845,7 +884,7 @@ extern "C" int mp_detector_create(const mp_detector_config* cfg, const mp_named_
 extern "C" size_t mp_detector_workspace_bytes(const mp_detector* d, int n_images, int H, int W) {
   if (!d || n_images <= 0 || H <= 0 || W <= 0) return 0;
   DetPlan p;
-  if (det_make_plan(d, n_images, H, W, &p)) return 0;
+  if (det_make_plan(d->cfg, n_images, H, W, &p)) return 0;
   return p.total * sizeof(float);
 }
 
@@ -853,87 +892,83 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
                                    int32_t* d_counts, float* d_masks, void* d_ws, size_t ws_bytes, mp_stream stream) {
   MP_REQUIRE(d && d_images && d_boxes && d_scores && d_labels && d_counts && d_ws, "mp_detector_forward: null pointer");
   MP_REQUIRE(n > 0 && n <= 4096 && H > 0 && W > 0, "mp_detector_forward: bad size");
+  const mp_detector_config& cfg = d->cfg;
+  const DetLayers& net = d->net;
+  const int C = cfg.n_classes, R = cfg.rpn_post_nms_top_n, Kp = cfg.rpn_pre_nms_top_n, D = cfg.box_detections_per_img;
   DetPlan p;
-  int rc = det_make_plan(d, n, H, W, &p);
-  if (rc) return rc;
+  const int plan_rc = det_make_plan(cfg, n, H, W, &p);
+  if (plan_rc) return plan_rc;
   MP_REQUIRE(ws_bytes >= p.total * sizeof(float), "mp_detector_forward: workspace %zu < %zu bytes", ws_bytes, p.total * sizeof(float));
-  MP_REQUIRE((long)n * p.a_total < (1L << 31) && (long)n * (d->C - 1) * d->cfg.rpn_post_nms_top_n < (1L << 31),
+  MP_REQUIRE((long)n * p.a_total < (1L << 31) && (long)n * (C - 1) * R < (1L << 31),
              "mp_detector_forward: %d images of %d anchors exceed the 32-bit index range of the selection kernels; split the batch", n, p.a_total);
   // The selection kernels rank by counting (O(len^2) compares per segment: deterministic, no library sort).  That is ~3e9 compares for
   // the 57.6 k P2 anchors of a 480x640 frame (1.5 ms) but grows quadratically: bound the segment sizes instead of degrading silently
   // (torchvision's default 800x1333 transform gives ~200 k anchors on P2 = 4e10 compares per frame -- use a radix select there).
-  MP_REQUIRE((long)p.hr * p.wr <= 1024L * 1024L && d->C <= 256,
+  MP_REQUIRE((long)p.hr * p.wr <= 1024L * 1024L && C <= 256,
              "mp_detector_forward: resized frame %dx%d / %d classes exceed what the rank-sort selection is sized for (<= 1024x1024, <= 256 classes)",
-             p.hr, p.wr, d->C);
-  const mp_detector_config& cfg = d->cfg;
+             p.hr, p.wr, C);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)d_ws;
-  auto F = [&](const std::string& k) { return ws + p.off.at(k); };
-  auto I = [&](const std::string& k) { return reinterpret_cast<int*>(ws + p.off.at(k)); };
-  float* SK = F("splitk");
+  auto F = [&](const DetBuf& b) { return ws + b.off; };
+  auto I = [&](const DetBuf& b) { return reinterpret_cast<int*>(ws + b.off); };
+  auto B4 = [&](const DetBuf& b) { return reinterpret_cast<float4*>(ws + b.off); };
   // zero everything: borders of every padded map, the pad region of the batched input, counters (cheap next to ResNet-50)
   MP_CHECK_HIP(hipMemsetAsync(d_ws, 0, p.total * sizeof(float), s));
-  const int C = d->C, R = cfg.rpn_post_nms_top_n, Kp = cfg.rpn_pre_nms_top_n, D = cfg.box_detections_per_img;
+  DetRun r{s, F(p.splitk), n};
 
   // ---- transform + backbone + FPN --------------------------------------------------------------------------------------------
   {
     ProfScope prof("det_preprocess", 0.0, (double)n * (12.0 * H * W + 16.0 * p.hr * p.wr), s);
-    hipLaunchKernelGGL(det_preprocess_kernel, dim3(ceil_div((long)p.hr * p.wr, 256), n), dim3(256), 0, s, d_images, H, W, p.hr, p.wr, p.sy, p.sx,
-                       cfg.image_mean[0], cfg.image_mean[1], cfg.image_mean[2], cfg.image_std[0], cfg.image_std[1], cfg.image_std[2], F("x0"),
-                       p.Hp, p.Wp, 3);
+    hipLaunchKernelGGL(det_preprocess_kernel, dim3(ceil_div((long)p.hr * p.wr, 256), n), dim3(256), 0, s, d_images, H, W, p.hr, p.wr, p.ratio_h,
+                       p.ratio_w, cfg.image_mean[0], cfg.image_mean[1], cfg.image_mean[2], cfg.image_std[0], cfg.image_std[1], cfg.image_std[2],
+                       F(p.x0), p.Hp, p.Wp, 3);
   }
-  rc = run_conv_layer(d->stem, F("x0"), n, p.Hp, p.Wp, 3, F("stem"), 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  rc = mp_maxpool3x3s2(F("stem"), n, p.Hp / 2, p.Wp / 2, 64, 1, F("pool"), 1, nullptr, nullptr, nullptr, s);
-  if (rc) return rc;
-  const float* x = F("pool");
+  r.conv(net.stem, F(p.x0), n, p.Hp, p.Wp, 3, F(p.stem), 1, nullptr, 1);
+  if (!r.rc) r.rc = mp_maxpool3x3s2(F(p.stem), n, p.Hp / 2, p.Wp / 2, 64, 1, F(p.pool), 1, nullptr, nullptr, nullptr, s);
+  const float* x = F(p.pool);
   int xh = p.Hp / 4, xw = p.Wp / 4;
-  const float* stage_out[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (size_t i = 0; i < d->blocks.size(); ++i) {
-    const Bottleneck& b = d->blocks[i];
-    const int st = d->stage_of_block[i];
-    const std::string S = "s" + std::to_string(st);
+  const float* stage_out[4];
+  for (int st = 0; st < 4; ++st) {
+    const DetStage& S = p.stage[st];
     const int oh = p.fh[st], ow = p.fw[st];
-    float* t1 = b.has_down ? F(S + ".t1in") : F(S + ".t1");
-    rc = run_conv_layer(b.c1, x, n, xh, xw, 1, t1, 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    rc = run_conv_layer(b.c2, t1, n, xh, xw, 1, F(S + ".t2"), 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    const float* idn = x;
-    if (b.has_down) {
-      rc = run_conv_layer(b.down, x, n, xh, xw, 1, F(S + ".d"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-      if (rc) return rc;
-      idn = F(S + ".d");
+    int cur = 1;   // the first block writes x[0]
+    for (int bi = 0; bi < RES_BLOCKS[st]; ++bi) {
+      const Bottleneck& b = net.block[st][bi];
+      const bool first = bi == 0;   // takes the previous stage's map (stride 2 from stage 1 on) and has the downsample branch
+      float* t1 = F(first ? S.t1in : S.t1);
+      r.conv(b.c1, x, n, xh, xw, 1, t1, 1, nullptr, 1);
+      r.conv(b.c2, t1, n, xh, xw, 1, F(S.t2), 1, nullptr, 1);
+      const float* idn = x;
+      if (first) {
+        r.conv(b.down, x, n, xh, xw, 1, F(S.d), 1, nullptr, 0);
+        idn = F(S.d);
+      }
+      cur ^= 1;
+      float* y = F(S.x[cur]);
+      r.conv(b.c3, F(S.t2), n, oh, ow, 1, y, 1, idn, 1);
+      x = y; xh = oh; xw = ow;
     }
-    const std::string yk = S + ((x == F(S + ".xa")) ? ".xb" : ".xa");
-    float* y = F(yk);
-    rc = run_conv_layer(b.c3, F(S + ".t2"), n, oh, ow, 1, y, 1, idn, 1, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    x = y; xh = oh; xw = ow;
-    stage_out[st] = y;
-    p.stage_buf[st] = yk;
+    stage_out[st] = x;
+    p.stage_buf[st] = cur;
   }
+  if (r.rc) return r.rc;
   // FPN (ops/feature_pyramid_network.py): last_inner = inner[3](C5); P5 = layer[3](last_inner); going down: lateral + nearest upsample
-  rc = run_conv_layer(d->fpn_inner[3], stage_out[3], n, p.fh[3], p.fw[3], 1, F("L3"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  rc = run_conv_layer(d->fpn_layer[3], F("L3"), n, p.fh[3], p.fw[3], 1, F("P5"), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  for (int l = 2; l >= 0; --l) {
-    const std::string sl = std::to_string(l), su = std::to_string(l + 1);
+  r.conv(net.fpn_inner[3], stage_out[3], n, p.fh[3], p.fw[3], 1, F(p.L[3]), 1, nullptr, 0);
+  r.conv(net.fpn_layer[3], F(p.L[3]), n, p.fh[3], p.fw[3], 1, F(p.P[3]), 1, nullptr, 0);
+  for (int l = 2; l >= 0 && !r.rc; --l) {
     {
       const long total = (long)n * p.fh[l] * p.fw[l] * (DET_FPN_C / 4);
       ProfScope prof("det_resize_nearest", 0.0, (double)total * 32.0, s);
-      hipLaunchKernelGGL(det_resize_nearest_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("L" + su), p.fh[l + 1], p.fw[l + 1], F("U" + sl),
+      hipLaunchKernelGGL(det_resize_nearest_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F(p.L[l + 1]), p.fh[l + 1], p.fw[l + 1], F(p.U[l]),
                          p.fh[l], p.fw[l], DET_FPN_C, n, 1, 1, 0, 0);
     }
-    rc = run_conv_layer(d->fpn_inner[l], stage_out[l], n, p.fh[l], p.fw[l], 1, F("L" + sl), 1, F("U" + sl), 0, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    rc = run_conv_layer(d->fpn_layer[l], F("L" + sl), n, p.fh[l], p.fw[l], 1, F("P" + std::to_string(l + 2)), 1, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
+    r.conv(net.fpn_inner[l], stage_out[l], n, p.fh[l], p.fw[l], 1, F(p.L[l]), 1, F(p.U[l]), 0);
+    r.conv(net.fpn_layer[l], F(p.L[l]), n, p.fh[l], p.fw[l], 1, F(p.P[l]), 1, nullptr, 0);
   }
+  if (r.rc) return r.rc;
   {  // LastLevelMaxPool: F.max_pool2d(P5, 1, 2, 0)
     const long total = (long)n * p.fh[4] * p.fw[4] * (DET_FPN_C / 4);
-    hipLaunchKernelGGL(det_resize_nearest_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("P5"), p.fh[3], p.fw[3], F("P6"), p.fh[4], p.fw[4],
+    hipLaunchKernelGGL(det_resize_nearest_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F(p.P[3]), p.fh[3], p.fw[3], F(p.P[4]), p.fh[4], p.fw[4],
                        DET_FPN_C, n, 1, 1, 2, 2);
   }
 
@@ -941,106 +976,89 @@ extern "C" int mp_detector_forward(mp_detector* d, const float* d_images, int n,
   RpnLevels L;
   L.off[0] = 0;
   for (int l = 0; l < DET_LEVELS; ++l) {
-    const std::string sl = std::to_string(l);
-    rc = run_conv_layer(d->rpn_conv, F("P" + std::to_string(l + 2)), n, p.fh[l], p.fw[l], 1, F("rpn_t" + sl), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    rc = run_conv_layer(d->rpn_head, F("rpn_t" + sl), n, p.fh[l], p.fw[l], 0, F("rpn_h" + sl), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    L.head[l] = F("rpn_h" + sl);
+    r.conv(net.rpn_conv, F(p.P[l]), n, p.fh[l], p.fw[l], 1, F(p.rpn_t[l]), 0, nullptr, 1);
+    r.conv(net.rpn_head, F(p.rpn_t[l]), n, p.fh[l], p.fw[l], 0, F(p.rpn_h[l]), 0, nullptr, 0);
+    L.head[l] = F(p.rpn_h[l]);
     L.gh[l] = p.fh[l]; L.gw[l] = p.fw[l];
     L.off[l + 1] = L.off[l] + p.fh[l] * p.fw[l] * DET_A;
     L.stride_y[l] = p.Hp / p.fh[l];   // anchor_utils.py: strides = image_size // grid_size (padded batch size)
     L.stride_x[l] = p.Wp / p.fw[l];
     memcpy(L.base[l], d->base_anchors[l], sizeof(L.base[l]));
   }
+  if (r.rc) return r.rc;
   {
     const long total = (long)n * p.a_total;
-    hipLaunchKernelGGL(det_rpn_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, L, n, F("keys"));
+    hipLaunchKernelGGL(det_rpn_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, L, n, F(p.keys));
   }
   int max_len = 0;
   for (int l = 0; l < DET_LEVELS; ++l) max_len = std::max(max_len, L.off[l + 1] - L.off[l]);
-  hipLaunchKernelGGL(det_rpn_seg_offsets_kernel, dim3(ceil_div((long)n * DET_LEVELS + 1, 256)), dim3(256), 0, s, L, n, I("seg_off"));
+  hipLaunchKernelGGL(det_rpn_seg_offsets_kernel, dim3(ceil_div((long)n * DET_LEVELS + 1, 256)), dim3(256), 0, s, L, n, I(p.seg_off));
   {
     ProfScope prof("det_rank_topk", 0.0, 0.0, s);
-    hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div(max_len, 256), n * DET_LEVELS), dim3(256), 0, s, F("keys"), I("seg_off"), Kp, I("idx1"),
-                       I("cnt1"));
+    hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div(max_len, 256), n * DET_LEVELS), dim3(256), 0, s, F(p.keys), I(p.seg_off), Kp, I(p.idx1),
+                       I(p.cnt1));
   }
   {
     const long total = (long)n * DET_LEVELS * Kp;
-    hipLaunchKernelGGL(det_rpn_gather_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, L, n, F("keys"), I("idx1"), I("cnt1"), Kp, (float)p.hr,
-                       (float)p.wr, cfg.rpn_min_size, cfg.rpn_score_thresh, reinterpret_cast<float4*>(F("cand_box")), F("cand_score"),
-                       I("cand_keep"));
+    hipLaunchKernelGGL(det_rpn_gather_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, L, n, F(p.keys), I(p.idx1), I(p.cnt1), Kp, (float)p.hr,
+                       (float)p.wr, cfg.rpn_min_size, cfg.rpn_score_thresh, B4(p.cand_box), F(p.cand_score), I(p.cand_keep));
     ProfScope prof("det_nms", 0.0, 0.0, s);
-    hipLaunchKernelGGL(det_nms_kernel, dim3(n * DET_LEVELS), dim3(256), 0, s, reinterpret_cast<const float4*>(F("cand_box")), I("cand_keep"),
-                       (const int*)nullptr, Kp, cfg.rpn_nms_thresh);
-    hipLaunchKernelGGL(det_masked_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("cand_score"), I("cand_keep"), total, F("keys2"));
+    hipLaunchKernelGGL(det_nms_kernel, dim3(n * DET_LEVELS), dim3(256), 0, s, B4(p.cand_box), I(p.cand_keep), (const int*)nullptr, Kp,
+                       cfg.rpn_nms_thresh);
+    hipLaunchKernelGGL(det_masked_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F(p.cand_score), I(p.cand_keep), total, F(p.keys2));
   }
-  hipLaunchKernelGGL(det_seg_offsets_kernel, dim3(ceil_div((long)n + 1, 256)), dim3(256), 0, s, n, DET_LEVELS * Kp, I("seg_off2"));
-  hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div(DET_LEVELS * Kp, 256), n), dim3(256), 0, s, F("keys2"), I("seg_off2"), R, I("idx2"),
-                     I("proposal_counts"));
-  hipLaunchKernelGGL(det_gather_boxes_kernel, dim3(ceil_div((long)n * R, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("cand_box")),
-                     F("cand_score"), DET_LEVELS * Kp, I("idx2"), I("proposal_counts"), R, n, reinterpret_cast<float4*>(F("proposals")),
-                     F("proposal_scores"));
-  hipLaunchKernelGGL(det_clamp_counts_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, I("proposal_counts"), n, R);
+  r.rank_topk(F(p.keys2), 1, DET_LEVELS * Kp, R, I(p.seg_off2), I(p.idx2), I(p.proposal_counts));
+  hipLaunchKernelGGL(det_gather_boxes_kernel, dim3(ceil_div((long)n * R, 256)), dim3(256), 0, s, B4(p.cand_box), F(p.cand_score), DET_LEVELS * Kp,
+                     I(p.idx2), I(p.proposal_counts), R, n, B4(p.proposals), F(p.proposal_scores));
+  hipLaunchKernelGGL(det_clamp_counts_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, I(p.proposal_counts), n, R);
 
   // ---- box head (roi_heads.py) ----------------------------------------------------------------------------------------------------
   PyramidRef py;
-  for (int l = 0; l < 4; ++l) { py.feat[l] = F("P" + std::to_string(l + 2)); py.h[l] = p.fh[l]; py.w[l] = p.fw[l]; }
+  for (int l = 0; l < 4; ++l) { py.feat[l] = F(p.P[l]); py.h[l] = p.fh[l]; py.w[l] = p.fw[l]; }
   {
     const long total = (long)n * R * 49 * (DET_FPN_C / 4);
     ProfScope prof("det_roi_align", 0.0, (double)total * 16.0 * 5.0, s);
-    hipLaunchKernelGGL(det_roi_align_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, py, reinterpret_cast<const float4*>(F("proposals")),
-                       I("proposal_counts"), R, n, 7, 0, F("roi7"));
+    hipLaunchKernelGGL(det_roi_align_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, py, B4(p.proposals), I(p.proposal_counts), R, n, 7, 0,
+                       F(p.roi7));
   }
-  rc = run_conv_layer(d->fc6, F("roi7"), n * R, 1, 1, 0, F("fc6"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  rc = run_conv_layer(d->fc7, F("fc6"), n * R, 1, 1, 0, F("fc7"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  rc = run_conv_layer(d->pred, F("fc7"), n * R, 1, 1, 0, F("class_logits"), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-  if (rc) return rc;
-  hipLaunchKernelGGL(det_box_post_kernel, dim3(ceil_div((long)n * R, 256)), dim3(256), 0, s, F("class_logits"), d->Cpred_s, C,
-                     reinterpret_cast<const float4*>(F("proposals")), I("proposal_counts"), R, n, (float)p.hr, (float)p.wr, cfg.box_score_thresh,
-                     cfg.box_min_size, reinterpret_cast<float4*>(F("c2_box")), F("c2_key"));
+  r.conv(net.fc6, F(p.roi7), n * R, 1, 1, 0, F(p.fc6), 0, nullptr, 1);
+  r.conv(net.fc7, F(p.fc6), n * R, 1, 1, 0, F(p.fc7), 0, nullptr, 1);
+  r.conv(net.pred, F(p.fc7), n * R, 1, 1, 0, F(p.class_logits), 0, nullptr, 0);
+  if (r.rc) return r.rc;
+  hipLaunchKernelGGL(det_box_post_kernel, dim3(ceil_div((long)n * R, 256)), dim3(256), 0, s, F(p.class_logits), pad4(5 * C), C, B4(p.proposals),
+                     I(p.proposal_counts), R, n, (float)p.hr, (float)p.wr, cfg.box_score_thresh, cfg.box_min_size, B4(p.c2_box), F(p.c2_key));
   const int n_seg2 = n * (C - 1);
   // (seg_off is free again: the RPN sort that used it was enqueued earlier on the same stream)
-  hipLaunchKernelGGL(det_seg_offsets_kernel, dim3(ceil_div((long)n_seg2 + 1, 256)), dim3(256), 0, s, n_seg2, R, I("seg_off"));
-  hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div(R, 256), n_seg2), dim3(256), 0, s, F("c2_key"), I("seg_off"), R, I("c2_idx"), I("c2_cnt"));
+  r.rank_topk(F(p.c2_key), C - 1, R, R, I(p.seg_off), I(p.c2_idx), I(p.c2_cnt));
   {
     const long total = (long)n_seg2 * R;
-    hipLaunchKernelGGL(det_sorted_gather_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_box")), F("c2_key"),
-                       I("c2_idx"), I("c2_cnt"), R, total, reinterpret_cast<float4*>(F("c2_sbox")), F("c2_skey"), I("c2_keep"), I("c2_inv"));
-    hipLaunchKernelGGL(det_nms_kernel, dim3(n_seg2), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_sbox")), I("c2_keep"), I("c2_cnt"), R,
-                       cfg.box_nms_thresh);
-    hipLaunchKernelGGL(det_final_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F("c2_key"), I("c2_keep"), I("c2_inv"), C - 1, R, total,
-                       F("c2_fkey"));
+    hipLaunchKernelGGL(det_sorted_gather_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, B4(p.c2_box), F(p.c2_key), I(p.c2_idx), I(p.c2_cnt), R,
+                       total, B4(p.c2_sbox), F(p.c2_skey), I(p.c2_keep), I(p.c2_inv));
+    hipLaunchKernelGGL(det_nms_kernel, dim3(n_seg2), dim3(256), 0, s, B4(p.c2_sbox), I(p.c2_keep), I(p.c2_cnt), R, cfg.box_nms_thresh);
+    hipLaunchKernelGGL(det_final_keys_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, F(p.c2_key), I(p.c2_keep), I(p.c2_inv), C - 1, R, total,
+                       F(p.c2_fkey));
   }
-  hipLaunchKernelGGL(det_seg_offsets_kernel, dim3(ceil_div((long)n + 1, 256)), dim3(256), 0, s, n, (C - 1) * R, I("seg_off3"));
-  hipLaunchKernelGGL(det_rank_topk_kernel, dim3(ceil_div((long)(C - 1) * R, 256), n), dim3(256), 0, s, F("c2_fkey"), I("seg_off3"), D, I("f_idx"),
-                     I("f_cnt"));
-  hipLaunchKernelGGL(det_final_kernel, dim3(ceil_div((long)n * D, 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(F("c2_box")), F("c2_key"),
-                     I("f_idx"), I("f_cnt"), D, C - 1, R, n, p.ratio_h, p.ratio_w, reinterpret_cast<float4*>(d_boxes), d_scores, d_labels,
-                     d_counts, reinterpret_cast<float4*>(F("det_resized")));
+  r.rank_topk(F(p.c2_fkey), 1, (C - 1) * R, D, I(p.seg_off3), I(p.f_idx), I(p.f_cnt));
+  hipLaunchKernelGGL(det_final_kernel, dim3(ceil_div((long)n * D, 256)), dim3(256), 0, s, B4(p.c2_box), F(p.c2_key), I(p.f_idx), I(p.f_cnt), D, C - 1,
+                     R, n, p.ratio_h, p.ratio_w, reinterpret_cast<float4*>(d_boxes), d_scores, d_labels, d_counts, B4(p.det_resized));
 
   // ---- mask head --------------------------------------------------------------------------------------------------------------------
   if (d_masks) {
     {
       const long total = (long)n * D * 196 * (DET_FPN_C / 4);
-      hipLaunchKernelGGL(det_roi_align_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, py, reinterpret_cast<const float4*>(F("det_resized")),
-                         d_counts, D, n, 14, 1, F("roi14"));
+      hipLaunchKernelGGL(det_roi_align_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, py, B4(p.det_resized), d_counts, D, n, 14, 1, F(p.roi14));
     }
-    const float* mx = F("roi14");
+    const float* mx = F(p.roi14);
     for (int i = 0; i < 4; ++i) {
-      float* my = (i & 1) ? F("m_b") : F("m_a");
-      rc = run_conv_layer(d->mask_fcn[i], mx, n * D, 14, 14, 1, my, 1, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-      if (rc) return rc;
+      float* my = F((i & 1) ? p.m_b : p.m_a);
+      r.conv(net.mask_fcn[i], mx, n * D, 14, 14, 1, my, 1, nullptr, 1);
       mx = my;
     }
-    rc = run_conv_layer(d->mask_deconv, mx, n * D, 14, 14, 1, F("m_up"), 0, nullptr, 1, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
-    rc = run_conv_layer(d->mask_logits, F("m_up"), n * D * 196 * 4, 1, 1, 0, F("mask_logits"), 0, nullptr, 0, s, SK, DET_SPLITK_FLOATS);
-    if (rc) return rc;
+    r.conv(net.mask_deconv, mx, n * D, 14, 14, 1, F(p.m_up), 0, nullptr, 1);
+    r.conv(net.mask_logits, F(p.m_up), n * D * 196 * 4, 1, 1, 0, F(p.mask_logits), 0, nullptr, 0);
+    if (r.rc) return r.rc;
     ProfScope prof("det_mask_paste", 0.0, (double)n * D * H * W * 4.0, s);
-    hipLaunchKernelGGL(det_mask_paste_kernel, dim3(ceil_div((long)H * W, 256), n * D), dim3(256), 0, s, F("mask_logits"), d->Cmask_s,
+    hipLaunchKernelGGL(det_mask_paste_kernel, dim3(ceil_div((long)H * W, 256), n * D), dim3(256), 0, s, F(p.mask_logits), pad4(C),
                        reinterpret_cast<const float4*>(d_boxes), d_labels, d_counts, D, H, W, d_masks);
   }
   MP_CHECK_HIP(hipGetLastError());
@@ -1054,58 +1072,12 @@ extern "C" int mp_detector_debug_tensor(const mp_detector* d, const char* what, 
                                         int64_t* row_stride, int64_t* n_elements) {
   MP_REQUIRE(d && what && d_ptr && shape4 && border && row_stride && n_elements, "mp_detector_debug_tensor: null pointer");
   MP_REQUIRE(d->ran, "mp_detector_debug_tensor: no forward has run yet");
-  const DetPlan& p = d->last;
-  const std::string w = what;
-  const bool is_stage = w.size() == 2 && w[0] == 'C' && w[1] >= '2' && w[1] <= '5';   // C2..C5: the buffer the stage's last block wrote
-  const bool is_inner = w.size() == 2 && w[0] == 'L' && w[1] >= '2' && w[1] <= '5';   // L2..L5: the FPN's top-down maps (plan buffers L0..L3)
-  auto it = p.off.find(is_stage ? p.stage_buf[w[1] - '2'] : is_inner ? "L" + std::to_string(w[1] - '2') : w);
-  MP_REQUIRE(it != p.off.end(), "mp_detector_debug_tensor: unknown tensor '%s'", what);
-  *d_ptr = (const float*)d->last_ws + it->second;
-  *border = 0;
-  const int R = d->cfg.rpn_post_nms_top_n, D = d->cfg.box_detections_per_img;
-  if (w.size() == 2 && (is_inner || (w[0] == 'P' && w[1] >= '2' && w[1] <= '6'))) {
-    const int l = w[1] - '2';
-    shape4[0] = p.n; shape4[1] = p.fh[l]; shape4[2] = p.fw[l]; shape4[3] = DET_FPN_C;
-    *border = 1;
-    *row_stride = DET_FPN_C;
-  } else if (is_stage) {
-    const int st = w[1] - '2';
-    shape4[0] = p.n; shape4[1] = p.fh[st]; shape4[2] = p.fw[st]; shape4[3] = 256 << st;
-    *border = 1;
-    *row_stride = shape4[3];
-  } else if (w == "pool") {   // stem + max-pool output, the input of the first body stage
-    shape4[0] = p.n; shape4[1] = p.Hp / 4; shape4[2] = p.Wp / 4; shape4[3] = 64;
-    *border = 1;
-    *row_stride = 64;
-  } else if (w == "roi7") {   // box head RoIAlign rows [7][7][256]
-    shape4[0] = (int64_t)p.n * R; shape4[1] = 7 * 7 * DET_FPN_C; shape4[2] = 1; shape4[3] = 1; *row_stride = 7 * 7 * DET_FPN_C;
-  } else if (w == "roi14") {  // mask head RoIAlign maps
-    shape4[0] = (int64_t)p.n * D; shape4[1] = 14; shape4[2] = 14; shape4[3] = DET_FPN_C;
-    *border = 1;
-    *row_stride = DET_FPN_C;
-  } else if (w == "proposals") {
-    shape4[0] = p.n; shape4[1] = R; shape4[2] = 4; shape4[3] = 1; *row_stride = 4;
-  } else if (w == "proposal_scores") {
-    shape4[0] = p.n; shape4[1] = R; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
-  } else if (w == "keys") {   // RPN objectness logits of every anchor, (level, y, x, a) order
-    shape4[0] = p.n; shape4[1] = p.a_total; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
-  } else if (w == "proposal_counts" || w == "f_cnt") {
-    shape4[0] = p.n; shape4[1] = 1; shape4[2] = 1; shape4[3] = 1; *row_stride = 1;
-  } else if (w == "class_logits") {
-    shape4[0] = (int64_t)p.n * R; shape4[1] = 5 * d->C; shape4[2] = 1; shape4[3] = 1; *row_stride = d->Cpred_s;
-  } else if (w == "mask_logits") {
-    shape4[0] = (int64_t)p.n * D * 196 * 4; shape4[1] = d->C; shape4[2] = 1; shape4[3] = 1; *row_stride = d->Cmask_s;
-  } else if (w == "det_resized") {
-    shape4[0] = p.n; shape4[1] = D; shape4[2] = 4; shape4[3] = 1; *row_stride = 4;
-  } else if (w == "x0") {
-    shape4[0] = p.n; shape4[1] = p.Hp; shape4[2] = p.Wp; shape4[3] = 4; *border = 3; *row_stride = 4;
-  } else {
-    set_error("mp_detector_debug_tensor: '%s' is an internal buffer without a published shape", what);
-    return MP_ERR_INVALID;
-  }
-  if (*border) *n_elements = shape4[0] * (shape4[1] + 2 * *border) * (shape4[2] + 2 * *border) * shape4[3];
-  else if (shape4[2] == 4) *n_elements = shape4[0] * shape4[1] * 4;          // box lists
-  else if (*row_stride > 1) *n_elements = shape4[0] * *row_stride;            // row matrices with a padded row
-  else *n_elements = shape4[0] * shape4[1];                                   // flat per-image lists / counters
+  const DetBuf* b = det_find_tap(d->last, what);
+  MP_REQUIRE(b, "mp_detector_debug_tensor: '%s' is not a published tensor (unknown, or an internal buffer)", what);
+  *d_ptr = (const float*)d->last_ws + b->off;
+  for (int k = 0; k < 4; ++k) shape4[k] = b->shape[k];
+  *border = b->border;
+  *row_stride = b->row_stride;
+  *n_elements = b->n_elements;
   return MP_OK;
 }

@@ -1525,21 +1525,29 @@ class DetectorNet(_Handle):
                                       counts.data_ptr(), _ptr(masks), self._ws.data_ptr(), self._ws.numel(), _stream()))
         return boxes, scores, labels, counts, masks
 
-    def debug_tensor(self, what: str) -> torch.Tensor:
-        """a COPY of an intermediate of the last forward (parity tests): padded maps come back as their [n,h,w,c] interior.
-        Taps: "x0", "pool", "C2".."C5", "L2".."L5", "P2".."P6", "keys", "proposals", "proposal_scores", "proposal_counts", "roi7", "class_logits",
-        "f_cnt", "det_resized", "roi14", "mask_logits" (shapes: mp_detector_debug_tensor in include/mp_engine.h)"""
+    def debug_buffer(self, what: str):
+        """the WHOLE buffer behind a tap of the last forward, borders and row padding included -> (flat tensor, shape4, border,
+        row_stride).  The tensor is a VIEW of the workspace (the next forward overwrites it), int32 for the two count taps (the C entry
+        has no slot for the element type), else float32."""
         lib = _lib.load()
         ptr, shp, border, rs, n_el = C.c_void_p(), (C.c_int64 * 4)(), C.c_int32(0), C.c_int64(0), C.c_int64(0)
         check(lib.mp_detector_debug_tensor(self.handle, what.encode(), C.byref(ptr), shp, C.byref(border), C.byref(rs), C.byref(n_el)))
         off = ptr.value - self._ws.data_ptr()
-        is_int = what in ("proposal_counts", "f_cnt")
-        flat = self._ws[off : off + 4 * n_el.value].view(torch.int32 if is_int else torch.float32).clone()
-        s, b = [int(v) for v in shp], border.value
+        if off < 0 or off + 4 * n_el.value > self._ws.numel():
+            raise EngineError(f"debug tap '{what}' lies outside the workspace of the last forward")
+        dt = torch.int32 if what in ("proposal_counts", "f_cnt") else torch.float32
+        return self._ws[off : off + 4 * n_el.value].view(dt), [int(v) for v in shp], border.value, rs.value
+
+    def debug_tensor(self, what: str) -> torch.Tensor:
+        """a COPY of an intermediate of the last forward (parity tests): padded maps come back as their [n,h,w,c] interior.
+        Taps: "x0", "pool", "C2".."C5", "L2".."L5", "P2".."P6", "keys", "proposals", "proposal_scores", "proposal_counts", "roi7", "class_logits",
+        "f_cnt", "det_resized", "roi14", "mask_logits" (shapes: mp_detector_debug_tensor in include/mp_engine.h)"""
+        flat, s, b, rs = self.debug_buffer(what)
+        flat = flat.clone()
         if b:
             return flat.view(s[0], s[1] + 2 * b, s[2] + 2 * b, s[3])[:, b : b + s[1], b : b + s[2]].contiguous()
         if s[2] == 4:
             return flat.view(s[0], s[1], 4)
-        if rs.value > 1:
-            return flat.view(s[0], rs.value)[:, : s[1]].contiguous()
+        if rs > 1:
+            return flat.view(s[0], rs)[:, : s[1]].contiguous()
         return flat.view(s[0], s[1])

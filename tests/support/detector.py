@@ -3,7 +3,6 @@ row matrices whose rows are padded past their logical width), the layout convers
 MultiScaleRoIAlign reference that takes its decisions in float32 as the kernel does, and a rank-for-rank matcher of selection results that tolerates only counted, near-tied exceptions."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, Optional, Sequence
 
 import numpy as np
@@ -19,17 +18,8 @@ def raw_debug(net, what: str):
     """the WHOLE buffer behind a debug tap, borders and row padding included -> (flat CPU tensor, shape4, border, row_stride).
     DetectorNet.debug_tensor returns the logical view only; this one lets a test check what lies outside it (zero borders, zero pad
     columns of the padded row matrices)."""
-    from megapose6d_amd import _lib
-    from megapose6d_amd._lib import check
-
-    lib = _lib.load()
-    ptr, shp, border, rs, n_el = C.c_void_p(), (C.c_int64 * 4)(), C.c_int32(0), C.c_int64(0), C.c_int64(0)
-    check(lib.mp_detector_debug_tensor(net.handle, what.encode(), C.byref(ptr), shp, C.byref(border), C.byref(rs), C.byref(n_el)))
-    off = ptr.value - net._ws.data_ptr()
-    assert off >= 0 and off + 4 * n_el.value <= net._ws.numel()
-    dt = torch.int32 if what in ("proposal_counts", "f_cnt") else torch.float32
-    flat = net._ws[off : off + 4 * n_el.value].view(dt).cpu().clone()
-    return flat, [int(v) for v in shp], border.value, rs.value
+    flat, shp, border, rs = net.debug_buffer(what)
+    return flat.cpu(), shp, border, rs
 
 
 def debug_rows(net, what: str) -> torch.Tensor:

@@ -616,3 +616,68 @@ def test_detector_convolutions_stay_on_the_fp32_kernel():
     convs = [k for k in prof if k.startswith("conv") and k != "conv_splitk_reduce"]
     assert convs and all(k.startswith("conv_nhwc_f32_mfma") for k in convs), sorted(prof)
     assert sum(int(prof[k]["launches"]) for k in convs) >= 80, prof   # the forward has 80 convolution layers (53 ResNet-50, 8 FPN, 10 RPN, 3 box head, 6 mask head)
+
+
+TAPS = ["x0", "pool", "C2", "C3", "C4", "C5", "L2", "L3", "L4", "L5", "P2", "P3", "P4", "P5", "P6", "keys", "proposals", "proposal_scores",
+        "proposal_counts", "roi7", "class_logits", "f_cnt", "det_resized", "roi14", "mask_logits"]
+
+
+def test_every_published_tap_resolves():
+    """every tap DetectorNet.debug_tensor documents, at the smallest frame the detector admits: the buffer lies inside the workspace the
+    plan reports, no two taps overlap, n_elements is what (shape4, border, row_stride) imply under the three published layouts, the two
+    count taps are int32; unknown and internal names, and a detector that has not run, are clean errors"""
+    from megapose6d_amd import _lib
+    from megapose6d_amd import engine as eng
+    from megapose6d_amd._lib import EngineError
+
+    run = _run("small")
+    net, spec = run.net, run.spec
+    total = _lib.load().mp_detector_workspace_bytes(net.handle, spec.n, spec.H, spec.W)
+    assert 0 < total <= net._ws.numel()
+    spans = []
+    for what in TAPS:
+        flat, (s0, s1, s2, s3), b, rs = net.debug_buffer(what)
+        if b:                      # padded NHWC map
+            n_el = s0 * (s1 + 2 * b) * (s2 + 2 * b) * s3
+        elif s2 == 4:              # box list
+            n_el = s0 * s1 * 4
+        elif rs > 1:               # row matrix, rows padded to row_stride
+            n_el = s0 * rs
+        else:                      # flat per-image list / counter
+            n_el = s0 * s1
+        assert flat.numel() == n_el, (what, flat.numel(), n_el)
+        assert flat.dtype == (torch.int32 if what in ("proposal_counts", "f_cnt") else torch.float32), what
+        lo = flat.data_ptr() - net._ws.data_ptr()
+        assert 0 <= lo and lo + 4 * n_el <= total, (what, lo, n_el, total)
+        spans.append((lo, lo + 4 * n_el, what))
+    spans.sort()
+    for a, b in zip(spans, spans[1:]):
+        assert a[1] <= b[0], (a, b)
+    for what in ("nope", "cand_box"):
+        with pytest.raises(EngineError, match=what):
+            net.debug_tensor(what)
+    fresh = eng.DetectorNet(run.sd, spec.C, spec.mn, spec.mx)
+    with pytest.raises(EngineError, match="no forward"):
+        fresh.debug_tensor("x0")
+    fresh.close()
+
+
+def test_missing_or_missized_checkpoint_tensor_is_a_clean_error():
+    """a checkpoint without one tensor of each kind the loader treats differently (plain convolution weight, FrozenBatchNorm term, a
+    tensor of a merged head, a permuted one), or with a mis-sized one, is an EngineError that names the key; the loader is intact after
+    it: the complete checkpoint loads"""
+    import re
+
+    from megapose6d_amd import engine as eng
+    from megapose6d_amd._lib import EngineError
+
+    sd = _state_dict(Spec(1, 64, 96, 64, 96, 2))
+    fc6 = "roi_heads.box_head.fc6.weight"
+    broken = [(k, {q: v for q, v in sd.items() if q != k})
+              for k in ("backbone.body.layer4.2.conv3.weight", "backbone.body.layer2.0.downsample.1.running_var", "rpn.head.bbox_pred.bias",
+                        "roi_heads.mask_predictor.conv5_mask.weight")]
+    broken.append((fc6, {**sd, fc6: sd[fc6][:-1]}))   # one row too few
+    for key, bad in broken:
+        with pytest.raises(EngineError, match=re.escape(key)):
+            eng.DetectorNet(bad, 2, 64, 96)
+        eng.DetectorNet(sd, 2, 64, 96).close()
