@@ -43,6 +43,15 @@ int mp_conv_wino_bf16_telemetry(int on);
  * launches, counted while the event profiler runs */
 int mp_conv_stem_bg_stats(double* background_wgs, double* total_wgs, int reset);
 
+/* Parity taps of a pose backbone (tests): the device address, the interior shape {N, H, W, C} and the border of an intermediate that
+ * survives a forward inside `d_ws`, for the workspace, batch and crop size of that forward (an error if the last forward on `d_ws` was
+ * another one).  Padded NHWC, border 1.  "stem": the stem map, written on the fp32 and f16 tensor paths only (an error after a record-path
+ * forward with the fused pool, which never writes it); "layer1".."layer4": the output of each stage; "layer1_act".."layer3_act"
+ * (pre-activation nets only): relu(bn1(.)) of the next stage's first block, the second output of the stage's last block;
+ * "layer2_down".."layer4_down": the 1x1 downsample of block 0 (with its BatchNorm on vanilla_resnet34).  No forward reads this entry. */
+int mp_backbone_debug_tensor(const mp_backbone* bb, const char* what, const void* d_ws, int batch, int h, int w, const void** d_ptr,
+                             int64_t shape4[4], int32_t* border);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,7 @@ SIGNATURES = {
     "mp_backbone_forward_xrec_mask": (_i, [_vp, _vp, _u32, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_backbone_forward_xrec_sparse": (_i, [_vp, _vp, _u32, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mp_backbone_flops": (C.c_double, [_vp, _i, _i, _i]),
+    "mp_backbone_debug_tensor": (_i, [_vp, C.c_char_p, _vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "mp_normalize_T": (_i, [_vp, _i, _vp, _vp]),
     "mp_init_extents": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "mp_init_poses_from_boxes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp]),

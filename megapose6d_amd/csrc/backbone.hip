@@ -53,7 +53,7 @@ struct mp_backbone {
   std::map<uint32_t, int> stem_tail_forms;       // ... -> which of the two blobs is packed for a tail-plane walk (mp_conv_stem_tail_forms bits)
   // workspace bookkeeping: borders are zeroed once per (pointer, batch, h, w); several workspaces may be live at once
   // (one per HIP stream when half-batches are interleaved on two streams)
-  struct WsKey { void* ptr; int batch, h, w; };
+  struct WsKey { void* ptr; int batch, h, w; bool stem_written; };   // stem_written: the last forward there wrote S (not the fused-pool record path)
   std::vector<WsKey> ws_known;
 };
 
@@ -113,6 +113,30 @@ Geometry geometry(const mp_backbone* bb, int h, int w) {
   return g;
 }
 
+// The carve-up of a workspace: [stem out S][per stage: A, Aact (wide only), B, C][split-K scratch].  Offsets in floats from the base, so
+// that the size (mp_backbone_workspace_bytes), the forward and the debug taps (mp_backbone_debug_tensor) read the same layout.
+struct WsLayout {
+  Geometry g;
+  size_t S = 0, A[4], Aact[4], B[4], C[4], SK = 0;   // Aact: the pre-activation nets only (0 and unused on the vanilla net)
+  size_t total = 0;                                  // floats, the split-K scratch included
+};
+
+WsLayout ws_layout(const mp_backbone* bb, int batch, int h, int w) {
+  WsLayout L;
+  L.g = geometry(bb, h, w);
+  size_t p = align_up(buf_floats(batch, L.g.h1, L.g.w1, bb->stageC[0]), 64);
+  for (int st = 0; st < 4; ++st) {
+    const size_t n = align_up(buf_floats(batch, L.g.hs[st], L.g.ws[st], bb->stageC[st]), 64);
+    L.A[st] = p; p += n;
+    L.Aact[st] = 0;
+    if (bb->wide) { L.Aact[st] = p; p += n; }
+    L.B[st] = p; p += n;
+    L.C[st] = p; p += n;
+  }
+  L.SK = p;
+  L.total = p + SPLITK_WS_FLOATS;
+  return L;
+}
 
 }  // namespace
 
@@ -206,12 +230,7 @@ extern "C" int mp_backbone_input_border(const mp_backbone* bb) { return bb ? bb-
 // workspace layout: [stem out][per stage: A, A_act (wide only), B, C]
 extern "C" size_t mp_backbone_workspace_bytes(const mp_backbone* bb, int batch, int h, int w) {
   if (!bb || batch <= 0) return 0;
-  const Geometry g = geometry(bb, h, w);
-  size_t fl = align_up(buf_floats(batch, g.h1, g.w1, bb->stageC[0]), 64);
-  const int per_stage = bb->wide ? 4 : 3;
-  for (int s = 0; s < 4; ++s) fl += per_stage * align_up(buf_floats(batch, g.hs[s], g.ws[s], bb->stageC[s]), 64);
-  fl += SPLITK_WS_FLOATS;
-  return fl * sizeof(float);
+  return ws_layout(bb, batch, h, w).total * sizeof(float);
 }
 
 extern "C" int mp_backbone_workspace_reset(mp_backbone* bb, const void* d_ws) {
@@ -276,10 +295,11 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
   const bool x_f16 = x_mode == 1;
   MP_REQUIRE(bb && d_x && d_out && d_ws, "mp_backbone_forward: null pointer");
   if (batch == 0) return MP_OK;
-  const size_t need = mp_backbone_workspace_bytes(bb, batch, h, w);
+  const WsLayout lay = ws_layout(bb, batch, h, w);
+  const size_t need = lay.total * sizeof(float);
   MP_REQUIRE(ws_bytes >= need, "mp_backbone_forward: workspace %zu < %zu bytes", ws_bytes, need);
   hipStream_t s = (hipStream_t)stream;
-  const Geometry g = geometry(bb, h, w);
+  const Geometry& g = lay.g;
   bool known = false;
   for (const auto& k : bb->ws_known) known = known || (k.ptr == d_ws && k.batch == batch && k.h == h && k.w == w);
   if (!known) {
@@ -287,20 +307,18 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
     for (size_t i = 0; i < bb->ws_known.size();)     // a pointer re-used with another geometry invalidates its old entry
       if (bb->ws_known[i].ptr == d_ws) bb->ws_known.erase(bb->ws_known.begin() + i); else ++i;
     if (bb->ws_known.size() >= 8) bb->ws_known.erase(bb->ws_known.begin());
-    bb->ws_known.push_back({d_ws, batch, h, w});
+    bb->ws_known.push_back({d_ws, batch, h, w, false});
   }
-  float* p = (float*)d_ws;
-  float* S = p; p += align_up(buf_floats(batch, g.h1, g.w1, bb->stageC[0]), 64);
+  float* const base = (float*)d_ws;
+  float* S = base + lay.S;
   float *A[4], *Aact[4], *Bf[4], *Cf[4];
   for (int st = 0; st < 4; ++st) {
-    const size_t n = align_up(buf_floats(batch, g.hs[st], g.ws[st], bb->stageC[st]), 64);
-    A[st] = p; p += n;
-    Aact[st] = nullptr;
-    if (bb->wide) { Aact[st] = p; p += n; }
-    Bf[st] = p; p += n;
-    Cf[st] = p; p += n;
+    A[st] = base + lay.A[st];
+    Aact[st] = bb->wide ? base + lay.Aact[st] : nullptr;
+    Bf[st] = base + lay.B[st];
+    Cf[st] = base + lay.C[st];
   }
-  float* SK = p;  // split-K scratch (SPLITK_WS_FLOATS)
+  float* SK = base + lay.SK;  // split-K scratch (SPLITK_WS_FLOATS)
   int rc;
   bool stem_pooled = false;
   // stem: conv + folded bn + relu, then 3x3/s2 max pool (+ first block's pre-activation for the wide nets)
@@ -346,6 +364,8 @@ static int backbone_forward_impl(mp_backbone* bb, const float* d_x, int x_mode, 
     rc = run_conv_layer(bb->stem, d_x, batch, h, w, bb->in_border, S, 1, nullptr, 1, s, SK, SPLITK_WS_FLOATS, nullptr, nullptr, nullptr, x_f16);
   }
   if (rc) return rc;
+  for (auto& k : bb->ws_known)
+    if (k.ptr == d_ws && k.batch == batch && k.h == h && k.w == w) k.stem_written = !stem_pooled;
   const Block& b0 = bb->blocks[0];
   if (!stem_pooled) {
     rc = mp_maxpool3x3s2(S, batch, g.h1, g.w1, bb->stageC[0], 1, A[0], 1, bb->wide ? Aact[0] : nullptr, bb->wide ? b0.pre.d_scale : nullptr,
@@ -410,6 +430,50 @@ extern "C" int mp_backbone_forward_xrec_sparse(mp_backbone* bb, const void* d_xr
 extern "C" int mp_backbone_forward_f16(mp_backbone* bb, const void* d_x_half, int batch, int h, int w, float* d_out, float* d_sigmoid,
                                        float* d_feat, void* d_ws, size_t ws_bytes, mp_stream stream) {
   return backbone_forward_impl(bb, (const float*)d_x_half, 1, 0, batch, h, w, d_out, d_sigmoid, d_feat, d_ws, ws_bytes, stream);
+}
+
+// Parity taps (tests): where an intermediate that survives a forward lies in the workspace.  Nothing on the forward path reads this.
+extern "C" int mp_backbone_debug_tensor(const mp_backbone* bb, const char* what, const void* d_ws, int batch, int h, int w, const void** d_ptr,
+                                        int64_t shape4[4], int32_t* border) {
+  MP_REQUIRE(bb && what && d_ws && d_ptr && shape4 && border, "mp_backbone_debug_tensor: null pointer");
+  MP_REQUIRE(batch > 0, "mp_backbone_debug_tensor: batch %d", batch);
+  const mp_backbone::WsKey* key = nullptr;
+  for (const auto& k : bb->ws_known)
+    if (k.ptr == d_ws && k.batch == batch && k.h == h && k.w == w) key = &k;
+  MP_REQUIRE(key, "mp_backbone_debug_tensor: the last forward on this workspace was not one of %d x %d x %d (or none has run)", batch, h, w);
+  const WsLayout lay = ws_layout(bb, batch, h, w);
+  const std::string name(what);
+  size_t off = 0;
+  int H = 0, W = 0, C = 0;
+  bool found = false;
+  if (name == "stem") {
+    MP_REQUIRE(key->stem_written, "mp_backbone_debug_tensor: 'stem' was not written: the record path pools inside the stem kernel "
+               "(the fp32 and f16 tensor paths write it)");
+    off = lay.S; H = lay.g.h1; W = lay.g.w1; C = bb->stageC[0];
+    found = true;
+  } else if (name.size() >= 6 && name.compare(0, 5, "layer") == 0 && name[5] >= '1' && name[5] <= '4') {
+    const int st = name[5] - '1';
+    const std::string rest = name.substr(6);
+    H = lay.g.hs[st]; W = lay.g.ws[st]; C = bb->stageC[st];
+    if (rest.empty()) {
+      off = lay.A[st];
+      found = true;
+    } else if (rest == "_act") {
+      MP_REQUIRE(bb->wide && st < 3, "mp_backbone_debug_tensor: '%s' does not apply: only the pre-activation nets write a second output, "
+                 "and only stages 1..3 have a next block", what);
+      off = lay.Aact[st];
+      found = true;
+    } else if (rest == "_down") {
+      MP_REQUIRE(st > 0, "mp_backbone_debug_tensor: '%s' does not apply: stage 1 has no downsample", what);
+      off = lay.C[st];
+      found = true;
+    }
+  }
+  MP_REQUIRE(found, "mp_backbone_debug_tensor: '%s' is not a published tensor (stem, layer1..4, layer1..3_act, layer2..4_down)", what);
+  *d_ptr = (const float*)d_ws + off;
+  shape4[0] = batch; shape4[1] = H; shape4[2] = W; shape4[3] = C;
+  *border = 1;
+  return MP_OK;
 }
 
 extern "C" double mp_backbone_flops(const mp_backbone* bb, int batch, int h, int w) {

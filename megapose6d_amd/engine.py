@@ -655,6 +655,28 @@ class Backbone(_Handle):
         fn = lib.mp_backbone_forward_f16 if x.dtype == torch.float16 else lib.mp_backbone_forward
         check(fn(self.handle, x.data_ptr(), batch, h, w, out.data_ptr(), _ptr(sigmoid), _ptr(feat), ws.data_ptr(), ws.numel(), _stream()))
 
+    def debug_buffer(self, what: str, batch: int, h: int, w: int, slot: int = 0):
+        """the WHOLE padded buffer behind a tap of the last forward on `slot` (which must have been one of batch x h x w) ->
+        (flat float32 tensor, [n, h, w, c] of the interior, border).  A VIEW of the workspace: the next forward overwrites it."""
+        ws = self._ws.get(slot)
+        if ws is None:
+            raise EngineError(f"debug tap '{what}': no forward has run on workspace slot {slot}")
+        ptr, shp, border = C.c_void_p(), (C.c_int64 * 4)(), C.c_int32(0)
+        check(_lib.load().mp_backbone_debug_tensor(self.handle, what.encode(), ws.data_ptr(), batch, h, w, C.byref(ptr), shp, C.byref(border)))
+        n, hh, ww, c = (int(v) for v in shp)
+        b = border.value
+        off, n_bytes = ptr.value - ws.data_ptr(), 4 * n * (hh + 2 * b) * (ww + 2 * b) * c
+        if off < 0 or off + n_bytes > ws.numel():
+            raise EngineError(f"debug tap '{what}' lies outside the workspace of the last forward")
+        return ws[off : off + n_bytes].view(torch.float32), [n, hh, ww, c], b
+
+    def debug_tensor(self, what: str, batch: int, h: int, w: int, slot: int = 0) -> torch.Tensor:
+        """a COPY of the [n, h, w, c] interior of an intermediate of the last forward (parity tests).  Taps: "stem" (not on the record path),
+        "layer1".."layer4", "layer1_act".."layer3_act" (pre-activation nets), "layer2_down".."layer4_down" (mp_backbone_debug_tensor in
+        include/mp_engine_debug.h)"""
+        flat, s, b = self.debug_buffer(what, batch, h, w, slot)
+        return flat.view(s[0], s[1] + 2 * b, s[2] + 2 * b, s[3])[:, b : b + s[1], b : b + s[2]].clone()
+
 
 # --------------------------------------------------------------------------- #
 def normalize_T(T: torch.Tensor) -> torch.Tensor:
