@@ -657,6 +657,47 @@ int mp_det_match(const double* d_iou /*[C], the index's order*/, const int32_t* 
                  mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* BOP's result files: COCO run-length encoding (RLE) of binary masks, the form in which the */
+/* detection and segmentation tasks carry a mask, both ways (csrc/rle.hip; contract in       */
+/* csrc/rle_core.h).  pycocotools is third party: its format is restated, parity unpinned.   */
+/* The compressed string and the files are host Python (megapose6d_amd/bop_files.py).        */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_rle_count and mp_rle_encode need (0 for arguments they reject). */
+size_t mp_rle_workspace_bytes(int n, int h, int w, int rows_per_segment);
+/* Masks are h x w bytes, row-major; a pixel is set when its byte is non-zero (the rule of mp_mask_pair_counts).  The list of mask m walks
+   it in column-major order, p = x * h + y, and alternates run lengths of unset and set pixels, starting with unset (so its first entry
+   is 0 when pixel 0 is set); a run continues from the bottom of a column into the top of the next; the entries sum to h * w.
+   d_n_counts[m] = the length of the list (1 .. h * w + 1), d_areas[m] = the number of set pixels, d_boxes[m] = x_min, y_min, x_max, y_max
+   of the set pixels, inclusive, (0, 0, -1, -1) for an empty mask.  rows_per_segment = the rows one lane walks: 0 the library's choice
+   (32), any other value only changes the decomposition, never a result.  16-byte loads where a row's 16 columns lie inside it on a
+   16-byte boundary, else byte loads with the same results (any width, any byte alignment of d_masks).  h, w >= 1, h * w <= 2^31 - 2,
+   at most 2^30 jobs (mask, row segment, 16 columns) and as many (mask, column, row segment) entries.  Two launches on `stream`, no
+   atomics, no workgroup waits for another.  What the call leaves in d_ws is the input of mp_rle_encode on the same masks and arguments.
+   n == 0 is a successful no-op; any bad argument (a null pointer where one is needed, h or w < 1, too many pixels or jobs, a negative
+   count, a workspace too small or not 16-byte aligned) returns non-zero before anything is launched. */
+int mp_rle_count(const uint8_t* d_masks /*[n,h,w]*/, int n, int h, int w, int rows_per_segment, int32_t* d_n_counts /*[n]*/,
+                 int32_t* d_areas /*[n] or NULL*/, int32_t* d_boxes /*[n,4] or NULL*/, void* d_ws, size_t ws_bytes, mp_stream stream);
+/* Writes the lists: mask m's into d_counts[h_offsets[m] .. h_offsets[m + 1] - 1].  To be called after mp_rle_count on the same masks,
+   arguments and workspace, with h_offsets (host memory, n + 1 entries) the exclusive sums of the d_n_counts it gave.  h_offsets must
+   start at 0, not descend and end within `capacity`, the number of int32 d_counts holds; every store is checked against the list's
+   length as h_offsets states it, so offsets that do not fit the masks cost wrong lists, never a store outside d_counts.  One launch on
+   `stream`; h_offsets is copied from pageable host memory.  n == 0 is a successful no-op; any bad argument returns non-zero before
+   anything is launched. */
+int mp_rle_encode(const uint8_t* d_masks /*[n,h,w]*/, int n, int h, int w, int rows_per_segment, const int64_t* h_offsets /*[n+1], host*/,
+                  int32_t* d_counts /*[h_offsets[n]]*/, long long capacity, void* d_ws, size_t ws_bytes, mp_stream stream);
+/* bytes of device scratch mp_rle_decode needs for n lists of h x w masks in `capacity` counts (0 for arguments it rejects). */
+size_t mp_rle_decode_workspace_bytes(int n, int h, int w, long long capacity);
+/* The masks of n lists: d_masks[m] (0 / 1 bytes, row-major) from d_counts[h_offsets[m] .. h_offsets[m + 1] - 1].  d_status[m] = 0 for a
+   well-formed list, else the OR of 1 (no entries), 2 (a negative entry), 4 (the entries do not sum to h * w), and the mask is all
+   zeros.  h_offsets (host memory) must start at 0, not descend and end within `capacity`, the number of int32 d_counts holds, and is
+   tested before anything is launched; the counts themselves are only summed and compared until their list has passed, so a wrong file
+   costs a status, never an access out of range.  A pixel is the parity of its run, found by a search of at most 32 steps over the
+   cumulative ends.  Limits of h, w and n as for mp_rle_count.  Three launches on `stream`, no atomics; h_offsets is copied from pageable
+   host memory.  n == 0 is a successful no-op; any bad argument returns non-zero before anything is launched. */
+int mp_rle_decode(const int32_t* d_counts /*[capacity]*/, const int64_t* h_offsets /*[n+1], host*/, long long capacity, int n, int h, int w,
+                  uint8_t* d_masks /*[n,h,w]*/, int32_t* d_status /*[n]*/, void* d_ws, size_t ws_bytes, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* BOP's model info: the exact diameter of a point set (the largest distance between two of */
 /* its points: `diameter` of a BOP dataset's models_info.json, bop_toolkit's calc_model_info */
 /* / calc_pts_diameter, an O(N^2) maximum) and its axis-aligned bounds                       */

@@ -183,6 +183,11 @@ SIGNATURES = {
     "mp_mask_pair_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "mp_det_match_workspace_bytes": (_sz, [_i, _i]),
     "mp_det_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mp_rle_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mp_rle_count": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mp_rle_encode": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _sz, _vp]),
+    "mp_rle_decode_workspace_bytes": (_sz, [_i, _i, _i, C.c_longlong]),
+    "mp_rle_decode": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mp_model_info_scratch_bytes": (_sz, [_i, _vp, _i]),
     "mp_model_info": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_symmetry_check_scratch_bytes": (_sz, [_i]),

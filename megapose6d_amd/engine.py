@@ -1078,6 +1078,78 @@ def det_match(iou: torch.Tensor, index: Dict[str, torch.Tensor], gt_ignore: torc
 
 
 # --------------------------------------------------------------------------- #
+# BOP's result files (bop_files): COCO run-length encoding of masks, csrc/rle.hip
+RLE_MAX_PIXELS = (1 << 31) - 2       # h * w
+RLE_STATUS_EMPTY, RLE_STATUS_NEGATIVE, RLE_STATUS_SUM = 1, 2, 4   # bits of rle_decode's status
+
+
+def _host_offsets(offsets, n_counts: int) -> np.ndarray:
+    h_off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets).astype(np.int64)
+    if h_off.ndim != 1 or len(h_off) < 1 or h_off[0] != 0 or (np.diff(h_off) < 0).any() or h_off[-1] > n_counts:
+        raise EngineError(f"offsets must be [n + 1], start at 0, not descend and end within the {n_counts} counts")
+    return h_off
+
+
+def rle_encode(masks: torch.Tensor, rows_per_segment: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """COCO run-length encoding of masks (mp_rle_count, mp_rle_encode; the format is stated in csrc/rle_core.h).  masks [n,h,w] uint8 or
+    bool on the device (a pixel is set when its byte is non-zero; taken through a uint8 view, no copy) -> counts [total] int32, the
+    lists one after the other, offsets [n + 1] int64 (mask m's list is counts[offsets[m]:offsets[m + 1]]), areas [n] int32, boxes [n,4]
+    int32 (x_min, y_min, x_max, y_max inclusive; 0 0 -1 -1 for an empty mask), all on the device.  A list walks the mask column by
+    column and alternates run lengths of unset and set pixels, starting with unset.  rows_per_segment (0: the library's choice) only
+    changes the decomposition, never a result.  ONE synchronisation: the n list lengths are read back between the two calls, as the
+    ragged total is not known before."""
+    masks = _dev_bytes("masks", masks)
+    if masks.dim() != 3:
+        raise EngineError(f"masks must be [n,h,w], got {tuple(masks.shape)}")
+    n, h, w = (int(v) for v in masks.shape)
+    dev = masks.device
+    n_counts = torch.empty(n, dtype=torch.int32, device=dev)
+    areas = torch.empty(n, dtype=torch.int32, device=dev)
+    boxes = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), areas, boxes
+    lib = _lib.load()
+    n_bytes = lib.mp_rle_workspace_bytes(n, h, w, int(rows_per_segment))
+    if n_bytes == 0:
+        raise EngineError(f"rle_encode: masks of {h} x {w} (at least 1 x 1, at most {RLE_MAX_PIXELS} pixels), rows_per_segment "
+                          f"{rows_per_segment} (not negative), or too many jobs in one call")
+    ws = _workspace(n_bytes, dev)
+    check(lib.mp_rle_count(masks.data_ptr(), n, h, w, int(rows_per_segment), n_counts.data_ptr(), areas.data_ptr(), boxes.data_ptr(),
+                           ws.data_ptr(), ws.numel(), _stream()))
+    h_off = np.zeros(n + 1, np.int64)
+    np.cumsum(n_counts.cpu().numpy(), dtype=np.int64, out=h_off[1:])       # the one synchronisation
+    total = int(h_off[-1])
+    counts = torch.empty(total, dtype=torch.int32, device=dev)
+    check(lib.mp_rle_encode(masks.data_ptr(), n, h, w, int(rows_per_segment), h_off.ctypes.data, counts.data_ptr(), total, ws.data_ptr(),
+                            ws.numel(), _stream()))
+    return counts, torch.from_numpy(h_off).to(dev), areas, boxes
+
+
+def rle_decode(counts: torch.Tensor, offsets, h: int, w: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Masks from run-length lists (mp_rle_decode).  counts [total] int32 on the device, offsets [n + 1] (host ints, an array or a
+    tensor: the launch tests a host copy of them) -> masks [n,h,w] uint8 (0 / 1), status [n] int32: 0 for a well-formed list, else the
+    OR of RLE_STATUS_EMPTY (no entries), RLE_STATUS_NEGATIVE (a negative entry) and RLE_STATUS_SUM (the entries do not sum to h * w), and
+    the mask is all zeros.  Nothing synchronises (a tensor of offsets on the device is read back before the launch)."""
+    counts = _dev_i32(counts)
+    if counts.dim() != 1:
+        raise EngineError(f"counts must be [total], got {tuple(counts.shape)}")
+    dev = counts.device
+    h_off = _host_offsets(offsets, counts.shape[0])
+    n, h, w = len(h_off) - 1, int(h), int(w)
+    if h < 1 or w < 1 or h * w > RLE_MAX_PIXELS:
+        raise EngineError(f"rle_decode: masks of {h} x {w}: at least 1 x 1, at most {RLE_MAX_PIXELS} pixels")
+    masks = torch.empty(n, h, w, dtype=torch.uint8, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return masks, status
+    lib = _lib.load()
+    ws = _workspace(lib.mp_rle_decode_workspace_bytes(n, h, w, counts.shape[0]), dev)
+    check(lib.mp_rle_decode(counts.data_ptr(), h_off.ctypes.data, counts.shape[0], n, h, w, masks.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                            ws.numel(), _stream()))
+    return masks, status
+
+
+# --------------------------------------------------------------------------- #
 # BOP's model info (evaluation): csrc/model_info.hip
 MODEL_INFO_TILE_STEP = 64            # a forced tile is a multiple of this ...
 MODEL_INFO_MAX_TILE = 1024           # ... and at most this
