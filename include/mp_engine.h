@@ -698,6 +698,51 @@ int mp_rle_decode(const int32_t* d_counts /*[capacity]*/, const int64_t* h_offse
                   uint8_t* d_masks /*[n,h,w]*/, int32_t* d_status /*[n]*/, void* d_ws, size_t ws_bytes, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Onboarding an object without a CAD model: posed depth views fused into a truncated     */
+/* signed distance field (TSDF) on a voxel grid in the object's frame, and the welded,     */
+/* coloured triangle mesh of its zero level by marching tetrahedra (csrc/tsdf.hip; contract */
+/* in csrc/tsdf_core.h).  The reference has no counterpart; Open3D / KinectFusion-style      */
+/* tools are third party and absent: parity with them is unpinned.                          */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of a volume of nx x ny x nz nodes: 2 planes of 32-bit words (fp32 sum of truncated distances, int32 count of views), 6 with
+   colours (+ fp32 sums of red, green, blue, int32 colour count); x fastest; 0 for dims out of range (each 2 .. 512, at most 2^27 nodes).
+   A volume of zero bytes is an empty one. */
+size_t mp_tsdf_volume_bytes(int nx, int ny, int nz, int color);
+/* Integrates n views, in ascending order, into the volume (rules: csrc/tsdf_core.h).  Node (i,j,k) lies at origin + voxel * (i,j,k) in
+   the object's frame; TCO maps object to camera (rows of 4; tco_floats = 12 or 16 per view); K is 3 x 3 row-major.  Per view and node:
+   pc = R p + t, skipped unless pc.z > z_min; pixel = floor(f * pc / pc.z + c), skipped outside the frame; with d_masks given, a pixel
+   with mask == 0 adds +1 to the sum and 1 to the count when `carve` (free space: the visual hull) and nothing otherwise; a depth that is
+   not finite or <= 0 adds nothing; else sd = depth - pc.z, skipped when sd < -mu, else min(1, sd / mu) is added to the sum and 1 to the
+   count, and with colours in the volume, d_rgb given and |sd| <= mu the pixel's bytes to the colour sums.  Sums and counts: calls
+   continue each other bit for bit.  A view whose K or TCO holds a non-finite entry contributes nothing, never an access out of range.
+   One launch on `stream`, one lane per node, no atomics.  n == 0 is a successful no-op; any bad argument (a null pointer where one is
+   needed, dims out of range, a non-finite origin, a non-finite or non-positive voxel or mu, a negative or non-finite z_min, frames
+   outside 1 .. 8192 a side) returns non-zero before anything is launched. */
+int mp_tsdf_integrate(void* d_volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel,
+                      const float* d_depth /*[n,h,w]*/, const uint8_t* d_masks /*[n,h,w] or NULL*/, const uint8_t* d_rgb /*[n,h,w,3] or NULL*/,
+                      const float* d_K /*[n,9]*/, const float* d_TCO /*[n,tco_floats]*/, int tco_floats, int n, int h, int w, float mu,
+                      float z_min, int carve, mp_stream stream);
+/* bytes of device scratch mp_tsdf_extract_count and mp_tsdf_extract need (0 for dims they reject). */
+size_t mp_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+/* Counts the surface: d_totals[0] = vertices, d_totals[1] = triangles of the zero level of f = sum / count over the nodes with
+   count >= min_views (>= 1), by marching tetrahedra over the cells whose eight corners are all observed (six tetrahedra around the
+   main diagonal; a vertex per edge with exactly one end inside, f < 0).  Four launches on `stream`, no atomics, no workgroup waits for
+   another.  What the call leaves in d_ws is the input of mp_tsdf_extract on the same volume.  Any bad argument (a null pointer, dims
+   out of range, min_views < 1, a workspace too small or not 16-byte aligned) returns non-zero before anything is launched. */
+int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int nz, int color, int min_views, int32_t* d_totals /*[2]*/, void* d_ws,
+                          size_t ws_bytes, mp_stream stream);
+/* Writes the mesh: vertices and colours (0 .. 1; white without colours) in the order of (node * 7 + edge kind), triangles in the
+   order of (cell, tetrahedron, triangle), wound so that normals point out of the object.  To be called after mp_tsdf_extract_count on
+   the same volume and workspace, with the two totals it gave; every store is checked against them, so totals that do not fit the
+   volume cost a wrong mesh, never a store outside the arrays.  One launch on `stream`.  n_vertices == n_triangles == 0 is a successful
+   no-op; any bad argument (a null pointer where one is needed, dims out of range, a bad origin or voxel, negative totals, capacities
+   smaller than the totals, a workspace too small or not 16-byte aligned) returns non-zero before anything is launched. */
+int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel, int n_vertices,
+                    int n_triangles, float* d_vertices /*[cap_vertices,3]*/, float* d_colors /*[cap_vertices,3]*/,
+                    int32_t* d_faces /*[cap_triangles,3]*/, long long cap_vertices, long long cap_triangles, void* d_ws, size_t ws_bytes,
+                    mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* BOP's model info: the exact diameter of a point set (the largest distance between two of */
 /* its points: `diameter` of a BOP dataset's models_info.json, bop_toolkit's calc_model_info */
 /* / calc_pts_diameter, an O(N^2) maximum) and its axis-aligned bounds                       */

@@ -188,6 +188,11 @@ SIGNATURES = {
     "mp_rle_encode": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _vp, _sz, _vp]),
     "mp_rle_decode_workspace_bytes": (_sz, [_i, _i, _i, C.c_longlong]),
     "mp_rle_decode": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mp_tsdf_volume_bytes": (_sz, [_i, _i, _i, _i]),
+    "mp_tsdf_integrate": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "mp_tsdf_extract_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mp_tsdf_extract_count": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mp_tsdf_extract": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _vp, _sz, _vp]),
     "mp_model_info_scratch_bytes": (_sz, [_i, _vp, _i]),
     "mp_model_info": (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_symmetry_check_scratch_bytes": (_sz, [_i]),

@@ -1150,6 +1150,81 @@ def rle_decode(counts: torch.Tensor, offsets, h: int, w: int) -> Tuple[torch.Ten
 
 
 # --------------------------------------------------------------------------- #
+# Onboarding without a CAD model (onboarding): TSDF fusion and marching tetrahedra, csrc/tsdf.hip
+TSDF_MIN_DIM, TSDF_MAX_DIM = 2, 512  # nodes a side
+TSDF_MAX_NODES = 1 << 27             # nx * ny * nz
+TSDF_MAX_SIDE = 8192                 # h, w of a frame
+
+
+def _tsdf_dims(volume: torch.Tensor) -> Tuple[int, int, int, int]:
+    if not volume.is_cuda or volume.dtype != torch.float32 or volume.dim() != 4 or volume.shape[0] not in (2, 6) or not volume.is_contiguous():
+        raise EngineError("a TSDF volume is a contiguous float32 device tensor [2 or 6, nz, ny, nx] (tsdf_volume)")
+    nz, ny, nx = (int(v) for v in volume.shape[1:])
+    return nx, ny, nz, int(volume.shape[0] == 6)
+
+
+def tsdf_volume(dims: Sequence[int], color: bool, device) -> torch.Tensor:
+    """An empty volume of dims = (nx, ny, nz) nodes: float32 zeros [2 or 6, nz, ny, nx] -- the sum of truncated distances, the count of
+    views (int32 bits: `volume[1].view(torch.int32)`), and with `color` the sums of red, green, blue and the colour count."""
+    nx, ny, nz = (int(v) for v in dims)
+    if _lib.load().mp_tsdf_volume_bytes(nx, ny, nz, int(bool(color))) == 0:
+        raise EngineError(f"tsdf_volume: {nx} x {ny} x {nz} nodes: each side {TSDF_MIN_DIM} .. {TSDF_MAX_DIM}, at most {TSDF_MAX_NODES} nodes")
+    return torch.zeros(6 if color else 2, nz, ny, nx, dtype=torch.float32, device=device)
+
+
+def tsdf_integrate(volume: torch.Tensor, origin: Sequence[float], voxel: float, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor,
+                   masks: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None, mu: Optional[float] = None, z_min: float = 1e-3,
+                   carve: bool = True) -> None:
+    """Fuses n posed depth views into `volume`, in place (mp_tsdf_integrate; the rules are stated in csrc/tsdf_core.h).  depth [n,h,w]
+    metres (not finite or <= 0: no measurement), K [n,3,3], TCO [n,4,4] or [n,3,4] object to camera, masks [n,h,w] uint8 / bool (0: not
+    the object; with `carve` such a pixel marks the nodes on its ray as free space, without it they are skipped), rgb [n,h,w,3] uint8.
+    Node (i,j,k) lies at origin + voxel * (i,j,k); mu is the truncation distance in metres (3 voxels when None).  Calls continue each
+    other bit for bit.  Nothing synchronises."""
+    nx, ny, nz, color = _tsdf_dims(volume)
+    depth = _dev_f32(depth)
+    if depth.dim() != 3:
+        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
+    n, h, w = (int(v) for v in depth.shape)
+    K, TCO = _dev_f32(K).reshape(n, -1) if n else _dev_f32(K), _dev_f32(TCO).reshape(n, -1) if n else _dev_f32(TCO)
+    if n and (K.shape[1] != 9 or TCO.shape[1] not in (12, 16)):
+        raise EngineError(f"K must be [n,3,3] and TCO [n,4,4] or [n,3,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
+    if masks is not None:
+        masks = _dev_bytes("masks", masks)
+        if tuple(masks.shape) != (n, h, w):
+            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
+    if rgb is not None:
+        rgb = _dev_bytes("rgb", rgb)
+        if tuple(rgb.shape) != (n, h, w, 3):
+            raise EngineError(f"rgb must be {(n, h, w, 3)}, got {tuple(rgb.shape)}")
+    mu = float(np.float32(3.0) * np.float32(voxel)) if mu is None else float(mu)
+    ox, oy, oz = (float(v) for v in origin)
+    check(_lib.load().mp_tsdf_integrate(volume.data_ptr(), nx, ny, nz, color, ox, oy, oz, float(voxel), depth.data_ptr(), _ptr(masks), _ptr(rgb),
+                                        K.data_ptr(), TCO.data_ptr(), int(TCO.shape[1]) if n else 16, n, h, w, mu, float(z_min), int(bool(carve)),
+                                        _stream()))
+
+
+def tsdf_extract(volume: torch.Tensor, origin: Sequence[float], voxel: float, min_views: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The welded triangle mesh of the zero level of the volume's field over the nodes seen by at least min_views views, by marching
+    tetrahedra (mp_tsdf_extract_count, mp_tsdf_extract) -> vertices [nv,3] float32 in the object's frame, colors [nv,3] float32 in
+    0 .. 1 (white without colours), faces [nt,3] int32, wound so that normals point out of the object; all on the device.  ONE
+    synchronisation: the two totals are read back between the two calls."""
+    nx, ny, nz, color = _tsdf_dims(volume)
+    dev = volume.device
+    lib = _lib.load()
+    ws = _workspace(lib.mp_tsdf_extract_workspace_bytes(nx, ny, nz), dev)
+    totals = torch.zeros(2, dtype=torch.int32, device=dev)
+    check(lib.mp_tsdf_extract_count(volume.data_ptr(), nx, ny, nz, color, int(min_views), totals.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    nv, nt = (int(v) for v in totals.cpu().tolist())      # the one synchronisation
+    vertices = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    colors = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nt, 3, dtype=torch.int32, device=dev)
+    ox, oy, oz = (float(v) for v in origin)
+    check(lib.mp_tsdf_extract(volume.data_ptr(), nx, ny, nz, color, ox, oy, oz, float(voxel), nv, nt, vertices.data_ptr(), colors.data_ptr(),
+                              faces.data_ptr(), nv, nt, ws.data_ptr(), ws.numel(), _stream()))
+    return vertices, colors, faces
+
+
+# --------------------------------------------------------------------------- #
 # BOP's model info (evaluation): csrc/model_info.hip
 MODEL_INFO_TILE_STEP = 64            # a forced tile is a multiple of this ...
 MODEL_INFO_MAX_TILE = 1024           # ... and at most this

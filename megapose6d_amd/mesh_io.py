@@ -14,6 +14,8 @@ UV textures: PLY `comment TextureFile <png>` with per-v
 PIL, flipped so that v grows with the row index, and expanded into an RGBA8 mip chain (`build_mip_chain`)
 -- the rasteriser's input.  Meshes without vertex colours render white (times the texture, if any), as
 Panda3D does.
+
+Written: `write_ply` (binary PLY with optional normals and vertex colours), for the meshes `megapose6d_amd.onboarding` reconstructs.
 """
 from __future__ import annotations
 
@@ -171,6 +173,47 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
         tex = Path(path).parent / texture_file
     return {"vertices": verts, "faces": faces, "normals": normals, "colors": colors, "uvs": face_uvs if tex is not None else None,
             "texture_path": tex}
+
+
+def write_ply(path, vertices, faces, colors=None, normals=None) -> Path:
+    """Writes a binary little-endian PLY that `read_ply` takes back: float32 x y z, with `normals` float32 nx ny nz, with `colors`
+    ([V,3] floats in 0 .. 1, or uint8) uchar red green blue, triangles as `list uchar int vertex_indices`."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+    if len(f) and (f.min() < 0 or f.max() >= len(v)):
+        raise ValueError(f"{path}: a face indexes outside the {len(v)} vertices")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(len(v), 3)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colors is not None:
+        colors = np.asarray(colors)
+        if colors.dtype != np.uint8:
+            colors = np.clip(np.rint(colors.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+        colors = colors.reshape(len(v), 3)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vrec = np.zeros(len(v), dtype=np.dtype(fields))
+    for k, n in enumerate("xyz"):
+        vrec[n] = v[:, k]
+    if normals is not None:
+        for k, n in enumerate(("nx", "ny", "nz")):
+            vrec[n] = normals[:, k]
+    if colors is not None:
+        for k, n in enumerate(("red", "green", "blue")):
+            vrec[n] = colors[:, k]
+    frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    frec["n"] = 3
+    frec["idx"] = f
+    names = {"<f4": "float", "u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property {names[t]} {n}" for n, t in fields]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    path = Path(path)
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vrec.tobytes())
+        out.write(frec.tobytes())
+    return path
 
 
 def read_obj(path) -> Dict[str, Optional[np.ndarray]]:

@@ -1,0 +1,151 @@
+"""Onboarding an object without a CAD model: a few dozen depth frames with known camera poses and object masks (a turntable, a robot arm,
+BOP's static onboarding sequences) fused into a truncated signed distance field, and its surface written as a coloured PLY that the
+renderer, MeshDataBase, bop_models_info, find_symmetries and the pose estimator take like any other mesh.
+
+The hot path is csrc/tsdf.hip (contract: csrc/tsdf_core.h): `TsdfVolume.integrate` is one launch per call, `TsdfVolume.extract` five
+launches and one read-back of two integers.  Sizing the volume (`volume_for_views`) is plain torch: it runs once per object.
+
+Not here: estimating the camera poses, smoothing, hole filling, keeping the largest component, decimation, texture atlases, distances
+along the ray, per-pixel weights.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import engine as eng
+from . import mesh_io
+from .object_dataset import RigidObject
+
+
+class TsdfVolume:
+    """A grid of nx x ny x nz nodes, node (i,j,k) at origin + voxel_size * (i,j,k) in the object's frame (metres), holding per node the
+    sum of truncated signed distances and the number of views that saw it (and, with `color`, colour sums): calls of `integrate`
+    continue each other bit for bit."""
+
+    def __init__(self, origin: Sequence[float], voxel_size: float, dims: Sequence[int], trunc_voxels: float = 3.0, color: bool = True,
+                 device="cuda"):
+        self.origin = tuple(float(np.float32(v)) for v in origin)
+        self.voxel_size = float(np.float32(voxel_size))
+        self.dims = tuple(int(v) for v in dims)
+        if len(self.origin) != 3 or len(self.dims) != 3:
+            raise ValueError("origin and dims have three entries")
+        if not (np.isfinite(self.origin).all() and np.isfinite(self.voxel_size) and self.voxel_size > 0):
+            raise ValueError(f"origin {origin} must be finite and voxel_size {voxel_size} finite and positive")
+        if not (np.isfinite(trunc_voxels) and trunc_voxels > 0):
+            raise ValueError(f"trunc_voxels {trunc_voxels} must be finite and positive")
+        nx, ny, nz = self.dims
+        if min(self.dims) < eng.TSDF_MIN_DIM or max(self.dims) > eng.TSDF_MAX_DIM or nx * ny * nz > eng.TSDF_MAX_NODES:
+            raise ValueError(f"dims {self.dims}: each side {eng.TSDF_MIN_DIM} .. {eng.TSDF_MAX_DIM}, at most {eng.TSDF_MAX_NODES} nodes")
+        self.trunc_voxels = float(trunc_voxels)
+        self.mu = float(np.float32(trunc_voxels) * np.float32(self.voxel_size))
+        self.color = bool(color)
+        self._volume = eng.tsdf_volume(self.dims, self.color, device)
+
+    @property
+    def volume(self) -> torch.Tensor:
+        """the planes [2 or 6, nz, ny, nx] as the kernels see them"""
+        return self._volume
+
+    @property
+    def counts(self) -> torch.Tensor:
+        """[nz, ny, nx] int32: the views that contributed to each node (a view of the volume; do not write)"""
+        return self._volume[1].view(torch.int32)
+
+    @property
+    def field(self) -> torch.Tensor:
+        """[nz, ny, nx] float32: sum / count, the mean truncated distance in units of the truncation (NaN where no view contributed)"""
+        return self._volume[0] / self.counts.to(torch.float32)
+
+    def integrate(self, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                  rgb: Optional[torch.Tensor] = None, carve: bool = True, z_min: float = 1e-3) -> "TsdfVolume":
+        """depth [n,h,w] metres, K [n,3,3], TCO [n,4,4] object to camera, masks [n,h,w] (non-zero: the object), rgb [n,h,w,3] uint8.
+        With masks and `carve`, pixels off the object mark the nodes on their rays as free space (the visual hull)."""
+        dev = self._volume.device
+        as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
+        eng.tsdf_integrate(self._volume, self.origin, self.voxel_size, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), as_dev(rgb),
+                           mu=self.mu, z_min=z_min, carve=carve)
+        return self
+
+    def extract(self, min_views: int = 1) -> Dict[str, np.ndarray]:
+        """-> vertices [V,3] float32, faces [T,3] int32, colors [V,3] float32 in 0 .. 1, normals [V,3] float32 (area-weighted, pointing
+        out of the object), as host arrays"""
+        v, c, f = eng.tsdf_extract(self._volume, self.origin, self.voxel_size, min_views)
+        v, c, f = v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy()
+        return dict(vertices=v, faces=f, colors=c, normals=mesh_io.vertex_normals(v, f).astype(np.float32))
+
+    def reset(self) -> None:
+        self._volume.zero_()
+
+
+def volume_for_views(depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor], resolution: int = 128,
+                     margin_voxels: int = 4) -> Tuple[Tuple[float, float, float], float, Tuple[int, int, int]]:
+    """The volume that holds what the views saw: the masked pixels with a measurement (every measured pixel without masks) are
+    back-projected through their centres into the object's frame, and their bounding box, grown by margin_voxels on every side, gets
+    `resolution` nodes along its longest side -> (origin, voxel_size, dims).  Plain torch on whatever device the tensors live on."""
+    depth = torch.as_tensor(depth).to(torch.float32)
+    K, TCO = torch.as_tensor(K).to(depth.device, torch.float64), torch.as_tensor(TCO).to(depth.device, torch.float64)
+    n, h, w = depth.shape
+    if resolution < 2 * margin_voxels + 2 or resolution > eng.TSDF_MAX_DIM or margin_voxels < 0:
+        raise ValueError(f"resolution {resolution} must be at least 2 * margin_voxels + 2 and at most {eng.TSDF_MAX_DIM}")
+    keep = torch.isfinite(depth) & (depth > 0)
+    if masks is not None:
+        keep = keep & (torch.as_tensor(masks).to(depth.device) != 0)
+    lo = torch.full((3,), float("inf"), dtype=torch.float64, device=depth.device)
+    hi = -lo
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth.device), torch.arange(w, device=depth.device), indexing="ij")
+    for v in range(n):
+        sel = keep[v]
+        if not bool(sel.any()):
+            continue
+        z = depth[v][sel].to(torch.float64)
+        pc = torch.stack([(xs[sel] + 0.5 - K[v, 0, 2]) / K[v, 0, 0] * z, (ys[sel] + 0.5 - K[v, 1, 2]) / K[v, 1, 1] * z, z], 1)
+        po = (pc - TCO[v, :3, 3]) @ TCO[v, :3, :3]          # R^T (pc - t)
+        lo, hi = torch.minimum(lo, po.min(0).values), torch.maximum(hi, po.max(0).values)
+    if not bool(torch.isfinite(lo).all() and torch.isfinite(hi).all()):
+        raise ValueError("volume_for_views: no view holds a measured pixel of the object (depth finite and > 0 inside the mask)")
+    lo, hi = lo.cpu().numpy(), hi.cpu().numpy()
+    side = float((hi - lo).max())
+    if side <= 0:
+        raise ValueError("volume_for_views: the measured pixels span no length")
+    voxel = side / (resolution - 1 - 2 * margin_voxels)
+    origin = lo - margin_voxels * voxel
+    dims = tuple(int(min(resolution, max(eng.TSDF_MIN_DIM, np.ceil((hi[c] - lo[c]) / voxel - 1e-9) + 1 + 2 * margin_voxels))) for c in range(3))
+    return tuple(float(v) for v in origin), float(voxel), dims
+
+
+def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                       rgb: Optional[torch.Tensor] = None, resolution: int = 128, out_dir=".", trunc_voxels: float = 3.0, min_views: int = 1,
+                       carve: bool = True, device="cuda") -> RigidObject:
+    """Posed depth views of one object -> `<out_dir>/<label>.ply` (metres, vertex normals, vertex colours: the views' where rgb is
+    given, else white) and the RigidObject that names it.  Raises a ValueError that names the cause when there is no surface."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() != 3 or depth.shape[0] == 0:
+        raise ValueError(f"reconstruct_object({label!r}): depth must be [n,h,w] with at least one view, got {tuple(depth.shape)}")
+    n = depth.shape[0]
+    K, TCO = torch.as_tensor(K), torch.as_tensor(TCO)
+    if tuple(K.shape) != (n, 3, 3) or tuple(TCO.shape) != (n, 4, 4):
+        raise ValueError(f"reconstruct_object({label!r}): K must be [{n},3,3] and TCO [{n},4,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
+    if not bool(torch.isfinite(K).all() and torch.isfinite(TCO).all()):
+        raise ValueError(f"reconstruct_object({label!r}): K or TCO holds a value that is not finite")
+    for name, t, shape in (("masks", masks, tuple(depth.shape)), ("rgb", rgb, tuple(depth.shape) + (3,))):
+        if t is not None and tuple(torch.as_tensor(t).shape) != shape:
+            raise ValueError(f"reconstruct_object({label!r}): {name} must be {shape}, got {tuple(torch.as_tensor(t).shape)}")
+    try:
+        origin, voxel, dims = volume_for_views(depth, K, TCO, masks, resolution=resolution)
+    except ValueError as e:
+        raise ValueError(f"reconstruct_object({label!r}): {e}") from e
+    vol = TsdfVolume(origin, voxel, dims, trunc_voxels=trunc_voxels, color=rgb is not None, device=device)
+    vol.integrate(depth, K, TCO, masks=masks, rgb=rgb, carve=carve)
+    mesh = vol.extract(min_views=min_views)
+    if len(mesh["faces"]) == 0:
+        seen = int((vol.counts >= min_views).sum())
+        raise ValueError(f"reconstruct_object({label!r}): the surface is empty: {seen} of {vol.counts.numel()} nodes were seen by at least "
+                         f"{min_views} view(s) and no complete cell holds a change of sign (poses, intrinsics or units that do not fit the depth?)")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    path = mesh_io.write_ply(out_dir / f"{label}.ply", mesh["vertices"], mesh["faces"], colors=mesh["colors"], normals=mesh["normals"])
+    return RigidObject(label, path, mesh_units="m")

@@ -1,0 +1,197 @@
+// TEST SUPPORT: host emulation of the TSDF kernels (megapose6d_amd/csrc/tsdf.hip), built from the same rules header (tsdf_core.h).
+// Same arguments as the C ABI, on host arrays, as plain loops: nodes in linear order, views in ascending order, a vertex index handed out
+// to every vertex-carrying edge as the walk meets it (no flags passes, no ranks, no scans, no workspace), triangles cell by cell from a
+// table of those indices.  Compiled with -ffp-contract=off, so the kernels are held to these results bit for bit.  Built by
+// tests/support/tsdf.py; tests/tsdf_asan_main.cpp includes this file.
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "tsdf_core.h"
+
+using namespace mp;
+
+namespace {
+
+struct Vol {
+  float* sum;
+  int32_t* count;
+  float* c[3];
+  int32_t* c_count;
+};
+
+Vol planes_of(void* volume, size_t N, int color) {
+  float* f = (float*)volume;
+  Vol v;
+  v.sum = f;
+  v.count = (int32_t*)(f + N);
+  for (int k = 0; k < 3; ++k) v.c[k] = color ? f + (2 + k) * N : nullptr;
+  v.c_count = color ? (int32_t*)(f + 5 * N) : nullptr;
+  return v;
+}
+
+bool grid_args_ok(int nx, int ny, int nz, float ox, float oy, float oz, float voxel) {
+  const float origin[3] = {ox, oy, oz};
+  return tsdf::dims_ok(nx, ny, nz) && tsdf::grid_ok(origin, voxel);
+}
+
+// the surface of a volume: per (node, kind) the vertex index or -1, and the triangles
+struct Surface {
+  std::vector<int32_t> vid;
+  std::vector<uint8_t> flags, complete;
+  int32_t n_vertices = 0, n_triangles = 0;
+};
+
+template <class FV, class FT>
+void walk_surface(const Vol& v, int nx, int ny, int nz, int min_views, Surface* s, FV on_vertex, FT on_triangle) {
+  const tsdf::Tables& tb = tsdf::tables();
+  const size_t N = (size_t)nx * ny * nz;
+  const int nxy = nx * ny;
+  s->flags.assign(N, 0);
+  s->complete.assign(N, 0);
+  s->vid.assign(N * tsdf::kEdgeKinds, -1);
+  for (size_t g = 0; g < N; ++g) s->flags[g] = (uint8_t)tsdf::node_flags(v.sum[g], v.count[g], min_views);
+  auto at = [&](int i, int j, int k) { return ((size_t)k * ny + j) * nx + i; };
+  for (int k = 0; k + 1 < nz; ++k)
+    for (int j = 0; j + 1 < ny; ++j)
+      for (int i = 0; i + 1 < nx; ++i) {
+        bool all = true;
+        for (int c = 0; c < 8; ++c) all = all && (s->flags[at(i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1))] & tsdf::kObserved);
+        s->complete[at(i, j, k)] = all;
+      }
+  for (int k = 0; k < nz; ++k)
+    for (int j = 0; j < ny; ++j)
+      for (int i = 0; i < nx; ++i)
+        for (int kind = 0; kind < tsdf::kEdgeKinds; ++kind) {
+          const int d = tb.kind_diff[kind], dx = d & 1, dy = (d >> 1) & 1, dz = (d >> 2) & 1;
+          if (i + dx >= nx || j + dy >= ny || k + dz >= nz) continue;
+          const size_t a = at(i, j, k), b = at(i + dx, j + dy, k + dz);
+          const int fa = s->flags[a], fb = s->flags[b];
+          if (!(fa & fb & tsdf::kObserved) || ((fa ^ fb) & tsdf::kInside) == 0) continue;
+          bool any = false;
+          for (int bx = 0; bx <= (dx ? 0 : 1); ++bx)
+            for (int by = 0; by <= (dy ? 0 : 1); ++by)
+              for (int bz = 0; bz <= (dz ? 0 : 1); ++bz) {
+                const int ci = i - bx, cj = j - by, ck = k - bz;
+                if (ci < 0 || cj < 0 || ck < 0 || ci + 1 >= nx || cj + 1 >= ny || ck + 1 >= nz) continue;
+                any = any || s->complete[at(ci, cj, ck)];
+              }
+          if (!any) continue;
+          s->vid[a * tsdf::kEdgeKinds + kind] = s->n_vertices;
+          on_vertex(s->n_vertices, i, j, k, dx, dy, dz, a, b);
+          ++s->n_vertices;
+        }
+  for (int k = 0; k + 1 < nz; ++k)
+    for (int j = 0; j + 1 < ny; ++j)
+      for (int i = 0; i + 1 < nx; ++i) {
+        const size_t g = at(i, j, k);
+        if (!s->complete[g]) continue;
+        int inside8 = 0;
+        for (int c = 0; c < 8; ++c)
+          inside8 |= ((s->flags[g + (c & 1) + ((c >> 1) & 1) * nx + (size_t)((c >> 2) & 1) * nxy] & tsdf::kInside) ? 1 : 0) << c;
+        for (int T = 0; T < tsdf::kTets; ++T) {
+          const int m = tsdf::tet_case(tb, T, inside8);
+          for (int tri = 0; tri < tb.count[m]; ++tri) {
+            int32_t idx[3];
+            for (int c = 0; c < 3; ++c) {
+              int code, kind;
+              tsdf::tri_edge(tb, T, m, tri, c, &code, &kind);
+              const size_t o = g + (code & 1) + ((code >> 1) & 1) * nx + (size_t)((code >> 2) & 1) * nxy;
+              idx[c] = s->vid[o * tsdf::kEdgeKinds + kind];
+            }
+            on_triangle(s->n_triangles, idx);
+            ++s->n_triangles;
+          }
+        }
+      }
+}
+
+}  // namespace
+
+extern "C" int tsdf_integrate_emul(void* volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel, const float* depth,
+                                   const uint8_t* masks, const uint8_t* rgb, const float* K, const float* TCO, int tco_floats, int n, int h, int w,
+                                   float mu, float z_min, int carve) {
+  if (!grid_args_ok(nx, ny, nz, ox, oy, oz, voxel)) return 1;
+  if (!(tsdf::finite_f(mu) && mu > 0.f && tsdf::finite_f(z_min) && z_min >= 0.f)) return 1;
+  if (n < 0 || (tco_floats != 12 && tco_floats != 16)) return 1;
+  if (n == 0) return 0;
+  if (!tsdf::frame_ok(h, w) || !volume || !depth || !K || !TCO) return 1;
+  const size_t N = (size_t)nx * ny * nz, hw = (size_t)h * w;
+  const Vol v = planes_of(volume, N, color);
+  for (int k = 0; k < nz; ++k)
+    for (int j = 0; j < ny; ++j)
+      for (int i = 0; i < nx; ++i) {
+        const size_t g = ((size_t)k * ny + j) * nx + i;
+        tsdf::Node nd = {v.sum[g], v.count[g], 0.f, 0.f, 0.f, 0};
+        if (color) {
+          nd.c0 = v.c[0][g];
+          nd.c1 = v.c[1][g];
+          nd.c2 = v.c[2][g];
+          nd.c_count = v.c_count[g];
+        }
+        const float px = tsdf::node_coord(ox, voxel, i), py = tsdf::node_coord(oy, voxel, j), pz = tsdf::node_coord(oz, voxel, k);
+        for (int q = 0; q < n; ++q) {
+          float view[tsdf::kViewFloats];
+          if (!tsdf::load_view(K + (size_t)q * 9, TCO + (size_t)q * tco_floats, view)) continue;
+          nd = tsdf::integrate(nd, tsdf::visit(px, py, pz, view, depth + q * hw, masks ? masks + q * hw : nullptr, rgb ? rgb + q * hw * 3 : nullptr, h, w,
+                                               mu, z_min, carve != 0, color != 0));
+        }
+        v.sum[g] = nd.sum;
+        v.count[g] = nd.count;
+        if (color) {
+          v.c[0][g] = nd.c0;
+          v.c[1][g] = nd.c1;
+          v.c[2][g] = nd.c2;
+          v.c_count[g] = nd.c_count;
+        }
+      }
+  return 0;
+}
+
+extern "C" int tsdf_extract_count_emul(const void* volume, int nx, int ny, int nz, int color, int min_views, int32_t* totals) {
+  if (!tsdf::dims_ok(nx, ny, nz) || min_views < 1 || !volume || !totals) return 1;
+  const Vol v = planes_of(const_cast<void*>(volume), (size_t)nx * ny * nz, color);
+  Surface s;
+  walk_surface(v, nx, ny, nz, min_views, &s, [](int32_t, int, int, int, int, int, int, size_t, size_t) {}, [](int32_t, const int32_t*) {});
+  totals[0] = s.n_vertices;
+  totals[1] = s.n_triangles;
+  return 0;
+}
+
+extern "C" int tsdf_extract_emul(const void* volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel, int min_views,
+                                 int n_vertices, int n_triangles, float* vertices, float* colors, int32_t* faces, long long cap_vertices,
+                                 long long cap_triangles) {
+  if (!grid_args_ok(nx, ny, nz, ox, oy, oz, voxel) || min_views < 1) return 1;
+  if (n_vertices < 0 || n_triangles < 0 || cap_vertices < n_vertices || cap_triangles < n_triangles) return 1;
+  if (n_vertices == 0 && n_triangles == 0) return 0;
+  if (!volume || (n_vertices && (!vertices || !colors)) || (n_triangles && !faces)) return 1;
+  const Vol v = planes_of(const_cast<void*>(volume), (size_t)nx * ny * nz, color);
+  const float org[3] = {ox, oy, oz};
+  Surface s;
+  walk_surface(
+      v, nx, ny, nz, min_views, &s,
+      [&](int32_t r, int i, int j, int k, int dx, int dy, int dz, size_t a, size_t b) {
+        if (r >= n_vertices) return;
+        const int ia[3] = {i, j, k}, ib[3] = {i + dx, j + dy, k + dz};
+        const float t = tsdf::edge_t(tsdf::field(v.sum[a], v.count[a]), tsdf::field(v.sum[b], v.count[b]));
+        for (int c = 0; c < 3; ++c) {
+          vertices[(size_t)r * 3 + c] = tsdf::lerp(tsdf::node_coord(org[c], voxel, ia[c]), tsdf::node_coord(org[c], voxel, ib[c]), t);
+          const float ca = color ? tsdf::node_color(v.c[c][a], v.c_count[a]) : 1.f, cb = color ? tsdf::node_color(v.c[c][b], v.c_count[b]) : 1.f;
+          colors[(size_t)r * 3 + c] = tsdf::lerp(ca, cb, t);
+        }
+      },
+      [&](int32_t r, const int32_t* idx) {
+        if (r >= n_triangles) return;
+        for (int c = 0; c < 3; ++c) faces[(size_t)r * 3 + c] = idx[c];
+      });
+  return 0;
+}
+
+extern "C" void tsdf_emul_limits(long long* v) {
+  v[0] = tsdf::kMinDim;
+  v[1] = tsdf::kMaxDim;
+  v[2] = tsdf::kMaxNodes;
+  v[3] = tsdf::kMaxSide;
+  v[4] = tsdf::kEdgeKinds;
+  v[5] = tsdf::kTets;
+}
