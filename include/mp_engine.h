@@ -743,6 +743,65 @@ int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int color, flo
                     mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Cleaning up a triangle mesh (a reconstruction's, a heavy scan's): its connected          */
+/* components, the selection of faces with the vertices they reference, and decimation by   */
+/* vertex clustering, Rossignac-Borrel (csrc/mesh_cleanup.hip; contract in                  */
+/* csrc/mesh_cleanup_core.h).  The reference has no counterpart; Open3D, trimesh and         */
+/* meshlab are third party and absent: parity with them is unpinned.                        */
+/* A mesh is V vertices [V,3] fp32 and F faces [F,3] int32, each 0 .. 2^29.  A face with an  */
+/* index outside [0, V) is bad: it joins nothing, is never emitted, and its index is never   */
+/* used as an address.  V == 0 or F == 0 is a success with zero totals.                      */
+/* ------------------------------------------------------------------------------------ */
+/* bytes of device scratch mp_mesh_components needs (0 for counts it rejects). */
+size_t mp_mesh_components_workspace_bytes(int V, int F);
+/* Connected components: d_labels[v] = the smallest vertex index of v's component (vertices joined by a chain of good faces; a vertex
+   on no good face is its own label), d_face_labels[f] = the label of the face's first vertex or -1 for a bad face, d_face_count[l] = the
+   good faces of label l (0 where l is not a label), d_totals = {components that own a face, the label of the one with the most faces
+   (the smaller label on equal counts; -1 without any), bad faces, status}.  A lock-free union-find (atomicMin hooks the larger root
+   under the smaller; d_labels is its parent array) whose loops are capped at V + 1 rounds: status is 0, or 1 when a loop reached the
+   cap, and the labels are then not to be used.  Five launches and a memset on `stream`, nothing synchronises; the result is unique, so
+   no arrival order changes it.  Any bad argument (a null pointer where one is needed, counts out of range, a workspace too small or
+   not 16-byte aligned) returns non-zero before anything is launched. */
+int mp_mesh_components(int V, const int32_t* d_faces /*[F,3]*/, int F, int32_t* d_labels /*[V]*/, int32_t* d_face_labels /*[F]*/,
+                       int32_t* d_face_count /*[V]*/, int32_t* d_totals /*[4]*/, void* d_ws, size_t ws_bytes, mp_stream stream);
+/* bytes of device scratch mp_mesh_select_count and mp_mesh_select need (0 for counts they reject). */
+size_t mp_mesh_select_workspace_bytes(int V, int F);
+/* Counts a selection: d_keep[f] != 0 keeps face f; d_totals = {vertices that a kept good face references, kept good faces, bad faces}.
+   Flags by plain byte stores, two ordered rank passes (16 bytes a lane), one scan; no atomics but the count of bad faces.  What the
+   call leaves in d_ws is the input of mp_mesh_select on the same mesh.  Bad arguments as above. */
+int mp_mesh_select_count(int V, const int32_t* d_faces /*[F,3]*/, int F, const uint8_t* d_keep /*[F]*/, int32_t* d_totals /*[3]*/, void* d_ws,
+                         size_t ws_bytes, mp_stream stream);
+/* Writes the selection: the kept good faces in input order, the vertices they reference in input order, renumbered; vertices and
+   (with d_colors) colours are copied bit for bit.  To be called after mp_mesh_select_count on the same mesh and workspace with the two
+   totals it gave; every store is checked against them.  One launch on `stream`.  Refused before anything is launched: negative totals,
+   capacities smaller than the totals, a null pointer where one is needed, counts out of range, a bad workspace. */
+int mp_mesh_select(const float* d_vertices /*[V,3]*/, const float* d_colors /*[V,3] or NULL*/, int V, const int32_t* d_faces /*[F,3]*/, int F,
+                   int n_vertices, int n_faces, float* d_out_vertices /*[cap_vertices,3]*/, float* d_out_colors /*[cap_vertices,3] or NULL*/,
+                   int32_t* d_out_faces /*[cap_faces,3]*/, long long cap_vertices, long long cap_faces, void* d_ws, size_t ws_bytes,
+                   mp_stream stream);
+/* bytes of device scratch mp_mesh_cluster_count and mp_mesh_cluster need (0 for counts or a grid they reject). */
+size_t mp_mesh_cluster_workspace_bytes(int V, int F, int gx, int gy, int gz);
+/* Counts a decimation by vertex clustering on the grid of gx x gy x gz cells (each side 1 .. 512, at most 2^27 cells) of size `cell`
+   from the origin: a vertex lies in cell floor((p - o) / cell) per axis; one outside the grid or with a non-finite coordinate is bad.
+   A face is kept iff it is good, none of its vertices is bad and its three cells differ pairwise; a cell is used iff a kept face
+   references it.  d_totals = {used cells = vertices out, kept faces, bad faces + faces dropped for a bad vertex}.  Two per-element
+   launches, two rank passes, one scan; what the call leaves in d_ws is the input of mp_mesh_cluster.  Refused before anything is
+   launched: dims out of range, a non-finite origin, a cell size that is not finite and > 0, and the bad arguments above. */
+int mp_mesh_cluster_count(const float* d_vertices /*[V,3]*/, int V, const int32_t* d_faces /*[F,3]*/, int F, float ox, float oy, float oz,
+                          float cell, int gx, int gy, int gz, int32_t* d_totals /*[3]*/, void* d_ws, size_t ws_bytes, mp_stream stream);
+/* Writes the decimated mesh: output vertex = the rank of its used cell in cell-id order, at the exact mean of ALL good vertices of the
+   cell (16.16 fixed-point grid coordinates summed in int64 by integer atomics, one float conversion per coordinate at the end; colours
+   likewise in steps of 1/65535): no floating-point atomic, bit-reproducible whatever the arrival order.  Faces in input order with
+   their corners in order; duplicate and opposite triangles are kept, so a closed mesh stays closed.  To be called after
+   mp_mesh_cluster_count on the same mesh, grid and workspace with the two totals it gave; every store is checked against them.  A
+   memset and two launches on `stream`.  Refused as mp_mesh_select and mp_mesh_cluster_count refuse. */
+int mp_mesh_cluster(const float* d_vertices /*[V,3]*/, const float* d_colors /*[V,3] or NULL*/, int V, const int32_t* d_faces /*[F,3]*/, int F,
+                    float ox, float oy, float oz, float cell, int gx, int gy, int gz, int n_vertices, int n_faces,
+                    float* d_out_vertices /*[cap_vertices,3]*/, float* d_out_colors /*[cap_vertices,3] or NULL*/,
+                    int32_t* d_out_faces /*[cap_faces,3]*/, long long cap_vertices, long long cap_faces, void* d_ws, size_t ws_bytes,
+                    mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* BOP's model info: the exact diameter of a point set (the largest distance between two of */
 /* its points: `diameter` of a BOP dataset's models_info.json, bop_toolkit's calc_model_info */
 /* / calc_pts_diameter, an O(N^2) maximum) and its axis-aligned bounds                       */

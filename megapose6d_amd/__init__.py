@@ -4,7 +4,7 @@ Only what the hot path needs: the HIP/C-ABI engine (`csrc/
 of the reference's renderer / PosePredictor / PoseEstimator interfaces.  Importing the package never touches the GPU; the
 first engine call loads `libmp_engine.so` and raises if it is missing (there is no CPU fallback).
 """
-from . import (detector, distances, distributed, engine, evaluation, icp_refiner, load_model, mask_rcnn, mesh_db, mesh_io, object_dataset, onboarding, pose_estimator,  # noqa: F401
+from . import (detector, distances, distributed, engine, evaluation, icp_refiner, load_model, mask_rcnn, mesh_cleanup, mesh_db, mesh_io, object_dataset, onboarding, pose_estimator,  # noqa: F401
                pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, types, visualization)
 from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner, TeaserppRefiner  # noqa: F401

@@ -105,6 +105,27 @@ __device__ __forceinline__ int block_compact(bool keep, int* wave_count, int* to
   return before + __popcll(votes & ((1ull << lane) - 1ull));
 }
 
+// ---- exclusive sum over the workgroup in thread order, and the workgroup's total (the same in every thread); wave_tot holds WAVES entries.
+// The barrier contract of block_compact: one barrier before the entries are written, one before they are read, none after.
+template <int WAVES>
+__device__ __forceinline__ int block_exclusive_sum(int v, int* wave_tot, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = __shfl_up(inc, d);
+    if (lane >= d) inc += o;
+  }
+  __syncthreads();
+  if (lane == 63) wave_tot[wave] = inc;
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += wave_tot[w];
+  int all = before;
+  for (int w = wave; w < WAVES; ++w) all += wave_tot[w];
+  *total = all;
+  return before + inc - v;
+}
+
 // ---- the object of a job: the largest o with job_off[o] <= job, job_off being the prefix array of the objects' job counts (n_obj + 1
 // entries, job_off[0] = 0); at most 31 halvings of n_obj
 __device__ __forceinline__ int object_of(const int32_t* __restrict__ job_off, int n_obj, int job) {

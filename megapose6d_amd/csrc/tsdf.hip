@@ -33,27 +33,6 @@ constexpr int kTsdfWaves = kTsdfBlock / 64;
 constexpr int kTsdfViewChunk = 32;    // views staged in LDS at a time: 2 KB of tables
 constexpr int kCellComplete = 0x80;   // the cell byte: complete | its number of triangles (<= 12)
 
-// exclusive sum over the workgroup in thread order, and the workgroup's total (the same in every thread); wave_tot holds WAVES entries.
-// The barrier contract of block_compact: one barrier before the entries are written, one before they are read, none after.
-template <int WAVES>
-__device__ __forceinline__ int block_exclusive_sum(int v, int* wave_tot, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d);
-    if (lane >= d) inc += o;
-  }
-  __syncthreads();
-  if (lane == 63) wave_tot[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += wave_tot[w];
-  int all = before;
-  for (int w = wave; w < WAVES; ++w) all += wave_tot[w];
-  *total = all;
-  return before + inc - v;
-}
-
 struct TsdfGrid {
   int nx, ny, nz, N;
   float ox, oy, oz, voxel;

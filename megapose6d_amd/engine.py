@@ -1225,6 +1225,123 @@ def tsdf_extract(volume: torch.Tensor, origin: Sequence[float], voxel: float, mi
 
 
 # --------------------------------------------------------------------------- #
+# Cleaning up a triangle mesh (mesh_cleanup): components, selection, vertex clustering, csrc/mesh_cleanup.hip
+MESH_MAX_COUNT = 1 << 29             # vertices, faces
+MESH_MAX_DIM = 512                   # cells a side
+MESH_MAX_CELLS = 1 << 27             # gx * gy * gz
+
+
+def _mesh_faces(faces: torch.Tensor) -> torch.Tensor:
+    faces = _dev_i32(faces)
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise EngineError(f"faces must be [F,3], got {tuple(faces.shape)}")
+    return faces
+
+
+def _mesh_vertices(vertices: torch.Tensor, colors: Optional[torch.Tensor]) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    vertices = _dev_f32(vertices)
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise EngineError(f"vertices must be [V,3], got {tuple(vertices.shape)}")
+    if colors is not None:
+        colors = _dev_f32(colors)
+        if tuple(colors.shape) != tuple(vertices.shape):
+            raise EngineError(f"colors must be {tuple(vertices.shape)}, got {tuple(colors.shape)}")
+    return vertices, colors
+
+
+def _mesh_grid(origin: Sequence[float], cell: float, dims: Sequence[int]):
+    ox, oy, oz = (float(v) for v in origin)
+    gx, gy, gz = (int(v) for v in dims)
+    return (ox, oy, oz, float(cell)), (gx, gy, gz)
+
+
+def mesh_components(vertices_or_V, faces: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The connected components of a mesh (mp_mesh_components; rules in csrc/mesh_cleanup_core.h).  vertices_or_V: the vertices [V,3]
+    or their number; faces [F,3] int32 on the device -> labels [V] int32 (the smallest vertex index of the vertex's component),
+    face_labels [F] int32 (-1 for a face with an index outside [0, V)), face_count [V] int32 (faces per label), totals [4] int32 on the
+    device: components that own a face, the label of the one with the most faces (-1 without any), bad faces, status (non-zero: a loop
+    of the union-find reached its cap and the labels are not to be used).  Nothing synchronises: the caller reads the totals when it
+    needs them."""
+    faces = _mesh_faces(faces)
+    V = int(vertices_or_V.shape[0]) if torch.is_tensor(vertices_or_V) else int(vertices_or_V)
+    F = int(faces.shape[0])
+    dev = faces.device
+    labels = torch.empty(max(V, 0), dtype=torch.int32, device=dev)
+    face_count = torch.empty(max(V, 0), dtype=torch.int32, device=dev)
+    face_labels = torch.empty(F, dtype=torch.int32, device=dev)
+    totals = torch.empty(4, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws = _workspace(lib.mp_mesh_components_workspace_bytes(V, F), dev)
+    check(lib.mp_mesh_components(V, faces.data_ptr(), F, labels.data_ptr(), face_labels.data_ptr(), face_count.data_ptr(), totals.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream()))
+    return labels, face_labels, face_count, totals
+
+
+def mesh_select(vertices: torch.Tensor, faces: torch.Tensor, keep: torch.Tensor, colors: Optional[torch.Tensor] = None):
+    """The faces with keep != 0 and the vertices they reference, renumbered, both in input order (mp_mesh_select_count,
+    mp_mesh_select).  keep [F] uint8 or bool -> vertices [nv,3], faces [nf,3] int32, colors [nv,3] or None, n_bad (faces with an index
+    outside [0, V): never kept).  ONE synchronisation: the totals are read back between the two calls."""
+    vertices, colors = _mesh_vertices(vertices, colors)
+    faces = _mesh_faces(faces)
+    keep = _dev_bytes("keep", keep)
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    if tuple(keep.shape) != (F,):
+        raise EngineError(f"keep must be [{F}], got {tuple(keep.shape)}")
+    dev = vertices.device
+    lib = _lib.load()
+    ws = _workspace(lib.mp_mesh_select_workspace_bytes(V, F), dev)
+    totals = torch.zeros(3, dtype=torch.int32, device=dev)
+    check(lib.mp_mesh_select_count(V, faces.data_ptr(), F, keep.data_ptr(), totals.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    nv, nf, n_bad = (int(v) for v in totals.cpu().tolist())      # the one synchronisation
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_c = None if colors is None else torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    check(lib.mp_mesh_select(vertices.data_ptr(), _ptr(colors), V, faces.data_ptr(), F, nv, nf, out_v.data_ptr(), _ptr(out_c), out_f.data_ptr(), nv, nf,
+                             ws.data_ptr(), ws.numel(), _stream()))
+    return out_v, out_f, out_c, n_bad
+
+
+def _mesh_cluster_count(lib, vertices, faces, grid, dims, ws) -> Tuple[int, int, int]:
+    totals = torch.zeros(3, dtype=torch.int32, device=vertices.device)
+    check(lib.mp_mesh_cluster_count(vertices.data_ptr(), int(vertices.shape[0]), faces.data_ptr(), int(faces.shape[0]), *grid, *dims, totals.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream()))
+    nv, nf, n_dropped = (int(v) for v in totals.cpu().tolist())  # the one synchronisation
+    return nv, nf, n_dropped
+
+
+def mesh_cluster_count(vertices: torch.Tensor, faces: torch.Tensor, origin: Sequence[float], cell: float, dims: Sequence[int]) -> Tuple[int, int, int]:
+    """What mesh_cluster would give on this grid, without building it (mp_mesh_cluster_count) -> vertices out, faces out, faces
+    dropped for a bad index or a vertex outside the grid.  One synchronisation."""
+    vertices, _ = _mesh_vertices(vertices, None)
+    faces = _mesh_faces(faces)
+    grid, dims = _mesh_grid(origin, cell, dims)
+    lib = _lib.load()
+    ws = _workspace(lib.mp_mesh_cluster_workspace_bytes(int(vertices.shape[0]), int(faces.shape[0]), *dims), vertices.device)
+    return _mesh_cluster_count(lib, vertices, faces, grid, dims, ws)
+
+
+def mesh_cluster(vertices: torch.Tensor, faces: torch.Tensor, origin: Sequence[float], cell: float, dims: Sequence[int],
+                 colors: Optional[torch.Tensor] = None):
+    """Decimation by vertex clustering (mp_mesh_cluster_count, mp_mesh_cluster): the vertices of one cell of the grid (origin, cell size,
+    dims = cells per axis) become their exact mean, triangles that lose a corner disappear -> vertices [nv,3] in cell order, faces
+    [nf,3] int32 in input order, colors [nv,3] or None, n_dropped.  Bit-reproducible.  ONE synchronisation."""
+    vertices, colors = _mesh_vertices(vertices, colors)
+    faces = _mesh_faces(faces)
+    grid, dims = _mesh_grid(origin, cell, dims)
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    dev = vertices.device
+    lib = _lib.load()
+    ws = _workspace(lib.mp_mesh_cluster_workspace_bytes(V, F, *dims), dev)
+    nv, nf, n_dropped = _mesh_cluster_count(lib, vertices, faces, grid, dims, ws)
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_c = None if colors is None else torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    check(lib.mp_mesh_cluster(vertices.data_ptr(), _ptr(colors), V, faces.data_ptr(), F, *grid, *dims, nv, nf, out_v.data_ptr(), _ptr(out_c),
+                              out_f.data_ptr(), nv, nf, ws.data_ptr(), ws.numel(), _stream()))
+    return out_v, out_f, out_c, n_dropped
+
+
+# --------------------------------------------------------------------------- #
 # BOP's model info (evaluation): csrc/model_info.hip
 MODEL_INFO_TILE_STEP = 64            # a forced tile is a multiple of this ...
 MODEL_INFO_MAX_TILE = 1024           # ... and at most this

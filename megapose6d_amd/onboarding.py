@@ -5,8 +5,11 @@ renderer, MeshDataBase, bop_models_info, find_symmetries and the pose estimator 
 The hot path is csrc/tsdf.hip (contract: csrc/tsdf_core.h): `TsdfVolume.integrate` is one launch per call, `TsdfVolume.extract` five
 launches and one read-back of two integers.  Sizing the volume (`volume_for_views`) is plain torch: it runs once per object.
 
-Not here: estimating the camera poses, smoothing, hole filling, keeping the largest component, decimation, texture atlases, distances
-along the ray, per-pixel weights.
+`reconstruct_object(..., keep_largest=True, max_faces=N)` passes the surface through mesh_cleanup (csrc/mesh_cleanup.hip) before it is
+written: only the component with the most faces, decimated by vertex clustering to at most N faces; the mesh stays on the device in between.
+
+Not here: estimating the camera poses, smoothing, hole filling, quadric decimation, texture atlases, distances along the ray, per-pixel
+weights.
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ import numpy as np
 import torch
 
 from . import engine as eng
-from . import mesh_io
+from . import mesh_cleanup, mesh_io
 from .object_dataset import RigidObject
 
 
@@ -73,9 +76,12 @@ class TsdfVolume:
     def extract(self, min_views: int = 1) -> Dict[str, np.ndarray]:
         """-> vertices [V,3] float32, faces [T,3] int32, colors [V,3] float32 in 0 .. 1, normals [V,3] float32 (area-weighted, pointing
         out of the object), as host arrays"""
-        v, c, f = eng.tsdf_extract(self._volume, self.origin, self.voxel_size, min_views)
-        v, c, f = v.cpu().numpy(), c.cpu().numpy(), f.cpu().numpy()
+        v, c, f = (t.cpu().numpy() for t in self.extract_device(min_views))
         return dict(vertices=v, faces=f, colors=c, normals=mesh_io.vertex_normals(v, f).astype(np.float32))
+
+    def extract_device(self, min_views: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """-> vertices [V,3] float32, colors [V,3] float32, faces [T,3] int32 as device tensors (what mesh_cleanup continues from)"""
+        return eng.tsdf_extract(self._volume, self.origin, self.voxel_size, min_views)
 
     def reset(self) -> None:
         self._volume.zero_()
@@ -119,9 +125,12 @@ def volume_for_views(depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, ma
 
 def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
                        rgb: Optional[torch.Tensor] = None, resolution: int = 128, out_dir=".", trunc_voxels: float = 3.0, min_views: int = 1,
-                       carve: bool = True, device="cuda") -> RigidObject:
+                       carve: bool = True, device="cuda", keep_largest: bool = False, max_faces: Optional[int] = None) -> RigidObject:
     """Posed depth views of one object -> `<out_dir>/<label>.ply` (metres, vertex normals, vertex colours: the views' where rgb is
-    given, else white) and the RigidObject that names it.  Raises a ValueError that names the cause when there is no surface."""
+    given, else white) and the RigidObject that names it.  Raises a ValueError that names the cause when there is no surface.
+    keep_largest: only the connected component with the most faces is written (loose fragments of noisy depth or leaking masks go);
+    max_faces: the surface is decimated by vertex clustering to at most that many faces (mesh_cleanup.simplify).  Both are off by
+    default, and the mesh is then the extracted one bit for bit."""
     depth = torch.as_tensor(depth)
     if depth.dim() != 3 or depth.shape[0] == 0:
         raise ValueError(f"reconstruct_object({label!r}): depth must be [n,h,w] with at least one view, got {tuple(depth.shape)}")
@@ -140,7 +149,14 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
         raise ValueError(f"reconstruct_object({label!r}): {e}") from e
     vol = TsdfVolume(origin, voxel, dims, trunc_voxels=trunc_voxels, color=rgb is not None, device=device)
     vol.integrate(depth, K, TCO, masks=masks, rgb=rgb, carve=carve)
-    mesh = vol.extract(min_views=min_views)
+    v, c, f = vol.extract_device(min_views=min_views)
+    mesh = dict(vertices=v, faces=f, colors=c)
+    if len(mesh["faces"]) > 0 and (keep_largest or max_faces is not None):
+        try:
+            mesh = mesh_cleanup.clean_mesh(mesh, keep_largest=keep_largest, max_faces=max_faces)
+        except ValueError as e:
+            raise ValueError(f"reconstruct_object({label!r}): {e}") from e
+    mesh = mesh_cleanup.to_host(mesh)
     if len(mesh["faces"]) == 0:
         seen = int((vol.counts >= min_views).sum())
         raise ValueError(f"reconstruct_object({label!r}): the surface is empty: {seen} of {vol.counts.numel()} nodes were seen by at least "
