@@ -287,7 +287,7 @@ def raster_render_scene(db: MeshDB, obj_off: Sequence[int], mesh_ids: torch.Tens
     assert instance is None or (instance.dtype == torch.int32 and instance.is_cuda and instance.is_contiguous() and instance.numel() >= n_cams * h * w)
     n_obj = int(obj_off[-1])
     need = lib.mp_raster_scene_workspace_bytes(db.handle, n_obj, h, w)
-    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    ws = _workspace(need, dev)
     check(lib.mp_raster_render_scene(db.handle, n_cams, off, d_off.data_ptr(), mesh_ids.data_ptr(), TCO.data_ptr(), K.data_ptr(),
                                      radius.data_ptr(), lights.data_ptr(), h, w, flags, _ptr(out), stride_v, stride_y, stride_x, c_rgb,
                                      c_normals, c_depth, _ptr(instance), ws.data_ptr(), ws.numel(), _stream()))
