@@ -743,6 +743,44 @@ int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int color, flo
                     mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* A texture atlas for a triangle mesh (a reconstruction's) from the posed colour + depth   */
+/* views it was made from: every triangle gets a chart, every texel of a chart gathers its  */
+/* colour from the views that see its surface point (csrc/texture_bake.hip; contract in     */
+/* csrc/texture_bake_core.h).  The reference has no counterpart; Open3D, xatlas and          */
+/* MVS-texturing are third party and absent: parity with them is unpinned.                  */
+/* The atlas is size x size texels (a power of two, 64 .. 8192; row 0 is v = 0), cut into    */
+/* blocks of B x B texels in row-major order; block k holds triangle 2k (the lower chart,    */
+/* legs of B - 3 texels from the block's first texel) and 2k + 1 (the upper chart, the lower */
+/* one turned by 180 degrees).                                                              */
+/* ------------------------------------------------------------------------------------ */
+/* B for n_triangles in an atlas of `size`: the largest of 64, 32, 16, 8, 4 with ceil(n_triangles / 2) <= (size / B)^2; 0 when none fits,
+   when size is no power of two in 64 .. 8192, or n_triangles < 1.  Host only. */
+int mp_texture_atlas_block(long long n_triangles, int size);
+/* Writes the per-corner texture coordinates of the charts: corner c of triangle t at the centre of its chart's corner texel,
+   ((i + 0.5) / size, (j + 0.5) / size).  One launch on `stream`.  Any bad argument (a null or misaligned pointer, n_triangles outside
+   1 .. 2^29, a bad size, triangles that do not fit) returns non-zero before anything is launched. */
+int mp_texture_atlas_uvs(int n_triangles, int size, float* d_uvs /*[n_triangles,3,2]*/, mp_stream stream);
+/* Bakes the atlas (rules: csrc/texture_bake_core.h).  Per texel of a chart: its chart coordinates (a, b), clamped onto the triangle,
+   give the surface point p = v0 + a (v1 - v0) + b (v2 - v0); per view, in ascending order: pc = R p + t, skipped unless pc.z > z_min and
+   the pixel floor(f * pc / pc.z + c) lies in the frame; skipped unless the face normal looks at the camera with cos > cos_min (weight
+   cos^2); a pixel counts when its mask is non-zero (d_masks given), its depth is finite, > 0 and within depth_tol of pc.z (the occlusion
+   test); the colour is the bilinear mix of the four pixels around the projection when all four count, else the nearest pixel's, else
+   the view is skipped.  The texel is the weighted mean over the views (best_view: the colour of the heaviest view), rounded half up;
+   d_seen the number of contributing views, capped at 255.  A texel no view contributes to takes the interpolated d_colors ([V,3] floats
+   in 0 .. 1) or white; texels of no triangle are four zero bytes.  TCO maps object to camera (rows of 4; tco_floats = 12 or 16 per
+   view); K is 3 x 3 row-major; a view whose K or TCO holds a non-finite entry contributes nothing.  A face with an index outside
+   [0, n_vertices), a non-finite vertex or no area bakes as unseen, never an access out of range.  One launch on `stream`, one lane per
+   texel, no atomics, no workspace.  n == 0 bakes the fallback everywhere (the view pointers may then be null); any bad argument (a
+   null pointer where one is needed, texels or a 32-bit input not 4-byte aligned, counts or size out of range, triangles that do not
+   fit, a non-finite or non-positive depth_tol, cos_min outside [0, 1), a negative or non-finite z_min, frames outside 1 .. 8192 a
+   side) returns non-zero before anything is launched. */
+int mp_texture_bake(const float* d_vertices /*[n_vertices,3]*/, int n_vertices, const int32_t* d_faces /*[n_triangles,3]*/, int n_triangles,
+                    const float* d_colors /*[n_vertices,3] or NULL*/, const float* d_depth /*[n,h,w]*/, const uint8_t* d_masks /*[n,h,w] or NULL*/,
+                    const uint8_t* d_rgb /*[n,h,w,3]*/, const float* d_K /*[n,9]*/, const float* d_TCO /*[n,tco_floats]*/, int tco_floats, int n,
+                    int h, int w, int size, float depth_tol, float cos_min, float z_min, int best_view, uint8_t* d_texels /*[size,size,4]*/,
+                    uint8_t* d_seen /*[size,size]*/, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Cleaning up a triangle mesh (a reconstruction's, a heavy scan's): its connected          */
 /* components, the selection of faces with the vertices they reference, and decimation by   */
 /* vertex clustering, Rossignac-Borrel (csrc/mesh_cleanup.hip; contract in                  */

@@ -1225,6 +1225,78 @@ def tsdf_extract(volume: torch.Tensor, origin: Sequence[float], voxel: float, mi
 
 
 # --------------------------------------------------------------------------- #
+# A texture atlas for a mesh from its posed views (onboarding.bake_texture), csrc/texture_bake.hip
+TEXTURE_MIN_SIZE, TEXTURE_MAX_SIZE = 64, 8192   # texels a side, a power of two
+
+
+def texture_atlas_block(n_triangles: int, size: int) -> int:
+    """The side B of the square blocks of a size x size atlas for n_triangles (mp_texture_atlas_block): the largest of 64, 32, 16, 8, 4
+    with ceil(n_triangles / 2) <= (size / B)^2, 0 when none fits or size is no power of two in 64 .. 8192.  Block k, in row-major
+    order, holds triangles 2k and 2k + 1 with legs of B - 3 texels."""
+    return int(_lib.load().mp_texture_atlas_block(int(n_triangles), int(size)))
+
+
+def _texture_block(what: str, n_triangles: int, size: int) -> int:
+    block = texture_atlas_block(n_triangles, size) if n_triangles >= 1 else 0
+    if block == 0:
+        raise EngineError(f"{what}: {n_triangles} triangles (at least 1) do not fit an atlas of {size} x {size} texels (a power of two, "
+                          f"{TEXTURE_MIN_SIZE} .. {TEXTURE_MAX_SIZE}; two triangles per block of at least 4 x 4)")
+    return block
+
+
+def texture_atlas_uvs(n_triangles: int, size: int, device="cuda") -> torch.Tensor:
+    """The per-corner texture coordinates [n_triangles,3,2] float32 of the atlas's charts (mp_texture_atlas_uvs): the centres of the
+    charts' corner texels, row 0 of the texture being v = 0.  Nothing synchronises."""
+    n_triangles, size = int(n_triangles), int(size)
+    _texture_block("texture_atlas_uvs", n_triangles, size)
+    uvs = torch.empty(n_triangles, 3, 2, dtype=torch.float32, device=device)
+    check(_lib.load().mp_texture_atlas_uvs(n_triangles, size, uvs.data_ptr(), _stream()))
+    return uvs
+
+
+def texture_bake(vertices: torch.Tensor, faces: torch.Tensor, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor,
+                 masks: Optional[torch.Tensor], rgb: torch.Tensor, size: int, colors: Optional[torch.Tensor] = None, depth_tol: float = 2e-3,
+                 cos_min: float = 0.2, z_min: float = 1e-3, best_view: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Bakes the texture atlas of a mesh from n posed views (mp_texture_bake; the rules are stated in csrc/texture_bake_core.h).
+    vertices [V,3] float32 in the object's frame, faces [T,3] int32, depth [n,h,w] metres (not finite or <= 0: no measurement), K
+    [n,3,3], TCO [n,4,4] or [n,3,4] object to camera, masks [n,h,w] uint8 / bool or None (0: not the object), rgb [n,h,w,3] uint8,
+    colors [V,3] floats in 0 .. 1 (what a texel no view sees takes; white without).  A view colours a texel when the texel's surface
+    point projects into its frame, faces it with cos > cos_min and lies within depth_tol metres of the view's own depth there; the texel
+    is the cos^2-weighted mean of the views' bilinear colours (best_view: the colour of the view that sees it most squarely).
+    -> texels [size,size,4] uint8 (RGBA, row 0 is v = 0; alpha 255 on charts, 0 elsewhere), seen [size,size] uint8 (contributing views,
+    capped at 255), on the device.  The charts' texture coordinates are texture_atlas_uvs(T, size).  Nothing synchronises."""
+    vertices, colors = _mesh_vertices(vertices, colors)
+    faces = _mesh_faces(faces)
+    size = int(size)
+    _texture_block("texture_bake", int(faces.shape[0]), size)
+    depth = _dev_f32(depth)
+    if depth.dim() != 3:
+        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
+    n, h, w = (int(v) for v in depth.shape)
+    K, TCO = _dev_f32(K).reshape(n, -1) if n else _dev_f32(K), _dev_f32(TCO).reshape(n, -1) if n else _dev_f32(TCO)
+    if n and (K.shape[1] != 9 or TCO.shape[1] not in (12, 16)):
+        raise EngineError(f"K must be [n,3,3] and TCO [n,4,4] or [n,3,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
+    if masks is not None:
+        masks = _dev_bytes("masks", masks)
+        if tuple(masks.shape) != (n, h, w):
+            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
+    if rgb is None:
+        raise EngineError("texture_bake: rgb is what the texture is made of")
+    rgb = _dev_bytes("rgb", rgb)
+    if tuple(rgb.shape) != (n, h, w, 3):
+        raise EngineError(f"rgb must be {(n, h, w, 3)}, got {tuple(rgb.shape)}")
+    dev = vertices.device
+    texels = torch.empty(size, size, 4, dtype=torch.uint8, device=dev)
+    seen = torch.empty(size, size, dtype=torch.uint8, device=dev)
+    ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)   # noqa: E731
+    check(_lib.load().mp_texture_bake(vertices.data_ptr() if vertices.shape[0] else None, int(vertices.shape[0]), faces.data_ptr(), int(faces.shape[0]),
+                                      _ptr(colors), ptr(depth), _ptr(masks) if n else None, ptr(rgb), ptr(K), ptr(TCO), int(TCO.shape[1]) if n else 16,
+                                      n, h, w, size, float(depth_tol), float(cos_min), float(z_min), int(bool(best_view)), texels.data_ptr(),
+                                      seen.data_ptr(), _stream()))
+    return texels, seen
+
+
+# --------------------------------------------------------------------------- #
 # Cleaning up a triangle mesh (mesh_cleanup): components, selection, vertex clustering, csrc/mesh_cleanup.hip
 MESH_MAX_COUNT = 1 << 29             # vertices, faces
 MESH_MAX_DIM = 512                   # cells a side

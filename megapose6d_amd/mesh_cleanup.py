@@ -13,7 +13,8 @@ The hot path is csrc/mesh_cleanup.hip (contract: csrc/mesh_cleanup_core.h) throu
 `simplify(max_faces=)` are plain torch / numpy on a few numbers.  `backend` is what runs the four operations: the device by default;
 the tests pass the host emulation.
 
-Not here: removal of duplicate triangles, quadric (edge-collapse) decimation, smoothing, hole filling, texture atlases, "largest" by area.
+Not here: removal of duplicate triangles, quadric (edge-collapse) decimation, smoothing, hole filling, "largest" by area, carrying an
+existing texture over to the clustered mesh (a new one is baked from the views: `onboarding.bake_texture`).
 """
 from __future__ import annotations
 

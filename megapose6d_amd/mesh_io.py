@@ -15,7 +15,8 @@ PIL, flipped so that v grows with the row index, and expanded into an RGBA8 mip 
 -- the rasteriser's input.  Meshes without vertex colours render white (times the texture, if any), as
 Panda3D does.
 
-Written: `write_ply` (binary PLY with optional normals and vertex colours), for the meshes `megapose6d_amd.onboarding` reconstructs.
+Written: `write_ply` (binary PLY with optional normals, vertex colours, per-face texture coordinates and the TextureFile comment) and
+`write_texture` (PNG), for the meshes `megapose6d_amd.onboarding` reconstructs and textures.
 """
 from __future__ import annotations
 
@@ -175,9 +176,13 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
             "texture_path": tex}
 
 
-def write_ply(path, vertices, faces, colors=None, normals=None) -> Path:
+def write_ply(path, vertices, faces, colors=None, normals=None, uvs=None, texture_file=None) -> Path:
     """Writes a binary little-endian PLY that `read_ply` takes back: float32 x y z, with `normals` float32 nx ny nz, with `colors`
-    ([V,3] floats in 0 .. 1, or uint8) uchar red green blue, triangles as `list uchar int vertex_indices`."""
+    ([V,3] floats in 0 .. 1, or uint8) uchar red green blue, triangles as `list uchar int vertex_indices`.  With `uvs` ([T,3,2], per
+    corner) and `texture_file` (the picture's name next to the PLY: `write_texture`), BOP's convention: `comment TextureFile <name>` and
+    per face `list uchar float texcoord` with u0 v0 u1 v1 u2 v2 in float32.  Without the two, the bytes are what they were before."""
+    if (uvs is None) != (texture_file is None):
+        raise ValueError(f"{path}: uvs and texture_file go together")
     v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
     f = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
     if len(f) and (f.min() < 0 or f.max() >= len(v)):
@@ -201,18 +206,41 @@ def write_ply(path, vertices, faces, colors=None, normals=None) -> Path:
     if colors is not None:
         for k, n in enumerate(("red", "green", "blue")):
             vrec[n] = colors[:, k]
-    frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    ffields = [("n", "u1"), ("idx", "<i4", (3,))] + ([("nt", "u1"), ("uv", "<f4", (6,))] if uvs is not None else [])
+    frec = np.zeros(len(f), dtype=np.dtype(ffields))
     frec["n"] = 3
     frec["idx"] = f
     names = {"<f4": "float", "u1": "uchar"}
-    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header = ["ply", "format binary_little_endian 1.0"]
+    if uvs is not None:
+        if not str(texture_file).strip() or any(ch in str(texture_file) for ch in "\r\n/\\"):
+            raise ValueError(f"{path}: texture_file {texture_file!r} must be a plain file name next to the PLY")
+        frec["nt"] = 6
+        frec["uv"] = np.asarray(uvs, dtype=np.float32).reshape(len(f), 6)
+        header += [f"comment TextureFile {texture_file}"]
+    header += [f"element vertex {len(v)}"]
     header += [f"property {names[t]} {n}" for n, t in fields]
-    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices"]
+    header += ["property list uchar float texcoord"] if uvs is not None else []
+    header += ["end_header"]
     path = Path(path)
     with open(path, "wb") as out:
         out.write(("\n".join(header) + "\n").encode("ascii"))
         out.write(vrec.tobytes())
         out.write(frec.tobytes())
+    return path
+
+
+def write_texture(path, image) -> Path:
+    """uint8 [H,W,3|4] with row 0 = v 0 (the engine's convention) -> a PNG through PIL, flipped so that `load_texture` returns the same
+    array (alpha is dropped: the loader reads RGB)."""
+    from PIL import Image
+
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"{path}: a texture is uint8 [H,W,3] or [H,W,4], got {img.dtype} {img.shape}")
+    path = Path(path)
+    Image.fromarray(np.ascontiguousarray(img[::-1, :, :3])).save(path, format="PNG")
     return path
 
 

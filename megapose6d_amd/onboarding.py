@@ -8,8 +8,11 @@ launches and one read-back of two integers.  Sizing the volume (`volume_for_view
 `reconstruct_object(..., keep_largest=True, max_faces=N)` passes the surface through mesh_cleanup (csrc/mesh_cleanup.hip) before it is
 written: only the component with the most faces, decimated by vertex clustering to at most N faces; the mesh stays on the device in between.
 
-Not here: estimating the camera poses, smoothing, hole filling, quadric decimation, texture atlases, distances along the ray, per-pixel
-weights.
+`bake_texture` (and `reconstruct_object(..., texture_size=S)`) gives the mesh a texture atlas baked from the same views (csrc/texture_bake.hip,
+contract: csrc/texture_bake_core.h): a chart per triangle, two launches; the PLY then carries texture coordinates and names a PNG.
+
+Not here: estimating the camera poses, smoothing, hole filling, quadric decimation, charts sized by area or packed by a parametrisation,
+transferring an existing texture, distances along the ray, per-pixel weights.
 """
 from __future__ import annotations
 
@@ -123,14 +126,86 @@ def volume_for_views(depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, ma
     return tuple(float(v) for v in origin), float(voxel), dims
 
 
+def mean_edge_length(vertices: torch.Tensor, faces: torch.Tensor) -> float:
+    """the mean length of the three edges of the faces whose indices are in range and whose corners are finite (0.0 without any); plain
+    torch, one read-back"""
+    f = faces.long()
+    ok = ((f >= 0) & (f < vertices.shape[0])).all(1)
+    if not bool(ok.any()):
+        return 0.0
+    tri = vertices[f[ok]]                                    # [T,3,3]
+    edges = (tri - tri.roll(1, dims=1)).norm(dim=2)
+    edges = edges[torch.isfinite(edges)]
+    return float(edges.mean()) if edges.numel() else 0.0
+
+
+def bake_texture(mesh, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                 rgb: Optional[torch.Tensor] = None, texture_size: int = 1024, depth_tol: Optional[float] = None, cos_min: float = 0.2,
+                 best_view: bool = False, device="cuda") -> Tuple[Dict[str, object], float]:
+    """A texture atlas for `mesh` from the posed views it was reconstructed from, so that its colour resolution no longer equals its
+    vertex density: every triangle gets a chart in a texture_size x texture_size atlas (engine.texture_atlas_uvs), every texel of a
+    chart the cos^2-weighted mean of the colours of the views that see its surface point (engine.texture_bake; best_view: the colour of
+    the view that sees it most squarely).  A texel no view sees takes the mesh's interpolated vertex colours, or white.
+
+    mesh: a dict with `vertices` [V,3], `faces` [T,3] and optionally `colors` [V,3] in 0 .. 1, numpy arrays or tensors; a device mesh (from
+    `mesh_cleanup.clean_mesh`) continues on its device.  depth [n,h,w], K [n,3,3], TCO [n,4,4], masks [n,h,w] or None, rgb [n,h,w,3] uint8.
+    -> (the mesh with `uvs` [T,3,2] float32, `texture` [S,S,3] uint8 (row 0 is v = 0: what `mesh_io.write_texture` takes) and `seen`
+    [S,S] uint8 (views per texel) added, all on the device; the share of the charts' texels that at least one view coloured).
+
+    depth_tol (metres) is how far a texel's surface point may lie from the depth a view measured at its pixel and still count as seen by
+    it, not as hidden behind something else.  It has to cover the distance between the mesh and the measured surface.  The surface of a
+    mesh decimated by vertex clustering lies within one cell of the measured one (a clustered vertex is the mean of vertices of one
+    cell), and its edges join the means of neighbouring cells, so their mean length is about one cell or more: None takes the mean edge
+    length of the mesh.  For a mesh as extracted, whose edges are shorter than a voxel, the right value is the truncation distance of
+    the volume (the band in which the views' depths were averaged into the surface): `reconstruct_object` passes the larger of the two.
+
+    Every triangle gets the same chart size whatever its area, so a mesh of uniform triangles (a TSDF surface, a clustered one) uses
+    the atlas best.  One launch for the coordinates, one for the bake, one read-back for the covered share (and one for the mean edge
+    length when depth_tol is None)."""
+    if rgb is None:
+        raise ValueError("bake_texture: rgb is what the texture is made of: give the views' colour frames")
+    dev = device
+    for t in (mesh["vertices"], mesh["faces"]):
+        if torch.is_tensor(t) and t.is_cuda:
+            dev = t.device
+    to_dev = lambda t, dt: torch.as_tensor(t).to(dev, dt).contiguous()   # noqa: E731
+    v, f = to_dev(mesh["vertices"], torch.float32).reshape(-1, 3), to_dev(mesh["faces"], torch.int32).reshape(-1, 3)
+    c = None if mesh.get("colors") is None else to_dev(mesh["colors"], torch.float32).reshape(-1, 3)
+    size = int(texture_size)
+    if f.shape[0] < 1 or eng.texture_atlas_block(int(f.shape[0]), size) == 0:
+        raise ValueError(f"bake_texture: {int(f.shape[0])} faces (at least 1) do not fit a texture of {size} x {size} (a power of two, "
+                         f"{eng.TEXTURE_MIN_SIZE} .. {eng.TEXTURE_MAX_SIZE}; two triangles share a block of at least 4 x 4 texels): "
+                         f"use a larger texture_size or fewer faces (max_faces)")
+    if depth_tol is None:
+        depth_tol = mean_edge_length(v, f)
+    if not (np.isfinite(depth_tol) and depth_tol > 0):
+        raise ValueError(f"bake_texture: depth_tol {depth_tol} must be finite and positive (a mesh without a usable edge has no default)")
+    as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
+    texels, seen = eng.texture_bake(v, f, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), as_dev(rgb), size, colors=c,
+                                    depth_tol=float(depth_tol), cos_min=cos_min, best_view=best_view)
+    chart = texels[..., 3] != 0
+    coverage = float(((seen != 0) & chart).sum() / chart.sum().clamp(min=1))
+    out = dict(mesh)
+    out.update(vertices=v, faces=f, colors=c, uvs=eng.texture_atlas_uvs(int(f.shape[0]), size, device=dev),
+               texture=texels[..., :3].contiguous(), seen=seen)
+    return out, coverage
+
+
 def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
                        rgb: Optional[torch.Tensor] = None, resolution: int = 128, out_dir=".", trunc_voxels: float = 3.0, min_views: int = 1,
-                       carve: bool = True, device="cuda", keep_largest: bool = False, max_faces: Optional[int] = None) -> RigidObject:
+                       carve: bool = True, device="cuda", keep_largest: bool = False, max_faces: Optional[int] = None,
+                       texture_size: Optional[int] = None) -> RigidObject:
     """Posed depth views of one object -> `<out_dir>/<label>.ply` (metres, vertex normals, vertex colours: the views' where rgb is
     given, else white) and the RigidObject that names it.  Raises a ValueError that names the cause when there is no surface.
     keep_largest: only the connected component with the most faces is written (loose fragments of noisy depth or leaking masks go);
     max_faces: the surface is decimated by vertex clustering to at most that many faces (mesh_cleanup.simplify).  Both are off by
-    default, and the mesh is then the extracted one bit for bit."""
+    default, and the mesh is then the extracted one bit for bit.
+    texture_size: after the clean-up the mesh gets a texture atlas of that many texels a side from the views' rgb (`bake_texture`), and
+    `<label>.png` is written next to a PLY that names it: no vertex colours (white times the texture, as the loader renders it),
+    texture coordinates per face corner, normals.  `mesh_io.load_rigid_object` then yields `uvs` and `texture_mips` with no further
+    argument.  Needs rgb.  None (the default): every byte written is what it was without the argument."""
+    if texture_size is not None and rgb is None:
+        raise ValueError(f"reconstruct_object({label!r}): texture_size {texture_size} needs rgb: a texture is baked from the views' colour frames")
     depth = torch.as_tensor(depth)
     if depth.dim() != 3 or depth.shape[0] == 0:
         raise ValueError(f"reconstruct_object({label!r}): depth must be [n,h,w] with at least one view, got {tuple(depth.shape)}")
@@ -156,6 +231,13 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
             mesh = mesh_cleanup.clean_mesh(mesh, keep_largest=keep_largest, max_faces=max_faces)
         except ValueError as e:
             raise ValueError(f"reconstruct_object({label!r}): {e}") from e
+    baked = None
+    if texture_size is not None and len(mesh["faces"]) > 0:
+        try:
+            baked, _ = bake_texture(mesh, depth, K, TCO, masks=masks, rgb=rgb, texture_size=texture_size,
+                                    depth_tol=max(vol.mu, mean_edge_length(mesh["vertices"], mesh["faces"])), device=device)
+        except ValueError as e:
+            raise ValueError(f"reconstruct_object({label!r}): {e}") from e
     mesh = mesh_cleanup.to_host(mesh)
     if len(mesh["faces"]) == 0:
         seen = int((vol.counts >= min_views).sum())
@@ -163,5 +245,10 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
                          f"{min_views} view(s) and no complete cell holds a change of sign (poses, intrinsics or units that do not fit the depth?)")
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
-    path = mesh_io.write_ply(out_dir / f"{label}.ply", mesh["vertices"], mesh["faces"], colors=mesh["colors"], normals=mesh["normals"])
+    if baked is not None:
+        texture = mesh_io.write_texture(out_dir / f"{label}.png", baked["texture"].cpu().numpy())
+        path = mesh_io.write_ply(out_dir / f"{label}.ply", mesh["vertices"], mesh["faces"], normals=mesh["normals"],
+                                 uvs=baked["uvs"].cpu().numpy(), texture_file=texture.name)
+    else:
+        path = mesh_io.write_ply(out_dir / f"{label}.ply", mesh["vertices"], mesh["faces"], colors=mesh["colors"], normals=mesh["normals"])
     return RigidObject(label, path, mesh_units="m")
