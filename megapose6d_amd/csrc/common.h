@@ -50,6 +50,22 @@ int device_lds_bytes();
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// The one way to lay out a caller-provided workspace (host only).  A feature states its regions once, as the take() calls of one
+// function of the base and the shape: on a null base that function only measures (null regions, total() = the size to provide), on
+// the caller's base it hands out the same regions.
+struct WsCarver {
+  char* base;   // null: measure
+  size_t off = 0;
+  explicit WsCarver(void* b) : base((char*)b) {}
+  // the next region: count elements, padded to a multiple of 256 bytes (unpadded: the last region of a size reported without padding)
+  template <typename T> T* take(size_t count, bool padded = true) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += padded ? align256(count * sizeof(T)) : count * sizeof(T);
+    return p;
+  }
+  size_t total(size_t slack = 0) const { return off + slack; }
+};
+
 // XCD-aware bijective remap of a linear workgroup id (8 XCDs, round-robin dispatch):
 // physical id p runs on XCD p % 8; give each XCD a contiguous chunk of logical ids so that
 // neighbouring tiles (shared halos / shared weight panels) hit the same private L2.

@@ -700,17 +700,38 @@ extern "C" int mp_icp_nn_max_points(void) { return 1 << IDX_BITS; }   // (the se
 // points per object the buffers of a call are sized for: every pixel of the frame, up to the key's limit
 static size_t nn_cap(int H, int W) { return std::min((size_t)H * W, (size_t)1 << IDX_BITS); }
 
-extern "C" size_t mp_icp_nn_workspace_bytes(int n_images, int n_rows, int H, int W) {
-  const size_t px = (size_t)H * W, cap = nn_cap(H, W);
-  const size_t imgs = (size_t)n_images + n_rows;
-  size_t b = 0;
-  b += 3 * align256(imgs * px * 4);            // fill ping / pong, gaussian temp
-  b += 2 * align256(imgs * px);                // valid ping / pong
-  b += align256(imgs * px * 6 * 4);            // points + normals of every image
-  b += 5 * align256((size_t)n_rows * cap * 6 * 4) + 2 * align256((size_t)n_rows * cap * 4) + align256((size_t)n_rows * cap * 4) + 2 * align256((size_t)n_rows * cap * 8);
-  b += align256((size_t)n_rows * sizeof(NnRow)) + align256(imgs * 4) + 4096;
-  return b;
-}
+struct NnWs {
+  float *fa, *fb, *raw, *pts;   // fill ping / pong, gaussian temp; points + normals of every image
+  unsigned char *va, *vb;       // valid ping / pong
+  NnScratch sc;
+  NnRow* rows;
+  size_t total;
+  NnWs(void* base, int n_images, int n_rows, int H, int W) {
+    const size_t imgs = (size_t)n_images + n_rows, px = (size_t)H * W, n = (size_t)n_rows * nn_cap(H, W);
+    WsCarver c(base);
+    fa = c.take<float>(imgs * px);
+    fb = c.take<float>(imgs * px);
+    raw = c.take<float>(imgs * px);
+    va = c.take<unsigned char>(imgs * px);
+    vb = c.take<unsigned char>(imgs * px);
+    pts = c.take<float>(imgs * px * 6);
+    sc.src = c.take<float>(n * 6);
+    sc.dst = c.take<float>(n * 6);
+    sc.src_t = c.take<float>(n * 6);
+    sc.moved = c.take<float>(n * 6);
+    sc.dst_s = c.take<float>(n * 6);
+    sc.d2 = c.take<float>(n);
+    sc.dev = c.take<float>(n);
+    sc.nn = c.take<int>(n);
+    sc.key = c.take<unsigned long long>(n);
+    sc.nnkey = c.take<unsigned long long>(n);
+    rows = c.take<NnRow>((size_t)n_rows);
+    c.take<int32_t>(imgs);   // part of the reported size; no kernel uses it
+    total = c.total(4096);
+  }
+};
+
+extern "C" size_t mp_icp_nn_workspace_bytes(int n_images, int n_rows, int H, int W) { return NnWs(nullptr, n_images, n_rows, H, W).total; }
 
 extern "C" int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const int32_t* d_im_ids, const float* d_depth_rend,
                                 const float* d_K_images, const float* d_K_rows, const float* d_TCO, int n_rows, int H, int W,
@@ -720,33 +741,18 @@ extern "C" int mp_icp_refine_nn(const float* d_depth_meas, int n_images, const i
                                 mp_stream stream) {
   MP_REQUIRE(d_depth_meas && d_im_ids && d_depth_rend && d_K_images && d_K_rows && d_TCO && d_TCO_out && d_ws, "mp_icp_refine_nn: null pointer");
   MP_REQUIRE(n_images > 0 && n_rows >= 0 && H > 2 && W > 2 && n_iterations > 0 && n_levels >= 1 && n_levels <= 8, "mp_icp_refine_nn: bad size");
-  MP_REQUIRE(ws_bytes >= mp_icp_nn_workspace_bytes(n_images, n_rows, H, W), "mp_icp_refine_nn: workspace too small");
+  const NnWs ws(d_ws, n_images, n_rows, H, W);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_icp_refine_nn: workspace too small");
   if (n_rows == 0) return MP_OK;
   MP_REQUIRE(n_rows <= 65535 && n_images <= 65535, "mp_icp_refine_nn: at most 65535 rows / images");
   MP_REQUIRE(n_min_points >= 6, "mp_icp_refine_nn: n_min_points must be >= 6 (an empty / degenerate cloud has no centroid and no 6-dof solve; the reference uses 1000)");
   hipStream_t s = (hipStream_t)stream;
   const size_t px = (size_t)H * W, cap = nn_cap(H, W);
   const int imgs = n_images + n_rows;   // image batch: the measured frames first, then the rendered depth of every object
-  unsigned char* w = (unsigned char*)d_ws;
-  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
-  float* fa = (float*)take(imgs * px * 4);
-  float* fb = (float*)take(imgs * px * 4);
-  float* raw = (float*)take(imgs * px * 4);
-  unsigned char* va = take(imgs * px);
-  unsigned char* vb = take(imgs * px);
-  float* pts = (float*)take(imgs * px * 6 * 4);
-  NnScratch sc;
-  sc.src = (float*)take((size_t)n_rows * cap * 24);
-  sc.dst = (float*)take((size_t)n_rows * cap * 24);
-  sc.src_t = (float*)take((size_t)n_rows * cap * 24);
-  sc.moved = (float*)take((size_t)n_rows * cap * 24);
-  sc.dst_s = (float*)take((size_t)n_rows * cap * 24);
-  sc.d2 = (float*)take((size_t)n_rows * cap * 4);
-  sc.dev = (float*)take((size_t)n_rows * cap * 4);
-  sc.nn = (int*)take((size_t)n_rows * cap * 4);
-  sc.key = (unsigned long long*)take((size_t)n_rows * cap * 8);
-  sc.nnkey = (unsigned long long*)take((size_t)n_rows * cap * 8);
-  NnRow* rows = (NnRow*)take((size_t)n_rows * sizeof(NnRow));
+  float *fa = ws.fa, *fb = ws.fb, *raw = ws.raw, *pts = ws.pts;
+  unsigned char *va = ws.va, *vb = ws.vb;
+  const NnScratch& sc = ws.sc;
+  NnRow* rows = ws.rows;
   ProfScope prof("icp_refine_nn", 0.0, (double)imgs * px * 40.0, s);
   // batch the images: raw = [measured frames | rendered depths]
   MP_CHECK_HIP(hipMemcpyAsync(raw, d_depth_meas, (size_t)n_images * px * 4, hipMemcpyDeviceToDevice, s));

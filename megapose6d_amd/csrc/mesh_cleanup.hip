@@ -383,77 +383,47 @@ __global__ __launch_bounds__(kMcBlock) void mc_uf_empty_kernel(int32_t* __restri
 }
 
 // ---- workspaces ----------------------------------------------------------------------------------------------------------------------------
-struct Bump {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off += align256(bytes);
-    return o;
-  }
-};
-
-struct RankPlan {
-  size_t bytes, lrank, base;
-  long long n;
-  int n_blocks;
-};
-
-static RankPlan rank_plan(Bump* b, long long n) {
-  RankPlan p;
-  p.n = n;
-  p.n_blocks = ceil_div(n, kRankSpan);
-  p.bytes = b->take((size_t)p.n_blocks * kRankSpan);
-  p.lrank = b->take((size_t)p.n_blocks * kMcBlock * sizeof(uint16_t));
-  p.base = b->take((size_t)p.n_blocks * sizeof(int32_t));
-  return p;
-}
-
-static RankBuf rank_buf(void* d_ws, const RankPlan& p) {
-  char* w = (char*)d_ws;
+static RankBuf rank_buf(WsCarver* c, long long n) {
   RankBuf r;
-  r.bytes = (uint8_t*)(w + p.bytes);
-  r.lrank = (uint16_t*)(w + p.lrank);
-  r.base = (int32_t*)(w + p.base);
-  r.n = p.n;
-  r.n_blocks = p.n_blocks;
+  r.n = n;
+  r.n_blocks = ceil_div(n, kRankSpan);
+  r.bytes = c->take<uint8_t>((size_t)r.n_blocks * kRankSpan);
+  r.lrank = c->take<uint16_t>((size_t)r.n_blocks * kMcBlock);
+  r.base = c->take<int32_t>((size_t)r.n_blocks);
   return r;
 }
 
-struct SelectPlan {
-  RankPlan v, f;
+struct SelectWs {
+  int32_t* counters;
+  RankBuf v, f;
   size_t total;
+  SelectWs(void* base, int V, int F) {
+    WsCarver c(base);
+    counters = c.take<int32_t>(kMcCounterBytes / sizeof(int32_t));
+    v = rank_buf(&c, V);
+    f = rank_buf(&c, F);
+    total = c.total();
+  }
 };
 
-static SelectPlan select_plan(int V, int F) {
-  Bump b;
-  b.take(kMcCounterBytes);
-  SelectPlan p;
-  p.v = rank_plan(&b, V);
-  p.f = rank_plan(&b, F);
-  p.total = b.off;
-  return p;
-}
-
-struct ClusterPlan {
-  size_t vcell, acc;
-  RankPlan u, f;
-  long long max_out;   // an output vertex is a used cell that holds a vertex
+struct ClusterWs {
+  int32_t *counters, *vcell;
+  RankBuf u, f;
+  long long max_out;          // an output vertex is a used cell that holds a vertex
+  unsigned long long* acc;    // [n_vertices][6] sums, then [n_vertices] int32 counts: at most max_out * 52 bytes
   size_t total;
+  ClusterWs(void* base, int V, int F, int gx, int gy, int gz) {
+    WsCarver c(base);
+    const long long cells = (long long)gx * gy * gz;
+    counters = c.take<int32_t>(kMcCounterBytes / sizeof(int32_t));
+    vcell = c.take<int32_t>((size_t)V);
+    u = rank_buf(&c, cells);
+    f = rank_buf(&c, F);
+    max_out = cells < V ? cells : V;
+    acc = (unsigned long long*)c.take<char>((size_t)max_out * (6 * sizeof(unsigned long long) + sizeof(int32_t)));
+    total = c.total();
+  }
 };
-
-static ClusterPlan cluster_plan(int V, int F, int gx, int gy, int gz) {
-  Bump b;
-  b.take(kMcCounterBytes);
-  ClusterPlan p;
-  const long long cells = (long long)gx * gy * gz;
-  p.vcell = b.take((size_t)V * sizeof(int32_t));
-  p.u = rank_plan(&b, cells);
-  p.f = rank_plan(&b, F);
-  p.max_out = cells < V ? cells : V;
-  p.acc = b.take((size_t)p.max_out * (6 * sizeof(unsigned long long) + sizeof(int32_t)));
-  p.total = b.off;
-  return p;
-}
 
 static McGrid mc_grid(float ox, float oy, float oz, float cell, int gx, int gy, int gz) {
   McGrid g;
@@ -529,13 +499,13 @@ extern "C" int mp_mesh_components(int V, const int32_t* d_faces, int F, int32_t*
   return MP_OK;
 }
 
-extern "C" size_t mp_mesh_select_workspace_bytes(int V, int F) { return meshc::counts_ok(V, F) ? select_plan(V, F).total : 0; }
+extern "C" size_t mp_mesh_select_workspace_bytes(int V, int F) { return meshc::counts_ok(V, F) ? SelectWs(nullptr, V, F).total : 0; }
 
 extern "C" int mp_mesh_select_count(int V, const int32_t* d_faces, int F, const uint8_t* d_keep, int32_t* d_totals, void* d_ws, size_t ws_bytes,
                                     mp_stream stream) {
   MC_REQUIRE_COUNTS("mp_mesh_select_count");
   MP_REQUIRE(d_totals && (F == 0 || (d_faces && d_keep)), "mp_mesh_select_count: null pointer");
-  const SelectPlan p = select_plan(V, F);
+  const SelectWs p(d_ws, V, F);
   MC_REQUIRE_WS("mp_mesh_select_count", p.total);
   hipStream_t s = (hipStream_t)stream;
   if (V == 0 || F == 0) {
@@ -543,14 +513,13 @@ extern "C" int mp_mesh_select_count(int V, const int32_t* d_faces, int F, const 
     return MP_OK;
   }
   ProfScope prof("mesh_select_count", 0.0, 15.0 * (double)F + 3.0 * (double)V, s);
-  int32_t* counters = (int32_t*)d_ws;
-  const RankBuf vr = rank_buf(d_ws, p.v), fr = rank_buf(d_ws, p.f);
-  MP_CHECK_HIP(hipMemsetAsync(counters, 0, kMcCounterBytes, s));
+  const RankBuf &vr = p.v, &fr = p.f;
+  MP_CHECK_HIP(hipMemsetAsync(p.counters, 0, kMcCounterBytes, s));
   MP_CHECK_HIP(hipMemsetAsync(vr.bytes, 0, (size_t)vr.n_blocks * kRankSpan, s));
   hipLaunchKernelGGL(mc_select_faces_kernel, dim3((unsigned)ceil_div(F, kMcBlock)), dim3(kMcBlock), 0, s, d_faces, F, V, d_keep, fr.bytes, vr.bytes,
-                     counters);
+                     p.counters);
   MP_CHECK_HIP(hipGetLastError());
-  return mc_rank_and_scan(vr, fr, counters, d_totals, s);
+  return mc_rank_and_scan(vr, fr, p.counters, d_totals, s);
 }
 
 extern "C" int mp_mesh_select(const float* d_vertices, const float* d_colors, int V, const int32_t* d_faces, int F, int n_vertices, int n_faces,
@@ -561,19 +530,19 @@ extern "C" int mp_mesh_select(const float* d_vertices, const float* d_colors, in
   if (V == 0 || F == 0 || (n_vertices == 0 && n_faces == 0)) return MP_OK;
   MP_REQUIRE(d_vertices && d_faces && (n_vertices == 0 || (d_out_vertices && (!d_colors || d_out_colors))) && (n_faces == 0 || d_out_faces),
              "mp_mesh_select: null pointer");
-  const SelectPlan p = select_plan(V, F);
+  const SelectWs p(d_ws, V, F);
   MC_REQUIRE_WS("mp_mesh_select", p.total);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("mesh_select", 0.0, 13.0 * (double)F + 1.0 * (double)V + 24.0 * (double)n_vertices + 24.0 * (double)n_faces, s);
   const int n = V > F ? V : F;
   hipLaunchKernelGGL(mc_select_emit_kernel, dim3((unsigned)ceil_div(n, kMcBlock)), dim3(kMcBlock), 0, s, d_vertices, d_colors, V, d_faces, F,
-                     rank_buf(d_ws, p.v), rank_buf(d_ws, p.f), n_vertices, n_faces, d_out_vertices, d_out_colors, d_out_faces);
+                     p.v, p.f, n_vertices, n_faces, d_out_vertices, d_out_colors, d_out_faces);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
 
 extern "C" size_t mp_mesh_cluster_workspace_bytes(int V, int F, int gx, int gy, int gz) {
-  return meshc::counts_ok(V, F) && meshc::dims_ok(gx, gy, gz) ? cluster_plan(V, F, gx, gy, gz).total : 0;
+  return meshc::counts_ok(V, F) && meshc::dims_ok(gx, gy, gz) ? ClusterWs(nullptr, V, F, gx, gy, gz).total : 0;
 }
 
 extern "C" int mp_mesh_cluster_count(const float* d_vertices, int V, const int32_t* d_faces, int F, float ox, float oy, float oz, float cell, int gx,
@@ -581,7 +550,7 @@ extern "C" int mp_mesh_cluster_count(const float* d_vertices, int V, const int32
   MC_REQUIRE_COUNTS("mp_mesh_cluster_count");
   MC_REQUIRE_GRID("mp_mesh_cluster_count");
   MP_REQUIRE(d_totals && (V == 0 || d_vertices) && (F == 0 || d_faces), "mp_mesh_cluster_count: null pointer");
-  const ClusterPlan p = cluster_plan(V, F, gx, gy, gz);
+  const ClusterWs p(d_ws, V, F, gx, gy, gz);
   MC_REQUIRE_WS("mp_mesh_cluster_count", p.total);
   hipStream_t s = (hipStream_t)stream;
   if (V == 0 || F == 0) {
@@ -590,9 +559,8 @@ extern "C" int mp_mesh_cluster_count(const float* d_vertices, int V, const int32
   }
   const McGrid gr = mc_grid(ox, oy, oz, cell, gx, gy, gz);
   ProfScope prof("mesh_cluster_count", 0.0, 16.0 * (double)V + 27.0 * (double)F + 2.2 * (double)gr.cells, s);
-  int32_t* counters = (int32_t*)d_ws;
-  int32_t* vcell = (int32_t*)((char*)d_ws + p.vcell);
-  const RankBuf ur = rank_buf(d_ws, p.u), fr = rank_buf(d_ws, p.f);
+  int32_t *counters = p.counters, *vcell = p.vcell;
+  const RankBuf &ur = p.u, &fr = p.f;
   MP_CHECK_HIP(hipMemsetAsync(counters, 0, kMcCounterBytes, s));
   MP_CHECK_HIP(hipMemsetAsync(ur.bytes, 0, (size_t)ur.n_blocks * kRankSpan, s));
   hipLaunchKernelGGL(mc_cells_kernel, dim3((unsigned)ceil_div(V, kMcBlock)), dim3(kMcBlock), 0, s, d_vertices, V, gr, vcell);
@@ -610,7 +578,7 @@ extern "C" int mp_mesh_cluster(const float* d_vertices, const float* d_colors, i
   MC_REQUIRE_GRID("mp_mesh_cluster");
   MC_REQUIRE_CAPS("mp_mesh_cluster");
   if (V == 0 || F == 0 || (n_vertices == 0 && n_faces == 0)) return MP_OK;
-  const ClusterPlan p = cluster_plan(V, F, gx, gy, gz);
+  const ClusterWs p(d_ws, V, F, gx, gy, gz);
   MP_REQUIRE(n_vertices <= p.max_out, "mp_mesh_cluster: %d vertices out, but %d vertices in %d x %d x %d cells give at most %lld", n_vertices, V, gx, gy,
              gz, p.max_out);
   MP_REQUIRE(d_vertices && d_faces && (n_vertices == 0 || (d_out_vertices && (!d_colors || d_out_colors))) && (n_faces == 0 || d_out_faces),
@@ -619,10 +587,10 @@ extern "C" int mp_mesh_cluster(const float* d_vertices, const float* d_colors, i
   hipStream_t s = (hipStream_t)stream;
   const McGrid gr = mc_grid(ox, oy, oz, cell, gx, gy, gz);
   ProfScope prof("mesh_cluster", 0.0, (d_colors ? 28.0 : 16.0) * (double)V + 13.0 * (double)F + 76.0 * (double)n_vertices + 24.0 * (double)n_faces, s);
-  const int32_t* vcell = (const int32_t*)((char*)d_ws + p.vcell);
-  unsigned long long* acc = (unsigned long long*)((char*)d_ws + p.acc);
+  const int32_t* vcell = p.vcell;
+  unsigned long long* acc = p.acc;
   int32_t* acc_count = (int32_t*)(acc + (size_t)6 * n_vertices);
-  const RankBuf ur = rank_buf(d_ws, p.u), fr = rank_buf(d_ws, p.f);
+  const RankBuf &ur = p.u, &fr = p.f;
   if (n_vertices > 0) {
     MP_CHECK_HIP(hipMemsetAsync(acc, 0, (size_t)n_vertices * (6 * sizeof(unsigned long long) + sizeof(int32_t)), s));
     const dim3 grid((unsigned)ceil_div(V, kMcBlock)), block(kMcBlock);

@@ -143,7 +143,17 @@ static bool model_info_jobs(int n_obj, const int32_t* h_n_points, int tile, std:
   return true;
 }
 
-static size_t model_info_prefix_bytes(int n_obj) { return align256(((size_t)n_obj + 1) * sizeof(int32_t)); }
+struct ModelInfoWs {
+  int32_t* off;      // the prefix array of job counts
+  int4* partials;    // one per job; they end the workspace, unpadded
+  size_t total;
+  ModelInfoWs(void* base, int n_obj, int32_t n_jobs) {
+    WsCarver c(base);
+    off = c.take<int32_t>((size_t)n_obj + 1);
+    partials = c.take<int4>((size_t)n_jobs, false);
+    total = c.total();
+  }
+};
 
 }  // namespace mp
 
@@ -152,7 +162,7 @@ using namespace mp;
 extern "C" size_t mp_model_info_scratch_bytes(int n_obj, const int32_t* h_n_points, int tile) {
   std::vector<int32_t> off;
   if (!model_info_jobs(n_obj, h_n_points, tile, &off)) return 0;
-  return model_info_prefix_bytes(n_obj) + (size_t)off[n_obj] * sizeof(int4);
+  return ModelInfoWs(nullptr, n_obj, off[n_obj]).total;
 }
 
 extern "C" int mp_model_info(const float* d_points, int stride, const int32_t* d_n_points, const int32_t* h_n_points, int n_obj, int tile,
@@ -167,17 +177,16 @@ extern "C" int mp_model_info(const float* d_points, int stride, const int32_t* d
   std::vector<int32_t> off;
   MP_REQUIRE(model_info_jobs(n_obj, h_n_points, tile, &off), "mp_model_info: more than 2^31 - 1 jobs in one launch");
   hipStream_t s = (hipStream_t)stream;
-  int32_t* d_off = (int32_t*)d_scratch;
-  int4* d_partials = (int4*)((char*)d_scratch + model_info_prefix_bytes(n_obj));
+  const ModelInfoWs ws(d_scratch, n_obj, off[n_obj]);
   double pairs = 0.0;
   for (int o = 0; o < n_obj; ++o) pairs += 0.5 * (double)h_n_points[o] * ((double)h_n_points[o] + 1.0);
   ProfScope prof("model_info", 8.0 * pairs, (double)n_obj * stride * 12.0, s);
   // pageable host memory: the runtime has taken the bytes when the call returns
-  MP_CHECK_HIP(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(model_info_pairs_kernel, dim3((unsigned)off[n_obj]), dim3(minfo::kBlock), 0, s, d_points, stride, d_n_points, d_off, n_obj,
-                     minfo::tile_of(tile), minfo::chunk_of(tile), d_partials);
+  MP_CHECK_HIP(hipMemcpyAsync(ws.off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(model_info_pairs_kernel, dim3((unsigned)off[n_obj]), dim3(minfo::kBlock), 0, s, d_points, stride, d_n_points, ws.off, n_obj,
+                     minfo::tile_of(tile), minfo::chunk_of(tile), ws.partials);
   MP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(model_info_reduce_kernel, dim3(n_obj), dim3(minfo::kBlock), 0, s, d_points, stride, d_n_points, d_off, d_partials, d_d2,
+  hipLaunchKernelGGL(model_info_reduce_kernel, dim3(n_obj), dim3(minfo::kBlock), 0, s, d_points, stride, d_n_points, ws.off, ws.partials, d_d2,
                      d_pair, d_bounds);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;

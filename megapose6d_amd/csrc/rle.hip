@@ -400,8 +400,6 @@ __global__ __launch_bounds__(kRleWalkBlock) void rle_fill_kernel(const int32_t* 
 struct RlePlan {
   int rows, S, U;
   long long n_jobs, n_ent;
-  size_t off_bytes, ent_bytes, stats_bytes, tot_bytes;
-  size_t total() const { return off_bytes + 2 * ent_bytes + stats_bytes + tot_bytes; }
 };
 
 static bool rle_plan(int n, int h, int w, int rows_per_segment, RlePlan* p) {
@@ -413,29 +411,36 @@ static bool rle_plan(int n, int h, int w, int rows_per_segment, RlePlan* p) {
   if ((long long)p->S * p->U > rle::kMaxJobs || (long long)p->S * w > rle::kMaxJobs) return false;
   p->n_jobs = (long long)n * p->S * p->U;
   p->n_ent = (long long)n * p->S * w;
-  if (p->n_jobs > rle::kMaxJobs || p->n_ent > rle::kMaxJobs) return false;
-  p->off_bytes = align256(((size_t)n + 1) * sizeof(int64_t));
-  p->ent_bytes = align256((size_t)p->n_ent * sizeof(int32_t));
-  p->stats_bytes = align256((size_t)p->n_jobs * rle::kStatsPerJob * sizeof(int32_t));
-  p->tot_bytes = align256((size_t)n * 2 * sizeof(int32_t));
-  return true;
+  return p->n_jobs <= rle::kMaxJobs && p->n_ent <= rle::kMaxJobs;
 }
 
-struct RleWs {
+struct RleWs {   // of mp_rle_count and mp_rle_encode
   int64_t* offsets;
   int32_t *ent_count, *ent_last, *job_stats, *mask_tot;
+  size_t total;
+  RleWs(void* base, int n, const RlePlan& p) {
+    WsCarver c(base);
+    offsets = c.take<int64_t>((size_t)n + 1);
+    ent_count = c.take<int32_t>((size_t)p.n_ent);
+    ent_last = c.take<int32_t>((size_t)p.n_ent);
+    job_stats = c.take<int32_t>((size_t)p.n_jobs * rle::kStatsPerJob);
+    mask_tot = c.take<int32_t>((size_t)n * 2);
+    total = c.total();
+  }
 };
 
-static RleWs rle_ws(void* d_ws, const RlePlan& p) {
-  char* b = (char*)d_ws;
-  RleWs v;
-  v.offsets = (int64_t*)b;
-  v.ent_count = (int32_t*)(b + p.off_bytes);
-  v.ent_last = (int32_t*)(b + p.off_bytes + p.ent_bytes);
-  v.job_stats = (int32_t*)(b + p.off_bytes + 2 * p.ent_bytes);
-  v.mask_tot = (int32_t*)(b + p.off_bytes + 2 * p.ent_bytes + p.stats_bytes);
-  return v;
-}
+struct RleDecodeWs {
+  int64_t* offsets;
+  int32_t *ends, *ent_run;
+  size_t total;
+  RleDecodeWs(void* base, int n, long long capacity, const RlePlan& p) {
+    WsCarver c(base);
+    offsets = c.take<int64_t>((size_t)n + 1);
+    ends = c.take<int32_t>((size_t)capacity);
+    ent_run = c.take<int32_t>((size_t)p.n_ent);
+    total = c.total(256);
+  }
+};
 
 // h_offsets [n + 1]: starts at 0, does not descend, no list longer than an int32, ends within capacity
 static bool rle_offsets_ok(const int64_t* h_offsets, int n, long long capacity) {
@@ -453,7 +458,7 @@ using namespace mp;
 
 extern "C" size_t mp_rle_workspace_bytes(int n, int h, int w, int rows_per_segment) {
   RlePlan p;
-  return rle_plan(n, h, w, rows_per_segment, &p) ? p.total() : 0;
+  return rle_plan(n, h, w, rows_per_segment, &p) ? RleWs(nullptr, n, p).total : 0;
 }
 
 extern "C" int mp_rle_count(const uint8_t* d_masks, int n, int h, int w, int rows_per_segment, int32_t* d_n_counts, int32_t* d_areas,
@@ -464,9 +469,9 @@ extern "C" int mp_rle_count(const uint8_t* d_masks, int n, int h, int w, int row
              h, w, rows_per_segment);
   if (n == 0) return MP_OK;
   MP_REQUIRE(d_masks && d_n_counts && d_ws, "mp_rle_count: null pointer");
-  MP_REQUIRE(ws_bytes >= p.total(), "mp_rle_count: workspace of %zu bytes, %zu needed", ws_bytes, p.total());
+  const RleWs ws(d_ws, n, p);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_rle_count: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0, "mp_rle_count: workspace not 16-byte aligned");
-  const RleWs ws = rle_ws(d_ws, p);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("rle_count", 0.0, (double)n * h * w + 8.0 * (double)p.n_ent, s);
   hipLaunchKernelGGL(rle_walk_kernel<false>, dim3((unsigned)ceil_div(p.n_jobs, kRleWalkBlock)), dim3(kRleWalkBlock), 0, s, d_masks, h, w, p.rows, p.S, p.U,
@@ -488,9 +493,9 @@ extern "C" int mp_rle_encode(const uint8_t* d_masks, int n, int h, int w, int ro
   MP_REQUIRE(d_masks && h_offsets && d_counts && d_ws, "mp_rle_encode: null pointer");
   MP_REQUIRE(capacity >= 0 && rle_offsets_ok(h_offsets, n, capacity),
              "mp_rle_encode: offsets must start at 0, not descend and end within the capacity of %lld counts", capacity);
-  MP_REQUIRE(ws_bytes >= p.total(), "mp_rle_encode: workspace of %zu bytes, %zu needed", ws_bytes, p.total());
+  const RleWs ws(d_ws, n, p);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_rle_encode: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0, "mp_rle_encode: workspace not 16-byte aligned");
-  const RleWs ws = rle_ws(d_ws, p);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("rle_encode", 0.0, (double)n * h * w + 8.0 * (double)p.n_ent + 4.0 * (double)h_offsets[n], s);
   // pageable host memory: the runtime has taken the bytes when the call returns
@@ -503,8 +508,7 @@ extern "C" int mp_rle_encode(const uint8_t* d_masks, int n, int h, int w, int ro
 
 extern "C" size_t mp_rle_decode_workspace_bytes(int n, int h, int w, long long capacity) {
   RlePlan p;
-  if (capacity < 0 || !rle_plan(n, h, w, 0, &p)) return 0;
-  return p.off_bytes + align256((size_t)capacity * sizeof(int32_t)) + p.ent_bytes + 256;
+  return capacity >= 0 && rle_plan(n, h, w, 0, &p) ? RleDecodeWs(nullptr, n, capacity, p).total : 0;
 }
 
 extern "C" int mp_rle_decode(const int32_t* d_counts, const int64_t* h_offsets, long long capacity, int n, int h, int w, uint8_t* d_masks,
@@ -516,24 +520,21 @@ extern "C" int mp_rle_decode(const int32_t* d_counts, const int64_t* h_offsets, 
   MP_REQUIRE(capacity >= 0 && rle_offsets_ok(h_offsets, n, capacity),
              "mp_rle_decode: offsets must start at 0, not descend and end within the %lld counts", capacity);
   MP_REQUIRE(d_counts || h_offsets[n] == 0, "mp_rle_decode: null pointer");
-  MP_REQUIRE(ws_bytes >= mp_rle_decode_workspace_bytes(n, h, w, capacity), "mp_rle_decode: workspace of %zu bytes, %zu needed", ws_bytes,
-             mp_rle_decode_workspace_bytes(n, h, w, capacity));
+  const RleDecodeWs ws(d_ws, n, capacity, p);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_rle_decode: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0, "mp_rle_decode: workspace not 16-byte aligned");
-  int64_t* d_offsets = (int64_t*)d_ws;
-  int32_t* d_ends = (int32_t*)((char*)d_ws + p.off_bytes);
-  int32_t* d_ent_run = (int32_t*)((char*)d_ws + p.off_bytes + align256((size_t)capacity * sizeof(int32_t)));
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("rle_decode", 0.0, (double)n * h * w + 8.0 * (double)h_offsets[n], s);
   // pageable host memory: the runtime has taken the bytes when the call returns
-  MP_CHECK_HIP(hipMemcpyAsync(d_offsets, h_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(rle_ends_kernel, dim3((unsigned)n), dim3(kRleBlock), 0, s, d_counts, (const int64_t*)d_offsets, (long long)h * w, d_ends,
+  MP_CHECK_HIP(hipMemcpyAsync(ws.offsets, h_offsets, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(rle_ends_kernel, dim3((unsigned)n), dim3(kRleBlock), 0, s, d_counts, (const int64_t*)ws.offsets, (long long)h * w, ws.ends,
                      d_status);
   MP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(rle_seek_kernel, dim3((unsigned)ceil_div(p.n_ent, kRleBlock)), dim3(kRleBlock), 0, s, (const int32_t*)d_ends,
-                     (const int64_t*)d_offsets, (const int32_t*)d_status, h, w, p.rows, p.S, p.n_ent, d_ent_run);
+  hipLaunchKernelGGL(rle_seek_kernel, dim3((unsigned)ceil_div(p.n_ent, kRleBlock)), dim3(kRleBlock), 0, s, (const int32_t*)ws.ends,
+                     (const int64_t*)ws.offsets, (const int32_t*)d_status, h, w, p.rows, p.S, p.n_ent, ws.ent_run);
   MP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(rle_fill_kernel, dim3((unsigned)ceil_div(p.n_jobs, kRleWalkBlock)), dim3(kRleWalkBlock), 0, s, (const int32_t*)d_ends,
-                     (const int64_t*)d_offsets, (const int32_t*)d_status, (const int32_t*)d_ent_run, h, w, p.rows, p.S, p.U, p.n_jobs, d_masks);
+  hipLaunchKernelGGL(rle_fill_kernel, dim3((unsigned)ceil_div(p.n_jobs, kRleWalkBlock)), dim3(kRleWalkBlock), 0, s, (const int32_t*)ws.ends,
+                     (const int64_t*)ws.offsets, (const int32_t*)d_status, (const int32_t*)ws.ent_run, h, w, p.rows, p.S, p.U, p.n_jobs, d_masks);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }

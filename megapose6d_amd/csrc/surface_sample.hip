@@ -241,12 +241,15 @@ __global__ __launch_bounds__(256) void surface_pick_kernel(const float* __restri
 namespace {
 
 struct Layout {
-  std::vector<int32_t> job_off;
-  size_t obj_e, job_max, job_bad, block_sum, w, C, bytes;
+  std::vector<int32_t> job_off;   // host: the prefix array of job counts, copied to d_job_off
+  int32_t *d_job_off, *d_obj_e, *d_job_bad;
+  float *d_job_max, *d_w;
+  uint64_t *d_block_sum, *d_C;
+  size_t bytes;
 };
 
-// the prefix array of job counts and the scratch layout; false for arguments the launch refuses
-bool surface_layout(int n_obj, const int32_t* h_face_off, int count, int block, Layout* L) {
+// the prefix array of job counts and the scratch layout on `base` (null: sizes only); false for arguments the launch refuses
+bool surface_layout(void* base, int n_obj, const int32_t* h_face_off, int count, int block, Layout* L) {
   if (n_obj < 1 || !h_face_off || count < 1 || !ssamp::block_ok(block) || h_face_off[0] < 0) return false;
   const int bs = ssamp::block_of(block);
   long long total = 0;
@@ -260,14 +263,15 @@ bool surface_layout(int n_obj, const int32_t* h_face_off, int count, int block, 
   }
   if ((long long)n_obj > 65535 || ((long long)count + ssamp::kThreads - 1) / ssamp::kThreads >= ssamp::kMaxJobs) return false;   // the pick grid
   const size_t n_jobs = (size_t)total, n_faces = (size_t)h_face_off[n_obj] - (size_t)h_face_off[0];
-  size_t at = align256(((size_t)n_obj + 1) * sizeof(int32_t));
-  L->obj_e = at;     at += align256((size_t)n_obj * sizeof(int32_t));
-  L->job_max = at;   at += align256(n_jobs * sizeof(float));
-  L->job_bad = at;   at += align256(n_jobs * sizeof(int32_t));
-  L->block_sum = at; at += align256(n_jobs * sizeof(uint64_t));
-  L->w = at;         at += align256(n_faces * sizeof(float));
-  L->C = at;         at += align256(n_faces * sizeof(uint64_t));
-  L->bytes = at;
+  WsCarver c(base);
+  L->d_job_off = c.take<int32_t>((size_t)n_obj + 1);
+  L->d_obj_e = c.take<int32_t>((size_t)n_obj);
+  L->d_job_max = c.take<float>(n_jobs);
+  L->d_job_bad = c.take<int32_t>(n_jobs);
+  L->d_block_sum = c.take<uint64_t>(n_jobs);
+  L->d_w = c.take<float>(n_faces);
+  L->d_C = c.take<uint64_t>(n_faces);
+  L->bytes = c.total();
   return true;
 }
 
@@ -279,7 +283,7 @@ using namespace mp;
 
 extern "C" size_t mp_surface_sample_scratch_bytes(int n_obj, const int32_t* h_face_off, int count, int block) {
   Layout L;
-  return surface_layout(n_obj, h_face_off, count, block, &L) ? L.bytes : 0;
+  return surface_layout(nullptr, n_obj, h_face_off, count, block, &L) ? L.bytes : 0;
 }
 
 extern "C" int mp_surface_sample(const float* d_vertices, const int32_t* d_faces, const int32_t* d_vert_off, const int32_t* d_face_off,
@@ -301,16 +305,11 @@ extern "C" int mp_surface_sample(const float* d_vertices, const int32_t* d_faces
                ssamp::kMaxBlocks, bs);
   }
   Layout L;
-  MP_REQUIRE(surface_layout(n_obj, h_face_off, count, block, &L), "mp_surface_sample: more than 2^31 - 1 jobs in one launch");
+  MP_REQUIRE(surface_layout(d_workspace, n_obj, h_face_off, count, block, &L), "mp_surface_sample: more than 2^31 - 1 jobs in one launch");
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)d_workspace;
-  int32_t* d_job_off = (int32_t*)ws;
-  int32_t* d_obj_e = (int32_t*)(ws + L.obj_e);
-  float* d_job_max = (float*)(ws + L.job_max);
-  int32_t* d_job_bad = (int32_t*)(ws + L.job_bad);
-  uint64_t* d_block_sum = (uint64_t*)(ws + L.block_sum);
-  float* d_w = (float*)(ws + L.w);
-  uint64_t* d_C = (uint64_t*)(ws + L.C);
+  int32_t *d_job_off = L.d_job_off, *d_obj_e = L.d_obj_e, *d_job_bad = L.d_job_bad;
+  float *d_job_max = L.d_job_max, *d_w = L.d_w;
+  uint64_t *d_block_sum = L.d_block_sum, *d_C = L.d_C;
   const unsigned n_jobs = (unsigned)L.job_off[n_obj];
   const double n_faces = (double)h_face_off[n_obj], n_samples = (double)n_obj * count;
   ProfScope prof("surface_sample", 30.0 * n_faces + 12.0 * n_samples, 80.0 * n_faces + 76.0 * n_samples, s);

@@ -351,30 +351,40 @@ namespace {
 
 struct SolveWs {   // the scratch of graph + cores + solve for n rows
   uint32_t* adj;
-  int32_t *deg, *core, *sel, *sel_list, *msel, *m_arr, *n_arr;
-  void* clique;   // the search stacks of selection 2 (null otherwise)
+  int32_t *deg, *core, *sel;   // three adjacent planes [n][kMaxPoints], cleared by one memset up to sel_list
+  int32_t *sel_list, *msel, *m_arr, *n_arr;
+  CliqueWs clique = {nullptr, nullptr};   // the search stacks of selection 2 (null otherwise)
+  SolveWs(WsCarver& c, int n, int stride, int selection) {
+    const size_t r = (size_t)n * kMaxPoints;
+    adj = c.take<uint32_t>(r * kWords);
+    deg = c.take<int32_t>(r);
+    core = c.take<int32_t>(r);
+    sel = c.take<int32_t>(r);
+    sel_list = c.take<int32_t>(r);
+    msel = c.take<int32_t>((size_t)n);
+    m_arr = c.take<int32_t>((size_t)n);
+    n_arr = c.take<int32_t>((size_t)n);
+    if (selection == kSelectMaxClique) clique = clique_search_ws(c, n, stride);
+  }
 };
 
-size_t solve_ws_bytes(int n, int stride, int selection) {
-  const size_t r = (size_t)n * kMaxPoints;
-  return align256(r * kWords * 4) + 4 * align256(r * 4) + 3 * align256((size_t)n * 4) + (selection == kSelectMaxClique ? clique_search_ws_bytes(n, stride) : 0);
-}
-
-SolveWs take_solve_ws(unsigned char*& w, int n, int stride, int selection) {
-  const size_t r = (size_t)n * kMaxPoints;
-  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
-  SolveWs s;
-  s.adj = (uint32_t*)take(r * kWords * 4);
-  s.deg = (int32_t*)take(r * 4);
-  s.core = (int32_t*)take(r * 4);
-  s.sel = (int32_t*)take(r * 4);
-  s.sel_list = (int32_t*)take(r * 4);
-  s.msel = (int32_t*)take((size_t)n * 4);
-  s.m_arr = (int32_t*)take((size_t)n * 4);
-  s.n_arr = (int32_t*)take((size_t)n * 4);
-  s.clique = selection == kSelectMaxClique ? take(clique_search_ws_bytes(n, stride)) : nullptr;
-  return s;
-}
+struct TeaserWs {   // SolveWs, then the samples and the compacted frame of mp_teaser_refine (mp_teaser_solve: a frame of no pixels)
+  WsCarver c;
+  SolveWs solve;
+  float *src_s, *dst_s, *pts, *mind;
+  int32_t *idx, *pix;
+  size_t total;
+  TeaserWs(void* base, int n_rows, int H, int W, int stride, int selection) : c(base), solve(c, n_rows, stride, selection) {
+    const size_t px = (size_t)H * W, n = (size_t)n_rows;
+    src_s = c.take<float>(n * kMaxPoints * 3);
+    dst_s = c.take<float>(n * kMaxPoints * 3);
+    idx = c.take<int32_t>(n * kMaxPoints);
+    pts = c.take<float>(n * px * 3);
+    pix = c.take<int32_t>(n * px);
+    mind = c.take<float>(n * px);
+    total = c.total(256);
+  }
+};
 
 bool solve_args_ok(float noise_bound, int selection, int tim_graph, int min_num_inliers, int max_steps) {
   return std::isfinite(noise_bound) && noise_bound > 0.0f && (selection == kSelectKcore || selection == kSelectNone || selection == kSelectMaxClique) &&
@@ -385,7 +395,7 @@ bool solve_args_ok(float noise_bound, int selection, int tim_graph, int min_num_
 int run_solve(const float* src, const float* dst, int n, int stride, const SolveWs& ws, float noise_bound, int selection, int tim_graph,
               int min_num_inliers, int max_steps, const float* TCO, float* TCO_out, double* Rt, int32_t* retval, int32_t* deg, int32_t* core,
               int32_t* sel, int32_t* info, int32_t* clique_info, hipStream_t s) {
-  MP_CHECK_HIP(hipMemsetAsync(ws.deg, 0xFF, 3 * align256((size_t)n * kMaxPoints * 4), s));   // deg, core, sel (adjacent): -1 past a row's M
+  MP_CHECK_HIP(hipMemsetAsync(ws.deg, 0xFF, (char*)ws.sel_list - (char*)ws.deg, s));   // deg, core, sel (adjacent): -1 past a row's M
   hipLaunchKernelGGL(teaser_graph, dim3(kMaxPoints / 32, n), dim3(kThreads), 0, s, src, dst, stride, ws.m_arr, noise_bound, ws.adj, ws.deg);
   hipLaunchKernelGGL(teaser_kcore, dim3(n), dim3(kThreads), 0, s, ws.adj, ws.m_arr, stride, selection, ws.core, ws.sel, ws.sel_list, ws.msel);
   if (selection == kSelectMaxClique) {   // the clique's members replace the vertices of the largest core number in sel, sel_list and msel
@@ -427,9 +437,7 @@ extern "C" int mp_fps(const float* d_points, const int32_t* d_counts, int n_rows
 extern "C" size_t mp_teaser_workspace_bytes_ex(int n_rows, int H, int W, int stride, int inlier_selection) {
   if (n_rows < 0 || H < 0 || W < 0 || (long long)H * W * 3 >= 2147483647LL || stride < 1 || stride > kMaxPoints) return 0;
   if (!(inlier_selection == kSelectKcore || inlier_selection == kSelectNone || inlier_selection == kSelectMaxClique)) return 0;
-  const size_t px = (size_t)H * W, n = (size_t)n_rows;
-  return solve_ws_bytes(n_rows, stride, inlier_selection) + 2 * align256(n * kMaxPoints * 12) + align256(n * kMaxPoints * 4) + align256(n * px * 12) +
-         2 * align256(n * px * 4) + 256;
+  return TeaserWs(nullptr, n_rows, H, W, stride, inlier_selection).total;
 }
 
 extern "C" size_t mp_teaser_workspace_bytes(int n_rows, int H, int W) { return mp_teaser_workspace_bytes_ex(n_rows, H, W, kMaxPoints, kSelectKcore); }
@@ -438,7 +446,9 @@ extern "C" int mp_max_clique_default_steps(void) { return kCliqueDefaultSteps; }
 
 extern "C" size_t mp_max_clique_workspace_bytes(int n_rows, int stride) {
   if (n_rows < 0 || stride < 1 || stride > kMaxPoints) return 0;
-  return solve_ws_bytes(n_rows, stride, kSelectMaxClique) + 256;
+  WsCarver c(nullptr);
+  const SolveWs measured(c, n_rows, stride, kSelectMaxClique);
+  return c.total(256);
 }
 
 extern "C" int mp_max_clique(const uint8_t* d_adjacency, const int32_t* d_counts, int n_rows, int stride, int max_steps, int32_t* d_members, int32_t* d_info,
@@ -449,8 +459,8 @@ extern "C" int mp_max_clique(const uint8_t* d_adjacency, const int32_t* d_counts
   MP_REQUIRE(ws_bytes >= mp_max_clique_workspace_bytes(n_rows, stride), "mp_max_clique: workspace too small");
   if (n_rows == 0) return MP_OK;
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)d_ws;
-  const SolveWs ws = take_solve_ws(w, n_rows, stride, kSelectMaxClique);
+  WsCarver c(d_ws);
+  const SolveWs ws(c, n_rows, stride, kSelectMaxClique);
   ProfScope prof("max_clique", 0.0, (double)n_rows * stride * stride, s);
   int rc = clique_pack_launch(d_adjacency, d_counts, n_rows, stride, ws.adj, ws.deg, ws.m_arr, s);
   if (rc != MP_OK) return rc;
@@ -473,8 +483,7 @@ extern "C" int mp_teaser_solve_ex(const float* d_src, const float* d_dst, const 
   MP_REQUIRE(ws_bytes >= mp_teaser_workspace_bytes_ex(n_rows, 0, 0, stride, inlier_selection), "mp_teaser_solve: workspace too small");
   if (n_rows == 0) return MP_OK;
   hipStream_t s = (hipStream_t)stream;
-  unsigned char* w = (unsigned char*)d_ws;
-  const SolveWs ws = take_solve_ws(w, n_rows, stride, inlier_selection);
+  const SolveWs ws = TeaserWs(d_ws, n_rows, 0, 0, stride, inlier_selection).solve;
   ProfScope prof("teaser_solve", 0.0, (double)n_rows * stride * 24.0, s);
   MP_CHECK_HIP(hipMemcpyAsync(ws.m_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));   // (the kernels clamp a count to 0 .. stride)
   MP_CHECK_HIP(hipMemcpyAsync(ws.n_arr, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));
@@ -505,15 +514,10 @@ extern "C" int mp_teaser_refine_ex(const float* d_depth_meas, int n_images, cons
   if (n_rows == 0) return MP_OK;
   hipStream_t s = (hipStream_t)stream;
   const size_t px = (size_t)H * W, n = (size_t)n_rows;
-  unsigned char* w = (unsigned char*)d_ws;
-  const SolveWs ws = take_solve_ws(w, n_rows, n_points, inlier_selection);
-  auto take = [&](size_t bytes) { unsigned char* p = w; w += align256(bytes); return p; };
-  float* src_s = (float*)take(n * kMaxPoints * 12);
-  float* dst_s = (float*)take(n * kMaxPoints * 12);
-  int32_t* idx = (int32_t*)take(n * kMaxPoints * 4);
-  float* pts = (float*)take(n * px * 12);
-  int32_t* pix = (int32_t*)take(n * px * 4);
-  float* mind = (float*)take(n * px * 4);
+  const TeaserWs rw(d_ws, n_rows, H, W, n_points, inlier_selection);
+  const SolveWs& ws = rw.solve;
+  float *src_s = rw.src_s, *dst_s = rw.dst_s, *pts = rw.pts, *mind = rw.mind;
+  int32_t *idx = rw.idx, *pix = rw.pix;
   ProfScope prof("teaser_refine", 0.0, (double)n_rows * px * 8.0, s);
   hipLaunchKernelGGL(teaser_compact, dim3(n_rows), dim3(kThreads), 0, s, d_depth_meas, d_im_ids, d_depth_rend, d_K_rows, H, W, mask_type, depth_delta_thresh,
                      pts, pix, ws.n_arr);

@@ -242,9 +242,12 @@ __global__ __launch_bounds__(kCliqueLanes) void clique_search(const uint32_t* __
   }
 }
 
-size_t clique_search_ws_bytes(int n_rows, int stride) {
+CliqueWs clique_search_ws(WsCarver& c, int n_rows, int stride) {
   const size_t blocks = (size_t)std::min(std::max(n_rows, 0), kCliqueMaxBlocks);
-  return align256(blocks * clique_order_entries(stride) * 4) + align256(blocks * clique_pset_words(stride) * 4);
+  CliqueWs w;
+  w.order = c.take<uint32_t>(blocks * clique_order_entries(stride));
+  w.pset = c.take<uint32_t>(blocks * clique_pset_words(stride));
+  return w;
 }
 
 int clique_pack_launch(const uint8_t* adjacency, const int32_t* counts, int n_rows, int stride, uint32_t* adj, int32_t* deg, int32_t* m_arr, hipStream_t s) {
@@ -254,14 +257,12 @@ int clique_pack_launch(const uint8_t* adjacency, const int32_t* counts, int n_ro
 }
 
 int clique_search_launch(const uint32_t* adj, const int32_t* core, const int32_t* m_arr, int n_rows, int stride, int max_steps, int32_t* sel,
-                         int32_t* sel_list, int32_t* msel, int32_t* info, void* ws, hipStream_t s) {
+                         int32_t* sel_list, int32_t* msel, int32_t* info, const CliqueWs& ws, hipStream_t s) {
   const int blocks = std::min(n_rows, kCliqueMaxBlocks);
-  uint32_t* order = (uint32_t*)ws;
-  uint32_t* pset = (uint32_t*)((unsigned char*)ws + align256((size_t)blocks * clique_order_entries(stride) * 4));
   const size_t lds = clique_lds_bytes(stride);
   if (lds > 64 * 1024) MP_CHECK_HIP(hipFuncSetAttribute((const void*)clique_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(clique_search, dim3(blocks), dim3(kCliqueLanes), lds, s, adj, core, m_arr, n_rows, stride, max_steps, order, pset, sel, sel_list, msel,
-                     info);
+  hipLaunchKernelGGL(clique_search, dim3(blocks), dim3(kCliqueLanes), lds, s, adj, core, m_arr, n_rows, stride, max_steps, ws.order, ws.pset, sel, sel_list,
+                     msel, info);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }

@@ -76,9 +76,11 @@ TSR_HD size_t clique_lds_bytes(int stride) {
 #if defined(__HIPCC__)
 // teaser_clique.hip, called by the entry points of teaser.hip.  adj [n][kMaxPoints][kWords] in the layout of teaser_graph; core, sel,
 // sel_list [n][kMaxPoints]; msel, m_arr [n]; info [n][kCliqueInfo] or null.
-size_t clique_search_ws_bytes(int n_rows, int stride);
+struct WsCarver;
+struct CliqueWs { uint32_t *order, *pset; };   // the search stacks of min(n_rows, kCliqueMaxBlocks) workgroups
+CliqueWs clique_search_ws(WsCarver& c, int n_rows, int stride);
 int clique_pack_launch(const uint8_t* adjacency, const int32_t* counts, int n_rows, int stride, uint32_t* adj, int32_t* deg, int32_t* m_arr, hipStream_t s);
 int clique_search_launch(const uint32_t* adj, const int32_t* core, const int32_t* m_arr, int n_rows, int stride, int max_steps, int32_t* sel,
-                         int32_t* sel_list, int32_t* msel, int32_t* info, void* ws, hipStream_t s);
+                         int32_t* sel_list, int32_t* msel, int32_t* info, const CliqueWs& ws, hipStream_t s);
 #endif
 }  // namespace mp

@@ -273,19 +273,12 @@ __global__ __launch_bounds__(kTsdfBlock) void tsdf_emit_kernel(TsdfVolume vol, T
   }
 }
 
-struct TsdfPlan {
-  int N, n_blocks;
-  size_t node_bytes, rank_bytes, block_bytes;
-  size_t total() const { return 3 * node_bytes + rank_bytes + 2 * block_bytes; }
-};
+struct TsdfPlan { int N, n_blocks; };
 
 static bool tsdf_plan(int nx, int ny, int nz, TsdfPlan* p) {
   if (!tsdf::dims_ok(nx, ny, nz)) return false;
   p->N = nx * ny * nz;
   p->n_blocks = ceil_div(p->N, kTsdfBlock);
-  p->node_bytes = align256((size_t)p->N);
-  p->rank_bytes = align256((size_t)p->N * sizeof(uint16_t));
-  p->block_bytes = align256((size_t)p->n_blocks * sizeof(int32_t));
   return true;
 }
 
@@ -293,19 +286,18 @@ struct TsdfWs {
   uint8_t *flags, *cell, *emask;
   uint16_t* lrank;
   int32_t *block_nv, *block_nt;
+  size_t total;
+  TsdfWs(void* base, const TsdfPlan& p) {
+    WsCarver c(base);
+    flags = c.take<uint8_t>((size_t)p.N);
+    cell = c.take<uint8_t>((size_t)p.N);
+    emask = c.take<uint8_t>((size_t)p.N);
+    lrank = c.take<uint16_t>((size_t)p.N);
+    block_nv = c.take<int32_t>((size_t)p.n_blocks);
+    block_nt = c.take<int32_t>((size_t)p.n_blocks);
+    total = c.total();
+  }
 };
-
-static TsdfWs tsdf_ws(void* d_ws, const TsdfPlan& p) {
-  char* b = (char*)d_ws;
-  TsdfWs v;
-  v.flags = (uint8_t*)b;
-  v.cell = (uint8_t*)(b + p.node_bytes);
-  v.emask = (uint8_t*)(b + 2 * p.node_bytes);
-  v.lrank = (uint16_t*)(b + 3 * p.node_bytes);
-  v.block_nv = (int32_t*)(b + 3 * p.node_bytes + p.rank_bytes);
-  v.block_nt = (int32_t*)(b + 3 * p.node_bytes + p.rank_bytes + p.block_bytes);
-  return v;
-}
 
 static TsdfGrid tsdf_grid(int nx, int ny, int nz, float ox, float oy, float oz, float voxel) {
   TsdfGrid g;
@@ -353,7 +345,7 @@ extern "C" int mp_tsdf_integrate(void* d_volume, int nx, int ny, int nz, int col
 
 extern "C" size_t mp_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {
   TsdfPlan p;
-  return tsdf_plan(nx, ny, nz, &p) ? p.total() : 0;
+  return tsdf_plan(nx, ny, nz, &p) ? TsdfWs(nullptr, p).total : 0;
 }
 
 extern "C" int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int nz, int color, int min_views, int32_t* d_totals, void* d_ws,
@@ -362,11 +354,11 @@ extern "C" int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int n
   MP_REQUIRE(tsdf_plan(nx, ny, nz, &p), "mp_tsdf_extract_count: volume of %d x %d x %d: each side 2 .. 512, at most 2^27 nodes", nx, ny, nz);
   MP_REQUIRE(min_views >= 1, "mp_tsdf_extract_count: min_views %d must be at least 1", min_views);
   MP_REQUIRE(d_volume && d_totals && d_ws, "mp_tsdf_extract_count: null pointer");
-  MP_REQUIRE(ws_bytes >= p.total(), "mp_tsdf_extract_count: workspace of %zu bytes, %zu needed", ws_bytes, p.total());
+  const TsdfWs ws(d_ws, p);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_tsdf_extract_count: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0 && (uintptr_t)d_volume % 4 == 0, "mp_tsdf_extract_count: workspace not 16-byte aligned or volume not 4-byte aligned");
   const TsdfGrid gr = tsdf_grid(nx, ny, nz, 0.f, 0.f, 0.f, 1.f);
   const TsdfVolume vol = tsdf_planes(const_cast<void*>(d_volume), gr.N, color);
-  const TsdfWs ws = tsdf_ws(d_ws, p);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("tsdf_extract_count", 0.0, 8.0 * (double)gr.N + 30.0 * (double)gr.N, s);
   const dim3 grid((unsigned)p.n_blocks), block(kTsdfBlock);
@@ -395,11 +387,11 @@ extern "C" int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int
   if (n_vertices == 0 && n_triangles == 0) return MP_OK;
   MP_REQUIRE(d_volume && d_ws && (d_vertices || n_vertices == 0) && (d_colors || n_vertices == 0) && (d_faces || n_triangles == 0),
              "mp_tsdf_extract: null pointer");
-  MP_REQUIRE(ws_bytes >= p.total(), "mp_tsdf_extract: workspace of %zu bytes, %zu needed", ws_bytes, p.total());
+  const TsdfWs ws(d_ws, p);
+  MP_REQUIRE(ws_bytes >= ws.total, "mp_tsdf_extract: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0 && (uintptr_t)d_volume % 4 == 0, "mp_tsdf_extract: workspace not 16-byte aligned or volume not 4-byte aligned");
   const TsdfGrid gr = tsdf_grid(nx, ny, nz, ox, oy, oz, voxel);
   const TsdfVolume vol = tsdf_planes(const_cast<void*>(d_volume), gr.N, color);
-  const TsdfWs ws = tsdf_ws(d_ws, p);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("tsdf_extract", 0.0, 6.0 * (double)gr.N + 24.0 * (double)n_vertices + 12.0 * (double)n_triangles, s);
   hipLaunchKernelGGL(tsdf_emit_kernel, dim3((unsigned)p.n_blocks), dim3(kTsdfBlock), 0, s, vol, gr, (const uint8_t*)ws.flags, (const uint8_t*)ws.cell,
