@@ -741,6 +741,31 @@ int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int color, flo
                     int n_triangles, float* d_vertices /*[cap_vertices,3]*/, float* d_colors /*[cap_vertices,3]*/,
                     int32_t* d_faces /*[cap_triangles,3]*/, long long cap_vertices, long long cap_triangles, void* d_ws, size_t ws_bytes,
                     mp_stream stream);
+/* Tracking the camera against the volume (csrc/tsdf_track.hip; contract in csrc/tsdf_track_core.h): the poses of unposed depth frames by
+   Gauss-Newton on the signed distances the volume holds at the frames' own back-projected pixels -- no raycast, no projective association. */
+/* records of 32 doubles a frame of h x w leaves in d_partials of mp_tsdf_track: one per group of 1024 pixels, ceil(h * w / 1024); 0 for a
+   refused frame size (a side outside 1 .. 8192).  Host only. */
+int mp_tsdf_track_groups(int h, int w);
+/* Tracks n frames against the same volume, each from its own pose d_TCO_in (object to camera, rows of 4, 16 floats), independently: n
+   frames in one call equal n calls of one.  Per iteration and pixel inside the mask (every pixel without masks) with a depth that is
+   finite and > 0: the pixel's centre back-projected, taken to the object's frame by the current pose, the field sum / count interpolated
+   trilinearly from the eight nodes around it (skipped outside the volume, where a corner has count < min_views, or where |f| >= 1), the
+   residual f * mu and its Jacobian for a small motion in the object's frame; the normal equations are summed in fp64 in one fixed order
+   (one record per group of 1024 pixels into d_partials, a typed output, every entry written by plain stores), solved with the damping
+   1e-9 * used, the increment applied through the Cayley map, the rotation re-orthonormalised, the pose rounded to fp32.  d_status: 0 ran
+   all iterations, 1 converged (|rotation| < eps_rot rad and |translation| < eps_trans metres; later iterations skip the frame), -1 lost
+   (fewer than min_pixels used pixels, a pivot that is not positive, a non-finite pose), -2 the frame's K or pose holds a non-finite
+   entry.  A frame of status -1 or -2 returns its input pose bit for bit in d_TCO_out.  d_used / d_rms: the used pixels and the
+   root-mean-square residual (metres) of the last iteration that ran.  1 + 2 * iters launches on `stream`, no atomics, no workgroup waits
+   for another, nothing is read back.  n == 0 is a successful no-op; any bad argument (a null pointer, dims out of range, a bad origin,
+   voxel or mu, min_views < 1, min_pixels < 1, iters outside 1 .. 64, an eps that is negative or not finite, n outside 0 .. 65535, frames
+   outside 1 .. 8192 a side, d_TCO_out == d_TCO_in, partials_capacity < n * groups, a misaligned volume or partials) returns non-zero
+   before anything is launched, with the outputs untouched. */
+int mp_tsdf_track(const void* d_volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel,
+                  const float* d_depth /*[n,h,w]*/, const uint8_t* d_masks /*[n,h,w] or NULL*/, const float* d_K /*[n,9]*/,
+                  const float* d_TCO_in /*[n,16]*/, int n, int h, int w, float mu, int min_views, int min_pixels, int iters, float eps_rot,
+                  float eps_trans, float* d_TCO_out /*[n,16]*/, int32_t* d_status /*[n]*/, int32_t* d_used /*[n]*/, float* d_rms /*[n]*/,
+                  double* d_partials /*[n,groups,32]*/, long long partials_capacity /*records*/, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* A texture atlas for a triangle mesh (a reconstruction's) from the posed colour + depth   */

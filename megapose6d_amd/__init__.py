@@ -10,7 +10,8 @@ from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner, TeaserppRefiner  # noqa: F401
 from .mask_rcnn import DetectorMaskRCNN  # noqa: F401
 from .object_dataset import RigidObject, RigidObjectDataset  # noqa: F401
-from .onboarding import TsdfVolume, reconstruct_object, volume_for_views  # noqa: F401
+from .onboarding import (TsdfVolume, reconstruct_object, reconstruct_object_unposed, track_views, volume_for_first_view,  # noqa: F401
+                         volume_for_views)
 from .load_model import NAMED_MODELS, create_model_pose, load_named_model, load_pose_models  # noqa: F401
 from .pose_estimator import CoarseRefinePoseEstimator, PoseEstimator  # noqa: F401
 from .pose_rigid import PosePredictor  # noqa: F401

@@ -193,7 +193,10 @@ SIGNATURES = {
     "mp_tsdf_extract_workspace_bytes": (_sz, [_i, _i, _i]),
     "mp_tsdf_extract_count": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mp_tsdf_extract": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _vp, _sz, _vp]),
-    "mp_texture_atlas_block": (_i, [C.c_longlong, _i]),
+    "mp_tsdf_track_groups": (_i, [_i, _i]),
+    "mp_tsdf_track": (_i, [_vp, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                           C.c_longlong, _vp]),
+    "mp_texture_atlas_block":(_i, [C.c_longlong, _i]),
     "mp_texture_atlas_uvs": (_i, [_i, _i, _vp, _vp]),
     "mp_texture_bake": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp]),
     "mp_mesh_components_workspace_bytes": (_sz, [_i, _i]),

@@ -1224,6 +1224,63 @@ def tsdf_extract(volume: torch.Tensor, origin: Sequence[float], voxel: float, mi
     return vertices, colors, faces
 
 
+TSDF_TRACK_RECORD = 32              # doubles of a group's record
+
+
+def tsdf_track_groups(h: int, w: int) -> int:
+    """Records of 32 doubles a frame of h x w leaves in the partial sums (mp_tsdf_track_groups): one per 1024 pixels; 0 for a frame
+    size the kernels refuse."""
+    return int(_lib.load().mp_tsdf_track_groups(int(h), int(w)))
+
+
+def tsdf_track(volume: torch.Tensor, origin: Sequence[float], voxel: float, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor,
+               masks: Optional[torch.Tensor] = None, mu: Optional[float] = None, min_views: int = 1, min_pixels: int = 64, iters: int = 10,
+               eps_rot: float = 1e-5, eps_trans: Optional[float] = None,
+               partials: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The poses of n unposed depth frames against `volume`, each tracked from its own pose TCO [n,4,4] (object to camera) by
+    Gauss-Newton on the signed distances the volume holds at the frame's back-projected pixels (mp_tsdf_track; the rules are stated in
+    csrc/tsdf_track_core.h).  depth [n,h,w] metres, K [n,3,3], masks [n,h,w] uint8 / bool or None (every measured pixel).  mu is the
+    truncation distance the volume was fused with (3 voxels when None); eps_rot (rad) and eps_trans (metres; 1e-3 voxel when None) end a
+    frame's iterations early.  -> (TCO [n,4,4] float32, status [n] int32: 0 ran all iterations, 1 converged, -1 lost, -2 a non-finite K
+    or pose; used [n] int32 pixels; rms [n] float32 metres), all on the device.  A frame of negative status returns its input pose bit
+    for bit.  Frames are independent.  Nothing synchronises.  `partials`: a float64 device tensor of at least n * tsdf_track_groups(h,
+    w) * 32 entries to be filled with the groups' records of the last iteration (for tests)."""
+    nx, ny, nz, color = _tsdf_dims(volume)
+    depth = _dev_f32(depth)
+    if depth.dim() != 3:
+        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
+    n, h, w = (int(v) for v in depth.shape)
+    K, TCO = _dev_f32(K), _dev_f32(TCO)
+    if tuple(K.shape) != (n, 3, 3) or tuple(TCO.shape) != (n, 4, 4):
+        raise EngineError(f"K must be [{n},3,3] and TCO [{n},4,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
+    if masks is not None:
+        masks = _dev_bytes("masks", masks)
+        if tuple(masks.shape) != (n, h, w):
+            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
+    dev = volume.device
+    out = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    used = torch.empty(n, dtype=torch.int32, device=dev)
+    rms = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out, status, used, rms
+    groups = tsdf_track_groups(h, w)
+    if groups == 0:
+        raise EngineError(f"tsdf_track: frames of {h} x {w}: 1 .. {TSDF_MAX_SIDE} a side")
+    if partials is None:
+        partials = torch.empty(n, groups, TSDF_TRACK_RECORD, dtype=torch.float64, device=dev)
+    elif not partials.is_cuda or partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise EngineError("tsdf_track: partials must be a contiguous float64 device tensor")
+    mu = float(np.float32(3.0) * np.float32(voxel)) if mu is None else float(mu)
+    eps_trans = float(np.float32(1e-3) * np.float32(voxel)) if eps_trans is None else float(eps_trans)
+    ox, oy, oz = (float(v) for v in origin)
+    check(_lib.load().mp_tsdf_track(volume.data_ptr(), nx, ny, nz, color, ox, oy, oz, float(voxel), depth.data_ptr(), _ptr(masks), K.data_ptr(),
+                                    TCO.data_ptr(), n, h, w, mu, int(min_views), int(min_pixels), int(iters), float(eps_rot), eps_trans,
+                                    out.data_ptr(), status.data_ptr(), used.data_ptr(), rms.data_ptr(), partials.data_ptr(),
+                                    partials.numel() // TSDF_TRACK_RECORD, _stream()))
+    return out, status, used, rms
+
+
 # --------------------------------------------------------------------------- #
 # A texture atlas for a mesh from its posed views (onboarding.bake_texture), csrc/texture_bake.hip
 TEXTURE_MIN_SIZE, TEXTURE_MAX_SIZE = 64, 8192   # texels a side, a power of two

@@ -11,7 +11,11 @@ written: only the component with the most faces, decimated by vertex clustering 
 `bake_texture` (and `reconstruct_object(..., texture_size=S)`) gives the mesh a texture atlas baked from the same views (csrc/texture_bake.hip,
 contract: csrc/texture_bake_core.h): a chart per triangle, two launches; the PLY then carries texture coordinates and names a PNG.
 
-Not here: estimating the camera poses, smoothing, hole filling, quadric decimation, charts sized by area or packed by a parametrisation,
+Frames WITHOUT camera poses (a hand-held depth camera, a turntable without encoders: BOP's dynamic onboarding) go through `track_views`
+/ `reconstruct_object_unposed`: every frame is tracked against the volume the frames before it built (csrc/tsdf_track.hip, contract:
+csrc/tsdf_track_core.h; `TsdfVolume.track` is 1 + 2 * iters launches and reads nothing back), then fused at its tracked pose.
+
+Not here: coarse-to-fine pyramids, robust weights, loop closure, photometric terms or a motion model for the tracking, smoothing, hole filling, quadric decimation, charts sized by area or packed by a parametrisation,
 transferring an existing texture, distances along the ray, per-pixel weights.
 """
 from __future__ import annotations
@@ -85,6 +89,16 @@ class TsdfVolume:
     def extract_device(self, min_views: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """-> vertices [V,3] float32, colors [V,3] float32, faces [T,3] int32 as device tensors (what mesh_cleanup continues from)"""
         return eng.tsdf_extract(self._volume, self.origin, self.voxel_size, min_views)
+
+    def track(self, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor] = None,
+              **kw) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The poses of unposed depth frames against what the volume holds, each from its own starting pose TCO [n,4,4]
+        (engine.tsdf_track, whose keywords pass through; the volume's truncation distance is given) -> (TCO [n,4,4], status [n], used
+        [n], rms [n]) on the device.  Nothing synchronises."""
+        dev = self._volume.device
+        as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
+        kw.setdefault("mu", self.mu)
+        return eng.tsdf_track(self._volume, self.origin, self.voxel_size, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), **kw)
 
     def reset(self) -> None:
         self._volume.zero_()
@@ -252,3 +266,125 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
     else:
         path = mesh_io.write_ply(out_dir / f"{label}.ply", mesh["vertices"], mesh["faces"], colors=mesh["colors"], normals=mesh["normals"])
     return RigidObject(label, path, mesh_units="m")
+
+
+def _first_view_points(depth0: torch.Tensor, K0: torch.Tensor, mask0: Optional[torch.Tensor]) -> torch.Tensor:
+    """[m,3] float64: frame 0's measured pixels inside the mask, back-projected through their centres into the camera's frame"""
+    depth0 = torch.as_tensor(depth0).to(torch.float32)
+    K0 = torch.as_tensor(K0).to(depth0.device, torch.float64)
+    h, w = depth0.shape
+    keep = torch.isfinite(depth0) & (depth0 > 0)
+    if mask0 is not None:
+        keep = keep & (torch.as_tensor(mask0).to(depth0.device) != 0)
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth0.device), torch.arange(w, device=depth0.device), indexing="ij")
+    z = depth0[keep].to(torch.float64)
+    return torch.stack([(xs[keep] + 0.5 - K0[0, 2]) / K0[0, 0] * z, (ys[keep] + 0.5 - K0[1, 2]) / K0[1, 1] * z, z], 1)
+
+
+def volume_for_first_view(depth0: torch.Tensor, K0: torch.Tensor, TCO0: torch.Tensor, mask0: Optional[torch.Tensor], resolution: int = 128,
+                          extent: Optional[float] = None) -> Tuple[Tuple[float, float, float], float, Tuple[int, int, int]]:
+    """The volume to track a sequence in when only its first frame is known: a cube of `resolution` nodes a side -> (origin,
+    voxel_size, dims).  Frame 0's measured pixels inside the mask are taken to the object's frame by TCO0; with L the longest side of
+    their bounding box, the cube has the side `extent`, or 2 L when extent is None, and is centred at the box's centre moved L / 2 along
+    the viewing direction: frame 0 sees only the near side of the object, the rest lies behind it.  An object that reaches deeper than
+    1.5 L behind its nearest visible point (a long object seen end-on) leaves that cube: give `extent`.  Plain torch, one read-back."""
+    if not (eng.TSDF_MIN_DIM <= int(resolution) <= eng.TSDF_MAX_DIM):
+        raise ValueError(f"resolution {resolution} must be {eng.TSDF_MIN_DIM} .. {eng.TSDF_MAX_DIM}")
+    pts = _first_view_points(depth0, K0, mask0)
+    if pts.shape[0] == 0:
+        raise ValueError("volume_for_first_view: frame 0 holds no measured pixel of the object (depth finite and > 0 inside the mask)")
+    T = torch.as_tensor(TCO0).to(pts.device, torch.float64)
+    po = (pts - T[:3, 3]) @ T[:3, :3]                        # R^T (pc - t)
+    box = torch.stack([po.min(0).values, po.max(0).values, T[2, :3]]).cpu().numpy()          # the camera's z axis in the object's frame
+    lo, hi, axis = box
+    L = float((hi - lo).max())
+    side = float(extent) if extent is not None else 2.0 * L
+    if not (np.isfinite(side) and side > 0):
+        raise ValueError(f"volume_for_first_view: the cube's side {side} must be finite and positive (frame 0's pixels span no length: give extent)")
+    centre = 0.5 * (lo + hi) + 0.5 * L * axis
+    voxel = side / (int(resolution) - 1)
+    return tuple(float(v) for v in centre - 0.5 * side), float(voxel), (int(resolution),) * 3
+
+
+def track_views(depth: torch.Tensor, K: torch.Tensor, masks: Optional[torch.Tensor] = None, TCO_first: Optional[torch.Tensor] = None,
+                resolution: int = 128, extent: Optional[float] = None, trunc_voxels: float = 3.0, iters: int = 10, min_pixels: int = 64,
+                rms_max: Optional[float] = None, device="cuda") -> Tuple[torch.Tensor, torch.Tensor, Dict[str, object]]:
+    """The camera poses of a sequence of depth frames of one object (a hand-held camera, a turntable without encoders: BOP's dynamic
+    onboarding), frame by frame against the volume the frames before it built: frame 0 is integrated at TCO_first, frame k is tracked
+    from the last tracked pose (`TsdfVolume.track`) and, when it tracked, integrated with carving at its tracked pose.  depth [n,h,w]
+    metres, K [n,3,3], masks [n,h,w] or None -> (TCO [n,4,4] float32 object to camera, tracked [n] bool, info), the first two on the device.
+
+    TCO_first fixes the object's frame; None puts its origin at the centroid of frame 0's points with the camera's axes.  The volume is
+    `volume_for_first_view`'s (resolution, extent).  A frame tracked when its status is 0 or 1, and, with rms_max (metres) given, its
+    residual is at most rms_max; None does not test the residual.  A lost frame keeps the pose before it, is flagged and is not
+    integrated -- a wrong pose would carve the object away -- and the sequence goes on from the last tracked pose.  Consecutive
+    frames must overlap within the truncation band (trunc_voxels voxels): there is no motion model beyond "hold the last pose".
+    One read-back of (status, used, rms) per frame.  info: `status`, `used`, `rms` as numpy arrays per frame (frame 0: 1, 0, 0), the
+    `volume` (a TsdfVolume) as the last frame left it."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() != 3 or depth.shape[0] == 0:
+        raise ValueError(f"track_views: depth must be [n,h,w] with at least one frame, got {tuple(depth.shape)}")
+    n = depth.shape[0]
+    K = torch.as_tensor(K)
+    if tuple(K.shape) != (n, 3, 3):
+        raise ValueError(f"track_views: K must be [{n},3,3], got {tuple(K.shape)}")
+    if masks is not None and tuple(torch.as_tensor(masks).shape) != tuple(depth.shape):
+        raise ValueError(f"track_views: masks must be {tuple(depth.shape)}, got {tuple(torch.as_tensor(masks).shape)}")
+    depth, K = depth.to(device, torch.float32), K.to(device, torch.float32)
+    masks = None if masks is None else torch.as_tensor(masks).to(device)
+    if TCO_first is None:
+        pts = _first_view_points(depth[0], K[0], None if masks is None else masks[0])
+        if pts.shape[0] == 0:
+            raise ValueError("track_views: frame 0 holds no measured pixel of the object (depth finite and > 0 inside the mask)")
+        first = torch.eye(4, dtype=torch.float64, device=depth.device)
+        first[:3, 3] = pts.mean(0)
+    else:
+        first = torch.as_tensor(TCO_first).to(depth.device, torch.float64)
+        if tuple(first.shape) != (4, 4) or not bool(torch.isfinite(first).all()):
+            raise ValueError("track_views: TCO_first must be a finite [4,4] pose")
+    try:
+        origin, voxel, dims = volume_for_first_view(depth[0], K[0], first, None if masks is None else masks[0], resolution=resolution, extent=extent)
+    except ValueError as e:
+        raise ValueError(f"track_views: {e}") from e
+    vol = TsdfVolume(origin, voxel, dims, trunc_voxels=trunc_voxels, color=False, device=device)
+    poses = torch.empty(n, 4, 4, dtype=torch.float32, device=depth.device)
+    poses[0] = first.to(torch.float32)
+    status, used, rms = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+    status[0] = 1
+    tracked = [True]
+    m = lambda k: None if masks is None else masks[k:k + 1]   # noqa: E731
+    vol.integrate(depth[:1], K[:1], poses[:1], masks=m(0))
+    last = poses[:1]
+    for k in range(1, n):
+        T, st, us, rm = vol.track(depth[k:k + 1], K[k:k + 1], last, masks=m(k), iters=iters, min_pixels=min_pixels)
+        back = torch.cat([st.to(torch.float64), us.to(torch.float64), rm.to(torch.float64)]).cpu().numpy()      # the frame's one read-back
+        status[k], used[k], rms[k] = int(back[0]), int(back[1]), back[2]
+        ok = status[k] >= 0 and (rms_max is None or float(rms[k]) <= rms_max)
+        tracked.append(bool(ok))
+        if ok:
+            last = T
+            vol.integrate(depth[k:k + 1], K[k:k + 1], T, masks=m(k))
+        poses[k] = last[0]
+    return poses, torch.as_tensor(tracked, device=depth.device), dict(status=status, used=used, rms=rms, volume=vol)
+
+
+def reconstruct_object_unposed(label: str, depth: torch.Tensor, K: torch.Tensor, masks: Optional[torch.Tensor] = None,
+                               rgb: Optional[torch.Tensor] = None, TCO_first: Optional[torch.Tensor] = None, resolution: int = 128,
+                               extent: Optional[float] = None, trunc_voxels: float = 3.0, iters: int = 10, min_pixels: int = 64,
+                               rms_max: Optional[float] = None, device="cuda", **kw) -> RigidObject:
+    """Depth frames of one object WITHOUT camera poses -> `<out_dir>/<label>.ply` and its RigidObject: `track_views` finds the poses,
+    `reconstruct_object` then fuses the frames that tracked at their tracked poses into a volume of its own, sized tightly around what
+    they saw (the tracking volume is twice as wide as the object and half as fine).  The object's frame is the one TCO_first fixes (see
+    `track_views`).  Every keyword of `reconstruct_object` passes through (out_dir, min_views, carve, keep_largest, max_faces,
+    texture_size); resolution and trunc_voxels hold for both passes.  Raises a ValueError that names the count when fewer than two
+    frames tracked."""
+    poses, tracked, info = track_views(depth, K, masks=masks, TCO_first=TCO_first, resolution=resolution, extent=extent, trunc_voxels=trunc_voxels,
+                                       iters=iters, min_pixels=min_pixels, rms_max=rms_max, device=device)
+    n_tracked = int(tracked.sum())
+    if n_tracked < 2:
+        raise ValueError(f"reconstruct_object_unposed({label!r}): {n_tracked} of {len(tracked)} frames tracked, at least 2 are needed "
+                         f"(status per frame: {info['status'].tolist()}; frames that overlap too little, or an object deeper than the volume: extent?)")
+    keep = tracked.to(poses.device)
+    pick = lambda t: None if t is None else torch.as_tensor(t).to(poses.device)[keep]   # noqa: E731
+    return reconstruct_object(label, pick(depth), pick(K), poses[keep], masks=pick(masks), rgb=pick(rgb), resolution=resolution,
+                              trunc_voxels=trunc_voxels, device=device, **kw)
