@@ -10,31 +10,22 @@
 //                        of two, so a tile is (16 / B)^2 whole blocks (B <= 16: at most 32 triangles) or a part of one block (2
 //                        triangles).  The tile's triangles -- corner 0, the two edges, the normal, |n|^2, the corner colours
 //                        [texbake::load_tri] -- are staged in LDS by the first lanes, one triangle each; a lane computes its surface
-//                        point once and keeps it, and reads the normal from LDS (lanes of one chart read one address).  The views (R, t,
-//                        fx, fy, cx, cy and whether K and TCO are finite) are staged in LDS kBakeViewChunk at a time, as
-//                        tsdf_integrate_kernel does, so their number is not limited.  The depth, mask and colour reads are gathers:
-//                        neighbouring texels of a chart project to neighbouring pixels.  The texel's four bytes are one 32-bit store,
-//                        rows of 16 texels = 64 B segments.  Tiles past the last triangle store zeros and return.
+//                        point once and keeps it, and reads the normal from LDS (lanes of one chart read one address).  The views come as
+//                        the PosedViews descriptor and are walked by walk_views (tsdf_views.h: the walk of tsdf_integrate_kernel, the
+//                        views staged in LDS kViewChunk at a time), so their number is not limited.  The depth, mask and colour reads
+//                        are gathers: neighbouring texels of a chart project to neighbouring pixels.  The texel's four bytes are one
+//                        32-bit store, rows of 16 texels = 64 B segments.  Tiles past the last triangle store zeros and return.
 #include "common.h"
 #include "texture_bake_core.h"
+#include "tsdf_views.h"
 
 namespace mp {
 
 constexpr int kBakeTile = 16;
 constexpr int kBakeBlock = kBakeTile * kBakeTile;
-constexpr int kBakeViewChunk = 32;                      // views staged in LDS at a time
 constexpr int kBakeMaxTris = 2 * (kBakeTile / texbake::kMinBlock) * (kBakeTile / texbake::kMinBlock);   // 32: a tile of 4 x 4 blocks of 4
 constexpr int kBakeTriStride = texbake::kTriFloats + 1;   // 23 words: odd, so the triangles of a tile start on different banks
 constexpr int kUvBlock = 256;
-
-struct BakeViews {
-  const float* depth;
-  const uint8_t* masks;
-  const uint8_t* rgb;
-  const float* K;
-  const float* TCO;
-  int tco_floats, n, h, w;
-};
 
 __global__ __launch_bounds__(kUvBlock) void texture_uvs_kernel(int T, int S, int B, float* __restrict__ uvs) {
   const long long g = (long long)blockIdx.x * kUvBlock + threadIdx.x;
@@ -46,13 +37,13 @@ __global__ __launch_bounds__(kUvBlock) void texture_uvs_kernel(int T, int S, int
 }
 
 __global__ __launch_bounds__(kBakeBlock) void texture_bake_kernel(const float* __restrict__ vertices, int V, const int32_t* __restrict__ faces, int T,
-                                                                  const float* __restrict__ colors, BakeViews vw, int S, int B, float depth_tol,
+                                                                  const float* __restrict__ colors, PosedViews vw, int S, int B, float depth_tol,
                                                                   float cos_min2, float z_min, int best_view, uint32_t* __restrict__ texels,
                                                                   uint8_t* __restrict__ seen) {
   __shared__ float tris[kBakeMaxTris * kBakeTriStride];
   __shared__ int tri_flags[kBakeMaxTris];   // texbake::kTri* flags, -1 for a slot past the last triangle
-  __shared__ float views[kBakeViewChunk][tsdf::kViewFloats];
-  __shared__ int view_ok[kBakeViewChunk];
+  __shared__ float views[kViewChunk][tsdf::kViewFloats];
+  __shared__ int view_ok[kViewChunk];
   const int tiles = S / kBakeTile;
   const int tile_x = blockIdx.x % tiles, tile_y = blockIdx.x / tiles;
   const int lx = threadIdx.x % kBakeTile, ly = threadIdx.x / kBakeTile;
@@ -82,22 +73,9 @@ __global__ __launch_bounds__(kBakeBlock) void texture_bake_kernel(const float* _
   float p[3] = {0.f, 0.f, 0.f};
   if (visits) texbake::surface_point(tri, a, b, p);
   texbake::Accum acc = texbake::accum_init();
-  const size_t hw = (size_t)vw.h * vw.w;
-  for (int v0 = 0; v0 < vw.n; v0 += kBakeViewChunk) {
-    const int m = vw.n - v0 < kBakeViewChunk ? vw.n - v0 : kBakeViewChunk;
-    __syncthreads();   // every lane has left the chunk before
-    if ((int)threadIdx.x < m)
-      view_ok[threadIdx.x] = tsdf::load_view(vw.K + (size_t)(v0 + threadIdx.x) * 9, vw.TCO + (size_t)(v0 + threadIdx.x) * vw.tco_floats, views[threadIdx.x]);
-    __syncthreads();
-    if (!visits) continue;
-    for (int q = 0; q < m; ++q) {
-      if (!view_ok[q]) continue;
-      const size_t v = (size_t)(v0 + q);
-      acc = texbake::accumulate(acc, texbake::visit(p, tri, views[q], vw.depth + v * hw, vw.masks ? vw.masks + v * hw : nullptr, vw.rgb + v * hw * 3,
-                                                    vw.h, vw.w, depth_tol, cos_min2, z_min),
-                                best_view != 0);
-    }
-  }
+  walk_views(vw, visits, views, view_ok, [&](const float* view, const float* depth, const uint8_t* mask, const uint8_t* rgb) {
+    acc = texbake::accumulate(acc, texbake::visit(p, tri, view, depth, mask, rgb, vw.h, vw.w, depth_tol, cos_min2, z_min), best_view != 0);
+  });
   if (flags < 0) {
     texels[out] = 0u;
     seen[out] = 0;
@@ -139,23 +117,12 @@ extern "C" int mp_texture_bake(const float* d_vertices, int n_vertices, const in
   MP_REQUIRE(B > 0, "mp_texture_bake: %d triangles do not fit an atlas of %d x %d texels in blocks of 4 x 4", n_triangles, size, size);
   MP_REQUIRE(texbake::params_ok(depth_tol, cos_min, z_min),
              "mp_texture_bake: depth_tol must be finite and > 0, cos_min in [0, 1), z_min finite and >= 0");
-  MP_REQUIRE(n >= 0 && (tco_floats == 12 || tco_floats == 16), "mp_texture_bake: n %d >= 0, TCO rows of 12 or 16 floats (got %d)", n, tco_floats);
-  MP_REQUIRE(n == 0 || tsdf::frame_ok(h, w), "mp_texture_bake: frames of %d x %d: 1 .. 8192 a side", h, w);
-  MP_REQUIRE(d_faces && d_texels && d_seen && (d_vertices || n_vertices == 0) && (n == 0 || (d_depth && d_rgb && d_K && d_TCO)),
-             "mp_texture_bake: null pointer");
-  MP_REQUIRE((uintptr_t)d_texels % 4 == 0 && (uintptr_t)d_vertices % 4 == 0 && (uintptr_t)d_faces % 4 == 0 && (uintptr_t)d_colors % 4 == 0 &&
-                 (uintptr_t)d_depth % 4 == 0 && (uintptr_t)d_K % 4 == 0 && (uintptr_t)d_TCO % 4 == 0,
+  PosedViews vw = {d_depth, d_masks, d_rgb, d_K, d_TCO, tco_floats, n, h, w};
+  if (int rc = require_views("mp_texture_bake", vw, true, INT32_MAX)) return rc;
+  if (n == 0) vw.h = vw.w = 1;   // no view: the fallback colours are still written
+  MP_REQUIRE(d_faces && d_texels && d_seen && (d_vertices || n_vertices == 0), "mp_texture_bake: null pointer");
+  MP_REQUIRE((uintptr_t)d_texels % 4 == 0 && (uintptr_t)d_vertices % 4 == 0 && (uintptr_t)d_faces % 4 == 0 && (uintptr_t)d_colors % 4 == 0,
              "mp_texture_bake: texels or a 32-bit input not 4-byte aligned");
-  BakeViews vw;
-  vw.depth = d_depth;
-  vw.masks = d_masks;
-  vw.rgb = d_rgb;
-  vw.K = d_K;
-  vw.TCO = d_TCO;
-  vw.tco_floats = tco_floats;
-  vw.n = n;
-  vw.h = n ? h : 1;
-  vw.w = n ? w : 1;
   const int tiles = size / kBakeTile;
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("texture_bake", 0.0, 5.0 * (double)size * size, s);

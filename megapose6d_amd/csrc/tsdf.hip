@@ -1,16 +1,17 @@
 // tsdf.hip -- the device side of onboarding an object without a CAD model: posed depth views fused into a truncated signed distance
 // field on a voxel grid, and the welded, coloured triangle mesh of its zero level by marching tetrahedra.
 //
-// The rules are tsdf_core.h, shared with the host emulation of the tests; this file adds the work distribution.  Every float of a node
+// The rules, the volume descriptor (tsdf::Volume over its tsdf::Grid) and the corner indexing are tsdf_core.h, shared with the host
+// emulation of the tests; the views descriptor, the staged walk over the views and the entries' argument checks are tsdf_views.h, shared
+// with texture_bake.hip and tsdf_track.hip; this file adds the work distribution.  Every float of a node
 // or a vertex is produced by one thread from those rules, every rank is an exclusive sum of integers in one fixed order, so no grid or
 // block size can change a result.  No atomics, no workgroup waits on another, no search at all: a triangle finds its vertices from
 // the scanned ranks of its edges' owners.
 //
 //   tsdf_integrate_kernel  one lane per node, x across the lanes: the volume's planes are read once and written once per call, coalesced,
-//                          and a node's sums and counts stay in registers over the call's views.  The views (R, t, fx, fy, cx, cy and
-//                          whether K and TCO are finite) are staged in LDS, kTsdfViewChunk at a time, by the first lanes of the
-//                          workgroup; every lane then reads the same entry.  The depth, mask and colour reads are gathers: neighbouring
-//                          nodes hit neighbouring pixels.
+//                          and a node's sums and counts stay in registers over the call's views [walk_views: the views are staged in
+//                          LDS kViewChunk at a time; every lane then reads the same entry].  The depth, mask and colour reads are
+//                          gathers: neighbouring nodes hit neighbouring pixels.
 //   tsdf_flags_kernel      per node: observed, inside [tsdf::node_flags].
 //   tsdf_cells_kernel      per cell (the node that is its c0): complete or not, and its number of triangles from the six cases.
 //   tsdf_count_kernel      per node: the mask of its seven edges that carry a vertex (the complete cells around an edge come from the
@@ -20,47 +21,25 @@
 //                          two grand totals -- the one read-back between mp_tsdf_extract_count and mp_tsdf_extract.
 //   tsdf_emit_kernel       per node: its vertices (position and colour interpolated from the owner towards the far node) and its cell's
 //                          triangles; every store guarded by the stated number of vertices / triangles.
+// (The split of a node index into i, j, k and an edge's far node g + dx + dy * nx + dz * nxy stay written out in the kernels, and the grid
+// is copied out of the descriptor, not referenced: behind a function, or through the reference, the cells, count and emit kernels compile
+// to other instruction streams than the measured ones.)
 // WORKSPACE of mp_tsdf_extract_count / mp_tsdf_extract (the extract reads what the count on the same volume left there): per node the
 // flags, the cell byte (0x80 complete | triangles), the edge mask (bytes), the vertex rank inside its workgroup (uint16), per workgroup
 // of kTsdfBlock nodes the vertex and triangle bases.
 #include "common.h"
-#include "tsdf_core.h"
+#include "tsdf_views.h"
 
 namespace mp {
 
 constexpr int kTsdfBlock = 256;
 constexpr int kTsdfWaves = kTsdfBlock / 64;
-constexpr int kTsdfViewChunk = 32;    // views staged in LDS at a time: 2 KB of tables
 constexpr int kCellComplete = 0x80;   // the cell byte: complete | its number of triangles (<= 12)
 
-struct TsdfGrid {
-  int nx, ny, nz, N;
-  float ox, oy, oz, voxel;
-};
-
-struct TsdfVolume {
-  float* sum;
-  int32_t* count;
-  float* c[3];      // null without colours
-  int32_t* c_count;
-};
-
-static TsdfVolume tsdf_planes(void* d_volume, int N, int color) {
-  float* f = (float*)d_volume;
-  TsdfVolume v;
-  v.sum = f;
-  v.count = (int32_t*)(f + (size_t)N);
-  for (int k = 0; k < 3; ++k) v.c[k] = color ? f + (size_t)(2 + k) * N : nullptr;
-  v.c_count = color ? (int32_t*)(f + (size_t)5 * N) : nullptr;
-  return v;
-}
-
-__global__ __launch_bounds__(kTsdfBlock) void tsdf_integrate_kernel(TsdfVolume vol, TsdfGrid gr, const float* __restrict__ depth,
-                                                                    const uint8_t* __restrict__ masks, const uint8_t* __restrict__ rgb,
-                                                                    const float* __restrict__ K, const float* __restrict__ TCO, int tco_floats,
-                                                                    int n, int h, int w, float mu, float z_min, int carve) {
-  __shared__ float views[kTsdfViewChunk][tsdf::kViewFloats];
-  __shared__ int view_ok[kTsdfViewChunk];
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_integrate_kernel(tsdf::Volume vol, PosedViews vw, float mu, float z_min, int carve) {
+  __shared__ float views[kViewChunk][tsdf::kViewFloats];
+  __shared__ int view_ok[kViewChunk];
+  const tsdf::Grid gr = vol;
   const int g = blockIdx.x * kTsdfBlock + threadIdx.x;
   const bool in = g < gr.N;
   const bool color = vol.c_count != nullptr;
@@ -80,21 +59,9 @@ __global__ __launch_bounds__(kTsdfBlock) void tsdf_integrate_kernel(TsdfVolume v
       nd.c_count = vol.c_count[g];
     }
   }
-  const size_t hw = (size_t)h * w;
-  for (int v0 = 0; v0 < n; v0 += kTsdfViewChunk) {
-    const int m = n - v0 < kTsdfViewChunk ? n - v0 : kTsdfViewChunk;
-    __syncthreads();   // every lane has left the chunk before
-    if ((int)threadIdx.x < m)
-      view_ok[threadIdx.x] = tsdf::load_view(K + (size_t)(v0 + threadIdx.x) * 9, TCO + (size_t)(v0 + threadIdx.x) * tco_floats, views[threadIdx.x]);
-    __syncthreads();
-    if (!in) continue;
-    for (int q = 0; q < m; ++q) {
-      if (!view_ok[q]) continue;
-      const size_t v = (size_t)(v0 + q);
-      nd = tsdf::integrate(nd, tsdf::visit(px, py, pz, views[q], depth + v * hw, masks ? masks + v * hw : nullptr, rgb ? rgb + v * hw * 3 : nullptr,
-                                           h, w, mu, z_min, carve != 0, color));
-    }
-  }
+  walk_views(vw, in, views, view_ok, [&](const float* view, const float* depth, const uint8_t* mask, const uint8_t* rgb) {
+    nd = tsdf::integrate(nd, tsdf::visit(px, py, pz, view, depth, mask, rgb, vw.h, vw.w, mu, z_min, carve != 0, color));
+  });
   if (!in) return;
   vol.sum[g] = nd.sum;
   vol.count[g] = nd.count;
@@ -117,7 +84,7 @@ __device__ __forceinline__ bool tsdf_cell_corners(const uint8_t* __restrict__ fl
   int all = tsdf::kObserved, ins = 0;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
-    const int f = flags[g + (c & 1) + ((c >> 1) & 1) * nx + ((c >> 2) & 1) * nxy];
+    const int f = flags[tsdf::corner_node(g, c, nx, nxy)];
     all &= f;
     ins |= ((f & tsdf::kInside) ? 1 : 0) << c;
   }
@@ -125,7 +92,7 @@ __device__ __forceinline__ bool tsdf_cell_corners(const uint8_t* __restrict__ fl
   return all != 0;
 }
 
-__global__ __launch_bounds__(kTsdfBlock) void tsdf_cells_kernel(const uint8_t* __restrict__ flags, TsdfGrid gr, uint8_t* __restrict__ cell) {
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_cells_kernel(const uint8_t* __restrict__ flags, tsdf::Grid gr, uint8_t* __restrict__ cell) {
   const int g = blockIdx.x * kTsdfBlock + threadIdx.x;
   if (g >= gr.N) return;
   const int i = g % gr.nx, j = (g / gr.nx) % gr.ny, k = g / (gr.nx * gr.ny);
@@ -137,7 +104,7 @@ __global__ __launch_bounds__(kTsdfBlock) void tsdf_cells_kernel(const uint8_t* _
   cell[g] = (uint8_t)out;
 }
 
-__global__ __launch_bounds__(kTsdfBlock) void tsdf_count_kernel(const uint8_t* __restrict__ flags, const uint8_t* __restrict__ cell, TsdfGrid gr,
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_count_kernel(const uint8_t* __restrict__ flags, const uint8_t* __restrict__ cell, tsdf::Grid gr,
                                                                 uint8_t* __restrict__ emask, uint16_t* __restrict__ lrank,
                                                                 int32_t* __restrict__ block_nv, int32_t* __restrict__ block_nt) {
   __shared__ int wave_tot[kTsdfWaves];
@@ -212,12 +179,13 @@ __device__ __forceinline__ int tsdf_vertex_index(const int32_t* __restrict__ blo
   return block_nv[o / kTsdfBlock] + (int)lrank[o] + __popc((int)emask[o] & ((1 << kind) - 1));
 }
 
-__global__ __launch_bounds__(kTsdfBlock) void tsdf_emit_kernel(TsdfVolume vol, TsdfGrid gr, const uint8_t* __restrict__ flags,
+__global__ __launch_bounds__(kTsdfBlock) void tsdf_emit_kernel(tsdf::Volume vol, const uint8_t* __restrict__ flags,
                                                                const uint8_t* __restrict__ cell, const uint8_t* __restrict__ emask,
                                                                const uint16_t* __restrict__ lrank, const int32_t* __restrict__ block_nv,
                                                                const int32_t* __restrict__ block_nt, int n_vertices, int n_triangles,
                                                                float* __restrict__ vertices, float* __restrict__ colors, int32_t* __restrict__ faces) {
   __shared__ int wave_tot[kTsdfWaves];
+  const tsdf::Grid gr = vol;
   const int g = blockIdx.x * kTsdfBlock + threadIdx.x;
   const bool in = g < gr.N;
   const int nxy = gr.nx * gr.ny;
@@ -264,7 +232,7 @@ __global__ __launch_bounds__(kTsdfBlock) void tsdf_emit_kernel(TsdfVolume vol, T
         for (int s = 0; s < 3; ++s) {
           int code, kind;
           tsdf::tri_edge(tb, T, m, tri, s, &code, &kind);
-          const int o = g + (code & 1) + ((code >> 1) & 1) * gr.nx + ((code >> 2) & 1) * nxy;
+          const int o = tsdf::corner_node(g, code, gr.nx, nxy);
           faces[(size_t)r * 3 + s] = tsdf_vertex_index(block_nv, lrank, emask, o, kind);
         }
       }
@@ -273,44 +241,23 @@ __global__ __launch_bounds__(kTsdfBlock) void tsdf_emit_kernel(TsdfVolume vol, T
   }
 }
 
-struct TsdfPlan { int N, n_blocks; };
-
-static bool tsdf_plan(int nx, int ny, int nz, TsdfPlan* p) {
-  if (!tsdf::dims_ok(nx, ny, nz)) return false;
-  p->N = nx * ny * nz;
-  p->n_blocks = ceil_div(p->N, kTsdfBlock);
-  return true;
-}
-
 struct TsdfWs {
   uint8_t *flags, *cell, *emask;
   uint16_t* lrank;
   int32_t *block_nv, *block_nt;
+  int n_blocks;
   size_t total;
-  TsdfWs(void* base, const TsdfPlan& p) {
+  TsdfWs(void* base, int N) : n_blocks(ceil_div(N, kTsdfBlock)) {
     WsCarver c(base);
-    flags = c.take<uint8_t>((size_t)p.N);
-    cell = c.take<uint8_t>((size_t)p.N);
-    emask = c.take<uint8_t>((size_t)p.N);
-    lrank = c.take<uint16_t>((size_t)p.N);
-    block_nv = c.take<int32_t>((size_t)p.n_blocks);
-    block_nt = c.take<int32_t>((size_t)p.n_blocks);
+    flags = c.take<uint8_t>((size_t)N);
+    cell = c.take<uint8_t>((size_t)N);
+    emask = c.take<uint8_t>((size_t)N);
+    lrank = c.take<uint16_t>((size_t)N);
+    block_nv = c.take<int32_t>((size_t)n_blocks);
+    block_nt = c.take<int32_t>((size_t)n_blocks);
     total = c.total();
   }
 };
-
-static TsdfGrid tsdf_grid(int nx, int ny, int nz, float ox, float oy, float oz, float voxel) {
-  TsdfGrid g;
-  g.nx = nx;
-  g.ny = ny;
-  g.nz = nz;
-  g.N = nx * ny * nz;
-  g.ox = ox;
-  g.oy = oy;
-  g.oz = oz;
-  g.voxel = voxel;
-  return g;
-}
 
 }  // namespace mp
 
@@ -323,45 +270,39 @@ extern "C" size_t mp_tsdf_volume_bytes(int nx, int ny, int nz, int color) {
 extern "C" int mp_tsdf_integrate(void* d_volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel, const float* d_depth,
                                  const uint8_t* d_masks, const uint8_t* d_rgb, const float* d_K, const float* d_TCO, int tco_floats, int n, int h,
                                  int w, float mu, float z_min, int carve, mp_stream stream) {
-  const float origin[3] = {ox, oy, oz};
-  MP_REQUIRE(tsdf::dims_ok(nx, ny, nz), "mp_tsdf_integrate: volume of %d x %d x %d: each side 2 .. 512, at most 2^27 nodes", nx, ny, nz);
-  MP_REQUIRE(tsdf::grid_ok(origin, voxel), "mp_tsdf_integrate: origin must be finite, voxel finite and > 0");
+  const PosedViews vw = {d_depth, d_masks, d_rgb, d_K, d_TCO, tco_floats, n, h, w};
+  if (int rc = require_volume("mp_tsdf_integrate", nx, ny, nz, ox, oy, oz, voxel)) return rc;
   MP_REQUIRE(tsdf::finite_f(mu) && mu > 0.f && tsdf::finite_f(z_min) && z_min >= 0.f,
              "mp_tsdf_integrate: the truncation distance must be finite and > 0, z_min finite and >= 0");
-  MP_REQUIRE(n >= 0 && (tco_floats == 12 || tco_floats == 16), "mp_tsdf_integrate: n %d >= 0, TCO rows of 12 or 16 floats (got %d)", n, tco_floats);
-  if (n == 0) return MP_OK;
-  MP_REQUIRE(tsdf::frame_ok(h, w), "mp_tsdf_integrate: frames of %d x %d: 1 .. 8192 a side", h, w);
-  MP_REQUIRE(d_volume && d_depth && d_K && d_TCO, "mp_tsdf_integrate: null pointer");
+  const int rc = require_views("mp_tsdf_integrate", vw, false, INT32_MAX);
+  if (rc != MP_OK || n == 0) return rc;
+  MP_REQUIRE(d_volume, "mp_tsdf_integrate: null pointer");
   MP_REQUIRE((uintptr_t)d_volume % 4 == 0, "mp_tsdf_integrate: volume not 4-byte aligned");
-  const TsdfGrid gr = tsdf_grid(nx, ny, nz, ox, oy, oz, voxel);
-  const TsdfVolume vol = tsdf_planes(d_volume, gr.N, color);
+  const tsdf::Volume vol = tsdf::volume_of(d_volume, nx, ny, nz, color, ox, oy, oz, voxel);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof("tsdf_integrate", 0.0, 8.0 * tsdf::planes(color) * (double)gr.N, s);
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)ceil_div(gr.N, kTsdfBlock)), dim3(kTsdfBlock), 0, s, vol, gr, d_depth, d_masks, d_rgb, d_K,
-                     d_TCO, tco_floats, n, h, w, mu, z_min, carve);
+  ProfScope prof("tsdf_integrate", 0.0, 8.0 * tsdf::planes(color) * (double)vol.N, s);
+  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)ceil_div(vol.N, kTsdfBlock)), dim3(kTsdfBlock), 0, s, vol, vw, mu, z_min, carve);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
 
 extern "C" size_t mp_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {
-  TsdfPlan p;
-  return tsdf_plan(nx, ny, nz, &p) ? TsdfWs(nullptr, p).total : 0;
+  return tsdf::dims_ok(nx, ny, nz) ? TsdfWs(nullptr, nx * ny * nz).total : 0;
 }
 
 extern "C" int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int nz, int color, int min_views, int32_t* d_totals, void* d_ws,
                                      size_t ws_bytes, mp_stream stream) {
-  TsdfPlan p;
-  MP_REQUIRE(tsdf_plan(nx, ny, nz, &p), "mp_tsdf_extract_count: volume of %d x %d x %d: each side 2 .. 512, at most 2^27 nodes", nx, ny, nz);
+  if (int rc = require_volume("mp_tsdf_extract_count", nx, ny, nz, 0.f, 0.f, 0.f, 1.f)) return rc;
   MP_REQUIRE(min_views >= 1, "mp_tsdf_extract_count: min_views %d must be at least 1", min_views);
   MP_REQUIRE(d_volume && d_totals && d_ws, "mp_tsdf_extract_count: null pointer");
-  const TsdfWs ws(d_ws, p);
+  const tsdf::Volume vol = tsdf::volume_of(const_cast<void*>(d_volume), nx, ny, nz, color, 0.f, 0.f, 0.f, 1.f);
+  const tsdf::Grid& gr = vol;
+  const TsdfWs ws(d_ws, gr.N);
   MP_REQUIRE(ws_bytes >= ws.total, "mp_tsdf_extract_count: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0 && (uintptr_t)d_volume % 4 == 0, "mp_tsdf_extract_count: workspace not 16-byte aligned or volume not 4-byte aligned");
-  const TsdfGrid gr = tsdf_grid(nx, ny, nz, 0.f, 0.f, 0.f, 1.f);
-  const TsdfVolume vol = tsdf_planes(const_cast<void*>(d_volume), gr.N, color);
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("tsdf_extract_count", 0.0, 8.0 * (double)gr.N + 30.0 * (double)gr.N, s);
-  const dim3 grid((unsigned)p.n_blocks), block(kTsdfBlock);
+  const dim3 grid((unsigned)ws.n_blocks), block(kTsdfBlock);
   hipLaunchKernelGGL(tsdf_flags_kernel, grid, block, 0, s, (const float*)vol.sum, (const int32_t*)vol.count, gr.N, min_views, ws.flags);
   MP_CHECK_HIP(hipGetLastError());
   hipLaunchKernelGGL(tsdf_cells_kernel, grid, block, 0, s, (const uint8_t*)ws.flags, gr, ws.cell);
@@ -369,7 +310,7 @@ extern "C" int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int n
   hipLaunchKernelGGL(tsdf_count_kernel, grid, block, 0, s, (const uint8_t*)ws.flags, (const uint8_t*)ws.cell, gr, ws.emask, ws.lrank, ws.block_nv,
                      ws.block_nt);
   MP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), block, 0, s, ws.block_nv, ws.block_nt, p.n_blocks, d_totals);
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), block, 0, s, ws.block_nv, ws.block_nt, ws.n_blocks, d_totals);
   MP_CHECK_HIP(hipGetLastError());
   return MP_OK;
 }
@@ -377,24 +318,20 @@ extern "C" int mp_tsdf_extract_count(const void* d_volume, int nx, int ny, int n
 extern "C" int mp_tsdf_extract(const void* d_volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel, int n_vertices,
                                int n_triangles, float* d_vertices, float* d_colors, int32_t* d_faces, long long cap_vertices,
                                long long cap_triangles, void* d_ws, size_t ws_bytes, mp_stream stream) {
-  TsdfPlan p;
-  const float origin[3] = {ox, oy, oz};
-  MP_REQUIRE(tsdf_plan(nx, ny, nz, &p), "mp_tsdf_extract: volume of %d x %d x %d: each side 2 .. 512, at most 2^27 nodes", nx, ny, nz);
-  MP_REQUIRE(tsdf::grid_ok(origin, voxel), "mp_tsdf_extract: origin must be finite, voxel finite and > 0");
+  if (int rc = require_volume("mp_tsdf_extract", nx, ny, nz, ox, oy, oz, voxel)) return rc;
   MP_REQUIRE(n_vertices >= 0 && n_triangles >= 0 && cap_vertices >= n_vertices && cap_triangles >= n_triangles,
              "mp_tsdf_extract: %d vertices and %d triangles must not be negative and must fit the capacity of %lld and %lld", n_vertices, n_triangles,
              cap_vertices, cap_triangles);
   if (n_vertices == 0 && n_triangles == 0) return MP_OK;
   MP_REQUIRE(d_volume && d_ws && (d_vertices || n_vertices == 0) && (d_colors || n_vertices == 0) && (d_faces || n_triangles == 0),
              "mp_tsdf_extract: null pointer");
-  const TsdfWs ws(d_ws, p);
+  const tsdf::Volume vol = tsdf::volume_of(const_cast<void*>(d_volume), nx, ny, nz, color, ox, oy, oz, voxel);
+  const TsdfWs ws(d_ws, vol.N);
   MP_REQUIRE(ws_bytes >= ws.total, "mp_tsdf_extract: workspace of %zu bytes, %zu needed", ws_bytes, ws.total);
   MP_REQUIRE((uintptr_t)d_ws % 16 == 0 && (uintptr_t)d_volume % 4 == 0, "mp_tsdf_extract: workspace not 16-byte aligned or volume not 4-byte aligned");
-  const TsdfGrid gr = tsdf_grid(nx, ny, nz, ox, oy, oz, voxel);
-  const TsdfVolume vol = tsdf_planes(const_cast<void*>(d_volume), gr.N, color);
   hipStream_t s = (hipStream_t)stream;
-  ProfScope prof("tsdf_extract", 0.0, 6.0 * (double)gr.N + 24.0 * (double)n_vertices + 12.0 * (double)n_triangles, s);
-  hipLaunchKernelGGL(tsdf_emit_kernel, dim3((unsigned)p.n_blocks), dim3(kTsdfBlock), 0, s, vol, gr, (const uint8_t*)ws.flags, (const uint8_t*)ws.cell,
+  ProfScope prof("tsdf_extract", 0.0, 6.0 * (double)vol.N + 24.0 * (double)n_vertices + 12.0 * (double)n_triangles, s);
+  hipLaunchKernelGGL(tsdf_emit_kernel, dim3((unsigned)ws.n_blocks), dim3(kTsdfBlock), 0, s, vol, (const uint8_t*)ws.flags, (const uint8_t*)ws.cell,
                      (const uint8_t*)ws.emask, (const uint16_t*)ws.lrank, (const int32_t*)ws.block_nv, (const int32_t*)ws.block_nt, n_vertices,
                      n_triangles, d_vertices, d_colors, d_faces);
   MP_CHECK_HIP(hipGetLastError());

@@ -1,6 +1,7 @@
 // tsdf_core.h -- the rules of onboarding an object without a CAD model: fusing posed depth views into a truncated signed distance
 // field (TSDF) on a voxel grid in the object's frame, and the welded triangle mesh of its zero level (marching tetrahedra), as they run
 // on the device (tsdf.hip), shared with the host emulation (tests/tsdf_emul.cpp) the way vsd_core.h is shared with tests/vsd_emul.cpp.
+// It also states the volume once [VolumeOf, Grid, volume_of, corner_node]: tsdf.hip, tsdf_track.hip and both emulations take that descriptor.
 //
 // CONTRACT (all arithmetic fp32, compiled with -ffp-contract=off, every operation a separate correctly rounded one in the order written;
 // lengths in metres; pixel (x, y) covers [x, x+1) x [y, y+1) as in vsd_core.h)
@@ -88,6 +89,46 @@ TSDF_HD bool grid_ok(const float* origin, float voxel) {
 TSDF_HD int planes(int color) { return color ? 6 : 2; }
 
 TSDF_HD float node_coord(float origin, float voxel, int i) { return origin + voxel * (float)i; }
+
+// ---- the volume, as every kernel, entry and emulation that touches one takes it -------------------------------------------------
+struct Grid {
+  int nx, ny, nz, N;   // N = nx * ny * nz
+  float ox, oy, oz, voxel;
+};
+
+// the planes of the CONTRACT over their grid, F and I = float and int32_t, or both const for an entry that only reads.  (Planes first, the
+// grid as a base of its own: a kernel that reads no plane takes the `Grid` alone.)
+template <class F, class I>
+struct Planes {
+  F* sum;
+  I* count;
+  F* c[3];      // null without colours
+  I* c_count;   // null without colours
+};
+template <class F, class I>
+struct VolumeOf : Planes<F, I>, Grid {};
+using Volume = VolumeOf<float, int32_t>;
+
+// `volume` must not be null; an entry that takes the volume const asks for const planes, or casts the const away here and stores nothing
+template <class F = float, class I = int32_t, class P>
+TSDF_HD VolumeOf<F, I> volume_of(P* volume, int nx, int ny, int nz, int color, float ox, float oy, float oz, float voxel) {
+  F* f = static_cast<F*>(volume);
+  const size_t N = (size_t)nx * ny * nz;
+  VolumeOf<F, I> v;
+  v.sum = f;
+  v.count = (I*)(f + N);
+  for (int k = 0; k < 3; ++k) v.c[k] = color ? f + (2 + k) * N : nullptr;
+  v.c_count = color ? (I*)(f + 5 * N) : nullptr;
+  (Grid&)v = {nx, ny, nz, (int)N, ox, oy, oz, voxel};
+  return v;
+}
+
+// the linear index of the corner `code` = dx + 2 dy + 4 dz of the cell at node g (nxy = nx * ny; I is int, or size_t where the caller
+// indexes in it)
+template <class I>
+TSDF_HD I corner_node(I g, int code, int nx, int nxy) {
+  return g + (I)(code & 1) + (I)((code >> 1) & 1) * (I)nx + (I)((code >> 2) & 1) * (I)nxy;
+}
 
 // K [9], T [12 ..] -> v [kViewFloats]; false when an entry is not finite (the view then contributes nothing)
 TSDF_HD bool load_view(const float* K, const float* T, float* v) {

@@ -1,9 +1,11 @@
 // tsdf_track.hip -- the device side of tracking the camera against the TSDF: the pose of an unposed depth frame by Gauss-Newton on the
 // signed distances the volume holds at the frame's own back-projected pixels.
 //
-// The rules are tsdf_track_core.h, shared with the host emulation of the tests; this file adds the work distribution.  Every fp32 term of
-// a pixel is produced by one lane from those rules, every fp64 sum has one owner and one order (lane, butterfly, waves, groups), so no
-// grid can change a result.  No atomics, no workgroup waits on another, nothing is read back inside a call: 1 + 2 * iters launches.
+// The rules are tsdf_track_core.h, shared with the host emulation of the tests; the volume is tsdf_core.h's descriptor with const
+// planes (tsdf::TrackVolume), and the entry's volume and frames are checked by tsdf_views.h's require_volume / require_views; this file
+// adds the work distribution.  Every fp32 term of a pixel is produced by one lane from those rules, every fp64 sum has one owner and one
+// order (lane, butterfly, waves, groups), so no grid can change a result.  No atomics, no workgroup waits on another, nothing is read back
+// inside a call: 1 + 2 * iters launches.
 //
 //   tsdf_track_init_kernel        one lane per frame: the input pose copied to the output, status 0 or -2 [tsdf::load_view], used and rms 0.
 //   tsdf_track_accumulate_kernel  grid (groups, n), one workgroup of 256 lanes per group of 1024 pixels of a frame.  It returns at once
@@ -18,6 +20,7 @@
 //                                 not 0; a lost frame gets its input pose back.
 #include "common.h"
 #include "tsdf_track_core.h"
+#include "tsdf_views.h"
 
 namespace mp {
 
@@ -115,32 +118,20 @@ extern "C" int mp_tsdf_track(const void* d_volume, int nx, int ny, int nz, int c
                              const uint8_t* d_masks, const float* d_K, const float* d_TCO_in, int n, int h, int w, float mu, int min_views,
                              int min_pixels, int iters, float eps_rot, float eps_trans, float* d_TCO_out, int32_t* d_status, int32_t* d_used,
                              float* d_rms, double* d_partials, long long partials_capacity, mp_stream stream) {
-  const float origin[3] = {ox, oy, oz};
-  MP_REQUIRE(tsdf::dims_ok(nx, ny, nz), "mp_tsdf_track: volume of %d x %d x %d: each side 2 .. 512, at most 2^27 nodes", nx, ny, nz);
-  MP_REQUIRE(tsdf::grid_ok(origin, voxel), "mp_tsdf_track: origin must be finite, voxel finite and > 0");
+  const PosedViews vw = {d_depth, d_masks, nullptr, d_K, d_TCO_in, 16, n, h, w};   // poses of 16 floats, no colour frames
+  if (int rc = require_volume("mp_tsdf_track", nx, ny, nz, ox, oy, oz, voxel)) return rc;
   MP_REQUIRE(tsdf::track_params_ok(mu, min_views, min_pixels, iters, eps_rot, eps_trans),
              "mp_tsdf_track: mu finite and > 0, min_views %d >= 1, min_pixels %d >= 1, iters %d in 1 .. %d, eps_rot and eps_trans finite and >= 0",
              min_views, min_pixels, iters, tsdf::kTrackMaxIters);
-  MP_REQUIRE(n >= 0 && n <= tsdf::kTrackMaxFrames, "mp_tsdf_track: n %d in 0 .. %d", n, tsdf::kTrackMaxFrames);
-  if (n == 0) return MP_OK;
+  const int rc = require_views("mp_tsdf_track", vw, false, tsdf::kTrackMaxFrames);
+  if (rc != MP_OK || n == 0) return rc;
   const int groups = tsdf::track_groups(h, w);
-  MP_REQUIRE(groups > 0, "mp_tsdf_track: frames of %d x %d: 1 .. 8192 a side", h, w);
-  MP_REQUIRE(d_volume && d_depth && d_K && d_TCO_in && d_TCO_out && d_status && d_used && d_rms && d_partials, "mp_tsdf_track: null pointer");
+  MP_REQUIRE(d_volume && d_TCO_out && d_status && d_used && d_rms && d_partials, "mp_tsdf_track: null pointer");
   MP_REQUIRE(d_TCO_in != d_TCO_out, "mp_tsdf_track: the output poses must not be the input poses (a lost frame returns its input)");
   MP_REQUIRE(partials_capacity >= (long long)n * groups, "mp_tsdf_track: partials of %lld records, %lld needed (%d frames of %d groups)",
              partials_capacity, (long long)n * groups, n, groups);
   MP_REQUIRE((uintptr_t)d_volume % 4 == 0 && (uintptr_t)d_partials % 8 == 0, "mp_tsdf_track: volume not 4-byte aligned or partials not 8-byte aligned");
-  tsdf::TrackVolume vol;
-  vol.sum = (const float*)d_volume;
-  vol.count = (const int32_t*)d_volume + (size_t)nx * ny * nz;
-  vol.nx = nx;
-  vol.ny = ny;
-  vol.nz = nz;
-  vol.ox = ox;
-  vol.oy = oy;
-  vol.oz = oz;
-  vol.voxel = voxel;
-  (void)color;   // the colour planes are not read
+  const tsdf::TrackVolume vol = tsdf::volume_of<const float, const int32_t>(d_volume, nx, ny, nz, color, ox, oy, oz, voxel);   // (the colour planes are not read)
   hipStream_t s = (hipStream_t)stream;
   ProfScope prof("tsdf_track", 0.0, (double)iters * n * ((double)h * w * 69.0 + (double)groups * 512.0), s);
   hipLaunchKernelGGL(tsdf_track_init_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, s, d_K, d_TCO_in, n, d_TCO_out, d_status, d_used, d_rms);

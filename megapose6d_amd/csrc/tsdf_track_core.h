@@ -82,36 +82,32 @@ TSDF_HD bool track_params_ok(float mu, int min_views, int min_pixels, int iters,
          eps_rot >= 0.f && finite_f(eps_trans) && eps_trans >= 0.f;
 }
 
-struct TrackVolume {
-  const float* sum;
-  const int32_t* count;
-  int nx, ny, nz;
-  float ox, oy, oz, voxel;
-};
+using TrackVolume = VolumeOf<const float, const int32_t>;   // the tracker only reads the volume
 
 // steps 2 .. 8 for the pixel (x, y) of depth d (step 1's mask is the caller's) under the loaded view v [kViewFloats]: false when the
 // pixel is skipped, else row = f, g [3], r, J [6]
 TSDF_HD bool track_row(int x, int y, float d, const float* v, const TrackVolume& vol, float mu, int min_views, float* row) {
   if (!(finite_f(d) && d > 0.f)) return false;
+  const Grid& gr = vol;
   const float pcx = ((((float)x + 0.5f) - v[14]) / v[12]) * d;
   const float pcy = ((((float)y + 0.5f) - v[15]) / v[13]) * d;
   const float e0 = pcx - v[9], e1 = pcy - v[10], e2 = d - v[11];
   const float p0 = (v[0] * e0 + v[3] * e1) + v[6] * e2;
   const float p1 = (v[1] * e0 + v[4] * e1) + v[7] * e2;
   const float p2 = (v[2] * e0 + v[5] * e1) + v[8] * e2;
-  const float qx = (p0 - vol.ox) / vol.voxel, qy = (p1 - vol.oy) / vol.voxel, qz = (p2 - vol.oz) / vol.voxel;
+  const float qx = (p0 - gr.ox) / gr.voxel, qy = (p1 - gr.oy) / gr.voxel, qz = (p2 - gr.oz) / gr.voxel;
   const float ix = floorf(qx), iy = floorf(qy), iz = floorf(qz);
-  if (!(ix >= 0.f && ix < (float)(vol.nx - 1) && iy >= 0.f && iy < (float)(vol.ny - 1) && iz >= 0.f && iz < (float)(vol.nz - 1))) return false;
+  if (!(ix >= 0.f && ix < (float)(gr.nx - 1) && iy >= 0.f && iy < (float)(gr.ny - 1) && iz >= 0.f && iz < (float)(gr.nz - 1))) return false;
   const float ux = qx - ix, uy = qy - iy, uz = qz - iz;
-  const size_t base = ((size_t)(int)iz * vol.ny + (size_t)(int)iy) * vol.nx + (size_t)(int)ix;
-  const size_t nxy = (size_t)vol.nx * vol.ny;
+  const size_t base = ((size_t)(int)iz * gr.ny + (size_t)(int)iy) * gr.nx + (size_t)(int)ix;
+  const int nxy = gr.nx * gr.ny;
   float F[8];
   bool seen = true;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
   for (int c = 0; c < 8; ++c) {
-    const size_t g = base + (c & 1) + (size_t)((c >> 1) & 1) * vol.nx + (size_t)((c >> 2) & 1) * nxy;
+    const size_t g = corner_node(base, c, gr.nx, nxy);
     const int32_t cnt = vol.count[g];
     seen = seen && cnt >= min_views;
     F[c] = field(vol.sum[g], cnt);
@@ -124,7 +120,7 @@ TSDF_HD bool track_row(int x, int y, float d, const float* v, const TrackVolume&
   const float dx = lerp(lerp(F[1] - F[0], F[3] - F[2], uy), lerp(F[5] - F[4], F[7] - F[6], uy), uz);
   const float dy = lerp(c10 - c00, c11 - c01, uz);
   const float dz = c1 - c0;
-  const float g0 = dx / vol.voxel, g1 = dy / vol.voxel, g2 = dz / vol.voxel;
+  const float g0 = dx / gr.voxel, g1 = dy / gr.voxel, g2 = dz / gr.voxel;
   const float m0 = g0 * mu, m1 = g1 * mu, m2 = g2 * mu;
   row[0] = f;
   row[1] = g0;

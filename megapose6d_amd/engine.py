@@ -1172,6 +1172,44 @@ def tsdf_volume(dims: Sequence[int], color: bool, device) -> torch.Tensor:
     return torch.zeros(6 if color else 2, nz, ny, nx, dtype=torch.float32, device=device)
 
 
+def _posed_views(depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, masks: Optional[torch.Tensor], rgb: Optional[torch.Tensor],
+                 poses_4x4: bool = False):
+    """A set of n posed views as the onboarding entries take it, checked: depth [n,h,w], K [n,3,3] and TCO [n,4,4] or [n,3,4] (rows of
+    any shape that holds those floats; `poses_4x4`: exactly [n,3,3] and [n,4,4], what tracking takes), masks [n,h,w] and rgb [n,h,w,3]
+    uint8 / bool or None -> (depth, K, TCO, masks, rgb) as contiguous device tensors and (n, h, w, tco_floats).  Without views K and TCO
+    are not looked at unless `poses_4x4`, and tco_floats is 16."""
+    depth = _dev_f32(depth)
+    if depth.dim() != 3:
+        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
+    n, h, w = (int(v) for v in depth.shape)
+    K, TCO = _dev_f32(K), _dev_f32(TCO)
+    given = tuple(K.shape), tuple(TCO.shape)
+    if poses_4x4:
+        K_ok, TCO_ok = tuple(K.shape) == (n, 3, 3), tuple(TCO.shape) == (n, 4, 4)
+    elif n:
+        K, TCO = K.reshape(n, -1), TCO.reshape(n, -1)
+        K_ok, TCO_ok = K.shape[1] == 9, TCO.shape[1] in (12, 16)
+    else:
+        K_ok = TCO_ok = True
+    if not K_ok:
+        raise EngineError(f"K must be [n,3,3], got {given[0]}")
+    if not TCO_ok:
+        raise EngineError(f"TCO must be [n,4,4]{'' if poses_4x4 else ' or [n,3,4]'}, got {given[1]}")
+    if masks is not None:
+        masks = _dev_bytes("masks", masks)
+        if tuple(masks.shape) != (n, h, w):
+            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
+    if rgb is not None:
+        rgb = _dev_bytes("rgb", rgb)
+        if tuple(rgb.shape) != (n, h, w, 3):
+            raise EngineError(f"rgb must be {(n, h, w, 3)}, got {tuple(rgb.shape)}")
+    return (depth, K, TCO, masks, rgb), (n, h, w, int(TCO.numel() // n) if n else 16)
+
+
+def _tsdf_mu(mu: Optional[float], voxel: float) -> float:   # the truncation distance in metres: 3 voxels when None
+    return float(np.float32(3.0) * np.float32(voxel)) if mu is None else float(mu)
+
+
 def tsdf_integrate(volume: torch.Tensor, origin: Sequence[float], voxel: float, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor,
                    masks: Optional[torch.Tensor] = None, rgb: Optional[torch.Tensor] = None, mu: Optional[float] = None, z_min: float = 1e-3,
                    carve: bool = True) -> None:
@@ -1181,25 +1219,10 @@ def tsdf_integrate(volume: torch.Tensor, origin: Sequence[float], voxel: float, 
     Node (i,j,k) lies at origin + voxel * (i,j,k); mu is the truncation distance in metres (3 voxels when None).  Calls continue each
     other bit for bit.  Nothing synchronises."""
     nx, ny, nz, color = _tsdf_dims(volume)
-    depth = _dev_f32(depth)
-    if depth.dim() != 3:
-        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
-    n, h, w = (int(v) for v in depth.shape)
-    K, TCO = _dev_f32(K).reshape(n, -1) if n else _dev_f32(K), _dev_f32(TCO).reshape(n, -1) if n else _dev_f32(TCO)
-    if n and (K.shape[1] != 9 or TCO.shape[1] not in (12, 16)):
-        raise EngineError(f"K must be [n,3,3] and TCO [n,4,4] or [n,3,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
-    if masks is not None:
-        masks = _dev_bytes("masks", masks)
-        if tuple(masks.shape) != (n, h, w):
-            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
-    if rgb is not None:
-        rgb = _dev_bytes("rgb", rgb)
-        if tuple(rgb.shape) != (n, h, w, 3):
-            raise EngineError(f"rgb must be {(n, h, w, 3)}, got {tuple(rgb.shape)}")
-    mu = float(np.float32(3.0) * np.float32(voxel)) if mu is None else float(mu)
+    (depth, K, TCO, masks, rgb), (n, h, w, tco_floats) = _posed_views(depth, K, TCO, masks, rgb)
     ox, oy, oz = (float(v) for v in origin)
     check(_lib.load().mp_tsdf_integrate(volume.data_ptr(), nx, ny, nz, color, ox, oy, oz, float(voxel), depth.data_ptr(), _ptr(masks), _ptr(rgb),
-                                        K.data_ptr(), TCO.data_ptr(), int(TCO.shape[1]) if n else 16, n, h, w, mu, float(z_min), int(bool(carve)),
+                                        K.data_ptr(), TCO.data_ptr(), tco_floats, n, h, w, _tsdf_mu(mu, voxel), float(z_min), int(bool(carve)),
                                         _stream()))
 
 
@@ -1246,17 +1269,7 @@ def tsdf_track(volume: torch.Tensor, origin: Sequence[float], voxel: float, dept
     for bit.  Frames are independent.  Nothing synchronises.  `partials`: a float64 device tensor of at least n * tsdf_track_groups(h,
     w) * 32 entries to be filled with the groups' records of the last iteration (for tests)."""
     nx, ny, nz, color = _tsdf_dims(volume)
-    depth = _dev_f32(depth)
-    if depth.dim() != 3:
-        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
-    n, h, w = (int(v) for v in depth.shape)
-    K, TCO = _dev_f32(K), _dev_f32(TCO)
-    if tuple(K.shape) != (n, 3, 3) or tuple(TCO.shape) != (n, 4, 4):
-        raise EngineError(f"K must be [{n},3,3] and TCO [{n},4,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
-    if masks is not None:
-        masks = _dev_bytes("masks", masks)
-        if tuple(masks.shape) != (n, h, w):
-            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
+    (depth, K, TCO, masks, _), (n, h, w, _) = _posed_views(depth, K, TCO, masks, None, poses_4x4=True)
     dev = volume.device
     out = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1271,12 +1284,11 @@ def tsdf_track(volume: torch.Tensor, origin: Sequence[float], voxel: float, dept
         partials = torch.empty(n, groups, TSDF_TRACK_RECORD, dtype=torch.float64, device=dev)
     elif not partials.is_cuda or partials.dtype != torch.float64 or not partials.is_contiguous():
         raise EngineError("tsdf_track: partials must be a contiguous float64 device tensor")
-    mu = float(np.float32(3.0) * np.float32(voxel)) if mu is None else float(mu)
     eps_trans = float(np.float32(1e-3) * np.float32(voxel)) if eps_trans is None else float(eps_trans)
     ox, oy, oz = (float(v) for v in origin)
     check(_lib.load().mp_tsdf_track(volume.data_ptr(), nx, ny, nz, color, ox, oy, oz, float(voxel), depth.data_ptr(), _ptr(masks), K.data_ptr(),
-                                    TCO.data_ptr(), n, h, w, mu, int(min_views), int(min_pixels), int(iters), float(eps_rot), eps_trans,
-                                    out.data_ptr(), status.data_ptr(), used.data_ptr(), rms.data_ptr(), partials.data_ptr(),
+                                    TCO.data_ptr(), n, h, w, _tsdf_mu(mu, voxel), int(min_views), int(min_pixels), int(iters), float(eps_rot),
+                                    eps_trans, out.data_ptr(), status.data_ptr(), used.data_ptr(), rms.data_ptr(), partials.data_ptr(),
                                     partials.numel() // TSDF_TRACK_RECORD, _stream()))
     return out, status, used, rms
 
@@ -1326,28 +1338,15 @@ def texture_bake(vertices: torch.Tensor, faces: torch.Tensor, depth: torch.Tenso
     faces = _mesh_faces(faces)
     size = int(size)
     _texture_block("texture_bake", int(faces.shape[0]), size)
-    depth = _dev_f32(depth)
-    if depth.dim() != 3:
-        raise EngineError(f"depth must be [n,h,w], got {tuple(depth.shape)}")
-    n, h, w = (int(v) for v in depth.shape)
-    K, TCO = _dev_f32(K).reshape(n, -1) if n else _dev_f32(K), _dev_f32(TCO).reshape(n, -1) if n else _dev_f32(TCO)
-    if n and (K.shape[1] != 9 or TCO.shape[1] not in (12, 16)):
-        raise EngineError(f"K must be [n,3,3] and TCO [n,4,4] or [n,3,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
-    if masks is not None:
-        masks = _dev_bytes("masks", masks)
-        if tuple(masks.shape) != (n, h, w):
-            raise EngineError(f"masks must be {(n, h, w)}, got {tuple(masks.shape)}")
     if rgb is None:
         raise EngineError("texture_bake: rgb is what the texture is made of")
-    rgb = _dev_bytes("rgb", rgb)
-    if tuple(rgb.shape) != (n, h, w, 3):
-        raise EngineError(f"rgb must be {(n, h, w, 3)}, got {tuple(rgb.shape)}")
+    (depth, K, TCO, masks, rgb), (n, h, w, tco_floats) = _posed_views(depth, K, TCO, masks, rgb)
     dev = vertices.device
     texels = torch.empty(size, size, 4, dtype=torch.uint8, device=dev)
     seen = torch.empty(size, size, dtype=torch.uint8, device=dev)
     ptr = (lambda t: t.data_ptr()) if n else (lambda t: None)   # noqa: E731
     check(_lib.load().mp_texture_bake(vertices.data_ptr() if vertices.shape[0] else None, int(vertices.shape[0]), faces.data_ptr(), int(faces.shape[0]),
-                                      _ptr(colors), ptr(depth), _ptr(masks) if n else None, ptr(rgb), ptr(K), ptr(TCO), int(TCO.shape[1]) if n else 16,
+                                      _ptr(colors), ptr(depth), _ptr(masks) if n else None, ptr(rgb), ptr(K), ptr(TCO), tco_floats,
                                       n, h, w, size, float(depth_tol), float(cos_min), float(z_min), int(bool(best_view)), texels.data_ptr(),
                                       seen.data_ptr(), _stream()))
     return texels, seen

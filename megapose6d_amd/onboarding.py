@@ -31,6 +31,39 @@ from . import mesh_cleanup, mesh_io
 from .object_dataset import RigidObject
 
 
+def _to_device(t, device) -> Optional[torch.Tensor]:
+    """`t` as a tensor on `device`; None stays None"""
+    return None if t is None else torch.as_tensor(t).to(device)
+
+
+def _check_views(who: str, depth, K, TCO=None, masks=None, rgb=None):
+    """The shapes of a view set: depth [n,h,w] with n >= 1, K [n,3,3] and, where given, TCO [n,4,4], masks [n,h,w], rgb [n,h,w,3] ->
+    (depth, K, TCO) as tensors.  A ValueError begins with `who`."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() != 3 or depth.shape[0] == 0:
+        raise ValueError(f"{who}: depth must be [n,h,w] with at least one view, got {tuple(depth.shape)}")
+    n, frame = depth.shape[0], tuple(depth.shape)
+    K, TCO = torch.as_tensor(K), None if TCO is None else torch.as_tensor(TCO)
+    for name, t, shape in (("K", K, (n, 3, 3)), ("TCO", TCO, (n, 4, 4)), ("masks", masks, frame), ("rgb", rgb, frame + (3,))):
+        if t is not None and tuple(torch.as_tensor(t).shape) != shape:
+            raise ValueError(f"{who}: {name} must be {shape}, got {tuple(torch.as_tensor(t).shape)}")
+    return depth, K, TCO
+
+
+def _frame_points(depth0: torch.Tensor, K0: torch.Tensor, mask0: Optional[torch.Tensor]) -> torch.Tensor:
+    """[m,3] float64: one frame's measured pixels (depth finite and > 0) inside the mask, back-projected through their centres into the
+    camera's frame"""
+    depth0 = torch.as_tensor(depth0).to(torch.float32)
+    K0 = torch.as_tensor(K0).to(depth0.device, torch.float64)
+    h, w = depth0.shape
+    keep = torch.isfinite(depth0) & (depth0 > 0)
+    if mask0 is not None:
+        keep = keep & (torch.as_tensor(mask0).to(depth0.device) != 0)
+    ys, xs = torch.meshgrid(torch.arange(h, device=depth0.device), torch.arange(w, device=depth0.device), indexing="ij")
+    z = depth0[keep].to(torch.float64)
+    return torch.stack([(xs[keep] + 0.5 - K0[0, 2]) / K0[0, 0] * z, (ys[keep] + 0.5 - K0[1, 2]) / K0[1, 1] * z, z], 1)
+
+
 class TsdfVolume:
     """A grid of nx x ny x nz nodes, node (i,j,k) at origin + voxel_size * (i,j,k) in the object's frame (metres), holding per node the
     sum of truncated signed distances and the number of views that saw it (and, with `color`, colour sums): calls of `integrate`
@@ -74,10 +107,8 @@ class TsdfVolume:
                   rgb: Optional[torch.Tensor] = None, carve: bool = True, z_min: float = 1e-3) -> "TsdfVolume":
         """depth [n,h,w] metres, K [n,3,3], TCO [n,4,4] object to camera, masks [n,h,w] (non-zero: the object), rgb [n,h,w,3] uint8.
         With masks and `carve`, pixels off the object mark the nodes on their rays as free space (the visual hull)."""
-        dev = self._volume.device
-        as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
-        eng.tsdf_integrate(self._volume, self.origin, self.voxel_size, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), as_dev(rgb),
-                           mu=self.mu, z_min=z_min, carve=carve)
+        views = (_to_device(t, self._volume.device) for t in (depth, K, TCO, masks, rgb))
+        eng.tsdf_integrate(self._volume, self.origin, self.voxel_size, *views, mu=self.mu, z_min=z_min, carve=carve)
         return self
 
     def extract(self, min_views: int = 1) -> Dict[str, np.ndarray]:
@@ -95,10 +126,9 @@ class TsdfVolume:
         """The poses of unposed depth frames against what the volume holds, each from its own starting pose TCO [n,4,4]
         (engine.tsdf_track, whose keywords pass through; the volume's truncation distance is given) -> (TCO [n,4,4], status [n], used
         [n], rms [n]) on the device.  Nothing synchronises."""
-        dev = self._volume.device
-        as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
         kw.setdefault("mu", self.mu)
-        return eng.tsdf_track(self._volume, self.origin, self.voxel_size, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), **kw)
+        views = (_to_device(t, self._volume.device) for t in (depth, K, TCO, masks))
+        return eng.tsdf_track(self._volume, self.origin, self.voxel_size, *views, **kw)
 
     def reset(self) -> None:
         self._volume.zero_()
@@ -114,18 +144,13 @@ def volume_for_views(depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, ma
     n, h, w = depth.shape
     if resolution < 2 * margin_voxels + 2 or resolution > eng.TSDF_MAX_DIM or margin_voxels < 0:
         raise ValueError(f"resolution {resolution} must be at least 2 * margin_voxels + 2 and at most {eng.TSDF_MAX_DIM}")
-    keep = torch.isfinite(depth) & (depth > 0)
-    if masks is not None:
-        keep = keep & (torch.as_tensor(masks).to(depth.device) != 0)
+    masks = _to_device(masks, depth.device)
     lo = torch.full((3,), float("inf"), dtype=torch.float64, device=depth.device)
     hi = -lo
-    ys, xs = torch.meshgrid(torch.arange(h, device=depth.device), torch.arange(w, device=depth.device), indexing="ij")
     for v in range(n):
-        sel = keep[v]
-        if not bool(sel.any()):
+        pc = _frame_points(depth[v], K[v], None if masks is None else masks[v])
+        if pc.shape[0] == 0:
             continue
-        z = depth[v][sel].to(torch.float64)
-        pc = torch.stack([(xs[sel] + 0.5 - K[v, 0, 2]) / K[v, 0, 0] * z, (ys[sel] + 0.5 - K[v, 1, 2]) / K[v, 1, 1] * z, z], 1)
         po = (pc - TCO[v, :3, 3]) @ TCO[v, :3, :3]          # R^T (pc - t)
         lo, hi = torch.minimum(lo, po.min(0).values), torch.maximum(hi, po.max(0).values)
     if not bool(torch.isfinite(lo).all() and torch.isfinite(hi).all()):
@@ -194,9 +219,8 @@ def bake_texture(mesh, depth: torch.Tensor, K: torch.Tensor, TCO: torch.Tensor, 
         depth_tol = mean_edge_length(v, f)
     if not (np.isfinite(depth_tol) and depth_tol > 0):
         raise ValueError(f"bake_texture: depth_tol {depth_tol} must be finite and positive (a mesh without a usable edge has no default)")
-    as_dev = lambda t: None if t is None else torch.as_tensor(t).to(dev)   # noqa: E731
-    texels, seen = eng.texture_bake(v, f, as_dev(depth), as_dev(K), as_dev(TCO), as_dev(masks), as_dev(rgb), size, colors=c,
-                                    depth_tol=float(depth_tol), cos_min=cos_min, best_view=best_view)
+    views = (_to_device(t, dev) for t in (depth, K, TCO, masks, rgb))
+    texels, seen = eng.texture_bake(v, f, *views, size, colors=c, depth_tol=float(depth_tol), cos_min=cos_min, best_view=best_view)
     chart = texels[..., 3] != 0
     coverage = float(((seen != 0) & chart).sum() / chart.sum().clamp(min=1))
     out = dict(mesh)
@@ -220,18 +244,9 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
     argument.  Needs rgb.  None (the default): every byte written is what it was without the argument."""
     if texture_size is not None and rgb is None:
         raise ValueError(f"reconstruct_object({label!r}): texture_size {texture_size} needs rgb: a texture is baked from the views' colour frames")
-    depth = torch.as_tensor(depth)
-    if depth.dim() != 3 or depth.shape[0] == 0:
-        raise ValueError(f"reconstruct_object({label!r}): depth must be [n,h,w] with at least one view, got {tuple(depth.shape)}")
-    n = depth.shape[0]
-    K, TCO = torch.as_tensor(K), torch.as_tensor(TCO)
-    if tuple(K.shape) != (n, 3, 3) or tuple(TCO.shape) != (n, 4, 4):
-        raise ValueError(f"reconstruct_object({label!r}): K must be [{n},3,3] and TCO [{n},4,4], got {tuple(K.shape)} and {tuple(TCO.shape)}")
+    depth, K, TCO = _check_views(f"reconstruct_object({label!r})", depth, K, TCO, masks, rgb)
     if not bool(torch.isfinite(K).all() and torch.isfinite(TCO).all()):
         raise ValueError(f"reconstruct_object({label!r}): K or TCO holds a value that is not finite")
-    for name, t, shape in (("masks", masks, tuple(depth.shape)), ("rgb", rgb, tuple(depth.shape) + (3,))):
-        if t is not None and tuple(torch.as_tensor(t).shape) != shape:
-            raise ValueError(f"reconstruct_object({label!r}): {name} must be {shape}, got {tuple(torch.as_tensor(t).shape)}")
     try:
         origin, voxel, dims = volume_for_views(depth, K, TCO, masks, resolution=resolution)
     except ValueError as e:
@@ -268,17 +283,12 @@ def reconstruct_object(label: str, depth: torch.Tensor, K: torch.Tensor, TCO: to
     return RigidObject(label, path, mesh_units="m")
 
 
-def _first_view_points(depth0: torch.Tensor, K0: torch.Tensor, mask0: Optional[torch.Tensor]) -> torch.Tensor:
-    """[m,3] float64: frame 0's measured pixels inside the mask, back-projected through their centres into the camera's frame"""
-    depth0 = torch.as_tensor(depth0).to(torch.float32)
-    K0 = torch.as_tensor(K0).to(depth0.device, torch.float64)
-    h, w = depth0.shape
-    keep = torch.isfinite(depth0) & (depth0 > 0)
-    if mask0 is not None:
-        keep = keep & (torch.as_tensor(mask0).to(depth0.device) != 0)
-    ys, xs = torch.meshgrid(torch.arange(h, device=depth0.device), torch.arange(w, device=depth0.device), indexing="ij")
-    z = depth0[keep].to(torch.float64)
-    return torch.stack([(xs[keep] + 0.5 - K0[0, 2]) / K0[0, 0] * z, (ys[keep] + 0.5 - K0[1, 2]) / K0[1, 1] * z, z], 1)
+def _first_view_points(depth0: torch.Tensor, K0: torch.Tensor, mask0: Optional[torch.Tensor], who: str = "_first_view_points") -> torch.Tensor:
+    """[m,3] float64: `_frame_points` of frame 0, which must hold a pixel of the object.  A ValueError begins with `who`."""
+    pts = _frame_points(depth0, K0, mask0)
+    if pts.shape[0] == 0:
+        raise ValueError(f"{who}: frame 0 holds no measured pixel of the object (depth finite and > 0 inside the mask)")
+    return pts
 
 
 def volume_for_first_view(depth0: torch.Tensor, K0: torch.Tensor, TCO0: torch.Tensor, mask0: Optional[torch.Tensor], resolution: int = 128,
@@ -290,9 +300,7 @@ def volume_for_first_view(depth0: torch.Tensor, K0: torch.Tensor, TCO0: torch.Te
     1.5 L behind its nearest visible point (a long object seen end-on) leaves that cube: give `extent`.  Plain torch, one read-back."""
     if not (eng.TSDF_MIN_DIM <= int(resolution) <= eng.TSDF_MAX_DIM):
         raise ValueError(f"resolution {resolution} must be {eng.TSDF_MIN_DIM} .. {eng.TSDF_MAX_DIM}")
-    pts = _first_view_points(depth0, K0, mask0)
-    if pts.shape[0] == 0:
-        raise ValueError("volume_for_first_view: frame 0 holds no measured pixel of the object (depth finite and > 0 inside the mask)")
+    pts = _first_view_points(depth0, K0, mask0, who="volume_for_first_view")
     T = torch.as_tensor(TCO0).to(pts.device, torch.float64)
     po = (pts - T[:3, 3]) @ T[:3, :3]                        # R^T (pc - t)
     box = torch.stack([po.min(0).values, po.max(0).values, T[2, :3]]).cpu().numpy()          # the camera's z axis in the object's frame
@@ -321,21 +329,12 @@ def track_views(depth: torch.Tensor, K: torch.Tensor, masks: Optional[torch.Tens
     frames must overlap within the truncation band (trunc_voxels voxels): there is no motion model beyond "hold the last pose".
     One read-back of (status, used, rms) per frame.  info: `status`, `used`, `rms` as numpy arrays per frame (frame 0: 1, 0, 0), the
     `volume` (a TsdfVolume) as the last frame left it."""
-    depth = torch.as_tensor(depth)
-    if depth.dim() != 3 or depth.shape[0] == 0:
-        raise ValueError(f"track_views: depth must be [n,h,w] with at least one frame, got {tuple(depth.shape)}")
+    depth, K, _ = _check_views("track_views", depth, K, masks=masks)
     n = depth.shape[0]
-    K = torch.as_tensor(K)
-    if tuple(K.shape) != (n, 3, 3):
-        raise ValueError(f"track_views: K must be [{n},3,3], got {tuple(K.shape)}")
-    if masks is not None and tuple(torch.as_tensor(masks).shape) != tuple(depth.shape):
-        raise ValueError(f"track_views: masks must be {tuple(depth.shape)}, got {tuple(torch.as_tensor(masks).shape)}")
     depth, K = depth.to(device, torch.float32), K.to(device, torch.float32)
-    masks = None if masks is None else torch.as_tensor(masks).to(device)
+    masks = _to_device(masks, device)
     if TCO_first is None:
-        pts = _first_view_points(depth[0], K[0], None if masks is None else masks[0])
-        if pts.shape[0] == 0:
-            raise ValueError("track_views: frame 0 holds no measured pixel of the object (depth finite and > 0 inside the mask)")
+        pts = _first_view_points(depth[0], K[0], None if masks is None else masks[0], who="track_views")
         first = torch.eye(4, dtype=torch.float64, device=depth.device)
         first[:3, 3] = pts.mean(0)
     else:

@@ -123,7 +123,7 @@ def test_uvs_equal_the_emulation_with_canaries():
 
 
 def test_more_views_than_a_staging_round():
-    """40 views against the kernel's 32 a round (csrc/texture_bake.hip: kBakeViewChunk): a partial last round with a non-finite K in it;
+    """40 views against the kernel's 32 a round (csrc/tsdf_views.h: kViewChunk): a partial last round with a non-finite K in it;
     the views past the first round contribute, so a round dropped or read twice shows"""
     v, f, c, views, S = _case("many")
     n = len(views["depth"])

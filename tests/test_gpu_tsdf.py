@@ -91,8 +91,8 @@ def test_entry_points_equal_the_emulation_split_and_unsplit(name):
 
 
 def test_the_second_rounds_of_the_view_and_scan_loops_are_what_is_tested():
-    """the sizes that make `many` and `tiny` worth their names, stated against the kernels' constants (csrc/tsdf.hip: kTsdfViewChunk = 32,
-    kTsdfBlock = 256): a partial last round of views, a non-finite view in it, vertices owned by nodes past the first round of the scan"""
+    """the sizes that make `many` and `tiny` worth their names, stated against the kernels' constants (csrc/tsdf_views.h: kViewChunk = 32,
+    csrc/tsdf.hip: kTsdfBlock = 256): a partial last round of views, a non-finite view in it, vertices owned by nodes past the first round of the scan"""
     g, views = st.fixture("many")
     n, nodes = len(views["depth"]), int(np.prod(g.dims))
     assert 32 < n < 64 and n % 32 != 0 and not np.isfinite(views["K"][35]).all() and -(-nodes // 256) > 256

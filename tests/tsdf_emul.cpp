@@ -13,23 +13,6 @@ using namespace mp;
 
 namespace {
 
-struct Vol {
-  float* sum;
-  int32_t* count;
-  float* c[3];
-  int32_t* c_count;
-};
-
-Vol planes_of(void* volume, size_t N, int color) {
-  float* f = (float*)volume;
-  Vol v;
-  v.sum = f;
-  v.count = (int32_t*)(f + N);
-  for (int k = 0; k < 3; ++k) v.c[k] = color ? f + (2 + k) * N : nullptr;
-  v.c_count = color ? (int32_t*)(f + 5 * N) : nullptr;
-  return v;
-}
-
 bool grid_args_ok(int nx, int ny, int nz, float ox, float oy, float oz, float voxel) {
   const float origin[3] = {ox, oy, oz};
   return tsdf::dims_ok(nx, ny, nz) && tsdf::grid_ok(origin, voxel);
@@ -43,10 +26,10 @@ struct Surface {
 };
 
 template <class FV, class FT>
-void walk_surface(const Vol& v, int nx, int ny, int nz, int min_views, Surface* s, FV on_vertex, FT on_triangle) {
+void walk_surface(const tsdf::Volume& v, int min_views, Surface* s, FV on_vertex, FT on_triangle) {
   const tsdf::Tables& tb = tsdf::tables();
-  const size_t N = (size_t)nx * ny * nz;
-  const int nxy = nx * ny;
+  const int nx = v.nx, ny = v.ny, nz = v.nz, nxy = nx * ny;
+  const size_t N = (size_t)v.N;
   s->flags.assign(N, 0);
   s->complete.assign(N, 0);
   s->vid.assign(N * tsdf::kEdgeKinds, -1);
@@ -56,7 +39,7 @@ void walk_surface(const Vol& v, int nx, int ny, int nz, int min_views, Surface* 
     for (int j = 0; j + 1 < ny; ++j)
       for (int i = 0; i + 1 < nx; ++i) {
         bool all = true;
-        for (int c = 0; c < 8; ++c) all = all && (s->flags[at(i + (c & 1), j + ((c >> 1) & 1), k + ((c >> 2) & 1))] & tsdf::kObserved);
+        for (int c = 0; c < 8; ++c) all = all && (s->flags[tsdf::corner_node(at(i, j, k), c, nx, nxy)] & tsdf::kObserved);
         s->complete[at(i, j, k)] = all;
       }
   for (int k = 0; k < nz; ++k)
@@ -88,7 +71,7 @@ void walk_surface(const Vol& v, int nx, int ny, int nz, int min_views, Surface* 
         if (!s->complete[g]) continue;
         int inside8 = 0;
         for (int c = 0; c < 8; ++c)
-          inside8 |= ((s->flags[g + (c & 1) + ((c >> 1) & 1) * nx + (size_t)((c >> 2) & 1) * nxy] & tsdf::kInside) ? 1 : 0) << c;
+          inside8 |= ((s->flags[tsdf::corner_node(g, c, nx, nxy)] & tsdf::kInside) ? 1 : 0) << c;
         for (int T = 0; T < tsdf::kTets; ++T) {
           const int m = tsdf::tet_case(tb, T, inside8);
           for (int tri = 0; tri < tb.count[m]; ++tri) {
@@ -96,7 +79,7 @@ void walk_surface(const Vol& v, int nx, int ny, int nz, int min_views, Surface* 
             for (int c = 0; c < 3; ++c) {
               int code, kind;
               tsdf::tri_edge(tb, T, m, tri, c, &code, &kind);
-              const size_t o = g + (code & 1) + ((code >> 1) & 1) * nx + (size_t)((code >> 2) & 1) * nxy;
+              const size_t o = tsdf::corner_node(g, code, nx, nxy);
               idx[c] = s->vid[o * tsdf::kEdgeKinds + kind];
             }
             on_triangle(s->n_triangles, idx);
@@ -116,8 +99,8 @@ extern "C" int tsdf_integrate_emul(void* volume, int nx, int ny, int nz, int col
   if (n < 0 || (tco_floats != 12 && tco_floats != 16)) return 1;
   if (n == 0) return 0;
   if (!tsdf::frame_ok(h, w) || !volume || !depth || !K || !TCO) return 1;
-  const size_t N = (size_t)nx * ny * nz, hw = (size_t)h * w;
-  const Vol v = planes_of(volume, N, color);
+  const size_t hw = (size_t)h * w;
+  const tsdf::Volume v = tsdf::volume_of(volume, nx, ny, nz, color, ox, oy, oz, voxel);
   for (int k = 0; k < nz; ++k)
     for (int j = 0; j < ny; ++j)
       for (int i = 0; i < nx; ++i) {
@@ -150,9 +133,9 @@ extern "C" int tsdf_integrate_emul(void* volume, int nx, int ny, int nz, int col
 
 extern "C" int tsdf_extract_count_emul(const void* volume, int nx, int ny, int nz, int color, int min_views, int32_t* totals) {
   if (!tsdf::dims_ok(nx, ny, nz) || min_views < 1 || !volume || !totals) return 1;
-  const Vol v = planes_of(const_cast<void*>(volume), (size_t)nx * ny * nz, color);
+  const tsdf::Volume v = tsdf::volume_of(const_cast<void*>(volume), nx, ny, nz, color, 0.f, 0.f, 0.f, 1.f);
   Surface s;
-  walk_surface(v, nx, ny, nz, min_views, &s, [](int32_t, int, int, int, int, int, int, size_t, size_t) {}, [](int32_t, const int32_t*) {});
+  walk_surface(v, min_views, &s, [](int32_t, int, int, int, int, int, int, size_t, size_t) {}, [](int32_t, const int32_t*) {});
   totals[0] = s.n_vertices;
   totals[1] = s.n_triangles;
   return 0;
@@ -165,11 +148,11 @@ extern "C" int tsdf_extract_emul(const void* volume, int nx, int ny, int nz, int
   if (n_vertices < 0 || n_triangles < 0 || cap_vertices < n_vertices || cap_triangles < n_triangles) return 1;
   if (n_vertices == 0 && n_triangles == 0) return 0;
   if (!volume || (n_vertices && (!vertices || !colors)) || (n_triangles && !faces)) return 1;
-  const Vol v = planes_of(const_cast<void*>(volume), (size_t)nx * ny * nz, color);
+  const tsdf::Volume v = tsdf::volume_of(const_cast<void*>(volume), nx, ny, nz, color, ox, oy, oz, voxel);
   const float org[3] = {ox, oy, oz};
   Surface s;
   walk_surface(
-      v, nx, ny, nz, min_views, &s,
+      v, min_views, &s,
       [&](int32_t r, int i, int j, int k, int dx, int dy, int dz, size_t a, size_t b) {
         if (r >= n_vertices) return;
         const int ia[3] = {i, j, k}, ib[3] = {i + dx, j + dy, k + dz};

@@ -13,20 +13,6 @@ using namespace mp;
 
 namespace {
 
-tsdf::TrackVolume volume_of(const void* volume, int nx, int ny, int nz, float ox, float oy, float oz, float voxel) {
-  tsdf::TrackVolume v;
-  v.sum = (const float*)volume;
-  v.count = (const int32_t*)volume + (size_t)nx * ny * nz;
-  v.nx = nx;
-  v.ny = ny;
-  v.nz = nz;
-  v.ox = ox;
-  v.oy = oy;
-  v.oz = oz;
-  v.voxel = voxel;
-  return v;
-}
-
 // the record of group G of one frame under the loaded view
 void group_record(const tsdf::TrackVolume& vol, const float* depth, const uint8_t* mask, const float* view, int h, int w, float mu, int min_views, int G,
                   double* record) {
@@ -83,7 +69,7 @@ extern "C" int tsdf_track_emul(const void* volume, int nx, int ny, int nz, int c
   const int groups = tsdf::track_groups(h, w);
   if (groups == 0 || !volume || !depth || !K || !TCO_in || !TCO_out || !status || !used || !rms || !partials) return 1;
   if (TCO_in == TCO_out || partials_capacity < (long long)n * groups) return 1;
-  const tsdf::TrackVolume vol = volume_of(volume, nx, ny, nz, ox, oy, oz, voxel);
+  const tsdf::TrackVolume vol = tsdf::volume_of<const float, const int32_t>(volume, nx, ny, nz, 0, ox, oy, oz, voxel);
   const size_t hw = (size_t)h * w;
   for (int v = 0; v < n; ++v) {
     const float* Tin = TCO_in + (size_t)v * 16;
@@ -123,7 +109,7 @@ extern "C" int tsdf_track_rows_emul(const void* volume, int nx, int ny, int nz, 
                                     float* rows) {
   if (!track_args_ok(nx, ny, nz, ox, oy, oz, voxel, mu, min_views, 1, 1, 0.f, 0.f) || !tsdf::frame_ok(h, w)) return 1;
   if (!volume || !depth || !K || !TCO || !used_out || !rows) return 1;
-  const tsdf::TrackVolume vol = volume_of(volume, nx, ny, nz, ox, oy, oz, voxel);
+  const tsdf::TrackVolume vol = tsdf::volume_of<const float, const int32_t>(volume, nx, ny, nz, 0, ox, oy, oz, voxel);
   float view[tsdf::kViewFloats];
   if (!tsdf::load_view(K, TCO, view)) return 2;
   for (int y = 0; y < h; ++y)
