@@ -23,6 +23,8 @@
 //                     contiguous pixel records (one launch fills the CNN input with full-line writes).
 //   (3) raster_classify + raster_tiles_light (compacted launch form): the (item, tile) pairs no view reaches leave (2) at once and are
 //                     written, background + crop, by a lighter kernel through the same TileWriter (raster_tile_io.h).
+//   (4) packed launch form of (2) (MP_RASTER_HEAVY_LIST = waves per workgroup): raster_classify also packs the reached pairs into a list,
+//                     and wave j of raster_tiles takes pair j of it -- no wave of the grid's live part is dead, a workgroup past the count leaves.
 // The mesh database and the workspace layout live in raster_db.hip (private interface: raster_bin.h).
 // Roofline: HBM-bound on the output writes ((3+3[+1])*4*h*w bytes per view + the mesh once per view).
 #include <cmath>
@@ -55,6 +57,12 @@ typedef rc::Lights LightsDev;
 constexpr int BIN_THREADS = 512;
 constexpr int LARGE_TILES = 16;    // a piece whose bbox touches more tiles is not replicated into tile lists
 constexpr int TILE_WAVES = 4;      // tiles (waves) per workgroup of raster_tiles: a 32 x 8 pixel strip
+constexpr int HEAVY_LIST_DEFAULT = 1;   // MP_RASTER_HEAVY_LIST when unset: waves per workgroup of the packed launch form, 0 = strips of TILE_WAVES.
+                                        // Measured, all raster_tiles/xrec launches of the config-2 step (refiner + coarse + scoring;
+                                        // profiles/raster_heavy_list_*): live waves per SIMD 2.19 (strips) -> 2.32 (W = 4) / 2.70 (2) / 2.85 (1) of 3;
+                                        // 5.20 (parent) -> 4.95 / 4.40 / 4.23 ms per launch: a wave placed on its own refills every freed slot, a
+                                        // workgroup of four waits for four slots and 40 KB of LDS at once.  The default holds for the instances without
+                                        // scratch in the packed form (lean, 4x MSAA: the pose pipeline's); the others keep the strips unless the switch is set
 constexpr int MAX_RUN = 32;        // channels per pixel one launch may stage
 constexpr int HDR_INTS = RASTER_BIN_HDR_INTS;   // per-view header (raster_bin.h, with the per-view workspace layout BinLayout)
 
@@ -432,14 +440,49 @@ __device__ __forceinline__ ViewHdr read_view_hdr(const int* __restrict__ ws, Bin
   return v;
 }
 
-// OUT, DEPTHREC: the output form (raster_tile_io.h)
-template <int NS, int OUT = OUT_F32, bool FULL = true, bool DEPTHREC = false>
-__global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu(MP_RASTER_WAVES, MP_RASTER_WAVES))) void raster_tiles(
+// Which (item, tile) does this wave of raster_tiles handle?  false = none: the wave leaves.  W = waves per workgroup.
+//   strip forms (LIST = false): a workgroup is W x-adjacent tiles of one item, for every pair of the launch.  Direct form (job_flags NULL): every
+//     pair is handled.  Compacted form (round 5): raster_classify marked the (item, tile) pairs that no view reaches -- 65 % of a pose-pipeline
+//     launch -- and raster_tiles_light writes those (background + crop).  A wave of such a pair leaves here, after one byte load, instead of
+//     waiting for four list headers and running the crop under this kernel's register budget.
+//   packed form (LIST = true): wave j of the grid takes reached pair j, read from the far end of the pair list raster_classify filled
+//     (heavy = the launch's counters: heavy[1] = the reached count, the list of n_pairs ints starts at heavy + 4).  The grid is sized for the worst case: a workgroup
+//     beyond the count leaves as a whole, and no wave of the others is dead -- a strip at the object's silhouette no longer holds slots and
+//     LDS for tiles nobody renders.  The pair is made wave-uniform (scalar), as the item is in the strip forms.
+// Which kernel and which wave write a tile does not enter the arithmetic: the pixels are the same bit for bit
+// (test_raster_compacted_launch_equals_the_direct_form, tests/test_gpu_raster_heavy_list.py).
+template <int W, bool LIST>
+__device__ __forceinline__ bool wave_pair(const BinLayout& lay, int wave, const unsigned char* __restrict__ job_flags, const int* __restrict__ heavy,
+                                          int n_pairs, int& item, int& tx, int& ty) {
+  if constexpr (LIST) {
+    const int j = (int)blockIdx.x * W + wave;
+    if (j >= heavy[1]) return false;
+    const int idx = __builtin_amdgcn_readfirstlane(heavy[4 + n_pairs - 1 - j]);
+    item = idx / lay.n_tiles;
+    const int tile = idx - item * lay.n_tiles;
+    ty = tile / lay.tiles_x;
+    tx = tile - ty * lay.tiles_x;
+    return true;
+  } else {
+    const int groups_x = (lay.tiles_x + W - 1) / W;
+    int b = blockIdx.x;
+    const int gx = b % groups_x; b /= groups_x;
+    ty = b % lay.tiles_y;
+    item = b / lay.tiles_y;
+    tx = gx * W + wave;
+    if (tx >= lay.tiles_x) return false;   // (no workgroup-level barrier in the kernel: waves are independent)
+    return !(job_flags && job_flags[(size_t)item * lay.n_tiles + ty * lay.tiles_x + tx] == 0);
+  }
+}
+
+// OUT, DEPTHREC: the output form (raster_tile_io.h); W, LIST: the launch form (wave_pair)
+template <int NS, int OUT = OUT_F32, bool FULL = true, bool DEPTHREC = false, int W = TILE_WAVES, bool LIST = false>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(MP_RASTER_WAVES, MP_RASTER_WAVES))) void raster_tiles(
     const MeshDev* __restrict__ meshes, const TexDev* __restrict__ texs, const int32_t* __restrict__ mesh_ids, const float* __restrict__ TCO,
     const float* __restrict__ K, const int* __restrict__ ws, BinLayout lay, int h, int w, uint32_t flags, LightsDev lights,
     float* __restrict__ out, long long stride_v, int views_per_item, int n_items, long long stride_view, long long stride_y,
     long long stride_x, int c_rgb, int c_normals, int c_depth, int c_lo, int run, uint32_t run_mask, CropArgs crop, uint32_t xrec_mask,
-    const float* __restrict__ depth_tcr, int depth_mode, const unsigned char* __restrict__ job_flags) {
+    const float* __restrict__ depth_tcr, int depth_mode, const unsigned char* __restrict__ job_flags, const int* __restrict__ heavy) {
   // LDS per wave: zb [64 * NS] u64 (z-buffer, later the shading results) | tasks [64 * NS] u32 | stage [64][run] floats
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;   // (a readfirstlane'd wave index makes the LDS bases scalar -- and the kernel 4 % slower, measured)
@@ -453,20 +496,10 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
   unsigned* tasks = (unsigned*)(mine + (size_t)64 * NS * sizeof(unsigned long long));
   TileWriter<OUT, DEPTHREC> tw((float*)(mine + ZT_BYTES), lane, c_lo, run, stride_x, xrec_mask, crop.C, depth_mode);
   tw.clear_record();   // (a stem record is zeroed once: every view's channels are written again below, the padding slots never)
-  const int groups_x = (lay.tiles_x + TILE_WAVES - 1) / TILE_WAVES;
-  int b = blockIdx.x;
-  const int gx = b % groups_x; b /= groups_x;
-  const int ty = b % lay.tiles_y;
-  const int item = b / lay.tiles_y;
-  const int tx = gx * TILE_WAVES + wave;
-  if (tx >= lay.tiles_x) return;   // (no workgroup-level barrier below: waves are independent)
+  int item, tx, ty;
+  if (!wave_pair<W, LIST>(lay, wave, job_flags, heavy, n_items * lay.n_tiles, item, tx, ty)) return;
   const int tile_x0 = tx * TILE, tile_y0 = ty * TILE;
   const int tile = ty * lay.tiles_x + tx;
-  // Compacted launch form (round 5): raster_classify marked the (item, tile) pairs that no view reaches -- 65 % of a pose-pipeline launch --
-  // and raster_tiles_light writes those (background + crop).  A wave of such a pair leaves here, after one byte load, instead of waiting
-  // for four list headers and running the crop under this kernel's register budget.  Which kernel writes a tile does not enter the
-  // arithmetic: the pixels are the same bit for bit (test_raster_compacted_launch_equals_the_direct_form).
-  if (job_flags && job_flags[(size_t)item * lay.n_tiles + tile] == 0) return;
   const int px = tile_x0 + (lane & 7), py = tile_y0 + (lane >> 3);
   const bool do_norm = (flags & MP_RASTER_NORMALS) && c_normals >= 0;
   const bool do_depth = (flags & MP_RASTER_DEPTH) && c_depth >= 0;
@@ -703,9 +736,15 @@ __global__ __launch_bounds__(64 * TILE_WAVES) __attribute__((amdgpu_waves_per_eu
 
 // ---- compacted launch form: classification of the (item, tile) pairs and the kernel for the pairs no view reaches --------------------------
 // one thread per pair: heavy iff some view of the item has a piece (binned or large) in the tile, or a view's lists overflowed;
-// flags[pair] = 1 | 0, the light pairs are appended to a list (order arbitrary: every job is independent)
+// flags[pair] = 1 | 0.  The two kinds partition the pairs, so one array of n_items * n_tiles ints holds both lists: the light pairs are
+// appended from its start (counters[0]; order arbitrary: every job is independent), the heavy ("reached") pairs from its far end
+// (counters[1]; entry k sits at pair_list[total - 1 - k]).  A block packs the heavy ones of its 256 consecutive pairs in pair order behind one
+// atomicAdd, so x-neighbouring tiles stay neighbours in the list (they share list records and crop lines in L2); the order of the blocks
+// varies from run to run and only decides which wave renders which tile.
 __global__ __launch_bounds__(256) void raster_classify(const unsigned char* __restrict__ view_flags, BinLayout lay, int views_per_item, int n_items,
-                                                       unsigned char* __restrict__ flags, int* __restrict__ counters, int* __restrict__ light_list) {
+                                                       unsigned char* __restrict__ flags, int* __restrict__ counters, int* __restrict__ pair_list) {
+  __shared__ int heavy_in_wave[4], heavy_base;
+  int* const light_list = pair_list;
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long total = (long)n_items * lay.n_tiles;
   const bool valid = idx < total;
@@ -721,6 +760,20 @@ __global__ __launch_bounds__(256) void raster_classify(const unsigned char* __re
   if (lane == 0 && ml) base = atomicAdd(counters, __popcll(ml));
   base = __builtin_amdgcn_readfirstlane(base);
   if (valid && !heavy) light_list[base + __popcll(ml & ((1ull << lane) - 1ull))] = (int)idx;
+  const int wave = threadIdx.x >> 6;
+  const unsigned long long mh = __ballot(valid && heavy);
+  if (lane == 0) heavy_in_wave[wave] = __popcll(mh);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n = heavy_in_wave[0] + heavy_in_wave[1] + heavy_in_wave[2] + heavy_in_wave[3];
+    heavy_base = n ? atomicAdd(counters + 1, n) : 0;
+  }
+  __syncthreads();
+  if (valid && heavy) {
+    int k = heavy_base + __popcll(mh & ((1ull << lane) - 1ull));
+    for (int v = 0; v < wave; ++v) k += heavy_in_wave[v];
+    pair_list[total - 1 - k] = (int)idx;
+  }
 }
 
 // A light job: the tile of an item that no view reaches = background in every view channel + the observation crop, staged and stored by
@@ -845,6 +898,16 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   unsigned char* const view_flags = job_flags + (((size_t)n_views * lay.n_tiles + 15) & ~(size_t)15);
   const char* compact_env = getenv("MP_RASTER_COMPACT");
   const bool compact = !(compact_env && compact_env[0] && atoi(compact_env) == 0);   // (the ONE place the switch is parsed: "0" / "00" = direct form)
+  // packed launch form of raster_tiles (compacted form only): MP_RASTER_HEAVY_LIST = waves per workgroup, 0 = the strips of TILE_WAVES tiles
+  const char* heavy_env = getenv("MP_RASTER_HEAVY_LIST");
+  // (exactly one of the characters 0 1 2 4, anything else is refused; the direct form has no list and ignores a valid value).  Unset: HEAVY_LIST_DEFAULT where the packed
+  // instance has no scratch -- lean (no texture, no point light) at 4x MSAA -- and the strips elsewhere (unmeasured there; the packed instances
+  // at one sample per pixel and the textured ones carry 32 - 144 bytes of scratch per lane)
+  const bool heavy_set = heavy_env && heavy_env[0];
+  MP_REQUIRE(!heavy_set || (strchr("0124", heavy_env[0]) && heavy_env[1] == 0), "mp_raster_render: MP_RASTER_HEAVY_LIST must be 0, 1, 2 or 4 (got '%s')",
+             heavy_env);
+  const bool packed_clean = ns == 4 && !(db->any_texture || L.n_point > 0);
+  const int heavy_w = !compact ? 0 : heavy_set ? heavy_env[0] - '0' : packed_clean ? HEAVY_LIST_DEFAULT : 0;
   note_launch(d_ws, compact, n_views, h, w);
   const bool do_norm = (flags & MP_RASTER_NORMALS) && c_normals >= 0, do_depth = (flags & MP_RASTER_DEPTH) && c_depth >= 0;
   // channel run [c_lo, c_hi) one pixel record of this launch spans, and which of its channels are written
@@ -876,7 +939,7 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   }
   const int groups_x = ceil_div(lay.tiles_x, TILE_WAVES);
   const long long n_wg = (long long)n_items * lay.tiles_y * groups_x;
-  MP_REQUIRE(n_wg < (1LL << 31), "mp_raster_render: grid too large");
+  MP_REQUIRE(n_wg < (1LL << 31) && (long long)n_items * lay.n_tiles < (1LL << 31) - 4,"mp_raster_render: grid too large");
   const int n_ch = (c_rgb >= 0 ? 3 : 0) + (do_norm ? 3 : 0) + (do_depth ? 1 : 0);
   // algorithmic bytes: output channels written once + the mesh (32 B/vertex, 12 B/triangle) read once per view
   // (+ the fused crop role: C output channels written + at most the same-sized source window read per item)
@@ -901,7 +964,7 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   // LDS staging per pixel, in floats: the channel run -- or, for stem records, the record itself if that is longer (a 6-channel model, 3 crop
   // + 3 render channels, has a 16-element = 32-byte record but a run of only 6 floats: the record's zero padding is part of what is staged)
   const int run_lds = xrec ? std::max(run, ((int)stride_x + 1) / 2) : run;
-  const size_t lds = (size_t)TILE_WAVES * (tiles_zt_bytes(ns) + (((size_t)64 * run_lds * sizeof(float) + 15) & ~(size_t)15) + HDR_LDS_BYTES);
+  const size_t lds_wave = tiles_zt_bytes(ns) + (((size_t)64 * run_lds * sizeof(float) + 15) & ~(size_t)15) + HDR_LDS_BYTES;
   const double out_es = f16 ? 2.0 : 4.0;   // bytes per output element
   const double alg_bytes = xrec ? (double)n_views * (32.0 * db->max_verts + 12.0 * db->max_faces) + (double)n_items * (2.0 * stride_x + 4.0 * crop.C) * h * w :
                            (double)n_views * ((double)n_ch * out_es * h * w + 32.0 * db->max_verts + 12.0 * db->max_faces) +
@@ -917,14 +980,23 @@ static int raster_render_impl(const mp_mesh_db* db, const int32_t* d_mesh_ids, c
   }
   {
     ProfScope prof(f16 ? "raster_tiles/f16" : xrec ? "raster_tiles/xrec" : "raster_tiles", 0.0, alg_bytes, s);
+    // one launch statement for the strip forms (W = TILE_WAVES) and the packed forms: the grid of a packed form covers every pair, W per workgroup
+    auto launch = [&](auto ns4, auto full_c, auto out_c, auto depthrec_c, auto w_c, auto list_c) {
+      constexpr int Wv = w_c.value;
+      const long long grid = list_c.value ? ((long long)n_items * lay.n_tiles + Wv - 1) / Wv : n_wg;
+      hipLaunchKernelGGL((raster_tiles<ns4.value ? 4 : 1, out_c.value, full_c.value, depthrec_c.value, Wv, list_c.value>), dim3((unsigned)grid),
+                         dim3(64 * Wv), (size_t)Wv * lds_wave, s, db->d_meshes, db->d_texs, d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L,
+                         d_out, (long long)stride_v, views_per_item, n_items, (long long)stride_view, (long long)stride_y, (long long)stride_x,
+                         c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop, f32_mask, d_tcr, depth_mode,
+                         compact ? job_flags : (const unsigned char*)nullptr, (const int*)counters);
+    };
     with_bool(ns == 4, [&](auto ns4) {
       with_bool(full, [&](auto full_c) {
         with_out_form(f16, xrec, depthrec, [&](auto out_c, auto depthrec_c) {
-          hipLaunchKernelGGL((raster_tiles<ns4.value ? 4 : 1, out_c.value, full_c.value, depthrec_c.value>), dim3((unsigned)n_wg),
-                             dim3(64 * TILE_WAVES), lds, s, db->d_meshes, db->d_texs, d_mesh_ids, d_TCO, d_K, (const int*)d_ws, lay, h, w, flags, L,
-                             d_out, (long long)stride_v, views_per_item, n_items, (long long)stride_view, (long long)stride_y, (long long)stride_x,
-                             c_rgb, c_normals, c_depth, c_lo, run_lds, mask, crop, f32_mask, d_tcr, depth_mode,
-                             compact ? job_flags : (const unsigned char*)nullptr);
+          if (heavy_w == 1) launch(ns4, full_c, out_c, depthrec_c, std::integral_constant<int, 1>{}, std::true_type{});
+          else if (heavy_w == 2) launch(ns4, full_c, out_c, depthrec_c, std::integral_constant<int, 2>{}, std::true_type{});
+          else if (heavy_w == 4) launch(ns4, full_c, out_c, depthrec_c, std::integral_constant<int, 4>{}, std::true_type{});
+          else launch(ns4, full_c, out_c, depthrec_c, std::integral_constant<int, TILE_WAVES>{}, std::false_type{});
         });
       });
     });

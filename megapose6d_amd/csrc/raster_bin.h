@@ -40,8 +40,10 @@ struct BinLayout {
 // the layout raster_bin uses for this database at h x w (what mp_raster_workspace_bytes sizes per view)
 BinLayout raster_bin_layout(const mp_mesh_db* db, int h, int w);
 
-// behind the per-view blocks (batch renderer only): [4 counters][light job list: one int per (view, tile)][job flags: one byte per
-// (item, tile), sized for items = views][per-view tile flags: one byte per (view, tile)]
+// behind the per-view blocks (batch renderer only): [4 counters: light pairs, heavy pairs, -, -][pair list: one int per (view, tile)][job
+// flags: one byte per (item, tile), sized for items = views][per-view tile flags: one byte per (view, tile)].  The first n_items * n_tiles
+// ints of the pair list hold both lists of raster_classify, which partition the pairs: the light ones from the start, the heavy ones from the
+// far end (heavy entry k at index n_items * n_tiles - 1 - k).
 inline size_t raster_job_tail_offset_ints(const BinLayout& lay, int n_views) { return ((size_t)n_views * (size_t)lay.view_ints + 3) & ~(size_t)3; }
 
 // Enqueue raster_bin for n_views views (one workgroup each): view v = mesh d_mesh_ids[v] under pose d_TCO[v] and intrinsics d_K[v]
