@@ -982,6 +982,43 @@ int mp_draw_boxes(const uint8_t* d_images /*[n,h,w,3]*/, const float* d_boxes /*
                   uint8_t* d_out /*[n,h,w,3]*/, mp_stream stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Training-free detector: LINE-2D template matching on quantised gradient orientations   */
+/* (the colour modality of LINE-MOD, Hinterstoisser et al., PAMI 2012), for objects that   */
+/* have a mesh but no trained detector (csrc/template_match.hip; contract in               */
+/* csrc/template_match_core.h).  Not in the reference; OpenCV's linemod is third party and */
+/* absent, parity unpinned.  Integer arithmetic throughout, no atomics, no scratch: every  */
+/* buffer is a typed tensor whose shape the caller states.                                 */
+/* ------------------------------------------------------------------------------------ */
+/* Quantised gradient orientations of n images d_images uint8 [n,h,w,3].  With blur != 0 each channel is first smoothed by the separable
+   binomial (1 4 6 4 1) / 16, border replicated, rounded to nearest once after both passes.  Per channel the 3x3 Sobel responses (border
+   replicated); the channel with the largest gx^2 + gy^2 wins (the lowest on a tie), mag2 = that sum.  The angle of (gx, gy) modulo 180
+   degrees falls into one of eight half-open bins [k 22.5, (k + 1) 22.5), decided by integer comparisons ((|gy| + |gx|)^2 < 2 gx^2 for
+   tan 22.5, (|gy| - |gx|)^2 < 2 gx^2 for tan 67.5).  A pixel is a candidate when mag2 >= weak_threshold^2 and mag2 > 0; it keeps bit o when
+   at least 5 of the 9 pixels of its 3x3 neighbourhood (those inside the image) are candidates of bin o.  d_ori uint8 [n,h,w] (0 or one bit),
+   d_mag2 int32 [n,h,w] or NULL.  h, w in 1 .. 8192, n * h * w * 3 < 2^31, weak_threshold in 0 .. 1443.  One launch on `stream`.  n == 0 is
+   a successful no-op; any other bad argument returns non-zero before anything is launched. */
+int mp_tm_quantize(const uint8_t* d_images /*[n,h,w,3]*/, int n, int h, int w, int blur, int weak_threshold, uint8_t* d_ori /*[n,h,w]*/,
+                   int32_t* d_mag2 /*[n,h,w] or NULL*/, mp_stream stream);
+/* Linearised response maps of d_ori: s(x, y) = the OR of d_ori over [x, x + T) x [y, y + T) clipped to the image, T in 1 .. 8; r_o(x, y) = 4
+   when bit o is set in s, else 1 when bit o - 1 or o + 1 (circular over eight) is, else 0.  d_resp uint8 [n][8][T][T][gh][gw] with gh =
+   ceil(h / T), gw = ceil(w / T): r_o(x, y) at [n][o][y mod T][x mod T][y div T][x div T], 0 in the cells beyond the image; every byte is
+   written.  n * 8 * T * T * gh * gw < 2^31.  One launch.  n == 0 is a successful no-op; any other bad argument returns non-zero before
+   anything is launched. */
+int mp_tm_response(const uint8_t* d_ori /*[n,h,w]*/, int n, int h, int w, int T, uint8_t* d_resp /*[n,8,T,T,gh,gw]*/, mp_stream stream);
+/* Every template at every grid location.  templates int32 [n_templates,5] = (object, first feature, n_features f, width, height), features
+   uint8 [n_features,4] = (dx, dy, orientation index, 0), each on the device and as a host copy: the host copy is validated before anything
+   is launched (0 <= object < n_objects, 1 <= f <= 63, sides in 1 .. 256, first + f <= n_features, dx < width, dy < height, index < 8).
+   Template t at location (gx, gy) has its corner at pixel (gx T, gy T), is valid when its box lies inside the image, and scores the sum
+   over its features of r_o(gx T + dx, gy T + dy).  Per (image, object, location) the best valid template by the exact ratio score / (4 f)
+   (cross-multiplied integers), a tie to the lower index: d_best_score, d_best_f uint8 and d_best_template int32, each
+   [n,n_objects,gh,gw]; 0, 0 and -1 where no template is valid.  n_objects in 1 .. 65535, n <= 65535, n_templates in 0 .. 2^20.  One
+   launch.  n == 0 is a successful no-op; any other bad argument returns non-zero before anything is launched. */
+int mp_tm_match(const uint8_t* d_resp /*[n,8,T,T,gh,gw]*/, int n, int h, int w, int T, const int32_t* d_templates /*[n_templates,5]*/,
+                const int32_t* h_templates /*host copy*/, const uint8_t* d_features /*[n_features,4]*/, const uint8_t* h_features /*host copy*/,
+                int n_templates, int n_features, int n_objects, uint8_t* d_best_score /*[n,n_objects,gh,gw]*/,
+                uint8_t* d_best_f /*[n,n_objects,gh,gw]*/, int32_t* d_best_template /*[n,n_objects,gh,gw]*/, mp_stream stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Depth refiner (ICP): replaces inference/icp_refiner.py:128-175 icp_refinement +          */
 /* :195-262 ICPRefiner.refine_poses (masks refiner_utils.py:30-56).  The reference's ICP    */
 /* core is OpenCV-contrib ppf_match_3d_ICP (third party, parity unpinned); this is a        */

@@ -5,7 +5,7 @@ of the reference's renderer / PosePredictor / PoseEstimator interfaces.  Importi
 first engine call loads `libmp_engine.so` and raises if it is missing (there is no CPU fallback).
 """
 from . import (detector, distances, distributed, engine, evaluation, icp_refiner, load_model, mask_rcnn, mesh_cleanup, mesh_db, mesh_io, object_dataset, onboarding, pose_estimator,  # noqa: F401
-               pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, types, visualization)
+               pose_rigid, prediction_runner, renderer, scene_renderer, symmetries, tcoll, template_detector, types, visualization)
 from .detector import Detector  # noqa: F401
 from .icp_refiner import DepthRefiner, ICPRefiner, TeaserppRefiner  # noqa: F401
 from .mask_rcnn import DetectorMaskRCNN  # noqa: F401
@@ -18,6 +18,7 @@ from .pose_rigid import PosePredictor  # noqa: F401
 from .prediction_runner import PredictionRunner  # noqa: F401
 from .renderer import Panda3dBatchRenderer  # noqa: F401
 from .scene_renderer import Panda3dSceneRenderer  # noqa: F401
+from .template_detector import TemplateMatchingModel, TemplateSet, make_template_detector, select_features  # noqa: F401
 from .symmetries import ContinuousSymmetry, DiscreteSymmetry, make_symmetries_poses  # noqa: F401
 from .types import (BatchRenderOutput, CameraRenderingData, ObservationTensor, Panda3dCameraData, Panda3dLightData,  # noqa: F401
                     Panda3dObjectData, PosePredictorOutput)

@@ -213,6 +213,9 @@ SIGNATURES = {
     "mp_symmetry_check": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_overlay": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mp_draw_boxes": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mp_tm_quantize": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mp_tm_response": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "mp_tm_match": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mp_surface_sample_scratch_bytes": (_sz, [_i, _vp, _i, _i]),
     "mp_surface_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "mp_fps_workspace_bytes": (_sz, [_i, _i]),

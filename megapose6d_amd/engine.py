@@ -1639,6 +1639,97 @@ def draw_boxes(images: torch.Tensor, boxes: torch.Tensor, image_ids: torch.Tenso
 
 
 # --------------------------------------------------------------------------- #
+# training-free detector (LINE-2D template matching): csrc/template_match.hip
+TM_MAX_SIDE = 8192                   # h, w
+TM_MAX_T = 8                         # spreading / grid step
+TM_MAX_WEAK = 1443                   # weak_threshold
+TM_MAX_FEATURES = 63                 # features of one template
+TM_MAX_BOX = 256                     # width, height of one template
+
+
+def _tm_grid(h: int, w: int, T: int) -> Tuple[int, int]:
+    if not 1 <= int(T) <= TM_MAX_T:
+        raise EngineError(f"T must be in 1 .. {TM_MAX_T}, got {T}")
+    return -(-h // T), -(-w // T)
+
+
+def _tm_sizes(name: str, n: int, h: int, w: int) -> None:
+    if not (1 <= h <= TM_MAX_SIDE and 1 <= w <= TM_MAX_SIDE) or n * h * w * 3 >= 2 ** 31:
+        raise EngineError(f"{name}: h and w must be in 1 .. {TM_MAX_SIDE} and n * h * w * 3 below 2^31, got n {n}, h {h}, w {w}")
+
+
+def tm_quantize(images: torch.Tensor, blur: bool = True, weak_threshold: int = 30, with_mag2: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Quantised gradient orientations (mp_tm_quantize).  images uint8 [n,h,w,3] on the device; blur: the binomial (1 4 6 4 1) / 16 first;
+    a pixel is a candidate when its squared gradient magnitude is at least weak_threshold^2 -> ori uint8 [n,h,w] (0 or one of eight bits:
+    the orientation at least 5 candidates of the 3x3 agree on) and mag2 int32 [n,h,w] (None without with_mag2).  Nothing synchronises."""
+    images = _dev_bytes("images", images)
+    if images.dim() != 4 or images.shape[3] != 3:
+        raise EngineError(f"images must be uint8 [n,h,w,3], got {tuple(images.shape)}")
+    n, h, w = (int(v) for v in images.shape[:3])
+    _tm_sizes("images", n, h, w)
+    weak = int(weak_threshold)
+    if not 0 <= weak <= TM_MAX_WEAK:
+        raise EngineError(f"weak_threshold must be in 0 .. {TM_MAX_WEAK}, got {weak_threshold}")
+    ori = torch.empty((n, h, w), dtype=torch.uint8, device=images.device)
+    mag2 = torch.empty((n, h, w), dtype=torch.int32, device=images.device) if with_mag2 else None
+    check(_lib.load().mp_tm_quantize(images.data_ptr(), n, h, w, int(bool(blur)), weak, ori.data_ptr(), _ptr(mag2), _stream()))
+    return ori, mag2
+
+
+def tm_response(ori: torch.Tensor, T: int = 8) -> torch.Tensor:
+    """Linearised response maps (mp_tm_response).  ori uint8 [n,h,w] of tm_quantize; T in 1 .. 8: the orientations are spread over T x T
+    windows and the maps stored for stride-T access -> resp uint8 [n,8,T,T,gh,gw], gh = ceil(h / T), gw = ceil(w / T): the response (4, 1
+    or 0) of orientation o at pixel (x, y) sits at [n, o, y mod T, x mod T, y div T, x div T].  Nothing synchronises."""
+    ori = _dev_bytes("ori", ori)
+    if ori.dim() != 3:
+        raise EngineError(f"ori must be uint8 [n,h,w], got {tuple(ori.shape)}")
+    n, h, w = (int(v) for v in ori.shape)
+    _tm_sizes("ori", n, h, w)
+    gh, gw = _tm_grid(h, w, T)
+    if n * 8 * T * T * gh * gw >= 2 ** 31:
+        raise EngineError(f"the response maps of n {n}, h {h}, w {w}, T {T} have 2^31 bytes or more")
+    resp = torch.empty((n, 8, T, T, gh, gw), dtype=torch.uint8, device=ori.device)
+    check(_lib.load().mp_tm_response(ori.data_ptr(), n, h, w, int(T), resp.data_ptr(), _stream()))
+    return resp
+
+
+def tm_match(resp: torch.Tensor, h: int, w: int, templates: torch.Tensor, features: torch.Tensor, n_objects: int, host_templates: np.ndarray,
+             host_features: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Every template at every grid location (mp_tm_match).  resp uint8 [n,8,T,T,gh,gw] of tm_response for images of h x w; templates int32
+    [n_templates,5] = (object, first feature, n_features, width, height) and features uint8 [n_features,4] = (dx, dy, orientation index, 0)
+    on the device, host_templates / host_features the same tables as numpy arrays (validated on the host before the launch) -> best_score,
+    best_f uint8 and best_template int32, each [n,n_objects,gh,gw]: the valid template with the largest score / (4 f) at the location
+    (the lower index on a tie), or 0, 0, -1.  Nothing synchronises."""
+    resp = _dev_bytes("resp", resp)
+    if resp.dim() != 6 or resp.shape[1] != 8 or resp.shape[2] != resp.shape[3]:
+        raise EngineError(f"resp must be uint8 [n,8,T,T,gh,gw], got {tuple(resp.shape)}")
+    n, T = int(resp.shape[0]), int(resp.shape[2])
+    h, w, n_objects = int(h), int(w), int(n_objects)
+    _tm_sizes("resp", n, h, w)
+    gh, gw = _tm_grid(h, w, T)
+    if tuple(resp.shape[4:]) != (gh, gw):
+        raise EngineError(f"resp {tuple(resp.shape)} is not the maps of images of {h} x {w} at T {T}: gh, gw must be {gh}, {gw}")
+    if not 1 <= n_objects <= 65535 or n > 65535 or n * n_objects * gh * gw >= 2 ** 31:
+        raise EngineError(f"n_objects must be in 1 .. 65535, n at most 65535 and n * n_objects * gh * gw below 2^31, got n {n}, n_objects {n_objects}")
+    templates = _dev_i32(templates)
+    features = _dev_bytes("features", features)
+    host_templates = np.ascontiguousarray(host_templates, np.int32)
+    host_features = np.ascontiguousarray(host_features, np.uint8)
+    if templates.dim() != 2 or templates.shape[1] != 5 or features.dim() != 2 or features.shape[1] != 4:
+        raise EngineError(f"templates must be int32 [n_templates,5] and features uint8 [n_features,4], got {tuple(templates.shape)}, {tuple(features.shape)}")
+    if host_templates.shape != tuple(templates.shape) or host_features.shape != tuple(features.shape):
+        raise EngineError(f"the host copies {host_templates.shape}, {host_features.shape} must have the shapes of the tables {tuple(templates.shape)}, {tuple(features.shape)}")
+    shape = (n, n_objects, gh, gw)
+    best_score = torch.empty(shape, dtype=torch.uint8, device=resp.device)
+    best_f = torch.empty(shape, dtype=torch.uint8, device=resp.device)
+    best_template = torch.empty(shape, dtype=torch.int32, device=resp.device)
+    check(_lib.load().mp_tm_match(resp.data_ptr(), n, h, w, T, templates.data_ptr(), host_templates.ctypes.data, features.data_ptr(),
+                                  host_features.ctypes.data, templates.shape[0], features.shape[0], n_objects, best_score.data_ptr(), best_f.data_ptr(),
+                                  best_template.data_ptr(), _stream()))
+    return best_score, best_f, best_template
+
+
+# --------------------------------------------------------------------------- #
 # points drawn uniformly over mesh surfaces (mesh database): csrc/surface_sample.hip
 SURFACE_BLOCK_STEP = 64              # a forced block is a multiple of this ...
 SURFACE_MAX_BLOCK = 2048             # ... and at most this; an object has at most this many blocks
